@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — Mrays/s of the ray-casting hot path on N MI355X (one process per GPU).
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
@@ -75,7 +75,13 @@ def parse_args():
     ap.add_argument("--selftest-cpu", action="store_true",
                     help="exercise only the multi-process glue (tile partition, barrier, max-reduce, frame assembly + CRC) on "
                          "CPU/gloo with a synthetic frame; renders nothing")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the float image of the last timed step (assembled over the ranks) as DIR/rgb.npy, "
+                         "or a fixed seeded sample of its pixels if it exceeds 60 MB (DIR/rgb_sample.npy + DIR/rgb_sample_index.npy)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def init_dist(selftest):
@@ -159,6 +165,25 @@ def synthetic_frame(width, height):
     """A frame that is a pure function of the pixel coordinates (the --selftest-cpu stand-in for a rendered one)."""
     y, x = np.mgrid[0:height, 0:width].astype(np.float32)
     return np.stack([x * 0.25 + y, x - y * 0.5, (x * 7.0 + y * 13.0) % 31.0], axis=-1).astype(np.float32)
+
+
+DUMP_MAX_BYTES = 60 * 10**6  # array bytes of --dump-outputs: with the .npy headers the files stay under 64 MB
+
+
+def dump_outputs(out_dir, img):
+    """--dump-outputs: the H x W x 3 float32 image as out_dir/rgb.npy.  Above DUMP_MAX_BYTES a fixed sample of its pixels instead
+    (seed 0, the same pixels for every run of the same shape): rgb_sample.npy (n x 3 float32) and their row-major pixel indices
+    rgb_sample_index.npy (float64, exact below 2^53)."""
+    os.makedirs(out_dir, exist_ok=True)
+    img = np.ascontiguousarray(img, dtype=np.float32)
+    if img.nbytes <= DUMP_MAX_BYTES:
+        np.save(os.path.join(out_dir, "rgb.npy"), img)
+        return
+    flat = img.reshape(-1, img.shape[-1])
+    n = DUMP_MAX_BYTES // (flat.shape[1] * 4 + 8)
+    idx = np.sort(np.random.default_rng(0).choice(flat.shape[0], size=n, replace=False))
+    np.save(os.path.join(out_dir, "rgb_sample.npy"), flat[idx])
+    np.save(os.path.join(out_dir, "rgb_sample_index.npy"), idx.astype(np.float64))
 
 
 def available_cpus():
@@ -333,11 +358,13 @@ def main():
     local_frame = ctx.read_rgb32f()  # device epilogue (pack to rgb32f) + D2H through pinned staging + the copy into the caller's array
     d2h_ms = max_over_ranks(dist, (time.perf_counter() - g0) * 1e3, dev)
     g1 = time.perf_counter()
-    crc, _img = assemble_frame(dist, rank, n_gpus, local_frame, args.width, args.height, tile)
+    crc, img = assemble_frame(dist, rank, n_gpus, local_frame, args.width, args.height, tile)
     if part_world != n_gpus:
         crc = None  # a share of the frame, not the frame
     crc_ms = max_over_ranks(dist, (time.perf_counter() - g1) * 1e3, dev)  # shared-framebuffer copies (N > 1) + zlib.crc32 over the float image on rank 0
     gather_ms = d2h_ms + crc_ms
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, img)
 
     # exact node / triangle fetch counts and wave-level step statistics from the counting variant of the same kernels
     # the same frame on one lane (RT_WF_LANES=1: every stage kernel alone on the chip) - what the rocprofv3 summaries under profiles/ time

@@ -36,10 +36,10 @@ def test_numpy_dtype_sizes_match_header():
     assert T.BVH_NODE.fields["left_child"][1] == 32
 
 
-def test_render_params_and_stats_match_c_layout():
+def test_render_params_and_stats_match_c_layout(tmp_path):
     src = ('#include <stdio.h>\n#include "rt_hip.h"\nint main(void){printf("%zu %zu %zu %zu\\n", sizeof(rt_render_params),'
            ' offsetof(rt_render_params, width), sizeof(rt_stats), offsetof(rt_stats, kernel_ms));return 0;}\n')
-    exe = "/tmp/_rt_layout_probe"
+    exe = str(tmp_path / "rt_layout_probe")
     subprocess.run(["gcc", "-x", "c", "-I", os.path.join(ROOT, "include"), "-o", exe, "-"], input=src.encode(), check=True)
     vals = list(map(int, subprocess.check_output([exe]).split()))
     assert vals == [T.RENDER_PARAMS.itemsize, T.RENDER_PARAMS.fields["width"][1], T.STATS.itemsize, T.STATS.fields["kernel_ms"][1]]

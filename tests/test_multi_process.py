@@ -43,6 +43,24 @@ def test_frame_assembly_single_process_crc_matches():
     assert crc == zlib.crc32(full.tobytes()) & 0xFFFFFFFF and img is not None
 
 
+def test_dump_outputs_writes_the_frame_or_a_fixed_sample_of_it(tmp_path, monkeypatch):
+    import numpy as np
+    import bench
+    full = bench.synthetic_frame(200, 90)
+    bench.dump_outputs(str(tmp_path / "whole"), full)
+    got = np.load(tmp_path / "whole" / "rgb.npy")
+    assert got.dtype == np.float32 and got.tobytes() == full.tobytes()
+    # over the budget: a sample of pixels, the same ones on every run, with their indices
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", full.nbytes // 4)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), full)
+    sample, idx = (np.load(tmp_path / "a" / f) for f in ("rgb_sample.npy", "rgb_sample_index.npy"))
+    assert sample.dtype == np.float32 and idx.dtype == np.float64 and sample.nbytes + idx.nbytes <= bench.DUMP_MAX_BYTES
+    assert len(np.unique(idx)) == len(idx) > 0 and np.array_equal(sample, full.reshape(-1, 3)[idx.astype(np.int64)])
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "rgb_sample_index.npy"))
+    assert not os.path.exists(tmp_path / "a" / "rgb.npy")
+
+
 def test_tile_ownership_is_a_partition():
     import bench
     for (w, h) in [(1920, 1080), (3840, 2160), (200, 100), (128, 128)]:
