@@ -6,6 +6,7 @@ device is present, the calls raise.
 """
 import ctypes as C
 import os
+import sys
 
 import numpy as np
 
@@ -27,6 +28,10 @@ FLAG_NO_BEAMS = 64
 FLAG_STAGE_TIMES = 128
 PREPARE_SHADOW_GRIDS = 1
 PREPARE_QUALITY_TREE = 2
+QUERY_COUNTERS = 1  # RT_QUERY_COUNTERS of rt_intersect / rt_occluded
+QUERY_CHUNK = 4194304  # RT_QUERY_CHUNK: host batches are staged in chunks of at most this many rays
+PRIM_MISS = 0xFFFFFFFF
+PRIM_SPHERE_FLAG = 0x80000000
 EXTENDED_AVAILABLE = True
 
 # every symbol include/rt_hip.h declares
@@ -34,6 +39,7 @@ ABI_SYMBOLS = [
     "rt_create", "rt_upload_scene", "rt_upload_scene_packed", "rt_upload_textures", "rt_prepare", "rt_render", "rt_dispatch_tile",
     "rt_read_rgb32f", "rt_read_rgba8_channels", "rt_read_rgba8_combined", "rt_read_hits",
     "rt_get_stats", "rt_last_error", "rt_destroy", "rt_version",
+    "rt_intersect", "rt_occluded", "rt_camera_rays",
 ]
 
 
@@ -73,11 +79,94 @@ def _p(a):
     return C.c_void_p(a.ctypes.data) if a is not None and a.size else C.c_void_p(0)
 
 
+# -- ray batches (rt_intersect / rt_occluded / rt_camera_rays) ---------------------------------------------------------
+# A batch is a C-contiguous float32 array of shape (N, 8), one rt_ray per row: ox oy oz tmin dx dy dz tmax; numpy, or a torch
+# tensor on the CPU or on a device of the context.  torch is imported only when a tensor is handed in.
+
+def _is_torch(x):
+    return type(x).__module__.split(".")[0] == "torch"
+
+
+def _check_batch(a, name, cols, dtype_name):
+    """Raises before any library call when `a` is not a C-contiguous (N, cols) array of dtype_name ("float32" or "bool")."""
+    if _is_torch(a):
+        import torch
+        want = {"float32": torch.float32, "bool": torch.bool}[dtype_name]
+        if a.dtype != want:
+            raise TypeError(f"{name}: dtype {a.dtype}, expected torch.{dtype_name}")
+        shape, contiguous = tuple(a.shape), a.is_contiguous()
+    elif isinstance(a, np.ndarray):
+        if a.dtype != np.dtype(dtype_name):
+            raise TypeError(f"{name}: dtype {a.dtype}, expected {dtype_name}")
+        shape, contiguous = a.shape, a.flags.c_contiguous
+    else:
+        raise TypeError(f"{name}: a numpy array or a torch tensor, not {type(a).__name__}")
+    if (cols and (len(shape) != 2 or shape[1] != cols)) or (not cols and len(shape) != 1):
+        raise ValueError(f"{name}: shape {shape}, expected {'(N, %d)' % cols if cols else '(N,)'}")
+    if not contiguous:
+        raise ValueError(f"{name}: not C-contiguous")
+    return shape[0]
+
+
+def _addr(a):
+    return C.c_void_p(a.data_ptr() if _is_torch(a) else a.ctypes.data)
+
+
+def _empty_like_batch(rays, shape, dtype_name):
+    if _is_torch(rays):
+        import torch
+        return torch.empty(shape, dtype={"float32": torch.float32, "bool": torch.bool}[dtype_name], device=rays.device)
+    return np.empty(shape, np.dtype(dtype_name))
+
+
+def _sync_torch(*tensors):
+    """The library reads device tensors on its own stream: finish what torch has queued for them first."""
+    for a in tensors:
+        if _is_torch(a) and a.device.type != "cpu":
+            import torch
+            torch.cuda.current_stream(a.device).synchronize()
+
+
+def make_rays(origins, directions, tmin=1e-5, tmax=float("inf")):
+    """(N, 3) origins and directions (numpy or torch, the result has the same kind and device) -> an (N, 8) float32 ray batch.
+    tmin / tmax: scalars or (N,) arrays."""
+    if _is_torch(origins):
+        import torch
+        o = origins.reshape(-1, 3)
+        out = torch.empty((o.shape[0], 8), dtype=torch.float32, device=o.device)
+    else:
+        o = np.asarray(origins, np.float32).reshape(-1, 3)
+        out = np.empty((o.shape[0], 8), np.float32)
+    out[:, 0:3] = o
+    out[:, 3] = tmin
+    out[:, 4:7] = directions.reshape(-1, 3) if _is_torch(directions) else np.asarray(directions, np.float32).reshape(-1, 3)
+    out[:, 7] = tmax
+    return out
+
+
+def split_hits(hits):
+    """(N, 4) hit records -> (t, u, v, prim).  prim: uint32 for numpy, int64 for torch (a miss is 4294967295 = PRIM_MISS)."""
+    if _is_torch(hits):
+        import torch
+        prim = hits[:, 3].contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+        return hits[:, 0], hits[:, 1], hits[:, 2], prim
+    return hits[:, 0], hits[:, 1], hits[:, 2], np.ascontiguousarray(hits[:, 3]).view(np.uint32)
+
+
+def _init_torch_device_runtime():
+    """torch ships its own HIP runtime.  In one process it has to come up before the library's: torch initialised after a
+    context exists reports "No HIP GPUs are available".  Done only when the program has imported torch."""
+    torch = sys.modules.get("torch")
+    if torch is not None and torch.cuda.is_available():
+        torch.cuda.init()
+
+
 class Context:
     """One rt_ctx.  Mirrors the life cycle RenderState/BufferManager/ComputeRenderer have in the reference."""
 
     def __init__(self, device_ids=(0,)):
         self.lib = load()
+        _init_torch_device_runtime()
         self._h = C.c_void_p(0)
         ids = (C.c_int * len(device_ids))(*device_ids)
         rc = self.lib.rt_create(C.byref(self._h), ids, C.c_int(len(device_ids)))
@@ -215,6 +304,44 @@ class Context:
         d = dict(zip(names, [int(v) for v in out]))
         d["failures"] = int(fails)
         return d
+
+    # -- ray queries ---------------------------------------------------------------------
+    def _query(self, fn, rays, out, cols, dtype_name, counters):
+        n = _check_batch(rays, "rays", 8, "float32")
+        shape = (n, cols) if cols else (n,)
+        if out is None:
+            out = _empty_like_batch(rays, shape, dtype_name)
+        else:
+            if _is_torch(out) != _is_torch(rays):
+                raise TypeError("out: must be the same kind (numpy / torch) as rays")
+            if _check_batch(out, "out", cols, dtype_name) != n:
+                raise ValueError(f"out: {len(out)} rows for {n} rays")
+        _sync_torch(rays, out)
+        self._check(getattr(self.lib, fn)(self._h, _addr(rays), C.c_size_t(n), _addr(out), C.c_uint32(QUERY_COUNTERS if counters else 0)))
+        return out
+
+    def intersect(self, rays, out=None, counters=False):
+        """rt_intersect: closest hit of each ray of an (N, 8) batch -> (N, 4) float32 (t, u, v, prim_id bits; split_hits),
+        same kind and device as `rays`."""
+        return self._query("rt_intersect", rays, out, 4, "float32", counters)
+
+    def occluded(self, rays, out=None, counters=False):
+        """rt_occluded: any hit in each ray's range -> (N,) bool, same kind and device as `rays`."""
+        return self._query("rt_occluded", rays, out, 0, "bool", counters)
+
+    def camera_rays(self, width, height, camera, mode=MODE_LEGACY, out=None):
+        """rt_camera_rays: the width x height pixel-centre rays of mode 0/1 as a (width * height, 8) batch, row-major, y down.
+        `out` (optional): a numpy array or torch tensor (CPU or device) to write them to."""
+        cam = np.zeros((), T.CAMERA)
+        cam[...] = camera
+        n = width * height
+        if out is None:
+            out = np.empty((n, 8), np.float32)
+        elif _check_batch(out, "out", 8, "float32") != n:
+            raise ValueError(f"out: {len(out)} rows for {n} pixels")
+        _sync_torch(out)
+        self._check(self.lib.rt_camera_rays(self._h, _p(cam), C.c_uint32(width), C.c_uint32(height), C.c_uint32(mode), _addr(out)))
+        return out
 
     def stats(self):
         st = np.zeros((), dtype=T.STATS)

@@ -73,8 +73,9 @@ __device__ __forceinline__ void camera_ray(const DevCamera& cam, float sx, float
 // ------------------------------------------------------------------------------------
 // Spheres: test_sphere_intersections (shader/src/lib.rs:252-269) +
 // test_sphere_intersection (shader/src/intersection.rs:52-87).  Linear, wave-uniform loop.
+// Accepts tmin < t < hit.t; the frames pass tmin = RT_MIN_RAY_DISTANCE, the ray queries (ray_query.hip) the ray's own.
 // ------------------------------------------------------------------------------------
-__device__ __forceinline__ void test_spheres(const DevScene& sc, V3 o, V3 d, Hit& hit) {
+__device__ __forceinline__ void test_spheres(const DevScene& sc, V3 o, V3 d, Hit& hit, float tmin) {
     for (uint32_t i = 0; i < sc.n_spheres; i++) {
         const DevSphere& s = sc.spheres[i];
         V3 oc = o - ld3(s.center);
@@ -86,8 +87,8 @@ __device__ __forceinline__ void test_spheres(const DevScene& sc, V3 o, V3 d, Hit
         float sq = sqrtf(disc);
         float t1 = (-b - sq) / (2.0f * a);
         float t2 = (-b + sq) / (2.0f * a);
-        float t = (t1 > RT_MIN_RAY_DISTANCE) ? t1 : t2;
-        if (t > RT_MIN_RAY_DISTANCE && t < hit.t) {
+        float t = (t1 > tmin) ? t1 : t2;
+        if (t > tmin && t < hit.t) {
             hit.t = t;
             hit.prim = RT_PRIM_SPHERE_FLAG | i;
             hit.slot = i;
@@ -107,7 +108,8 @@ __device__ __forceinline__ void test_spheres(const DevScene& sc, V3 o, V3 d, Hit
 // The arithmetic of TriangleIntersector::ray_triangle_intersect (shader/src/intersection.rs:91-138) up to the distance: false when
 // the ray is parallel (|a| < 1e-5) or passes outside (u, v); `t` is the distance along d otherwise (the callers apply the range).
 // One statement for the leaves of the BVH and for the light grids' lists (wavefront.hip), so both accept exactly the same rays.
-__device__ __forceinline__ bool moller_trumbore(V3 v0, V3 e1, V3 e2, V3 o, V3 d, float& t) {
+// `uv` (optional): the barycentrics the test accepted (weights of v1 and v2), which the ray queries report.
+__device__ __forceinline__ bool moller_trumbore(V3 v0, V3 e1, V3 e2, V3 o, V3 d, float& t, float* uv = nullptr) {
     V3 h = cross(d, e2);
     float a = dot(e1, h);
     if (fabsf(a) < RT_MIN_RAY_DISTANCE) return false;
@@ -119,11 +121,16 @@ __device__ __forceinline__ bool moller_trumbore(V3 v0, V3 e1, V3 e2, V3 o, V3 d,
     float v = f * dot(d, q);
     if (v < 0.0f || u + v > 1.0f) return false;
     t = f * dot(e2, q);
+    if (uv) {
+        uv[0] = u;
+        uv[1] = v;
+    }
     return true;
 }
 
 // Returns the record's leaf_count word (the run length when `slot` is the first triangle of a leaf).
-__device__ __forceinline__ uint32_t test_triangle(const DevTri* __restrict__ tris, uint32_t slot, V3 o, V3 d, Hit& hit) {
+// Accepts tmin < t, and t < hit.t or the tie below.
+__device__ __forceinline__ uint32_t test_triangle(const DevTri* __restrict__ tris, uint32_t slot, V3 o, V3 d, Hit& hit, float tmin) {
     const float4* p = reinterpret_cast<const float4*>(tris + slot);
     float4 q0 = p[0], q1 = p[1], q2 = p[2];
     // one 48-byte record = three 16-byte loads issued together (otherwise the compiler splits them by first use
@@ -139,7 +146,7 @@ __device__ __forceinline__ uint32_t test_triangle(const DevTri* __restrict__ tri
     // equal t: the lower index wins among TRIANGLES only; against a sphere hit or the segment's own limit (prim = MISS, shadow
     // segments) the comparison stays strict, as in find_closest_intersection (lib.rs:214-248: the sphere is kept unless the
     // triangle is strictly closer)
-    if (t > RT_MIN_RAY_DISTANCE && (t < hit.t || (t == hit.t && prim < hit.prim && hit.prim < RT_PRIM_SPHERE_FLAG))) {
+    if (t > tmin && (t < hit.t || (t == hit.t && prim < hit.prim && hit.prim < RT_PRIM_SPHERE_FLAG))) {
         hit.t = t;
         hit.prim = prim;
         hit.slot = slot;
@@ -149,12 +156,12 @@ __device__ __forceinline__ uint32_t test_triangle(const DevTri* __restrict__ tri
 
 // All triangles of the leaf `ref`.  ANY_HIT: stop at the first accepted one and return true.
 template <bool COUNT, bool ANY_HIT>
-__device__ __forceinline__ bool test_leaf(const DevTri* __restrict__ tris, uint32_t ref, V3 o, V3 d, Hit& hit, Counts& cnt) {
+__device__ __forceinline__ bool test_leaf(const DevTri* __restrict__ tris, uint32_t ref, V3 o, V3 d, Hit& hit, Counts& cnt, float tmin) {
     const uint32_t start = ref & RT_DEV_LEAF_START_MASK;
     uint32_t n = 1;
     for (uint32_t i = 0; i < n; i++) {
         if (COUNT) cnt.tris++;
-        const uint32_t lc = test_triangle(tris, start + i, o, d, hit);
+        const uint32_t lc = test_triangle(tris, start + i, o, d, hit, tmin);
         if (i == 0) n = lc;
         if (ANY_HIT && hit.prim != RT_PRIM_MISS) return true;
     }
@@ -284,9 +291,9 @@ __device__ __forceinline__ uint32_t visit_node8(const uint4* __restrict__ nodes,
 // The walk of one lane on its own (reference-mode kernel, nested-loop megakernel): groups on a per-lane stack of 64-bit
 // entries (lane-interleaved: entry k of this lane at stack[k * 64]), a node's leaves tested right after its visit, before its
 // inner children (their hits cull the children's subtrees).  ANY_HIT (shadow segments of the extended mode): return at the
-// first accepted triangle.
+// first accepted triangle.  Triangles are accepted in (tmin, hit.t); the boxes filter by [0, hit.t] only (conservative for any tmin >= 0).
 template <bool COUNT, bool ANY_HIT>
-__device__ __forceinline__ void traverse(const DevScene& sc, V3 o, V3 d, uint2* __restrict__ stack, Hit& hit, Counts& cnt) {
+__device__ __forceinline__ void traverse(const DevScene& sc, V3 o, V3 d, uint2* __restrict__ stack, Hit& hit, Counts& cnt, float tmin) {
     if (sc.n_nodes == 0) return;
     const FilterRay fr = make_filter_ray(o, d);
     const uint32_t oct = ray_octant(fr);
@@ -315,7 +322,7 @@ __device__ __forceinline__ void traverse(const DevScene& sc, V3 o, V3 d, uint2* 
             const uint32_t sl = first_slot(t, oct);
             t ^= 1u << sl;
             const uint32_t first = tb + RT_DEV_LEAF_STRIDE * (uint32_t)__popc(lm & ((1u << sl) - 1u));
-            if (test_leaf<COUNT, ANY_HIT>(sc.tris, RT_DEV_LEAF_FLAG | first, o, d, hit, cnt)) return;
+            if (test_leaf<COUNT, ANY_HIT>(sc.tris, RT_DEV_LEAF_FLAG | first, o, d, hit, cnt, tmin)) return;
         }
         g_base = cb;
         g_bits = (hm & im) | (im << 8);
@@ -330,9 +337,22 @@ __device__ __forceinline__ Hit find_closest(const DevScene& sc, V3 o, V3 d, uint
     hit.t = RT_F32_MAX; // f32::MAX - 2.0 == f32::MAX
     hit.prim = RT_PRIM_MISS;
     hit.slot = 0;
-    test_spheres(sc, o, d, hit);
-    traverse<COUNT, false>(sc, o, d, stack, hit, cnt);
+    test_spheres(sc, o, d, hit, RT_MIN_RAY_DISTANCE);
+    traverse<COUNT, false>(sc, o, d, stack, hit, cnt, RT_MIN_RAY_DISTANCE);
     return hit;
+}
+
+// any hit in (tmin, tmax)?  Spheres first, then the BVH with early exit.
+template <bool COUNT>
+__device__ __forceinline__ bool occluded(const DevScene& sc, V3 o, V3 d, float tmin, float tmax, uint2* stack, Counts& cnt) {
+    Hit h;
+    h.t = tmax;
+    h.prim = RT_PRIM_MISS;
+    h.slot = 0;
+    test_spheres(sc, o, d, h, tmin);
+    if (h.prim != RT_PRIM_MISS) return true;
+    traverse<COUNT, true>(sc, o, d, stack, h, cnt, tmin);
+    return h.prim != RT_PRIM_MISS;
 }
 
 // ------------------------------------------------------------------------------------

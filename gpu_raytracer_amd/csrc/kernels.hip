@@ -66,19 +66,6 @@ __global__ __launch_bounds__(WAVE) void k_render_reference(DevScene sc, DevFrame
 }
 
 
-// any hit in (1e-5, tmax)?  Spheres first, then the BVH with early exit.
-template <bool COUNT>
-__device__ __forceinline__ bool occluded(const DevScene& sc, V3 o, V3 d, float tmax, uint2* stack, Counts& cnt) {
-    Hit h;
-    h.t = tmax;
-    h.prim = RT_PRIM_MISS;
-    h.slot = 0;
-    test_spheres(sc, o, d, h);
-    if (h.prim != RT_PRIM_MISS) return true;
-    traverse<COUNT, true>(sc, o, d, stack, h, cnt);
-    return h.prim != RT_PRIM_MISS;
-}
-
 template <bool COUNT>
 __device__ __forceinline__ V3 ext_direct(const DevScene& sc, const DevMaterial& m, V3 point, V3 normal, bool ambient, bool shadows,
                                          uint2* stack, Counts& cnt, SegCounts& seg) {
@@ -94,7 +81,7 @@ __device__ __forceinline__ V3 ext_direct(const DevScene& sc, const DevMaterial& 
         }
         if (shadows) {
             seg.shadow++;
-            if (occluded<COUNT>(sc, point + normal * EXT_EPS, sdir, sdist, stack, cnt)) continue;
+            if (occluded<COUNT>(sc, point + normal * EXT_EPS, sdir, RT_MIN_RAY_DISTANCE, sdist, stack, cnt)) continue;
         }
         total = total + contrib;
     }
@@ -297,7 +284,7 @@ __global__ __launch_bounds__(WAVE, RT_SM_MIN_WAVES) void k_render_extended_sm(De
         hit.slot = 0;
         anyhit = any;
         oct = ray_octant(fray);
-        test_spheres(sc, so, sd, hit);
+        test_spheres(sc, so, sd, hit, RT_MIN_RAY_DISTANCE);
         sp = 0;
         g_base = 0;
         g_bits = 1u | (1u << 8); // the root as the only child of a group
@@ -530,7 +517,7 @@ __global__ __launch_bounds__(WAVE, RT_SM_MIN_WAVES) void k_render_extended_sm(De
                     uint32_t n_tri = 1;
                     for (uint32_t i = 0; i < n_tri; i++) {
                         if (COUNT) cnt.tris++;
-                        const uint32_t lc = test_triangle(sc.tris, start + i, o, d, hit);
+                        const uint32_t lc = test_triangle(sc.tris, start + i, o, d, hit, RT_MIN_RAY_DISTANCE);
                         if (i == 0) n_tri = lc;
                         if (anyhit && hit.prim != RT_PRIM_MISS) {
                             stop = true;

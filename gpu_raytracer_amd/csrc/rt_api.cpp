@@ -22,6 +22,7 @@
 #include "device_layout.h"
 #include "half.h"
 #include "kernels.h"
+#include "ray_query.h"
 #include "shadow_grid.h"
 #include "wavefront.h"
 
@@ -71,6 +72,10 @@ struct DeviceState {
     uint32_t stage_events_used = 0;
     bool wf_beams_off = false; // this frame walks the tree for its camera segments too (RT_FLAG_NO_BEAMS)
     std::vector<void*> wf_allocs;
+    void* rq_in = nullptr;  // ray queries: staging of host batches (rays in, hit records / bytes out), grown on demand
+    void* rq_out = nullptr;
+    size_t rq_in_bytes = 0, rq_out_bytes = 0;
+    std::vector<hipEvent_t> rq_events; // an event pair around each launch of a query
 };
 
 } // namespace
@@ -137,6 +142,11 @@ void free_scene(DeviceState& d) {
     d.grids = nullptr;
     d.grids_tried = false;
     d.grids_partial = false;
+    // the staging of the ray queries goes with the scene it was used for (released by the next upload and by rt_destroy)
+    (void)hipFree(d.rq_in);
+    (void)hipFree(d.rq_out);
+    d.rq_in = d.rq_out = nullptr;
+    d.rq_in_bytes = d.rq_out_bytes = 0;
 }
 void free_targets(DeviceState& d) {
     (void)hipSetDevice(d.device);
@@ -1018,6 +1028,7 @@ void rt_destroy(rt_ctx* ctx) {
         for (hipEvent_t e : {d.ev_start, d.ev_join, d.ev_res[0], d.ev_res[1]})
             if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : d.stage_events) (void)hipEventDestroy(e);
+        for (hipEvent_t e : d.rq_events) (void)hipEventDestroy(e);
         if (d.stream2) (void)hipStreamDestroy(d.stream2);
         if (d.stream) (void)hipStreamDestroy(d.stream);
     }
@@ -1521,6 +1532,200 @@ int rt_get_stats(rt_ctx* ctx, rt_stats* out) {
     if (!out) return ctx->fail(RT_ERR_BAD_ARG, "rt_get_stats: null out");
     if (int rcp = sync_pending(ctx)) return rcp;
     *out = ctx->stats;
+    return RT_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// Ray queries (rt_hip.h "Ray queries"): rt_intersect, rt_occluded, rt_camera_rays.
+// ------------------------------------------------------------------------------------
+} // extern "C"
+
+namespace {
+
+struct QueryPtr {
+    bool device = false; // device memory of one of the context's devices (else host memory of any kind: staged)
+    size_t dev = 0;      // ... its index in ctx->devs
+};
+
+// Where `p` lives.  Pageable memory the runtime has never seen may come back as an error or as unregistered: both are host memory.
+int classify_ptr(rt_ctx* ctx, const char* fn, const char* what, const void* p, QueryPtr& q) {
+    q = QueryPtr{};
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return RT_OK;
+    }
+    if (a.type != hipMemoryTypeDevice || a.isManaged) return RT_OK; // pinned, managed, unregistered
+    for (size_t j = 0; j < ctx->devs.size(); j++)
+        if (ctx->devs[j].device == a.device) {
+            if (reinterpret_cast<uintptr_t>(p) & 15u)
+                return ctx->fail(RT_ERR_BAD_ARG, "%s: %s is device memory that is not 16-byte aligned (%p)", fn, what, p);
+            q.device = true;
+            q.dev = j;
+            return RT_OK;
+        }
+    return ctx->fail(RT_ERR_BAD_ARG, "%s: %s is device memory of HIP device %d, which is not a device of this context", fn, what, a.device);
+}
+
+int ensure_buffer(rt_ctx* ctx, void** buf, size_t* cap, size_t bytes) {
+    if (*cap >= bytes) return RT_OK;
+    (void)hipFree(*buf);
+    *buf = nullptr;
+    *cap = 0;
+    HIPCHK(ctx, hipMalloc(buf, bytes));
+    *cap = bytes;
+    return RT_OK;
+}
+
+int ensure_query_events(rt_ctx* ctx, DeviceState& d, size_t n) {
+    while (d.rq_events.size() < n) {
+        hipEvent_t e = nullptr;
+        HIPCHK(ctx, hipEventCreate(&e));
+        d.rq_events.push_back(e);
+    }
+    return RT_OK;
+}
+
+// Both query kinds: out_elem = 16 (rt_hit) or 1 (occluded byte).
+int run_query(rt_ctx* ctx, const char* fn, const rt_ray* rays, size_t n, void* out, size_t out_elem, uint32_t flags) {
+    const double w0 = now_ms();
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (n == 0) return RT_OK;
+    const char* out_name = out_elem == 1 ? "occluded" : "hits";
+    if (!rays || !out) return ctx->fail(RT_ERR_BAD_ARG, "%s: %s is NULL with n = %zu", fn, !rays ? "rays" : out_name, n);
+    if (flags & ~RT_QUERY_COUNTERS) return ctx->fail(RT_ERR_BAD_ARG, "%s: unknown flag bits 0x%x", fn, flags & ~RT_QUERY_COUNTERS);
+    if (!ctx->uploaded) return ctx->fail(RT_ERR_NOT_UPLOADED, "%s: no scene uploaded", fn);
+    if (int rcp = sync_pending(ctx)) return rcp;
+    QueryPtr pin, pout;
+    if (int rc = classify_ptr(ctx, fn, "rays", rays, pin)) return rc;
+    if (int rc = classify_ptr(ctx, fn, out_name, out, pout)) return rc;
+    if (pin.device != pout.device || pin.dev != pout.dev)
+        return ctx->fail(RT_ERR_BAD_ARG, "%s: rays (%s %zu) and %s (%s %zu) must both be host memory or both device memory of the same device", fn,
+                         pin.device ? "device memory of context device" : "host memory", pin.device ? pin.dev : (size_t)0, out_name,
+                         pout.device ? "device memory of context device" : "host memory", pout.device ? pout.dev : (size_t)0);
+    const bool counters = (flags & RT_QUERY_COUNTERS) != 0;
+    const size_t nd = ctx->devs.size();
+    std::vector<size_t> first(nd, 0), count(nd, 0);
+    if (pin.device) count[pin.dev] = n; // a device batch runs where it lives
+    else
+        for (size_t j = 0; j < nd; j++) first[j] = n * j / nd, count[j] = n * (j + 1) / nd - first[j]; // contiguous ranges, one per device
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(rays);
+    uint8_t* dst = reinterpret_cast<uint8_t*>(out);
+    // every device's range is enqueued before any is waited for
+    auto enqueue = [&](size_t j) -> int {
+        DeviceState& d = ctx->devs[j];
+        HIPCHK(ctx, hipSetDevice(d.device));
+        const DevScene sc = scene_for(ctx, d);
+        const size_t chunks = (count[j] + RT_QUERY_CHUNK - 1) / RT_QUERY_CHUNK;
+        if (int rc = ensure_query_events(ctx, d, 2 * chunks)) return rc;
+        if (!pin.device) {
+            const size_t m = std::min<size_t>(count[j], RT_QUERY_CHUNK);
+            if (int rc = ensure_buffer(ctx, &d.rq_in, &d.rq_in_bytes, m * sizeof(rt_ray))) return rc;
+            if (int rc = ensure_buffer(ctx, &d.rq_out, &d.rq_out_bytes, m * out_elem)) return rc;
+        }
+        if (counters) HIPCHK(ctx, hipMemsetAsync(d.counters, 0, 3 * sizeof(unsigned long long), d.stream));
+        for (size_t c = 0; c < chunks; c++) {
+            const size_t off = first[j] + c * RT_QUERY_CHUNK, m = std::min<size_t>(RT_QUERY_CHUNK, first[j] + count[j] - off);
+            const void* in = src + off * sizeof(rt_ray);
+            void* res = dst + off * out_elem;
+            if (!pin.device) {
+                HIPCHK(ctx, hipMemcpyAsync(d.rq_in, in, m * sizeof(rt_ray), hipMemcpyHostToDevice, d.stream));
+                in = d.rq_in;
+                res = d.rq_out;
+            }
+            HIPCHK(ctx, hipEventRecord(d.rq_events[2 * c], d.stream));
+            HIPCHK(ctx, rt::launch_ray_query(sc, in, res, (uint32_t)m, out_elem == 1, counters ? d.counters : nullptr, d.stream));
+            HIPCHK(ctx, hipEventRecord(d.rq_events[2 * c + 1], d.stream));
+            if (!pin.device) HIPCHK(ctx, hipMemcpyAsync(dst + off * out_elem, d.rq_out, m * out_elem, hipMemcpyDeviceToHost, d.stream));
+        }
+        return RT_OK;
+    };
+    auto drain = [&]() { // after a failure: nothing of this call is left writing into the caller's memory
+        for (auto& d : ctx->devs) {
+            (void)hipSetDevice(d.device);
+            (void)hipStreamSynchronize(d.stream);
+        }
+    };
+    for (size_t j = 0; j < nd; j++)
+        if (count[j] > 0)
+            if (int rc = enqueue(j)) {
+                drain();
+                return rc;
+            }
+    double kernel_ms = 0.0;
+    unsigned long long nodes = 0, tris = 0;
+    for (size_t j = 0; j < nd; j++) {
+        if (count[j] == 0) continue;
+        DeviceState& d = ctx->devs[j];
+        hipError_t e = hipSetDevice(d.device);
+        if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
+        if (e != hipSuccess) {
+            drain();
+            return ctx->fail(RT_ERR_HIP, "%s: device %d: %s", fn, d.device, hipGetErrorString(e));
+        }
+        double ms = 0.0;
+        for (size_t c = 0; 2 * c + 1 < d.rq_events.size() && c * RT_QUERY_CHUNK < count[j]; c++) {
+            float cm = 0.0f;
+            HIPCHK(ctx, hipEventElapsedTime(&cm, d.rq_events[2 * c], d.rq_events[2 * c + 1]));
+            ms += cm;
+        }
+        kernel_ms = std::max(kernel_ms, ms);
+        if (counters) {
+            unsigned long long cn[3];
+            HIPCHK(ctx, hipMemcpy(cn, d.counters, sizeof cn, hipMemcpyDeviceToHost));
+            nodes += cn[1];
+            tris += cn[2];
+        }
+    }
+    rt_stats& st = ctx->stats;
+    st.rays = n;
+    st.primary_rays = st.continuation_rays = st.shadow_rays = st.pixels = 0;
+    st.node_visits = counters ? nodes : 0;
+    st.tri_tests = counters ? tris : 0;
+    st.kernel_ms = kernel_ms;
+    st.wall_ms = now_ms() - w0;
+    return RT_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int rt_intersect(rt_ctx* ctx, const rt_ray* rays, size_t n, rt_hit* hits, uint32_t flags) {
+    return run_query(ctx, "rt_intersect", rays, n, hits, sizeof(rt_hit), flags);
+}
+
+int rt_occluded(rt_ctx* ctx, const rt_ray* rays, size_t n, uint8_t* occluded, uint32_t flags) {
+    return run_query(ctx, "rt_occluded", rays, n, occluded, 1, flags);
+}
+
+int rt_camera_rays(rt_ctx* ctx, const rt_camera* camera, uint32_t width, uint32_t height, uint32_t mode, rt_ray* out) {
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (mode != RT_MODE_LEGACY && mode != RT_MODE_WAVEFRONT) return ctx->fail(RT_ERR_BAD_ARG, "rt_camera_rays: mode %u (0 or 1)", mode);
+    const size_t n = (size_t)width * height;
+    if (n == 0) return RT_OK;
+    if (!camera || !out) return ctx->fail(RT_ERR_BAD_ARG, "rt_camera_rays: %s is NULL", !camera ? "camera" : "out");
+    if (int rcp = sync_pending(ctx)) return rcp;
+    QueryPtr po;
+    if (int rc = classify_ptr(ctx, "rt_camera_rays", "out", out, po)) return rc;
+    DeviceState& d = ctx->devs[po.dev];
+    HIPCHK(ctx, hipSetDevice(d.device));
+    if (!po.device)
+        if (int rc = ensure_buffer(ctx, &d.rq_in, &d.rq_in_bytes, std::min<size_t>(n, RT_QUERY_CHUNK) * sizeof(rt_ray))) return rc;
+    // the frames' camera constants (make_camera) and ray generation (camera_ray): the rays are those rt_render traces
+    const DevCamera cam = make_camera(*camera, (float)width, (float)height, mode != RT_MODE_LEGACY);
+    uint8_t* dst = reinterpret_cast<uint8_t*>(out);
+    for (size_t off = 0; off < n; off += RT_QUERY_CHUNK) {
+        const size_t m = std::min<size_t>(RT_QUERY_CHUNK, n - off);
+        void* res = po.device ? (void*)(dst + off * sizeof(rt_ray)) : d.rq_in;
+        hipError_t e = rt::launch_camera_rays(cam, width, mode != RT_MODE_LEGACY, res, off, (uint32_t)m, d.stream);
+        if (e == hipSuccess && !po.device) e = hipMemcpyAsync(dst + off * sizeof(rt_ray), d.rq_in, m * sizeof(rt_ray), hipMemcpyDeviceToHost, d.stream);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(d.stream);
+            return ctx->fail(RT_ERR_HIP, "rt_camera_rays: %s", hipGetErrorString(e));
+        }
+    }
+    HIPCHK(ctx, hipStreamSynchronize(d.stream));
     return RT_OK;
 }
 

@@ -305,7 +305,7 @@ __global__ __launch_bounds__(WAVE, RT_WF8_MIN_WAVES) void k_wf_trace(DevScene sc
                     // the order is free, and measured the first occluder lies nearer the light than the vertex - occluded segments (61 %
                     // of them) needed 11.4 node visits near-first against 9.6 for visible ones; far-first: -3 % frame time, same bits.
                     if (ANY) oct ^= 7u << 8;
-                    test_spheres(sc, o, d, hit);
+                    test_spheres(sc, o, d, hit, RT_MIN_RAY_DISTANCE);
                     sp = 0;
                     cur = WF8_NONE;
                     t_bits = 0;
@@ -391,7 +391,7 @@ __global__ __launch_bounds__(WAVE, RT_WF8_MIN_WAVES) void k_wf_trace(DevScene sc
                     const uint32_t i = lut[oct + (t_bits & 0xFFu)];
                     t_bits ^= 1u << i;
                     const uint32_t first = t_base + RT_DEV_LEAF_STRIDE * (uint32_t)__popc(__builtin_amdgcn_ubfe(t_bits, 8u, i));
-                    if (test_leaf<COUNT, ANY>(sc.tris, RT_DEV_LEAF_FLAG | first, o, d, hit, cnt)) { // occluded: nothing more to do
+                    if (test_leaf<COUNT, ANY>(sc.tris, RT_DEV_LEAF_FLAG | first, o, d, hit, cnt, RT_MIN_RAY_DISTANCE)) { // occluded: nothing more to do
                         cur = WF8_NONE;
                         g_bits = t_bits = 0u;
                         sp = 0;
@@ -691,7 +691,7 @@ __global__ __launch_bounds__(WAVE) void k_wf_trace_camera(DevScene sc, rt::WfBuf
             hit.t = valid ? RT_F32_MAX : -1.0f; // (lanes without a path never ask for another triangle)
             hit.prim = RT_PRIM_MISS;
             hit.slot = 0;
-            if (valid) test_spheres(sc, o, d, hit);
+            if (valid) test_spheres(sc, o, d, hit, RT_MIN_RAY_DISTANCE);
             {
                 for (uint32_t i = 0; i < n_list; i++) {
                     if (RT_BEAM_EARLY_OUT && __ballot(s_d[i] < hit.t) == 0ull) break; // sorted: every later triangle is farther still
@@ -716,8 +716,8 @@ __global__ __launch_bounds__(WAVE) void k_wf_trace_camera(DevScene sc, rt::WfBuf
                 h2.prim = RT_PRIM_MISS;
                 h2.slot = 0;
                 Counts c2 = {0u, 0u};
-                test_spheres(sc, o, d, h2);
-                traverse<false, false>(sc, o, d, reinterpret_cast<uint2*>(s_cam + RT_BEAM_CAP * 4u) + lane, h2, c2);
+                test_spheres(sc, o, d, h2, RT_MIN_RAY_DISTANCE);
+                traverse<false, false>(sc, o, d, reinterpret_cast<uint2*>(s_cam + RT_BEAM_CAP * 4u) + lane, h2, c2, RT_MIN_RAY_DISTANCE);
                 if (h2.prim != hit.prim || h2.t != hit.t) {
                     if (atomicAdd(&wb.totals[6], 1ull) == 0ull) {
                         wb.totals[8] = b;
@@ -817,7 +817,7 @@ __device__ __forceinline__ uint32_t grid_segment_head(const DevScene& sc, const 
     hit.t = dist;
     hit.prim = RT_PRIM_MISS;
     hit.slot = 0;
-    test_spheres(sc, o, d, hit);
+    test_spheres(sc, o, d, hit, RT_MIN_RAY_DISTANCE);
     if (hit.prim != RT_PRIM_MISS) return GRID_OCCLUDED; // by a sphere: nothing left to do
     const uint32_t kind = g.kind;
     uint32_t cell = 0xFFFFFFFFu; // no cell: an empty list

@@ -202,6 +202,70 @@ int rt_read_hits(rt_ctx* ctx, uint32_t* prim_ids, float* t, size_t n_pixels);
 
 int rt_get_stats(rt_ctx* ctx, rt_stats* out);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Ray queries: closest hit and occlusion for caller-supplied rays (no reference counterpart; Embree's rtcIntersect /
+ * rtcOccluded are the model).  They trace the uploaded scene with the frames' rules and leave the last frame alone.
+ *
+ * Range: a triangle or sphere is accepted at tmin < t < tmax, both strict; t is parametric along `direction`, which
+ * need not be normalised.  A tmin below RT_MIN_RAY_DISTANCE (1e-5, negative values included) is raised to it: the
+ * floor the tree's box filter is conservative for, and the render path's own.  tmax = +inf is allowed.
+ * Rules: the Moller-Trumbore arithmetic, the tie rule (equal t: the lower original triangle index wins among
+ * triangles, strict against spheres) and "spheres first" of the frames.  A camera ray (rt_camera_rays) therefore gives
+ * exactly the prim_id and t bits rt_read_hits gives for its pixel, and the answer does not depend on the tree
+ * (RT_PREPARE_QUALITY_TREE or not).
+ * Hit record: prim_id = original triangle index, 0x80000000 | i for sphere i, 0xFFFFFFFF for a miss (as rt_read_hits).
+ * Triangle: u, v = the Moller-Trumbore barycentrics (weights of v1 and v2) of the arithmetic that accepted the hit.
+ * Sphere: u = v = 0.  Miss: t = the ray's tmax as given, u = v = 0.
+ * Occlusion: occluded[i] = 1 if any primitive is accepted in the range, else 0 (any-hit walk, early exit); always equal
+ * to rt_intersect's prim_id != 0xFFFFFFFF.
+ * Degenerate rays (a non-finite origin or direction component, a zero direction, a NaN bound, or !(tmin < tmax) after
+ * the floor) are misses / not occluded, without a walk.  The kernel checks this itself.
+ * Buffers: each pointer is classified by the library.  Device memory of one of the context's devices is read and
+ * written in place on that device (input and output on the same device, 16-byte aligned: RT_ERR_BAD_ARG otherwise);
+ * host memory of any kind (pageable, pinned, managed) is staged through per-device buffers in chunks of at most
+ * RT_QUERY_CHUNK rays, and on a context with several devices split into one contiguous range per device.
+ * Synchronous: the results are in place when the call returns.  Device-resident input must be complete before the call:
+ * the library reads it on its own stream.  A query first waits for an rt_dispatch_tile still in flight.
+ * Statistics: rays = n; primary_rays, continuation_rays, shadow_rays, pixels = 0; kernel_ms (max over devices) and
+ * wall_ms; node_visits / tri_tests with RT_QUERY_COUNTERS (else 0).  rt_read_* still return the last frame.
+ * Errors: n == 0 is RT_OK and does nothing; a NULL pointer with n > 0 or unknown flag bits are RT_ERR_BAD_ARG; a query
+ * before any upload is RT_ERR_NOT_UPLOADED.  An empty scene gives all misses.
+ * --------------------------------------------------------------------------------------------------------------- */
+typedef struct rt_ray {
+    float origin[3];
+    float tmin;
+    float direction[3];
+    float tmax;
+} rt_ray; /* 32 bytes */
+
+typedef struct rt_hit {
+    float t;
+    float u, v;
+    uint32_t prim_id;
+} rt_hit; /* 16 bytes */
+
+RT_STATIC_ASSERT(sizeof(rt_ray) == 32, "rt_ray is 32 B");
+RT_STATIC_ASSERT(offsetof(rt_ray, tmin) == 12 && offsetof(rt_ray, direction) == 16 && offsetof(rt_ray, tmax) == 28, "rt_ray offsets");
+RT_STATIC_ASSERT(sizeof(rt_hit) == 16, "rt_hit is 16 B");
+RT_STATIC_ASSERT(offsetof(rt_hit, u) == 4 && offsetof(rt_hit, v) == 8 && offsetof(rt_hit, prim_id) == 12, "rt_hit offsets");
+
+/* flags of rt_intersect / rt_occluded (a set of their own, not RT_FLAG_*) */
+#define RT_QUERY_COUNTERS 1u /* run the counting variant of the query kernel: fills rt_stats.node_visits / tri_tests */
+
+#define RT_QUERY_CHUNK 4194304u /* host batches are staged in chunks of at most this many rays */
+
+/* Closest hit of each of the n rays. */
+int rt_intersect(rt_ctx* ctx, const rt_ray* rays, size_t n, rt_hit* hits, uint32_t flags);
+
+/* Any hit of each of the n rays: occluded[i] = 0 or 1. */
+int rt_occluded(rt_ctx* ctx, const rt_ray* rays, size_t n, uint8_t* occluded, uint32_t flags);
+
+/* The width x height pixel-centre camera rays of mode 0 (RT_MODE_LEGACY: direction normalised twice, as Ray::new) or
+ * mode 1 (RT_MODE_WAVEFRONT: once), computed by the frames' own ray generation; any other mode is RT_ERR_BAD_ARG.
+ * Row-major, y down, tmin = RT_MIN_RAY_DISTANCE, tmax = FLT_MAX.  `out` (width * height records) may be host or
+ * device memory, classified as for the queries.  Needs no scene.  Synchronous. */
+int rt_camera_rays(rt_ctx* ctx, const rt_camera* camera, uint32_t width, uint32_t height, uint32_t mode, rt_ray* out);
+
 /* Last error text of this context (or of the failed rt_create when ctx is NULL). */
 const char* rt_last_error(rt_ctx* ctx);
 
