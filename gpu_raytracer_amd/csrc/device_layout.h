@@ -138,7 +138,32 @@ struct DevTargets {
     uint8_t* chan[3];    // three Rgba8Unorm channel textures, width*height*4 bytes each
     uint32_t* prim_id;   // per-pixel closest primitive (modes 0/1)
     float* hit_t;        // per-pixel hit distance       (modes 0/1)
-    unsigned long long* counters; // [0] rays [1] node visits [2] tri tests [3] camera [4] continuation [5] shadow segments
+    unsigned long long* counters; // RT_CNT_SLOTS words, DevCounterSlot
+};
+
+// Slots of DevTargets::counters (zeroed per frame and device; rt_intersect / rt_occluded zero the first three).  Written by k_render_reference,
+// k_render_extended, k_render_extended_sm and k_rq_trace; read by run_frame, run_query and (the diagnostic slots) rt_debug_counters.
+enum DevCounterSlot : uint32_t {
+    RT_CNT_SEGMENTS = 0,     // segments traced: camera + continuation + shadow (modes 0/1: pixels traced; queries: not written)
+    RT_CNT_NODE_VISITS = 1,  // counting variants only
+    RT_CNT_TRI_TESTS = 2,    // counting variants only
+    RT_CNT_CAMERA = 3,       // camera segments (modes 0/1: pixels traced)
+    RT_CNT_CONTINUATION = 4, // extended mode only
+    RT_CNT_SHADOW = 5,       // extended mode only
+    // 6, 7: unused.  8-15: wave-level diagnostics of the counting variant of k_render_extended_sm, summed over waves (no other kernel
+    // writes them): transition passes, lanes served in them, node iterations, lanes active in them, leaf iterations, lanes active in them,
+    // cycles in transition phases, cycles in traversal phases
+    RT_CNT_DIAG = 8,
+    RT_CNT_SM_TRANSITION_PASSES = RT_CNT_DIAG,
+    RT_CNT_SM_TRANSITION_LANES = 9,
+    RT_CNT_SM_NODE_ITERS = 10,
+    RT_CNT_SM_NODE_LANES = 11,
+    RT_CNT_SM_LEAF_ITERS = 12,
+    RT_CNT_SM_LEAF_LANES = 13,
+    RT_CNT_SM_CYCLES_TRANSITION = 14,
+    RT_CNT_SM_CYCLES_TRAVERSAL = 15,
+    RT_CNT_N_DIAG = 8,
+    RT_CNT_SLOTS = 16
 };
 
 #endif

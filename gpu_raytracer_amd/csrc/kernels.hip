@@ -16,6 +16,7 @@
 
 #include <algorithm>
 
+#include "../../include/rt_hip.h"
 #include "device_common.h"
 
 using namespace rtdev;
@@ -58,10 +59,10 @@ __global__ __launch_bounds__(WAVE) void k_render_reference(DevScene sc, DevFrame
     if ((fr.channel_mask & 2u) && tg.chan[1]) reinterpret_cast<uint32_t*>(tg.chan[1])[pix] = (unorm8(color.y) << 8) | 0xFF000000u;
     if ((fr.channel_mask & 4u) && tg.chan[2]) reinterpret_cast<uint32_t*>(tg.chan[2])[pix] = (unorm8(color.z) << 16) | 0xFF000000u;
     if (COUNT && tg.counters) {
-        atomicAdd(&tg.counters[0], traced ? 1ull : 0ull);
-        atomicAdd(&tg.counters[1], (unsigned long long)cnt.nodes);
-        atomicAdd(&tg.counters[2], (unsigned long long)cnt.tris);
-        atomicAdd(&tg.counters[3], traced ? 1ull : 0ull);
+        atomicAdd(&tg.counters[RT_CNT_SEGMENTS], traced ? 1ull : 0ull);
+        atomicAdd(&tg.counters[RT_CNT_NODE_VISITS], (unsigned long long)cnt.nodes);
+        atomicAdd(&tg.counters[RT_CNT_TRI_TESTS], (unsigned long long)cnt.tris);
+        atomicAdd(&tg.counters[RT_CNT_CAMERA], traced ? 1ull : 0ull);
     }
 }
 
@@ -102,7 +103,7 @@ __device__ __forceinline__ V3 ext_trace_path(const DevScene& sc, const DevFrame&
     V3 radiance = v3(0.0f, 0.0f, 0.0f);
     V3 throughput = v3(1.0f, 1.0f, 1.0f);
     uint32_t channel = 3;
-    const bool shadows = (fr.flags & 2u) == 0;
+    const bool shadows = (fr.flags & RT_FLAG_NO_SHADOWS) == 0;
     for (uint32_t depth = 0;; depth++) {
         if (depth == 0) seg.camera++; else seg.continuation++;
         Hit hit = find_closest<COUNT>(sc, o, d, stack, cnt);
@@ -205,13 +206,13 @@ __global__ __launch_bounds__(WAVE) void k_render_extended(DevScene sc, DevFrame 
     unsigned long long c0 = wave_sum(seg.camera), c1 = wave_sum(seg.continuation), c2 = wave_sum(seg.shadow);
     unsigned long long n0 = COUNT ? wave_sum(cnt.nodes) : 0ull, n1 = COUNT ? wave_sum(cnt.tris) : 0ull;
     if (threadIdx.x == 0 && tg.counters) {
-        atomicAdd(&tg.counters[0], c0 + c1 + c2);
-        atomicAdd(&tg.counters[3], c0);
-        atomicAdd(&tg.counters[4], c1);
-        atomicAdd(&tg.counters[5], c2);
+        atomicAdd(&tg.counters[RT_CNT_SEGMENTS], c0 + c1 + c2);
+        atomicAdd(&tg.counters[RT_CNT_CAMERA], c0);
+        atomicAdd(&tg.counters[RT_CNT_CONTINUATION], c1);
+        atomicAdd(&tg.counters[RT_CNT_SHADOW], c2);
         if (COUNT) {
-            atomicAdd(&tg.counters[1], n0);
-            atomicAdd(&tg.counters[2], n1);
+            atomicAdd(&tg.counters[RT_CNT_NODE_VISITS], n0);
+            atomicAdd(&tg.counters[RT_CNT_TRI_TESTS], n1);
         }
     }
 }
@@ -250,7 +251,7 @@ __global__ __launch_bounds__(WAVE, RT_SM_MIN_WAVES) void k_render_extended_sm(De
     const uint4* __restrict__ nodes = reinterpret_cast<const uint4*>(sc.nodes);
     Counts cnt = {0u, 0u};
     SegCounts seg = {0u, 0u, 0u};
-    const bool shadows = (fr.flags & 2u) == 0;
+    const bool shadows = (fr.flags & RT_FLAG_NO_SHADOWS) == 0;
 
     // ---- per-lane path state ----
     uint32_t state = px.valid ? ST_NEW_SAMPLE : ST_DONE;
@@ -293,9 +294,7 @@ __global__ __launch_bounds__(WAVE, RT_SM_MIN_WAVES) void k_render_extended_sm(De
         state = finished ? (any ? ST_SHADOW_DONE : ST_CLOSEST_DONE) : ST_TRAVERSING;
     };
 
-    // diagnostics of the counting variant (wave-level, lane 0 accumulates): [8] transition passes, [9] lanes served,
-    // [10] node iterations, [11] lanes active in them, [12] leaf iterations, [13] lanes active, [14]/[15] cycles in
-    // transition / traversal phases
+    // diagnostics of the counting variant (wave-level, lane 0 accumulates): counters[RT_CNT_SM_*] (device_layout.h)
     unsigned long long dg_tp = 0, dg_tl = 0, dg_ni = 0, dg_nl = 0, dg_li = 0, dg_ll = 0, dg_ct = 0, dg_cv = 0;
     for (;;) {
         // =========================== transition phase ===========================
@@ -537,21 +536,21 @@ __global__ __launch_bounds__(WAVE, RT_SM_MIN_WAVES) void k_render_extended_sm(De
     unsigned long long c0 = wave_sum(seg.camera), c1 = wave_sum(seg.continuation), c2 = wave_sum(seg.shadow);
     unsigned long long n0 = COUNT ? wave_sum(cnt.nodes) : 0ull, n1 = COUNT ? wave_sum(cnt.tris) : 0ull;
     if (threadIdx.x == 0 && tg.counters) {
-        atomicAdd(&tg.counters[0], c0 + c1 + c2);
-        atomicAdd(&tg.counters[3], c0);
-        atomicAdd(&tg.counters[4], c1);
-        atomicAdd(&tg.counters[5], c2);
+        atomicAdd(&tg.counters[RT_CNT_SEGMENTS], c0 + c1 + c2);
+        atomicAdd(&tg.counters[RT_CNT_CAMERA], c0);
+        atomicAdd(&tg.counters[RT_CNT_CONTINUATION], c1);
+        atomicAdd(&tg.counters[RT_CNT_SHADOW], c2);
         if (COUNT) {
-            atomicAdd(&tg.counters[1], n0);
-            atomicAdd(&tg.counters[2], n1);
-            atomicAdd(&tg.counters[8], dg_tp);
-            atomicAdd(&tg.counters[9], dg_tl);
-            atomicAdd(&tg.counters[10], dg_ni);
-            atomicAdd(&tg.counters[11], dg_nl);
-            atomicAdd(&tg.counters[12], dg_li);
-            atomicAdd(&tg.counters[13], dg_ll);
-            atomicAdd(&tg.counters[14], dg_ct);
-            atomicAdd(&tg.counters[15], dg_cv);
+            atomicAdd(&tg.counters[RT_CNT_NODE_VISITS], n0);
+            atomicAdd(&tg.counters[RT_CNT_TRI_TESTS], n1);
+            atomicAdd(&tg.counters[RT_CNT_SM_TRANSITION_PASSES], dg_tp);
+            atomicAdd(&tg.counters[RT_CNT_SM_TRANSITION_LANES], dg_tl);
+            atomicAdd(&tg.counters[RT_CNT_SM_NODE_ITERS], dg_ni);
+            atomicAdd(&tg.counters[RT_CNT_SM_NODE_LANES], dg_nl);
+            atomicAdd(&tg.counters[RT_CNT_SM_LEAF_ITERS], dg_li);
+            atomicAdd(&tg.counters[RT_CNT_SM_LEAF_LANES], dg_ll);
+            atomicAdd(&tg.counters[RT_CNT_SM_CYCLES_TRANSITION], dg_ct);
+            atomicAdd(&tg.counters[RT_CNT_SM_CYCLES_TRAVERSAL], dg_cv);
         }
     }
 }
@@ -609,12 +608,11 @@ hipError_t launch_render_reference(const DevScene& sc, const DevFrame& fr, const
     return hipGetLastError();
 }
 
-hipError_t launch_render_extended(const DevScene& sc, const DevFrame& fr, const DevTargets& tg, bool counters, hipStream_t stream) {
+hipError_t launch_render_extended(const DevScene& sc, const DevFrame& fr, const DevTargets& tg, FrameKernel kernel, bool counters, hipStream_t stream) {
     uint32_t n_tiles = fr.n_owned_tiles;
     if (n_tiles == 0) return hipSuccess;
     dim3 grid(n_tiles * blocks_per_tile(fr.tile_size)), block(WAVE);
-    const bool v1 = (fr.flags & 4u) != 0; // RT_FLAG_KERNEL_V1: nested loops; otherwise (RT_FLAG_KERNEL_SM) the state machine
-    if (v1) {
+    if (kernel != FrameKernel::MEGAKERNEL_SM) { // the nested loops (also the one-pass kernel)
         if (counters)
             hipLaunchKernelGGL(k_render_extended<true>, grid, block, lds_bytes(sc), stream, sc, fr, tg);
         else

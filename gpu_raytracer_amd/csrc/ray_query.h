@@ -9,7 +9,7 @@
 namespace rt {
 
 // n rt_ray records (32 bytes, 16-byte aligned) at `rays` -> n rt_hit records (16 bytes) at `out`, or n bytes (0/1) when any_hit.
-// counters != null (the counting variant): counters[1] += node visits, counters[2] += triangle tests.  Asynchronous on `stream`.
+// counters != null (the counting variant): counters[RT_CNT_NODE_VISITS] += node visits, counters[RT_CNT_TRI_TESTS] += triangle tests.  Asynchronous on `stream`.
 hipError_t launch_ray_query(const DevScene& sc, const void* rays, void* out, uint32_t n, bool any_hit, unsigned long long* counters,
                             hipStream_t stream);
 

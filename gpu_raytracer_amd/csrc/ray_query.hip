@@ -53,8 +53,8 @@ __global__ __launch_bounds__(WAVE) void k_rq_trace(DevScene sc, const float4* __
         reinterpret_cast<uint4*>(out)[i] = make_uint4(__float_as_uint(hit.t), __float_as_uint(uv[0]), __float_as_uint(uv[1]), hit.prim);
     }
     if (COUNT) {
-        atomicAdd(&counters[1], (unsigned long long)cnt.nodes);
-        atomicAdd(&counters[2], (unsigned long long)cnt.tris);
+        atomicAdd(&counters[RT_CNT_NODE_VISITS], (unsigned long long)cnt.nodes);
+        atomicAdd(&counters[RT_CNT_TRI_TESTS], (unsigned long long)cnt.tris);
     }
 }
 

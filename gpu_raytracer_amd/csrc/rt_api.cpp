@@ -64,13 +64,11 @@ struct DeviceState {
     rt::WfBuffers wf{};                                    // wavefront pipeline state (extended mode)
     rt::WfBuffers wf2{};                                   // ... of the second lane (its own path state, queues and counters; the pixel sums are shared)
     std::vector<void*> wf2_allocs;
-    bool used_wavefront = false;
-    bool used_two_lanes = false;
+    bool used_two_lanes = false; // the last pipeline frame ran on two lanes (its allocation is reused by a frame of the same shape)
     uint32_t wf_lights = 0;
     uint32_t wf_spp = 0; // spp the current wavefront allocation was sized for
     std::vector<hipEvent_t> stage_events; // RT_FLAG_STAGE_TIMES: event pairs around the launches of the dominant stage kernel
     uint32_t stage_events_used = 0;
-    bool wf_beams_off = false; // this frame walks the tree for its camera segments too (RT_FLAG_NO_BEAMS)
     std::vector<void*> wf_allocs;
     void* rq_in = nullptr;  // ray queries: staging of host batches (rays in, hit records / bytes out), grown on demand
     void* rq_out = nullptr;
@@ -89,7 +87,7 @@ struct rt_ctx {
     rt_stats stats{};
     uint32_t frame_w = 0, frame_h = 0, frame_tile = RT_TILE_SIZE, frame_tiles_x = 0, frame_tiles_y = 0;
     bool frame_valid = false;
-    unsigned long long diag[8] = {0}; // diagnostics of the counting kernel variant (rt_debug_counters)
+    unsigned long long diag[RT_CNT_N_DIAG] = {0}; // diagnostics of the counting kernel variant (rt_debug_counters)
     unsigned long long grid_diag[2] = {0}; // ... of the light grids: shadow segments they answered, list entries read
     double stage_ms[2] = {0.0, 0.0};       // RT_FLAG_STAGE_TIMES: [0] sum of the k_wf_shadow_grid launch durations of the last frame (device 0), [1] launches
     int fail_upload_at = -1;          // test hook: the next scene upload fails before its k-th device array (rt_debug_fail_upload)
@@ -569,7 +567,7 @@ int ensure_wavefront(rt_ctx* ctx, DeviceState& d, uint32_t n_blocks, uint32_t ba
     w.q_ext_cap = (uint32_t)ext_slots;
     w.q_shadow_cap = (uint32_t)shadow_slots;
     HIPCHK(ctx, alloc((void**)&w.counters, rt::WF_N_COUNTERS * sizeof(uint32_t)));
-    HIPCHK(ctx, alloc((void**)&w.totals, 16 * sizeof(unsigned long long)));
+    HIPCHK(ctx, alloc((void**)&w.totals, rt::WF_N_TOTALS * sizeof(unsigned long long)));
     if (lane == 0) HIPCHK(ctx, alloc((void**)&w.accum, (size_t)std::max(1u, n_blocks) * 64 * 16));
     else w.accum = d.wf.accum; // one running sum per pixel: the lanes' resolves are ordered by events
     if (lane == 0) { // the camera beams of the frame: per block a leaf list, built once per frame and read by both lanes
@@ -652,129 +650,306 @@ int sync_pending(rt_ctx* ctx) {
     return RT_OK;
 }
 
+// The tiles device j (of nd) takes of a frame: the context owns the tiles i with i % world == rank (rt_hip.h); its device j takes every
+// nd-th of those.
+void assign_tiles(DevFrame& f, DeviceState& d, uint32_t world, uint32_t rank, size_t nd, size_t j) {
+    const uint32_t total_tiles = f.tiles_x * f.tiles_y, stride = world * (uint32_t)nd, first = rank + world * (uint32_t)j;
+    f.tile_first = d.tile_first = first;
+    f.tile_stride = d.tile_stride = stride;
+    f.n_owned_tiles = d.n_owned = first < total_tiles ? (total_tiles - first + stride - 1) / stride : 0;
+}
+
+struct KernelChoice {
+    rt::FrameKernel kernel;
+    bool fallback; // the default (the pipeline) was asked for and the frame did not fit it: RT_STAT_MEGAKERNEL_FALLBACK
+};
+
+// Which kernel renders one device's share `f` of a frame.  The flags choose first.  Primary rays only over a tiny tree (BASELINE
+// configs[1]: Cornell, 12 triangles, max_bounces 0): the queue pipeline would move 132 bytes of path state per sample through six
+// kernels for a closest hit that costs a few dozen instructions (measured 15.9 ms and 46.7 GB of HBM traffic per 1080p 64-spp frame);
+// the nested-loop kernel loops the pixel's samples in registers, traces the closest hit and the per-light shadow segments inline and
+// stores the pixel once: 2.6 ms, same bits (the per-sample order is fixed by the CPU statement).  SURVEY 7 step 6, shader/src/lib.rs:86-88
+// (one write per pixel).  RT_FLAG_KERNEL_PIPELINE keeps the pipeline.  The pipeline needs one visibility bit per light and every path
+// slot of ONE sample per owned pixel block addressable; anything else (more than 32 lights, a single device's share beyond ~134 M
+// pixels) takes the state-machine megakernel.
+KernelChoice choose_kernel(const rt_ctx* ctx, const DevFrame& f) {
+    using rt::FrameKernel;
+    const DevScene& sc = ctx->scene_counts;
+    if (f.mode != RT_MODE_EXTENDED) return {FrameKernel::REFERENCE, false};
+    if (f.flags & RT_FLAG_KERNEL_V1) return {FrameKernel::MEGAKERNEL_V1, false};
+    if (f.flags & RT_FLAG_KERNEL_SM) return {FrameKernel::MEGAKERNEL_SM, false};
+    if (!(f.flags & RT_FLAG_KERNEL_PIPELINE) && f.max_bounce == 0 && sc.n_nodes <= single_pass_max_nodes()) return {FrameKernel::SINGLE_PASS, false};
+    const bool fits = sc.n_lights <= RT_WF_MAX_LIGHTS && (uint64_t)f.n_owned_tiles * rt::blocks_per_tile(f.tile_size) * 64u <= wavefront_max_paths(sc.n_lights);
+    return fits ? KernelChoice{FrameKernel::PIPELINE, false} : KernelChoice{FrameKernel::MEGAKERNEL_SM, true};
+}
+
+// One device's walk through the batches and bounces of its share of a pipeline frame (setup_pipeline), one step at a time (run_frame).
+struct WfRun {
+    enum Phase { GENERATE, BOUNCE, RESOLVE, DONE };
+    Phase phase = DONE;    // (from the start for a device whose share took another kernel)
+    bool pipeline = false; // the device's share takes the pipeline
+    size_t dev = 0;
+    DevFrame f{};
+    DevScene dsc{};
+    uint32_t batch = 1, first = 0, j = 0, it = 0, alive = 0; // samples per batch, first sample and number of the batch, bounce, live paths
+    bool two = false;   // batches alternate between the device's two lanes
+    bool beams = false; // camera segments test their block's beam list (else they walk the tree)
+    hipStream_t poll_stream = nullptr;
+};
+
+// Pipeline setup of one device's share `f` of a frame: light grids, lanes, batch, path-state allocation, the camera beams and the start of
+// the second lane.  The launches of the batches follow in run_frame: a device's every-8-bounces read-back of its live paths must not hold
+// back the launches of the next device.
+int setup_pipeline(rt_ctx* ctx, size_t j, const DevFrame& f, WfRun& r) {
+    DeviceState& d = ctx->devs[j];
+    const uint32_t n_lights = ctx->scene_counts.n_lights;
+    if (!(f.flags & (RT_FLAG_NO_SHADOW_GRID | RT_FLAG_NO_SHADOWS))) // the first frame that traces shadow segments through the pipeline builds the light grids
+        if (int rc = ensure_grids(ctx, d)) return rc;
+    const uint32_t n_blocks = f.n_owned_tiles * rt::blocks_per_tile(f.tile_size);
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(ctx, hipMemGetInfo(&free_b, &total_b));
+    const char* lanes_env = std::getenv("RT_WF_LANES"); // (read per frame: tests and A/B runs switch it)
+    // by default only for frames whose shadow stage runs on light grids: with the BVH walk both big stages are VALU-bound and sharing
+    // the chip gains nothing (bistro-like 4K share: 136.7 ms on two lanes against 127.3 on one)
+    bool two_lanes_on = lanes_env ? std::atoi(lanes_env) >= 2 : (RT_WF_LANES_DEFAULT >= 2 && d.grids != nullptr && !(f.flags & RT_FLAG_NO_SHADOW_GRID));
+    // ... and not for a frame of long paths that fits ONE batch: two lanes would cut it in two, every launch would come twice, and
+    // beyond four bounces most launches serve few paths and cost their latency whatever they serve (bistro-like 4K share, 64 spp,
+    // 8 bounces, 66 M paths: one batch on one lane 105.3 ms, two of 32 samples on two lanes 116.7; 4 bounces: the two lanes win)
+    if (!lanes_env && two_lanes_on && f.max_bounce > 4 && wavefront_batch(n_blocks, f.spp, n_lights, free_b, false) >= f.spp) two_lanes_on = false;
+    const uint32_t batch = d.wf.n_blocks == n_blocks && d.wf_spp == f.spp && d.wf.batch && d.wf_lights >= n_lights && d.used_two_lanes == (two_lanes_on && f.spp >= 2) ? d.wf.batch // same frame shape as last time: keep the allocation
+                                                                                               : wavefront_batch(n_blocks, f.spp, n_lights, two_lanes_on ? free_b / 2 : free_b, two_lanes_on);
+    d.wf_spp = f.spp;
+    // Two lanes (RT_WF_LANES=2, the default when a frame has two or more batches): batches alternate between two streams with their own
+    // path state, so that one batch's shadow stage (bound by HBM bandwidth since the light grids) runs beside the other's closest-hit
+    // traversal (bound by VALU issue).  The pixel sums are added in batch order: a resolve waits for the previous batch's.
+    const uint32_t n_batches = (f.spp + batch - 1) / batch;
+    const bool two = two_lanes_on && n_batches >= 2 && d.stream2;
+    if (int rc = ensure_wavefront(ctx, d, n_blocks, batch, n_lights, two)) return rc;
+    HIPCHK(ctx, hipMemsetAsync(d.wf.totals, 0, rt::WF_N_TOTALS * sizeof(unsigned long long), d.stream));
+    HIPCHK(ctx, hipEventRecord(d.ev0, d.stream)); // re-record: allocation above is not part of the kernel time
+    // camera beams: on by default, RT_WF_BEAMS=0 (development knob) or RT_FLAG_NO_BEAMS walks the tree for every camera segment
+    const char* be = std::getenv("RT_WF_BEAMS");
+    const bool beams = !(f.flags & RT_FLAG_NO_BEAMS) && (be ? std::atoi(be) != 0 : true);
+    if (beams) HIPCHK(ctx, rt::wf_beams(scene_for(ctx, d), f, d.wf, d.stream));
+    if (two) {
+        HIPCHK(ctx, hipEventRecord(d.ev_start, d.stream));
+        HIPCHK(ctx, hipStreamWaitEvent(d.stream2, d.ev_start, 0));
+        HIPCHK(ctx, hipMemsetAsync(d.wf2.totals, 0, rt::WF_N_TOTALS * sizeof(unsigned long long), d.stream2));
+    }
+    d.wf.grids = d.wf2.grids = (f.flags & RT_FLAG_NO_SHADOW_GRID) ? nullptr : d.grids;
+    const char* pe = std::getenv("RT_WF_PROBE");
+    d.wf.probe = d.wf2.probe = pe ? (uint32_t)std::atoi(pe) : 0u;
+    d.used_two_lanes = two;
+    r = WfRun{};
+    r.phase = WfRun::GENERATE;
+    r.pipeline = true;
+    r.dev = j;
+    r.f = f;
+    r.dsc = scene_for(ctx, d);
+    r.batch = batch;
+    r.two = two;
+    r.beams = beams;
+    return RT_OK;
+}
+
+// The lane of r's current batch: its buffers (a copy: the kernels take them by value) and its stream.
+struct WfLane { rt::WfBuffers w; hipStream_t st; };
+WfLane lane_of(const DeviceState& d, const WfRun& r) {
+    const bool second = r.two && (r.j & 1u);
+    WfLane l{second ? d.wf2 : d.wf, second ? d.stream2 : d.stream};
+    if (!r.beams) l.w.beam_count = nullptr;
+    return l;
+}
+uint32_t batch_samples(const WfRun& r) { return std::min(r.batch, r.f.spp - r.first); }
+
+// One step per phase of a pipeline walk, on the lane `l` of its current batch (the caller has made r's device current).
+// GENERATE: the paths of the current batch.
+int wf_step_generate(rt_ctx* ctx, WfRun& r, const WfLane& l) {
+    HIPCHK(ctx, rt::wf_generate(r.dsc, r.f, l.w, r.first, batch_samples(r), l.st));
+    r.it = 0;
+    r.phase = WfRun::BOUNCE;
+    return RT_OK;
+}
+
+// BOUNCE: one bounce of the current batch.  After every 8th the live paths are read back and the device goes on `polls`: run_frame waits
+// for them when every device has its next launches queued, and a batch of long paths stops as soon as every path has ended.
+int wf_step_bounce(rt_ctx* ctx, DeviceState& d, WfRun& r, const WfLane& l, bool counters, std::vector<WfRun*>& polls) {
+    hipEvent_t* gev = nullptr;
+    if ((r.f.flags & RT_FLAG_STAGE_TIMES) && r.dev == 0 && rt::wf_runs_shadow_grid(r.f, l.w)) { // (bench.py: the dominant kernel's launch durations, measured live)
+        if (d.stage_events.size() < (size_t)d.stage_events_used + 2) {
+            hipEvent_t a = nullptr, b = nullptr;
+            HIPCHK(ctx, hipEventCreate(&a));
+            HIPCHK(ctx, hipEventCreate(&b));
+            d.stage_events.push_back(a);
+            d.stage_events.push_back(b);
+        }
+        gev = d.stage_events.data() + d.stage_events_used;
+        d.stage_events_used += 2;
+    }
+    HIPCHK(ctx, rt::wf_bounce(r.dsc, r.f, l.w, r.it, batch_samples(r), counters, l.st, gev));
+    if (r.it >= r.f.max_bounce) r.phase = WfRun::RESOLVE;
+    else if ((r.it & 7u) == 7u) {
+        HIPCHK(ctx, hipMemcpyAsync(&r.alive, l.w.counters + rt::WF_EXT_COUNT, 4, hipMemcpyDeviceToHost, l.st));
+        r.poll_stream = l.st;
+        polls.push_back(&r);
+    } else r.it++;
+    return RT_OK;
+}
+
+// RESOLVE: the batch's samples into the pixel sums, in batch order; after the last batch the frame ends when both lanes have.
+int wf_step_resolve(rt_ctx* ctx, DeviceState& d, WfRun& r, const WfLane& l) {
+    const uint32_t n = batch_samples(r);
+    if (r.two && r.j > 0) HIPCHK(ctx, hipStreamWaitEvent(l.st, d.ev_res[(r.j - 1u) & 1u], 0));
+    HIPCHK(ctx, rt::wf_resolve(r.f, l.w, targets_for(d), n, r.first == 0, r.first + n >= r.f.spp, l.st));
+    if (r.two) HIPCHK(ctx, hipEventRecord(d.ev_res[r.j & 1u], l.st));
+    r.first += r.batch;
+    r.j++;
+    if (r.first < r.f.spp) {
+        r.phase = WfRun::GENERATE;
+        return RT_OK;
+    }
+    if (r.two) {
+        HIPCHK(ctx, hipEventRecord(d.ev_join, d.stream2));
+        HIPCHK(ctx, hipStreamWaitEvent(d.stream, d.ev_join, 0));
+    }
+    HIPCHK(ctx, hipEventRecord(d.ev1, d.stream));
+    r.phase = WfRun::DONE;
+    return RT_OK;
+}
+
+// What a frame took and counted, over the devices that rendered it.
+struct FrameTotals {
+    double kernel_ms = 0.0;
+    uint64_t pixels = 0;
+    unsigned long long segments = 0, camera = 0, continuation = 0, shadow = 0, node_visits = 0, tri_tests = 0;
+    unsigned long long diag[RT_CNT_N_DIAG] = {0};          // rt_debug_counters
+    unsigned long long grid_answered = 0, grid_entries = 0; // rt_debug_shadow_grid
+};
+
+// DevTargets::counters of one device (reference-mode kernels, megakernels).
+void add_counters(FrameTotals& t, const unsigned long long (&c)[RT_CNT_SLOTS]) {
+    t.segments += c[RT_CNT_SEGMENTS], t.camera += c[RT_CNT_CAMERA], t.continuation += c[RT_CNT_CONTINUATION], t.shadow += c[RT_CNT_SHADOW];
+    t.node_visits += c[RT_CNT_NODE_VISITS], t.tri_tests += c[RT_CNT_TRI_TESTS];
+    for (int k = 0; k < RT_CNT_N_DIAG; k++) t.diag[k] += c[RT_CNT_DIAG + k];
+}
+
+// WfBuffers::totals of a device's second lane into those of its first.
+void merge_lanes(unsigned long long (&t)[rt::WF_N_TOTALS], const unsigned long long (&t2)[rt::WF_N_TOTALS]) {
+    for (int k = 0; k < rt::WF_N_TOTALS; k++) t[k] = k == rt::WF_TOTAL_STACK_MAX ? std::max(t[k], t2[k]) : t[k] + t2[k];
+}
+
+// WfBuffers::totals of one device (the pipeline).  Its diagnostics go to rt_debug_counters in slot order, the high-water mark first.
+int add_totals(rt_ctx* ctx, FrameTotals& t, const unsigned long long (&w)[rt::WF_N_TOTALS]) {
+    t.segments += w[rt::WF_TOTAL_CAMERA] + w[rt::WF_TOTAL_CONTINUATION] + w[rt::WF_TOTAL_SHADOW];
+    t.camera += w[rt::WF_TOTAL_CAMERA], t.continuation += w[rt::WF_TOTAL_CONTINUATION], t.shadow += w[rt::WF_TOTAL_SHADOW];
+    t.node_visits += w[rt::WF_TOTAL_NODE_VISITS], t.tri_tests += w[rt::WF_TOTAL_TRI_TESTS];
+    if (w[rt::WF_TOTAL_ERROR] != 0)
+        return ctx->fail(RT_ERR_INTERNAL, "wavefront pipeline: %s (frame discarded)",
+                         (w[rt::WF_TOTAL_ERROR] & 2ull) ? "a traversal stack grew beyond the depth the tree reports" : "a queue reservation exceeded its allocation");
+    t.diag[0] = std::max(t.diag[0], w[rt::WF_TOTAL_STACK_MAX]);
+    for (int k = 1; k < RT_CNT_N_DIAG; k++) t.diag[k] += w[rt::WF_TOTAL_STACK_MAX + k];
+    t.grid_answered += w[rt::WF_TOTAL_GRID_ANSWERED], t.grid_entries += w[rt::WF_TOTAL_GRID_ENTRIES];
+    return RT_OK;
+}
+
+// Pixels of device d's share of frame fr: the explicit tile of a dispatch, or the tiles the device owns.
+uint64_t share_pixels(const DevFrame& fr, const DeviceState& d) {
+    if (fr.single_tile)
+        return (uint64_t)std::min(fr.tile_w, fr.width - std::min(fr.width, fr.tile_off_x)) * std::min(fr.tile_h, fr.height - std::min(fr.height, fr.tile_off_y));
+    uint64_t pixels = 0;
+    for (uint32_t k = 0; k < d.n_owned; k++) {
+        const uint32_t tile = d.tile_first + k * d.tile_stride, ty = tile / fr.tiles_x, tx = tile % fr.tiles_x;
+        pixels += (uint64_t)std::min(fr.tile_size, fr.width - tx * fr.tile_size) * std::min(fr.tile_size, fr.height - ty * fr.tile_size);
+    }
+    return pixels;
+}
+
+// Waits for device j's share of a frame and adds its kernel time, stage times, counters and pixels to `t`.
+int collect_device(rt_ctx* ctx, size_t j, const DevFrame& fr, bool counters, const WfRun& r, FrameTotals& t) {
+    DeviceState& d = ctx->devs[j];
+    HIPCHK(ctx, hipSetDevice(d.device));
+    HIPCHK(ctx, hipStreamSynchronize(d.stream));
+    float ms = 0.0f;
+    HIPCHK(ctx, hipEventElapsedTime(&ms, d.ev0, d.ev1));
+    t.kernel_ms = std::max(t.kernel_ms, (double)ms);
+    if (j == 0 && d.stage_events_used) {
+        if (d.stream2) HIPCHK(ctx, hipStreamSynchronize(d.stream2));
+        for (uint32_t k = 0; k + 1 < d.stage_events_used; k += 2) {
+            float sm = 0.0f;
+            HIPCHK(ctx, hipEventElapsedTime(&sm, d.stage_events[k], d.stage_events[k + 1]));
+            ctx->stage_ms[0] += sm;
+            ctx->stage_ms[1] += 1.0;
+        }
+    }
+    if (r.pipeline) {
+        unsigned long long w[rt::WF_N_TOTALS];
+        HIPCHK(ctx, hipMemcpy(w, d.wf.totals, sizeof w, hipMemcpyDeviceToHost));
+        if (r.two) {
+            unsigned long long w2[rt::WF_N_TOTALS];
+            HIPCHK(ctx, hipMemcpy(w2, d.wf2.totals, sizeof w2, hipMemcpyDeviceToHost));
+            merge_lanes(w, w2);
+        }
+        if (int rc = add_totals(ctx, t, w)) return rc;
+    } else if (counters || fr.mode == RT_MODE_EXTENDED) {
+        unsigned long long c[RT_CNT_SLOTS];
+        HIPCHK(ctx, hipMemcpy(c, d.counters, sizeof c, hipMemcpyDeviceToHost));
+        add_counters(t, c);
+    }
+    t.pixels += share_pixels(fr, d);
+    return RT_OK;
+}
+
+// rt_stats (and what rt_debug_counters / rt_debug_shadow_grid report) of a frame from its totals.
+void finish_frame(rt_ctx* ctx, const DevFrame& fr, bool counters, const FrameTotals& t, uint32_t stat_flags, double w0) {
+    rt_stats& st = ctx->stats;
+    st.pixels = t.pixels;
+    if (fr.mode == RT_MODE_EXTENDED) { // segments counted on the device
+        st.rays = t.segments, st.primary_rays = t.camera, st.continuation_rays = t.continuation, st.shadow_rays = t.shadow;
+    } else {
+        const bool traced = fr.mode == RT_MODE_LEGACY || fr.cur_bounce <= fr.max_bounce;
+        st.rays = traced ? t.pixels : 0; // modes 0/1: one segment per pixel
+        st.primary_rays = st.rays;
+        st.continuation_rays = st.shadow_rays = 0;
+    }
+    st.node_visits = counters ? t.node_visits : 0;
+    st.tri_tests = counters ? t.tri_tests : 0;
+    for (int k = 0; k < RT_CNT_N_DIAG; k++) ctx->diag[k] = counters ? t.diag[k] : 0;
+    ctx->grid_diag[0] = counters ? t.grid_answered : 0, ctx->grid_diag[1] = counters ? t.grid_entries : 0;
+    st.kernel_ms = t.kernel_ms, st.wall_ms = now_ms() - w0, st.flags = stat_flags;
+}
+
 // Launch one frame (or one explicit tile) on every device and wait.
 int run_frame(rt_ctx* ctx, DevFrame fr, bool counters, uint32_t world, uint32_t rank, bool single_tile) {
-    double w0 = now_ms();
-    if (!single_tile || counters) {
-        int rcp = sync_pending(ctx);
-        if (rcp != RT_OK) return rcp;
-    }
-    size_t nd = single_tile ? 1 : ctx->devs.size();
-    uint32_t total_tiles = fr.tiles_x * fr.tiles_y;
-    bool fallback = false; // the extended mode was asked for its default (queue) pipeline and got the megakernel
-    bool single = false;   // ... took the one-pass kernel by rule (primary rays only, tiny tree)
-    struct WfRun { // one device's walk through the batches and bounces of its share of a wavefront-pipeline frame
-        enum Phase { GENERATE, BOUNCE, RESOLVE, DONE };
-        size_t dev = 0;
-        DevFrame f{};
-        DevScene dsc{};
-        uint32_t batch = 1, first = 0, j = 0, it = 0, alive = 0;
-        bool two = false;
-        Phase phase = GENERATE;
-        hipStream_t poll_stream = nullptr;
-    };
-    std::vector<WfRun> runs;
-    runs.reserve(nd); // (polls hold pointers into it)
+    const double w0 = now_ms();
+    if (!single_tile || counters)
+        if (int rc = sync_pending(ctx)) return rc;
+    const size_t nd = single_tile ? 1 : ctx->devs.size();
+    std::vector<WfRun> runs(nd); // one per device (polls hold pointers into it)
+    uint32_t stat_flags = 0;
     for (size_t j = 0; j < nd; j++) ctx->devs[j].stage_events_used = 0;
     ctx->stage_ms[0] = ctx->stage_ms[1] = 0.0;
     for (size_t j = 0; j < nd; j++) {
         DeviceState& d = ctx->devs[j];
         HIPCHK(ctx, hipSetDevice(d.device));
-        int rc = ensure_targets(ctx, d, fr.width, fr.height);
-        if (rc != RT_OK) return rc;
+        if (int rc = ensure_targets(ctx, d, fr.width, fr.height)) return rc;
         DevFrame f = fr;
-        if (!single_tile) {
-            // the context owns the tiles i with i % world == rank (rt_hip.h); its device j takes every nd-th of those
-            uint32_t stride = world * (uint32_t)nd, first = rank + world * (uint32_t)j;
-            f.tile_first = first;
-            f.tile_stride = stride;
-            f.n_owned_tiles = first < total_tiles ? (total_tiles - first + stride - 1) / stride : 0;
-            d.tile_first = first;
-            d.tile_stride = stride;
-            d.n_owned = f.n_owned_tiles;
-        }
-        HIPCHK(ctx, hipMemsetAsync(d.counters, 0, 16 * sizeof(unsigned long long), d.stream));
+        if (!single_tile) assign_tiles(f, d, world, rank, nd, j);
+        HIPCHK(ctx, hipMemsetAsync(d.counters, 0, RT_CNT_SLOTS * sizeof(unsigned long long), d.stream));
         HIPCHK(ctx, hipEventRecord(d.ev0, d.stream));
-        // the queue-based pipeline needs one visibility bit per light and every path slot of ONE sample per owned pixel block
-        // addressable; anything else (more than 32 lights, a single device's share beyond ~134 M pixels) takes the megakernel
-        // Primary rays only over a tiny tree (BASELINE configs[1]: Cornell, 12 triangles, max_bounces 0): the queue pipeline would move
-        // 132 bytes of path state per sample through six kernels for a closest hit that costs a few dozen instructions (measured 15.9 ms
-        // and 46.7 GB of HBM traffic per 1080p 64-spp frame); the nested-loop kernel loops the pixel's samples in registers, traces the
-        // closest hit and the per-light shadow segments inline and stores the pixel once: 2.6 ms, same bits (the per-sample order is
-        // fixed by the CPU statement).  SURVEY 7 step 6, shader/src/lib.rs:86-88 (one write per pixel).  RT_FLAG_KERNEL_PIPELINE keeps the pipeline.
-        const bool single_pass = f.mode == RT_MODE_EXTENDED && !(f.flags & (RT_FLAG_KERNEL_V1 | RT_FLAG_KERNEL_SM | RT_FLAG_KERNEL_PIPELINE)) && f.max_bounce == 0 &&
-                                 ctx->scene_counts.n_nodes <= single_pass_max_nodes();
-        if (single_pass) {
-            single = true;
-            f.flags |= RT_FLAG_KERNEL_V1; // (launch_render_extended picks its kernel by this bit: the nested loops, not the state machine)
+        const KernelChoice k = choose_kernel(ctx, f);
+        stat_flags |= (k.fallback ? RT_STAT_MEGAKERNEL_FALLBACK : 0u) | (k.kernel == rt::FrameKernel::SINGLE_PASS ? RT_STAT_SINGLE_PASS : 0u);
+        if (k.kernel == rt::FrameKernel::PIPELINE) {
+            if (int rc = setup_pipeline(ctx, j, f, runs[j])) return rc;
+            continue;
         }
-        const bool wavefront = f.mode == RT_MODE_EXTENDED && !(f.flags & (RT_FLAG_KERNEL_V1 | RT_FLAG_KERNEL_SM)) && !single_pass &&
-                               ctx->scene_counts.n_lights <= RT_WF_MAX_LIGHTS &&
-                               (uint64_t)f.n_owned_tiles * rt::blocks_per_tile(f.tile_size) * 64u <= wavefront_max_paths(ctx->scene_counts.n_lights);
-        if (f.mode == RT_MODE_EXTENDED && !wavefront && !single_pass && !(f.flags & (RT_FLAG_KERNEL_V1 | RT_FLAG_KERNEL_SM))) fallback = true;
-        if (wavefront) {
-            if (!(f.flags & (RT_FLAG_NO_SHADOW_GRID | RT_FLAG_NO_SHADOWS))) { // the first frame that traces shadow segments through the pipeline builds the light grids
-                rc = ensure_grids(ctx, d);
-                if (rc != RT_OK) return rc;
-            }
-            const uint32_t n_blocks = f.n_owned_tiles * rt::blocks_per_tile(f.tile_size);
-            size_t free_b = 0, total_b = 0;
-            HIPCHK(ctx, hipMemGetInfo(&free_b, &total_b));
-            const char* lanes_env = std::getenv("RT_WF_LANES"); // (read per frame: tests and A/B runs switch it)
-            // by default only for frames whose shadow stage runs on light grids: with the BVH walk both big stages are VALU-bound and sharing
-            // the chip gains nothing (bistro-like 4K share: 136.7 ms on two lanes against 127.3 on one)
-            bool two_lanes_on = lanes_env ? std::atoi(lanes_env) >= 2 : (RT_WF_LANES_DEFAULT >= 2 && d.grids != nullptr && !(f.flags & RT_FLAG_NO_SHADOW_GRID));
-            // ... and not for a frame of long paths that fits ONE batch: two lanes would cut it in two, every launch would come twice, and
-            // beyond four bounces most launches serve few paths and cost their latency whatever they serve (bistro-like 4K share, 64 spp,
-            // 8 bounces, 66 M paths: one batch on one lane 105.3 ms, two of 32 samples on two lanes 116.7; 4 bounces: the two lanes win)
-            if (!lanes_env && two_lanes_on && f.max_bounce > 4 && wavefront_batch(n_blocks, f.spp, ctx->scene_counts.n_lights, free_b, false) >= f.spp) two_lanes_on = false;
-            const uint32_t batch = d.wf.n_blocks == n_blocks && d.wf_spp == f.spp && d.wf.batch && d.wf_lights >= ctx->scene_counts.n_lights && d.used_two_lanes == (two_lanes_on && f.spp >= 2) ? d.wf.batch // same frame shape as last time: keep the allocation
-                                                                                               : wavefront_batch(n_blocks, f.spp, ctx->scene_counts.n_lights, two_lanes_on ? free_b / 2 : free_b, two_lanes_on);
-            d.wf_spp = f.spp;
-            // Two lanes (RT_WF_LANES=2, the default when a frame has two or more batches): batches alternate between two streams with their own
-            // path state, so that one batch's shadow stage (bound by HBM bandwidth since the light grids) runs beside the other's closest-hit
-            // traversal (bound by VALU issue).  The pixel sums are added in batch order: a resolve waits for the previous batch's.
-            const uint32_t n_batches = (f.spp + batch - 1) / batch;
-            const bool two = two_lanes_on && n_batches >= 2 && d.stream2;
-            rc = ensure_wavefront(ctx, d, n_blocks, batch, ctx->scene_counts.n_lights, two);
-            if (rc != RT_OK) return rc;
-            HIPCHK(ctx, hipMemsetAsync(d.wf.totals, 0, 16 * sizeof(unsigned long long), d.stream));
-            HIPCHK(ctx, hipEventRecord(d.ev0, d.stream)); // re-record: allocation above is not part of the kernel time
-            { // camera beams: on by default, RT_WF_BEAMS=0 (development knob) or RT_FLAG_NO_BEAMS walks the tree for every camera segment
-                const char* be = std::getenv("RT_WF_BEAMS");
-                const bool beams = !(f.flags & RT_FLAG_NO_BEAMS) && (be ? std::atoi(be) != 0 : true);
-                d.wf_beams_off = !beams;
-                if (beams) HIPCHK(ctx, rt::wf_beams(scene_for(ctx, d), f, d.wf, d.stream));
-            }
-            if (two) {
-                HIPCHK(ctx, hipEventRecord(d.ev_start, d.stream));
-                HIPCHK(ctx, hipStreamWaitEvent(d.stream2, d.ev_start, 0));
-                HIPCHK(ctx, hipMemsetAsync(d.wf2.totals, 0, 16 * sizeof(unsigned long long), d.stream2));
-            }
-            d.wf.grids = d.wf2.grids = (f.flags & RT_FLAG_NO_SHADOW_GRID) ? nullptr : d.grids;
-            { const char* pe = std::getenv("RT_WF_PROBE"); d.wf.probe = d.wf2.probe = pe ? (uint32_t)std::atoi(pe) : 0u; }
-            // the launches themselves follow below, one step per device in turn (WfRun): a device's every-8-bounces read-back of its live
-            // paths must not hold back the launches of the next device (it was inside this loop)
-            WfRun r;
-            r.dev = j;
-            r.f = f;
-            r.dsc = scene_for(ctx, d);
-            r.batch = batch;
-            r.two = two;
-            runs.push_back(r);
-            d.used_two_lanes = two;
-            d.used_wavefront = true;
-        } else if (f.mode == RT_MODE_EXTENDED) {
-            d.used_wavefront = false;
-            HIPCHK(ctx, rt::launch_render_extended(scene_for(ctx, d), f, targets_for(d), counters, d.stream));
-        } else
-            HIPCHK(ctx, rt::launch_render_reference(scene_for(ctx, d), f, targets_for(d), counters, d.stream));
-        if (!wavefront) HIPCHK(ctx, hipEventRecord(d.ev1, d.stream));
+        if (k.kernel == rt::FrameKernel::REFERENCE) HIPCHK(ctx, rt::launch_render_reference(scene_for(ctx, d), f, targets_for(d), counters, d.stream));
+        else HIPCHK(ctx, rt::launch_render_extended(scene_for(ctx, d), f, targets_for(d), k.kernel, counters, d.stream));
+        HIPCHK(ctx, hipEventRecord(d.ev1, d.stream));
     }
-    // The wavefront pipeline's launches: every device advances by one step (a batch's generation, one bounce, a batch's resolve) in
-    // turn, so that several devices of one context fill up side by side; the devices that have just passed a multiple of 8 bounces are
-    // then polled together ("long paths: stop as soon as every path has ended").
-    for (bool busy = !runs.empty(); busy;) {
+    // The pipeline's launches: every device advances by one step (a batch's generation, one bounce, a batch's resolve) in turn, so that
+    // several devices of one context fill up side by side; the devices that have just passed a multiple of 8 bounces are then polled
+    // together, after every device has its next launches queued.
+    for (bool busy = true; busy;) {
         busy = false;
         std::vector<WfRun*> polls;
         for (WfRun& r : runs) {
@@ -782,150 +957,31 @@ int run_frame(rt_ctx* ctx, DevFrame fr, bool counters, uint32_t world, uint32_t 
             busy = true;
             DeviceState& d = ctx->devs[r.dev];
             HIPCHK(ctx, hipSetDevice(d.device));
-            const uint32_t n = std::min(r.batch, r.f.spp - r.first);
-            const uint32_t lane = r.two ? (r.j & 1u) : 0u;
-            rt::WfBuffers w = lane ? d.wf2 : d.wf; // (a copy: the kernels take it by value)
-            if (d.wf_beams_off) w.beam_count = nullptr;
-            hipStream_t st = lane ? d.stream2 : d.stream;
-            if (r.phase == WfRun::GENERATE) {
-                HIPCHK(ctx, rt::wf_generate(r.dsc, r.f, w, r.first, n, st));
-                r.it = 0;
-                r.phase = WfRun::BOUNCE;
-            } else if (r.phase == WfRun::BOUNCE) {
-                hipEvent_t* gev = nullptr;
-                if ((r.f.flags & RT_FLAG_STAGE_TIMES) && r.dev == 0 && w.grids) { // (bench.py: the dominant kernel's launch durations, measured live)
-                    if (d.stage_events.size() < (size_t)d.stage_events_used + 2) {
-                        hipEvent_t a = nullptr, b = nullptr;
-                        HIPCHK(ctx, hipEventCreate(&a));
-                        HIPCHK(ctx, hipEventCreate(&b));
-                        d.stage_events.push_back(a);
-                        d.stage_events.push_back(b);
-                    }
-                    gev = d.stage_events.data() + d.stage_events_used;
-                    d.stage_events_used += 2;
-                }
-                HIPCHK(ctx, rt::wf_bounce(r.dsc, r.f, w, r.it, n, counters, st, gev));
-                if (r.it >= r.f.max_bounce) r.phase = WfRun::RESOLVE;
-                else if ((r.it & 7u) == 7u) {
-                    HIPCHK(ctx, hipMemcpyAsync(&r.alive, w.counters + rt::WF_EXT_COUNT, 4, hipMemcpyDeviceToHost, st));
-                    r.poll_stream = st;
-                    polls.push_back(&r);
-                } else r.it++;
-            } else { // RESOLVE
-                if (r.two && r.j > 0) HIPCHK(ctx, hipStreamWaitEvent(st, d.ev_res[(r.j - 1u) & 1u], 0));
-                HIPCHK(ctx, rt::wf_resolve(r.f, w, targets_for(d), n, r.first == 0, r.first + n >= r.f.spp, st));
-                if (r.two) HIPCHK(ctx, hipEventRecord(d.ev_res[r.j & 1u], st));
-                r.first += r.batch;
-                r.j++;
-                if (r.first < r.f.spp) r.phase = WfRun::GENERATE;
-                else {
-                    if (r.two) { // the frame ends when both lanes have
-                        HIPCHK(ctx, hipEventRecord(d.ev_join, d.stream2));
-                        HIPCHK(ctx, hipStreamWaitEvent(d.stream, d.ev_join, 0));
-                    }
-                    HIPCHK(ctx, hipEventRecord(d.ev1, d.stream));
-                    r.phase = WfRun::DONE;
-                }
-            }
+            const WfLane l = lane_of(d, r);
+            const int rc = r.phase == WfRun::GENERATE ? wf_step_generate(ctx, r, l) : r.phase == WfRun::BOUNCE ? wf_step_bounce(ctx, d, r, l, counters, polls) : wf_step_resolve(ctx, d, r, l);
+            if (rc != RT_OK) return rc;
         }
-        for (WfRun* r : polls) { // (after every device has its next launches queued)
+        for (WfRun* r : polls) {
             HIPCHK(ctx, hipSetDevice(ctx->devs[r->dev].device));
             HIPCHK(ctx, hipStreamSynchronize(r->poll_stream));
             if (r->alive == 0) r->phase = WfRun::RESOLVE;
             else r->it++;
         }
     }
-    double kernel_ms = 0.0;
-    unsigned long long cnt[16] = {0}, grid_cnt[2] = {0, 0};
-    const bool extended = fr.mode == RT_MODE_EXTENDED;
-    uint64_t pixels = 0;
-    if (single_tile && !counters && !extended) { // one explicit tile of the reference's dispatch sequence: do not wait
-        const uint64_t px = (uint64_t)std::min(fr.tile_w, fr.width - std::min(fr.width, fr.tile_off_x)) *
-                            std::min(fr.tile_h, fr.height - std::min(fr.height, fr.tile_off_y));
+    if (single_tile && !counters && fr.mode != RT_MODE_EXTENDED) { // one explicit tile of the reference's dispatch sequence: do not wait
         rt_stats& st = ctx->stats;
-        st.pixels = px;
-        st.rays = st.primary_rays = (fr.mode == RT_MODE_LEGACY || fr.cur_bounce <= fr.max_bounce) ? px : 0;
+        st.pixels = share_pixels(fr, ctx->devs[0]);
+        st.rays = st.primary_rays = (fr.mode == RT_MODE_LEGACY || fr.cur_bounce <= fr.max_bounce) ? st.pixels : 0;
         st.continuation_rays = st.shadow_rays = st.node_visits = st.tri_tests = 0;
         st.kernel_ms = 0.0; // filled in by sync_pending
         st.wall_ms = now_ms() - w0;
         ctx->pending_dispatch = true;
         return RT_OK;
     }
-    for (size_t j = 0; j < nd; j++) {
-        DeviceState& d = ctx->devs[j];
-        HIPCHK(ctx, hipSetDevice(d.device));
-        HIPCHK(ctx, hipStreamSynchronize(d.stream));
-        float ms = 0.0f;
-        HIPCHK(ctx, hipEventElapsedTime(&ms, d.ev0, d.ev1));
-        kernel_ms = std::max(kernel_ms, (double)ms);
-        if (j == 0 && d.stage_events_used) {
-            if (d.stream2) HIPCHK(ctx, hipStreamSynchronize(d.stream2));
-            for (uint32_t k = 0; k + 1 < d.stage_events_used; k += 2) {
-                float sm = 0.0f;
-                HIPCHK(ctx, hipEventElapsedTime(&sm, d.stage_events[k], d.stage_events[k + 1]));
-                ctx->stage_ms[0] += sm;
-                ctx->stage_ms[1] += 1.0;
-            }
-        }
-        if (extended && d.used_wavefront) {
-            unsigned long long t[16];
-            HIPCHK(ctx, hipMemcpy(t, d.wf.totals, sizeof t, hipMemcpyDeviceToHost));
-            if (d.used_two_lanes) {
-                unsigned long long t2[16];
-                HIPCHK(ctx, hipMemcpy(t2, d.wf2.totals, sizeof t2, hipMemcpyDeviceToHost));
-                for (int k = 0; k < 16; k++) t[k] = k == 5 ? std::max(t[k], t2[k]) : t[k] + t2[k]; // ([5] is a high-water mark)
-            }
-            cnt[0] += t[0] + t[1] + t[2];
-            cnt[3] += t[0];
-            cnt[4] += t[1];
-            cnt[5] += t[2];
-            cnt[1] += t[3];
-            cnt[2] += t[4];
-            if (t[WF_TOTAL_ERROR] != 0)
-                return ctx->fail(RT_ERR_INTERNAL, "wavefront pipeline: %s (frame discarded)",
-                                 (t[WF_TOTAL_ERROR] & 2ull) ? "a traversal stack grew beyond the depth the tree reports" : "a queue reservation exceeded its allocation");
-            cnt[8] = std::max(cnt[8], t[5]); // diagnostics: stack high-water mark, visits with > 16 / > 24 entries
-            cnt[9] += t[6];
-            cnt[10] += t[7];
-            for (int k = 0; k < 5; k++) cnt[11 + k] += t[8 + k]; // wave-level step counts of the traversal stages
-            grid_cnt[0] += t[13];
-            grid_cnt[1] += t[14];
-        } else if (counters || extended) {
-            unsigned long long c[16];
-            HIPCHK(ctx, hipMemcpy(c, d.counters, sizeof c, hipMemcpyDeviceToHost));
-            for (int k = 0; k < 16; k++) cnt[k] += c[k];
-        }
-        if (single_tile) {
-            pixels += (uint64_t)std::min(fr.tile_w, fr.width - std::min(fr.width, fr.tile_off_x)) *
-                      std::min(fr.tile_h, fr.height - std::min(fr.height, fr.tile_off_y));
-        } else {
-            for (uint32_t k = 0; k < d.n_owned; k++) {
-                uint32_t tile = d.tile_first + k * d.tile_stride;
-                uint32_t ty = tile / fr.tiles_x, tx = tile % fr.tiles_x;
-                pixels += (uint64_t)std::min(fr.tile_size, fr.width - tx * fr.tile_size) * std::min(fr.tile_size, fr.height - ty * fr.tile_size);
-            }
-        }
-    }
-    rt_stats& st = ctx->stats;
-    st.pixels = pixels;
-    bool traced = fr.mode == RT_MODE_LEGACY || fr.cur_bounce <= fr.max_bounce;
-    if (extended) { // segments counted on the device
-        st.rays = cnt[0];
-        st.primary_rays = cnt[3];
-        st.continuation_rays = cnt[4];
-        st.shadow_rays = cnt[5];
-    } else {
-        st.rays = traced ? pixels : 0; // modes 0/1: one segment per pixel
-        st.primary_rays = st.rays;
-        st.continuation_rays = st.shadow_rays = 0;
-    }
-    st.node_visits = counters ? cnt[1] : 0;
-    st.tri_tests = counters ? cnt[2] : 0;
-    for (int k = 0; k < 8; k++) ctx->diag[k] = counters ? cnt[8 + k] : 0;
-    for (int k = 0; k < 2; k++) ctx->grid_diag[k] = counters ? grid_cnt[k] : 0;
-    st.kernel_ms = kernel_ms;
-    st.wall_ms = now_ms() - w0;
-    st.flags = (fallback ? RT_STAT_MEGAKERNEL_FALLBACK : 0u) | (single ? RT_STAT_SINGLE_PASS : 0u);
+    FrameTotals t;
+    for (size_t j = 0; j < nd; j++)
+        if (int rc = collect_device(ctx, j, fr, counters, runs[j], t)) return rc;
+    finish_frame(ctx, fr, counters, t, stat_flags, w0);
     return RT_OK;
 }
 
@@ -1001,7 +1057,7 @@ int rt_create(rt_ctx** out, const int* device_ids, int n_devices) {
             (e = hipEventCreateWithFlags(&d.ev_start, hipEventDisableTiming)) != hipSuccess || (e = hipEventCreateWithFlags(&d.ev_join, hipEventDisableTiming)) != hipSuccess ||
             (e = hipEventCreateWithFlags(&d.ev_res[0], hipEventDisableTiming)) != hipSuccess || (e = hipEventCreateWithFlags(&d.ev_res[1], hipEventDisableTiming)) != hipSuccess ||
             (e = hipEventCreate(&d.ev0)) != hipSuccess || (e = hipEventCreate(&d.ev1)) != hipSuccess ||
-            (e = hipMalloc((void**)&d.counters, 16 * sizeof(unsigned long long))) != hipSuccess) {
+            (e = hipMalloc((void**)&d.counters, RT_CNT_SLOTS * sizeof(unsigned long long))) != hipSuccess) {
             g_create_error = std::string("rt_create: ") + hipGetErrorString(e);
             ctx->devs.push_back(d);
             rt_destroy(ctx);
@@ -1463,9 +1519,6 @@ int rt_read_hits(rt_ctx* ctx, uint32_t* prim_ids, float* t, size_t n_pixels) {
     return RT_OK;
 }
 
-// Development aid (not part of rt_hip.h): wave-level diagnostics of the last RT_FLAG_COUNTERS render of the
-// state-machine kernel: transition passes, lanes served, node iterations, lanes active, leaf iterations, lanes
-// active, cycles in transition phases, cycles in traversal phases (summed over waves).
 // Development aid: the camera beams of the last extended-mode frame on the first device: per owned 8x8 pixel block the length of its
 // triangle list (0xFFFFFFFF: no list).  Returns the number of blocks (<= n), negative on error.
 int rt_debug_beams(rt_ctx* ctx, uint32_t* counts, uint32_t n) {
@@ -1490,6 +1543,12 @@ int rt_debug_stage_times(rt_ctx* ctx, double out[2]) {
     return RT_OK;
 }
 
+// Development aid (not part of rt_hip.h): the diagnostics of the last render, zero unless it ran with RT_FLAG_COUNTERS.  Their meaning
+// depends on the kernel that rendered it.  State-machine megakernel (DevCounterSlot RT_CNT_SM_*, summed over waves and devices):
+// transition passes, lanes served in them, node iterations, lanes active in them, leaf iterations, lanes active in them, cycles in
+// transition phases, cycles in traversal phases.  Pipeline (WfTotal 5-12, wavefront.h, over both lanes and the devices): traversal stack
+// high-water mark (a maximum), node visits that enter no child, children entered, node steps, leaf steps, lanes in leaf steps, leaf
+// trips, refills.  Other kernels: zeros.
 int rt_debug_counters(rt_ctx* ctx, unsigned long long out[8]) {
     if (!ctx || !out) return RT_ERR_BAD_ARG;
     for (int k = 0; k < 8; k++) out[k] = ctx->diag[k];
@@ -1623,7 +1682,7 @@ int run_query(rt_ctx* ctx, const char* fn, const rt_ray* rays, size_t n, void* o
             if (int rc = ensure_buffer(ctx, &d.rq_in, &d.rq_in_bytes, m * sizeof(rt_ray))) return rc;
             if (int rc = ensure_buffer(ctx, &d.rq_out, &d.rq_out_bytes, m * out_elem)) return rc;
         }
-        if (counters) HIPCHK(ctx, hipMemsetAsync(d.counters, 0, 3 * sizeof(unsigned long long), d.stream));
+        if (counters) HIPCHK(ctx, hipMemsetAsync(d.counters, 0, (RT_CNT_TRI_TESTS + 1) * sizeof(unsigned long long), d.stream));
         for (size_t c = 0; c < chunks; c++) {
             const size_t off = first[j] + c * RT_QUERY_CHUNK, m = std::min<size_t>(RT_QUERY_CHUNK, first[j] + count[j] - off);
             const void* in = src + off * sizeof(rt_ray);
@@ -1671,10 +1730,10 @@ int run_query(rt_ctx* ctx, const char* fn, const rt_ray* rays, size_t n, void* o
         }
         kernel_ms = std::max(kernel_ms, ms);
         if (counters) {
-            unsigned long long cn[3];
+            unsigned long long cn[RT_CNT_TRI_TESTS + 1];
             HIPCHK(ctx, hipMemcpy(cn, d.counters, sizeof cn, hipMemcpyDeviceToHost));
-            nodes += cn[1];
-            tris += cn[2];
+            nodes += cn[RT_CNT_NODE_VISITS];
+            tris += cn[RT_CNT_TRI_TESTS];
         }
     }
     rt_stats& st = ctx->stats;

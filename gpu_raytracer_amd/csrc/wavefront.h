@@ -11,6 +11,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "../../include/rt_hip.h"
 #include "device_layout.h"
 #include "shadow_grid.h"
 
@@ -35,6 +36,28 @@ enum WfCounter : uint32_t {
     WF_N_COUNTERS = 16
 };
 
+// totals[] slots (device memory, 64-bit; zeroed per frame and lane, read by run_frame; two lanes are merged by sum, except the high-water mark)
+enum WfTotal : uint32_t {
+    WF_TOTAL_CAMERA = 0,       // camera segments (k_wf_generate)
+    WF_TOTAL_CONTINUATION = 1, // continuation segments (k_wf_finish)
+    WF_TOTAL_SHADOW = 2,       // shadow segments (k_wf_shade)
+    WF_TOTAL_NODE_VISITS = 3,  // counting variants only (k_wf_trace, k_wf_trace_camera)
+    WF_TOTAL_TRI_TESTS = 4,    // counting variants only (k_wf_trace, k_wf_trace_camera, k_wf_shadow_grid)
+    // 5-12: diagnostics of the counting variant of k_wf_trace (rt_debug_counters, in this order)
+    WF_TOTAL_STACK_MAX = 5,       // traversal stack high-water mark (a maximum, not a sum)
+    WF_TOTAL_EMPTY_VISITS = 6,    // node visits that enter no child.  RT_WF_PROBE=2: segments of k_wf_trace_camera the tree walk disagrees with
+    WF_TOTAL_CHILDREN_ENTERED = 7, // children entered
+    WF_TOTAL_NODE_STEPS = 8,      // wave-level steps: node steps, leaf steps, lanes in leaf steps, leaf trips, refills.  RT_WF_PROBE=2: 8-12 hold
+    WF_TOTAL_LEAF_STEPS = 9,      // the first disagreement instead (block, both prims, both t, list length and slot, path slot)
+    WF_TOTAL_LEAF_LANES = 10,
+    WF_TOTAL_LEAF_TRIPS = 11,
+    WF_TOTAL_REFILLS = 12,
+    WF_TOTAL_GRID_ANSWERED = 13,  // counting variant of k_wf_shadow_grid: shadow segments answered by a light grid
+    WF_TOTAL_GRID_ENTRIES = 14,   // ... list entries they read
+    WF_TOTAL_ERROR = 15,          // non-zero (| 1: a queue reservation did not fit, | 2: a traversal stack outgrew the tree's depth): every later stage kernel returns at once
+    WF_N_TOTALS = 16
+};
+
 struct WfBuffers {
     // per path slot (P = samples_in_batch * n_blocks * 64)
     float4* ray_o;       // xyz origin
@@ -53,7 +76,7 @@ struct WfBuffers {
     uint32_t* q_shadow2; // the same entries, those the light grids (shadow_grid.h) leave to the BVH; dense
     const DevShadowGrid* grids; // one per light, or null: every shadow segment walks the BVH
     uint32_t* counters;  // WfCounter
-    unsigned long long* totals; // [0] camera [1] continuation [2] shadow segments, [3] node visits, [4] triangle tests, [13] shadow segments answered by a light grid, [14] list entries they read, [15] error word
+    unsigned long long* totals; // WF_N_TOTALS words, WfTotal
     float4* accum;       // per owned pixel slot: running sum over samples (in sample order)
     uint32_t q_ext_cap;  // slots allocated for each extension queue / the shadow queue: a window reservation that would
     uint32_t q_shadow_cap; // end beyond it raises totals[WF_TOTAL_ERROR] instead of writing (window_reserve)
@@ -74,7 +97,6 @@ struct WfBuffers {
 #define RT_BEAM_CAP 128u /* triangles per block list: 90 % of the headline frame's blocks need fewer (64 / 192 / 256 measured in profiles/ab_r03.json) */
 #endif
 #define RT_BEAM_OVERFLOW 0x80000000u /* beam_count[b]: this bit = no list; the low bits then number the blocks without a list (their place in the walk queue) */
-#define WF_TOTAL_ERROR 15 /* totals[] slot: non-zero = a queue reservation did not fit; every later stage kernel of the frame returns at once */
 #ifndef RT_WF8_LDS_STACK
 #define RT_WF8_LDS_STACK 8 /* 64-bit traversal stack entries per lane kept in LDS by the persistent kernels; deeper ones overflow to HBM */
 #endif
@@ -88,6 +110,8 @@ uint32_t wf_pick_window(uint32_t iterations, uint32_t per_lane); // the reservat
 uint32_t wf_persistent_waves(); // grid size (in 64-lane blocks) of the persistent traversal kernels on the current device
 hipError_t wf_beams(const DevScene& sc, const DevFrame& fr, const WfBuffers& wb, hipStream_t s); // once per frame and device, before the batches
 hipError_t wf_generate(const DevScene& sc, const DevFrame& fr, const WfBuffers& wb, uint32_t first_sample, uint32_t n_samples, hipStream_t s);
+// Whether wf_bounce launches k_wf_shadow_grid, and so records the grid_events around it: the frame traces shadow segments and has light grids.
+inline bool wf_runs_shadow_grid(const DevFrame& fr, const WfBuffers& wb) { return !(fr.flags & RT_FLAG_NO_SHADOWS) && wb.grids; }
 hipError_t wf_bounce(const DevScene& sc, const DevFrame& fr, const WfBuffers& wb, uint32_t iteration, uint32_t n_samples, bool counters, hipStream_t s,
                      hipEvent_t* grid_events = nullptr); // n_samples: samples per pixel in this batch (iteration 0); grid_events: two events recorded around the k_wf_shadow_grid launch
 hipError_t wf_resolve(const DevFrame& fr, const WfBuffers& wb, const DevTargets& tg, uint32_t n_samples, bool first_batch, bool last_batch, hipStream_t s);

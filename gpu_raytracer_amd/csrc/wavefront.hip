@@ -167,7 +167,7 @@ __global__ __launch_bounds__(256) void k_wf_generate(DevFrame fr, rt::WfBuffers 
         const uint32_t mine = px.valid ? 1u : 0u;
         const uint32_t incl = wave_incl_scan(mine), total = __shfl(incl, WAVE - 1, WAVE);
         if (total) {
-            const uint32_t at = window_reserve(wb.q_ext[0], &wb.counters[rt::WF_EXT_COUNT], win, window, mine, incl, total, wb.q_ext_cap, &wb.totals[WF_TOTAL_ERROR]);
+            const uint32_t at = window_reserve(wb.q_ext[0], &wb.counters[rt::WF_EXT_COUNT], win, window, mine, incl, total, wb.q_ext_cap, &wb.totals[rt::WF_TOTAL_ERROR]);
             if (mine && at != WF_NO_SLOT) wb.q_ext[0][at] = p;
             real += mine;
             // camera segments of a block without a beam list walk the tree in the persistent kernel: a second, dense queue in the buffer
@@ -183,7 +183,7 @@ __global__ __launch_bounds__(256) void k_wf_generate(DevFrame fr, rt::WfBuffers 
     }
     window_close(wb.q_ext[0], win);
     const unsigned long long r = wave_sum(real);
-    if (lane == 0 && r) atomicAdd(&wb.totals[0], r);
+    if (lane == 0 && r) atomicAdd(&wb.totals[rt::WF_TOTAL_CAMERA], r);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -212,7 +212,7 @@ template <bool COUNT, bool ANY>
 __global__ __launch_bounds__(WAVE, RT_WF8_MIN_WAVES) void k_wf_trace(DevScene sc, rt::WfBuffers wb, const uint32_t* __restrict__ queue, uint32_t count_slot,
                                                     uint32_t cursor_slot, uint32_t window_slot) {
     extern __shared__ uint32_t s_mem8[];
-    if (wb.totals[WF_TOTAL_ERROR] != 0ull) return;
+    if (wb.totals[rt::WF_TOTAL_ERROR] != 0ull) return;
     const uint32_t lane = threadIdx.x;
     uint2* __restrict__ stack = reinterpret_cast<uint2*>(s_mem8) + lane;                  // entry k of this lane: stack[k * 64]
     uint8_t* __restrict__ lut = reinterpret_cast<uint8_t*>(s_mem8 + RT_WF8_LDS_STACK * 2 * WAVE); // [octant][mask] -> slot to take next
@@ -365,7 +365,7 @@ __global__ __launch_bounds__(WAVE, RT_WF8_MIN_WAVES) void k_wf_trace(DevScene sc
                     if (g_bits & 0xFFu) { // siblings still to visit: park them
                         if (sp < RT_WF8_LDS_STACK) stack[sp * WAVE] = make_uint2(g_base, g_bits);
                         else if ((uint32_t)(sp - RT_WF8_LDS_STACK) < wb.ovf_entries) ovf[(sp - RT_WF8_LDS_STACK) * WAVE] = make_uint2(g_base, g_bits);
-                        else atomicOr(&wb.totals[WF_TOTAL_ERROR], 2ull); // a tree deeper than its reported depth: never written past the allocation, the frame is discarded
+                        else atomicOr(&wb.totals[rt::WF_TOTAL_ERROR], 2ull); // a tree deeper than its reported depth: never written past the allocation, the frame is discarded
                         sp++;
                     }
                     g_base = cb;
@@ -378,7 +378,7 @@ __global__ __launch_bounds__(WAVE, RT_WF8_MIN_WAVES) void k_wf_trace(DevScene sc
                         } else {
                             if (sp < RT_WF8_LDS_STACK) stack[sp * WAVE] = make_uint2(tb | WF8_KIND_T, nt | (lm << 8));
                             else if ((uint32_t)(sp - RT_WF8_LDS_STACK) < wb.ovf_entries) ovf[(sp - RT_WF8_LDS_STACK) * WAVE] = make_uint2(tb | WF8_KIND_T, nt | (lm << 8));
-                            else atomicOr(&wb.totals[WF_TOTAL_ERROR], 2ull);
+                            else atomicOr(&wb.totals[rt::WF_TOTAL_ERROR], 2ull);
                             sp++;
                         }
                     }
@@ -435,19 +435,19 @@ __global__ __launch_bounds__(WAVE, RT_WF8_MIN_WAVES) void k_wf_trace(DevScene sc
         unsigned long long n0 = wave_sum(cnt.nodes), n1 = wave_sum(cnt.tris);
         for (int off = 32; off > 0; off >>= 1) sp_max = max(sp_max, __shfl_down(sp_max, off, WAVE));
         if (lane == 0) {
-            atomicAdd(&wb.totals[3], n0);
-            atomicAdd(&wb.totals[4], n1);
-            atomicMax(&wb.totals[5], (unsigned long long)sp_max);
-            atomicAdd(&wb.totals[8], (unsigned long long)d_node_steps);
-            atomicAdd(&wb.totals[9], (unsigned long long)d_leaf_steps);
-            atomicAdd(&wb.totals[10], (unsigned long long)d_leaf_lanes);
-            atomicAdd(&wb.totals[11], (unsigned long long)d_leaf_trips);
-            atomicAdd(&wb.totals[12], (unsigned long long)d_refills);
+            atomicAdd(&wb.totals[rt::WF_TOTAL_NODE_VISITS], n0);
+            atomicAdd(&wb.totals[rt::WF_TOTAL_TRI_TESTS], n1);
+            atomicMax(&wb.totals[rt::WF_TOTAL_STACK_MAX], (unsigned long long)sp_max);
+            atomicAdd(&wb.totals[rt::WF_TOTAL_NODE_STEPS], (unsigned long long)d_node_steps);
+            atomicAdd(&wb.totals[rt::WF_TOTAL_LEAF_STEPS], (unsigned long long)d_leaf_steps);
+            atomicAdd(&wb.totals[rt::WF_TOTAL_LEAF_LANES], (unsigned long long)d_leaf_lanes);
+            atomicAdd(&wb.totals[rt::WF_TOTAL_LEAF_TRIPS], (unsigned long long)d_leaf_trips);
+            atomicAdd(&wb.totals[rt::WF_TOTAL_REFILLS], (unsigned long long)d_refills);
         }
         const unsigned long long e0 = wave_sum(d_empty), e1 = wave_sum(d_entered);
         if (lane == 0) {
-            atomicAdd(&wb.totals[6], e0);
-            atomicAdd(&wb.totals[7], e1);
+            atomicAdd(&wb.totals[rt::WF_TOTAL_EMPTY_VISITS], e0);
+            atomicAdd(&wb.totals[rt::WF_TOTAL_CHILDREN_ENTERED], e1);
         }
     }
 }
@@ -650,7 +650,7 @@ __global__ __launch_bounds__(WAVE) void k_wf_beams(DevScene sc, DevFrame fr, rt:
 template <bool COUNT>
 __global__ __launch_bounds__(WAVE) void k_wf_trace_camera(DevScene sc, rt::WfBuffers wb, uint32_t n_samples) {
     extern __shared__ uint4 s_cam[]; // RT_BEAM_CAP * 3 quads + RT_BEAM_CAP floats (+ a per-lane walk stack behind them for the development probe)
-    if (wb.totals[WF_TOTAL_ERROR] != 0ull) return;
+    if (wb.totals[rt::WF_TOTAL_ERROR] != 0ull) return;
     const uint32_t lane = threadIdx.x;
     float* s_d = reinterpret_cast<float*>(s_cam + RT_BEAM_CAP * 3u);
     Counts cnt = {0u, 0u};
@@ -719,12 +719,12 @@ __global__ __launch_bounds__(WAVE) void k_wf_trace_camera(DevScene sc, rt::WfBuf
                 test_spheres(sc, o, d, h2, RT_MIN_RAY_DISTANCE);
                 traverse<false, false>(sc, o, d, reinterpret_cast<uint2*>(s_cam + RT_BEAM_CAP * 4u) + lane, h2, c2, RT_MIN_RAY_DISTANCE);
                 if (h2.prim != hit.prim || h2.t != hit.t) {
-                    if (atomicAdd(&wb.totals[6], 1ull) == 0ull) {
-                        wb.totals[8] = b;
-                        wb.totals[9] = ((unsigned long long)hit.prim << 32) | h2.prim;
-                        wb.totals[10] = ((unsigned long long)__float_as_uint(hit.t) << 32) | __float_as_uint(h2.t);
-                        wb.totals[11] = ((unsigned long long)n_list << 32) | h2.slot;
-                        wb.totals[12] = p;
+                    if (atomicAdd(&wb.totals[rt::WF_TOTAL_EMPTY_VISITS], 1ull) == 0ull) {
+                        wb.totals[rt::WF_TOTAL_NODE_STEPS] = b;
+                        wb.totals[rt::WF_TOTAL_LEAF_STEPS] = ((unsigned long long)hit.prim << 32) | h2.prim;
+                        wb.totals[rt::WF_TOTAL_LEAF_LANES] = ((unsigned long long)__float_as_uint(hit.t) << 32) | __float_as_uint(h2.t);
+                        wb.totals[rt::WF_TOTAL_LEAF_TRIPS] = ((unsigned long long)n_list << 32) | h2.slot;
+                        wb.totals[rt::WF_TOTAL_REFILLS] = p;
                     }
                 }
             }
@@ -738,8 +738,8 @@ __global__ __launch_bounds__(WAVE) void k_wf_trace_camera(DevScene sc, rt::WfBuf
     if (COUNT) {
         const unsigned long long n0 = wave_sum(cnt.nodes), n1 = wave_sum(cnt.tris);
         if (lane == 0) {
-            atomicAdd(&wb.totals[3], n0);
-            atomicAdd(&wb.totals[4], n1);
+            atomicAdd(&wb.totals[rt::WF_TOTAL_NODE_VISITS], n0);
+            atomicAdd(&wb.totals[rt::WF_TOTAL_TRI_TESTS], n1);
         }
     }
 }
@@ -938,7 +938,7 @@ __global__ __launch_bounds__(256, RT_WF_GRID_MIN_WAVES) void k_wf_shadow_grid(De
     __shared__ DevShadowGrid s_grids[RT_WF_MAX_LIGHTS];
     __shared__ uint32_t s_fwd[4][128]; // per wave: entries to hand on, not yet appended
     __shared__ uint32_t s_park[4][RT_WF_GRID_PARK_WORDS][RT_WF_GRID_PARK];
-    if (wb.totals[WF_TOTAL_ERROR] != 0ull) return;
+    if (wb.totals[rt::WF_TOTAL_ERROR] != 0ull) return;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const unsigned long long below = (1ull << lane) - 1ull;
     uint32_t n_fwd = 0, n_park = 0; // (wave-uniform)
@@ -1042,9 +1042,9 @@ __global__ __launch_bounds__(256, RT_WF_GRID_MIN_WAVES) void k_wf_shadow_grid(De
     if (COUNT) {
         const unsigned long long t = wave_sum(n_tests), a = wave_sum(n_answered), en = wave_sum(n_entries);
         if ((threadIdx.x & 63u) == 0) {
-            atomicAdd(&wb.totals[4], t);
-            atomicAdd(&wb.totals[13], a);
-            atomicAdd(&wb.totals[14], en);
+            atomicAdd(&wb.totals[rt::WF_TOTAL_TRI_TESTS], t);
+            atomicAdd(&wb.totals[rt::WF_TOTAL_GRID_ANSWERED], a);
+            atomicAdd(&wb.totals[rt::WF_TOTAL_GRID_ENTRIES], en);
         }
     }
 }
@@ -1058,10 +1058,10 @@ __device__ __forceinline__ void wf_end_path(const rt::WfBuffers& wb, uint32_t id
 
 __global__ __launch_bounds__(256, RT_WF_SHADE_WAVES) void k_wf_shade(DevScene sc, DevFrame fr, rt::WfBuffers wb, const uint32_t* __restrict__ queue) {
     __shared__ DevLight s_lights[RT_WF_MAX_LIGHTS];
-    if (wb.totals[WF_TOTAL_ERROR] != 0ull) return;
+    if (wb.totals[rt::WF_TOTAL_ERROR] != 0ull) return;
     stage_lights(s_lights, sc);
     const uint32_t count = wb.counters[rt::WF_EXT_COUNT];
-    const bool shadows = (fr.flags & 2u) == 0;
+    const bool shadows = (fr.flags & RT_FLAG_NO_SHADOWS) == 0;
     // with light grids the shadow stage works per vertex (k_wf_shadow_grid): the lights that need a segment go into the vertex record's
     // visibility word as a mask, not into the shadow queue as entries
     const bool to_grids = shadows && wb.grids != nullptr;
@@ -1127,7 +1127,7 @@ __global__ __launch_bounds__(256, RT_WF_SHADE_WAVES) void k_wf_shade(DevScene sc
             uint32_t total = 0;
             for (uint32_t li = 0; li < sc.n_lights; li++) total += (uint32_t)__popcll(__ballot((mask >> li) & 1u));
             if (total) {
-                uint32_t at = window_reserve(wb.q_shadow, &wb.counters[rt::WF_SHADOW_COUNT], win, window, 0u, 0u, total, wb.q_shadow_cap, &wb.totals[WF_TOTAL_ERROR]);
+                uint32_t at = window_reserve(wb.q_shadow, &wb.counters[rt::WF_SHADOW_COUNT], win, window, 0u, 0u, total, wb.q_shadow_cap, &wb.totals[rt::WF_TOTAL_ERROR]);
                 n_shadow += (uint32_t)__popc(mask);
                 const unsigned long long below = (1ull << (threadIdx.x & 63u)) - 1ull;
                 for (uint32_t li = 0; at != WF_NO_SLOT && li < sc.n_lights; li++) {
@@ -1141,7 +1141,7 @@ __global__ __launch_bounds__(256, RT_WF_SHADE_WAVES) void k_wf_shade(DevScene sc
             const uint32_t mine = (uint32_t)__popc(mask);
             const uint32_t incl = wave_incl_scan(mine), total = __shfl(incl, WAVE - 1, WAVE);
             if (total) {
-                uint32_t at = window_reserve(wb.q_shadow, &wb.counters[rt::WF_SHADOW_COUNT], win, window, mine, incl, total, wb.q_shadow_cap, &wb.totals[WF_TOTAL_ERROR]);
+                uint32_t at = window_reserve(wb.q_shadow, &wb.counters[rt::WF_SHADOW_COUNT], win, window, mine, incl, total, wb.q_shadow_cap, &wb.totals[rt::WF_TOTAL_ERROR]);
                 n_shadow += mine;
                 while (mask && at != WF_NO_SLOT) {
                     const uint32_t li = (uint32_t)__ffs((int)mask) - 1u;
@@ -1154,7 +1154,7 @@ __global__ __launch_bounds__(256, RT_WF_SHADE_WAVES) void k_wf_shade(DevScene sc
     }
     window_close(wb.q_shadow, win);
     const unsigned long long ns = wave_sum(n_shadow);
-    if ((threadIdx.x & 63u) == 0 && ns) atomicAdd(&wb.totals[2], ns);
+    if ((threadIdx.x & 63u) == 0 && ns) atomicAdd(&wb.totals[rt::WF_TOTAL_SHADOW], ns);
 }
 
 // End of a bounce iteration: queue sizes move on, cursors are reset (one thread, a launch of its own).  Round 3 tried it inside
@@ -1180,10 +1180,10 @@ __global__ void k_wf_advance(rt::WfBuffers wb) {
 __global__ __launch_bounds__(256, RT_WF_SHADE_WAVES) void k_wf_finish(DevScene sc, DevFrame fr, rt::WfBuffers wb, const uint32_t* __restrict__ queue,
                                                   uint32_t* __restrict__ next_queue) {
     __shared__ DevLight s_lights[RT_WF_MAX_LIGHTS];
-    if (wb.totals[WF_TOTAL_ERROR] != 0ull) return;
+    if (wb.totals[rt::WF_TOTAL_ERROR] != 0ull) return;
     stage_lights(s_lights, sc);
     const uint32_t count = wb.counters[rt::WF_EXT_COUNT];
-    const bool shadows = (fr.flags & 2u) == 0;
+    const bool shadows = (fr.flags & RT_FLAG_NO_SHADOWS) == 0;
     const uint32_t stride = gridDim.x * blockDim.x;
     OutWindow win = {0u, 0u};
     uint32_t n_cont = 0;
@@ -1304,14 +1304,14 @@ __global__ __launch_bounds__(256, RT_WF_SHADE_WAVES) void k_wf_finish(DevScene s
         const uint32_t mine = cont ? 1u : 0u;
         const uint32_t incl = wave_incl_scan(mine), total = __shfl(incl, WAVE - 1, WAVE);
         if (total) {
-            const uint32_t at = window_reserve(next_queue, &wb.counters[rt::WF_EXT_NEXT], win, window, mine, incl, total, wb.q_ext_cap, &wb.totals[WF_TOTAL_ERROR]);
+            const uint32_t at = window_reserve(next_queue, &wb.counters[rt::WF_EXT_NEXT], win, window, mine, incl, total, wb.q_ext_cap, &wb.totals[rt::WF_TOTAL_ERROR]);
             if (cont && at != WF_NO_SLOT) next_queue[at] = id;
             n_cont += mine;
         }
     }
     window_close(next_queue, win);
     const unsigned long long nc = wave_sum(n_cont);
-    if ((threadIdx.x & 63u) == 0 && nc) atomicAdd(&wb.totals[1], nc);
+    if ((threadIdx.x & 63u) == 0 && nc) atomicAdd(&wb.totals[rt::WF_TOTAL_CONTINUATION], nc);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1431,16 +1431,16 @@ hipError_t wf_bounce(const DevScene& sc, const DevFrame& fr, const WfBuffers& wb
     } else if (counters) launch_trace<true, false>(sc, wb, cur_q, WF_EXT_COUNT, WF_EXT_CURSOR, WF_EXT_WINDOW, s);
     else launch_trace<false, false>(sc, wb, cur_q, WF_EXT_COUNT, WF_EXT_CURSOR, WF_EXT_WINDOW, s);
     hipLaunchKernelGGL(k_wf_shade, sgrid, sblock, 0, s, sc, fr, wb, (const uint32_t*)cur_q);
-    if ((fr.flags & 2u) == 0) {
-        if (wb.grids) { // the light grids answer what they can and hand the rest on to the traversal
-            const dim3 ggrid((uint32_t)(cu_count() * RT_WF_GRID_BLOCKS_PER_CU));
-            if (grid_events) (void)hipEventRecord(grid_events[0], s);
-            if (counters) hipLaunchKernelGGL(k_wf_shadow_grid<true>, ggrid, dim3(256), 0, s, sc, wb, (const uint32_t*)cur_q);
-            else hipLaunchKernelGGL(k_wf_shadow_grid<false>, ggrid, dim3(256), 0, s, sc, wb, (const uint32_t*)cur_q);
-            if (grid_events) (void)hipEventRecord(grid_events[1], s);
-            if (counters) launch_trace<true, true>(sc, wb, wb.q_shadow2, WF_SHADOW2_COUNT, WF_SHADOW2_CURSOR, WF_SHADOW2_WINDOW, s);
-            else launch_trace<false, true>(sc, wb, wb.q_shadow2, WF_SHADOW2_COUNT, WF_SHADOW2_CURSOR, WF_SHADOW2_WINDOW, s);
-        } else if (counters) launch_trace<true, true>(sc, wb, wb.q_shadow, WF_SHADOW_COUNT, WF_SHADOW_CURSOR, WF_SHADOW_WINDOW, s);
+    if (wf_runs_shadow_grid(fr, wb)) { // the light grids answer what they can and hand the rest on to the traversal
+        const dim3 ggrid((uint32_t)(cu_count() * RT_WF_GRID_BLOCKS_PER_CU));
+        if (grid_events) (void)hipEventRecord(grid_events[0], s);
+        if (counters) hipLaunchKernelGGL(k_wf_shadow_grid<true>, ggrid, dim3(256), 0, s, sc, wb, (const uint32_t*)cur_q);
+        else hipLaunchKernelGGL(k_wf_shadow_grid<false>, ggrid, dim3(256), 0, s, sc, wb, (const uint32_t*)cur_q);
+        if (grid_events) (void)hipEventRecord(grid_events[1], s);
+        if (counters) launch_trace<true, true>(sc, wb, wb.q_shadow2, WF_SHADOW2_COUNT, WF_SHADOW2_CURSOR, WF_SHADOW2_WINDOW, s);
+        else launch_trace<false, true>(sc, wb, wb.q_shadow2, WF_SHADOW2_COUNT, WF_SHADOW2_CURSOR, WF_SHADOW2_WINDOW, s);
+    } else if ((fr.flags & RT_FLAG_NO_SHADOWS) == 0) {
+        if (counters) launch_trace<true, true>(sc, wb, wb.q_shadow, WF_SHADOW_COUNT, WF_SHADOW_CURSOR, WF_SHADOW_WINDOW, s);
         else launch_trace<false, true>(sc, wb, wb.q_shadow, WF_SHADOW_COUNT, WF_SHADOW_CURSOR, WF_SHADOW_WINDOW, s);
     }
     hipLaunchKernelGGL(k_wf_finish, sgrid, sblock, 0, s, sc, fr, wb, (const uint32_t*)cur_q, next_q);

@@ -97,3 +97,5 @@ def test_stage_times_are_those_of_the_light_grid_launches(gpu_ctx):
     assert gpu_ctx.debug_stage_times() == (0.0, 0)
     gpu_ctx.render(640, 360, sc.camera, mode=2, spp=4, max_bounces=3, stage_times=True, no_shadow_grid=True)
     assert gpu_ctx.debug_stage_times() == (0.0, 0)  # no light-grid launches in that frame
+    gpu_ctx.render(640, 360, sc.camera, mode=2, spp=4, max_bounces=3, stage_times=True, no_shadows=True)
+    assert gpu_ctx.debug_stage_times() == (0.0, 0)  # the grids are built, but a frame without shadow segments launches none of their stage
