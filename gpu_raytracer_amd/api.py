@@ -30,6 +30,8 @@ PREPARE_SHADOW_GRIDS = 1
 PREPARE_QUALITY_TREE = 2
 QUERY_COUNTERS = 1  # RT_QUERY_COUNTERS of rt_intersect / rt_occluded
 QUERY_CHUNK = 4194304  # RT_QUERY_CHUNK: host batches are staged in chunks of at most this many rays
+UPDATE_REBUILD = 1  # RT_UPDATE_REBUILD of rt_update_geometry
+STAT_MEGAKERNEL_FALLBACK, STAT_SINGLE_PASS, STAT_REFIT, STAT_REBUILT = 1, 2, 4, 8  # RT_STAT_* (rt_stats.flags)
 PRIM_MISS = 0xFFFFFFFF
 PRIM_SPHERE_FLAG = 0x80000000
 EXTENDED_AVAILABLE = True
@@ -40,6 +42,7 @@ ABI_SYMBOLS = [
     "rt_read_rgb32f", "rt_read_rgba8_channels", "rt_read_rgba8_combined", "rt_read_hits",
     "rt_get_stats", "rt_last_error", "rt_destroy", "rt_version",
     "rt_intersect", "rt_occluded", "rt_camera_rays",
+    "rt_update_geometry",
 ]
 
 
@@ -205,6 +208,7 @@ class Context:
             self._h, _p(sp), C.c_uint32(len(sp)), _p(li), C.c_uint32(len(li)), _p(ve), C.c_uint32(len(ve)),
             _p(tr), C.c_uint32(len(tr)), _p(ma), C.c_uint32(len(ma)),
             _p(rn), C.c_uint32(0 if rn is None else len(rn)), _p(ri), C.c_uint32(0 if ri is None else len(ri))))
+        self._n_vertices, self._n_spheres = len(ve), len(sp)
 
     def upload_scene_packed(self, metadata, offsets, tri_bufs, triangles_per_buffer, materials):
         md = np.ascontiguousarray(metadata, dtype=np.uint32)
@@ -216,6 +220,35 @@ class Context:
         self._check(self.lib.rt_upload_scene_packed(
             self._h, _p(md), C.c_size_t(md.size), _p(off), ptrs, counts, C.c_uint32(triangles_per_buffer),
             _p(ma), C.c_uint32(len(ma))))
+        o = off.reshape(-1)[0]
+        self._n_vertices, self._n_spheres = int(o["vertices_count"]), int(o["spheres_count"])
+
+    def update_geometry(self, vertices=None, spheres=None, rebuild=False):
+        """rt_update_geometry: new positions for the uploaded scene, in place.  vertices: (n, 3) float32, numpy or a torch tensor on
+        the CPU or on a device of the context; spheres: a types.SPHERE structured array (numpy).  None = unchanged; the counts
+        must be those of the last upload.  The tree is refitted, or rebuilt with rebuild=True.  Returns the stats (flags:
+        STAT_REFIT / STAT_REBUILT)."""
+        n_up_v, n_up_s = getattr(self, "_n_vertices", None), getattr(self, "_n_spheres", None)
+        if n_up_v is None:
+            raise RtError(-4, "update_geometry: no scene uploaded")
+        if vertices is not None:
+            if _check_batch(vertices, "vertices", 3, "float32") != n_up_v:
+                raise ValueError(f"vertices: count {len(vertices)}, the scene was uploaded with {n_up_v}")
+        if spheres is not None:
+            if not isinstance(spheres, np.ndarray) or spheres.dtype != T.SPHERE:
+                raise TypeError(f"spheres: a numpy array of dtype types.SPHERE, not {getattr(spheres, 'dtype', type(spheres).__name__)}")
+            if spheres.ndim != 1:
+                raise ValueError(f"spheres: shape {spheres.shape}, expected (N,)")
+            if len(spheres) != n_up_s:
+                raise ValueError(f"spheres: count {len(spheres)}, the scene was uploaded with {n_up_s}")
+            spheres = np.ascontiguousarray(spheres)
+        if vertices is not None:
+            _sync_torch(vertices)
+        self._check(self.lib.rt_update_geometry(
+            self._h, _addr(vertices) if vertices is not None else C.c_void_p(0), C.c_uint32(0 if vertices is None else n_up_v),
+            _p(spheres) if spheres is not None else C.c_void_p(0), C.c_uint32(0 if spheres is None else n_up_s),
+            C.c_uint32(UPDATE_REBUILD if rebuild else 0)))
+        return self.stats()
 
     def upload_textures(self, textures, texture_data):
         """Bindings 6-7 (TextureInfo[] + texture bytes): validated and recorded, never sampled (as in the reference)."""

@@ -23,6 +23,7 @@
 #include "half.h"
 #include "kernels.h"
 #include "ray_query.h"
+#include "refit.h"
 #include "shadow_grid.h"
 #include "wavefront.h"
 
@@ -74,6 +75,13 @@ struct DeviceState {
     void* rq_out = nullptr;
     size_t rq_in_bytes = 0, rq_out_bytes = 0;
     std::vector<hipEvent_t> rq_events; // an event pair around each launch of a query
+    // rt_update_geometry (refit.h): the refit's view of the tree this device holds, made on the first update of that tree
+    uint32_t* rf_vidx = nullptr;   // per triangle record: the caller's vertex indices (RT_REFIT_NO_RECORD: padding)
+    uint32_t* rf_order = nullptr;  // node ids grouped by tree level (rt_ctx::rf_level_first)
+    float4* rf_boxes = nullptr;    // exact box per node (min, max): scratch of the level launches
+    uint32_t* rf_dropped = nullptr; // vertex indices of the triangles the tree has no record of (non-finite at upload)
+    uint32_t* rf_flag = nullptr;
+    float* rf_verts = nullptr;     // the positions of the last update (3 floats per vertex)
 };
 
 } // namespace
@@ -97,6 +105,13 @@ struct rt_ctx {
     std::vector<rt::BuildTri> build_tris; // the triangles of the last upload as the builders take them (rt_prepare RT_PREPARE_QUALITY_TREE rebuilds from them)
     std::vector<DevLight> host_lights; // what the lazy light-grid build needs of the last upload: the lights, ...
     float box_lo[3] = {0, 0, 0}, box_hi[3] = {0, 0, 0}; // ... the box of the triangles with finite vertices
+    std::vector<rt_triangle> up_triangles; // the triangles of the last upload in build_tris order (rt_update_geometry gathers through them)
+    std::vector<uint32_t> up_prim_ids;     // ... their prim ids when they are not the index (rt_upload_scene_packed)
+    uint32_t up_vertices = 0;              // vertex count of the last upload
+    bool rf_ready = false;                 // the devices hold the refit's view of the current tree (DeviceState::rf_*)
+    std::vector<uint32_t> rf_level_first;  // rf_order offsets of the tree levels, root level first, plus the end
+    uint32_t rf_n_dropped = 0;             // triangles without a record
+    bool host_geometry_stale = false;      // build_tris / box_lo / box_hi lag behind device-resident positions in devs[0].rf_verts
     uint32_t n_textures = 0;          // bindings 6-7 as last handed over (rt_upload_textures); never sampled, like the reference
     uint64_t texture_bytes = 0;
 
@@ -130,6 +145,13 @@ double now_ms() {
     return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
 }
 
+void free_refit(DeviceState& d) { // the refit's view of a tree goes with the tree
+    (void)hipSetDevice(d.device);
+    for (void* p : {(void*)d.rf_vidx, (void*)d.rf_order, (void*)d.rf_boxes, (void*)d.rf_dropped, (void*)d.rf_flag}) (void)hipFree(p);
+    d.rf_vidx = d.rf_order = d.rf_dropped = d.rf_flag = nullptr;
+    d.rf_boxes = nullptr;
+}
+
 void free_scene(DeviceState& d) {
     (void)hipSetDevice(d.device);
     (void)hipFree(d.nodes); (void)hipFree(d.tris); (void)hipFree(d.spheres); (void)hipFree(d.lights); (void)hipFree(d.materials);
@@ -145,6 +167,9 @@ void free_scene(DeviceState& d) {
     (void)hipFree(d.rq_out);
     d.rq_in = d.rq_out = nullptr;
     d.rq_in_bytes = d.rq_out_bytes = 0;
+    free_refit(d);
+    (void)hipFree(d.rf_verts);
+    d.rf_verts = nullptr;
 }
 void free_targets(DeviceState& d) {
     (void)hipSetDevice(d.device);
@@ -250,6 +275,109 @@ DevTargets targets_for(const DeviceState& d) {
 }
 
 int sync_pending(rt_ctx* ctx);
+int sync_host_geometry(rt_ctx* ctx);
+
+// Where the tree is built.  Default (method 2): ON the device (device_build.hip: Morton sort + PLOC + collapse + emission,
+// a few milliseconds), as soon as the scene is large enough for that to matter; the host builders remain for tiny scenes, as
+// the fallback when a device-built tree would be deeper than the kernels' stacks allow (degenerate inputs; the host build
+// bounds its depth), and on request: RT_BUILD_METHOD=0 binned SAH + insertion-based optimisation (1 % faster frames, 0.35 s
+// per 262 k triangles), 1 PLOC on the host (the statement the device build is checked against).
+int tree_method(size_t n_tris) {
+    int method = 2;
+    if (const char* e = std::getenv("RT_BUILD_METHOD")) method = std::atoi(e);
+    if (method == 2 && n_tris < RT_DEVICE_BUILD_MIN_TRIS) method = 0;
+    return method;
+}
+
+// A tree built for every device of the context, not yet handed over: per-device arrays of the device build, or the host build's.
+struct TreeBuild {
+    int method = 0; // as built: 2 device, 0 / 1 host (the device build falls back to 0)
+    std::vector<rt::DeviceBuild> dbuilds;
+    rt::BvhBuild bvh;
+    uint32_t nodes = 0, tris = 0, depth = 0;
+};
+
+void free_tree_build(rt_ctx* ctx, TreeBuild& tb) { // device-built arrays not (yet) handed to a device state
+    for (size_t j = 0; j < tb.dbuilds.size(); j++) {
+        (void)hipSetDevice(ctx->devs[j].device);
+        (void)hipFree(tb.dbuilds[j].nodes);
+        (void)hipFree(tb.dbuilds[j].tris);
+        tb.dbuilds[j].nodes = nullptr;
+        tb.dbuilds[j].tris = nullptr;
+    }
+}
+
+// The build part of a scene upload (and of rt_update_geometry's rebuild): `method` from tree_method.
+int build_tree(rt_ctx* ctx, const std::vector<rt::BuildTri>& bt, int method, TreeBuild& tb) {
+    rt::BvhBuildOptions opt;
+    if (const char* e = std::getenv("RT_BVH_COST_TRAVERSE")) opt.cost_traverse = (float)std::atof(e); // tuning knobs (development)
+    if (const char* e = std::getenv("RT_BVH_MAX_LEAF")) opt.max_leaf = (uint32_t)std::atoi(e);
+    if (const char* e = std::getenv("RT_BVH8_COST_TRAVERSE")) opt.cost_traverse8 = (float)std::atof(e);
+    if (const char* e = std::getenv("RT_BUILD_METHOD")) opt.method = std::atoi(e);
+    if (const char* e = std::getenv("RT_BUILD_REINSERT")) opt.reinsert = std::atoi(e) != 0;
+    if (const char* e = std::getenv("RT_PLOC_RADIUS")) opt.ploc_radius = (uint32_t)std::atoi(e);
+    opt.method = method == 1 ? 1 : 0;
+    std::vector<rt::DeviceBuild>& dbuilds = tb.dbuilds;
+    rt::BvhBuild& bvh = tb.bvh;
+    if (method == 2) {
+        dbuilds.resize(ctx->devs.size());
+        bool ok = true;
+        for (size_t j = 0; j < ctx->devs.size() && ok; j++) {
+            DeviceState& d = ctx->devs[j];
+            HIPCHK(ctx, hipSetDevice(d.device));
+            const hipError_t e = rt::device_build(bt.data(), bt.size(), opt, d.stream, &dbuilds[j]);
+            ok = e == hipSuccess && dbuilds[j].depth <= RT_DEV_MAX_BVH_DEPTH && dbuilds[j].n_nodes <= RT_DEV_MAX_NODES &&
+                 dbuilds[j].n_nodes == dbuilds[0].n_nodes && dbuilds[j].n_tris == dbuilds[0].n_tris;
+        }
+        if (!ok) { // fall back to the host build (depth bound, or the device ran out of memory for the temporaries)
+            free_tree_build(ctx, tb);
+            dbuilds.clear();
+            method = 0;
+        } else {
+            tb.nodes = dbuilds[0].n_nodes;
+            tb.tris = dbuilds[0].n_tris;
+            tb.depth = dbuilds[0].depth;
+        }
+    }
+    if (method != 2) {
+        rt::build_bvh(bt.data(), bt.size(), opt, bvh);
+        if (bvh.depth > RT_DEV_MAX_BVH_DEPTH) return ctx->fail(RT_ERR_INTERNAL, "BVH depth %u exceeds the bound %d", bvh.depth, RT_DEV_MAX_BVH_DEPTH);
+        if (bvh.nodes.size() > RT_DEV_MAX_NODES) return ctx->fail(RT_ERR_BAD_ARG, "scene needs %zu BVH nodes > %u", bvh.nodes.size(), RT_DEV_MAX_NODES);
+        tb.nodes = (uint32_t)bvh.nodes.size();
+        tb.tris = (uint32_t)bvh.tris.size();
+        tb.depth = bvh.depth;
+    }
+    tb.method = method;
+    return RT_OK;
+}
+
+// The hand-over part: device j's node / triangle arrays of a built tree (taken over from the device build, or uploaded).
+int take_nodes(rt_ctx* ctx, size_t j, TreeBuild& tb, DevNode8** dst) {
+    if (tb.dbuilds.empty()) return upload_array(ctx, dst, tb.bvh.nodes);
+    *dst = tb.dbuilds[j].nodes;
+    tb.dbuilds[j].nodes = nullptr;
+    return RT_OK;
+}
+int take_tris(rt_ctx* ctx, size_t j, TreeBuild& tb, DevTri** dst) {
+    if (tb.dbuilds.empty()) return upload_array(ctx, dst, tb.bvh.tris);
+    *dst = tb.dbuilds[j].tris;
+    tb.dbuilds[j].tris = nullptr;
+    return RT_OK;
+}
+
+// The box of the triangles with finite vertices (the light grids' bounds).
+void finite_box(const std::vector<rt::BuildTri>& bt, float box_lo[3], float box_hi[3]) {
+    for (int a = 0; a < 3; a++) box_lo[a] = INFINITY, box_hi[a] = -INFINITY;
+    for (const rt::BuildTri& t : bt) {
+        const float* vs[3] = {t.v0, t.v1, t.v2};
+        bool finite = true;
+        for (int k = 0; k < 3; k++)
+            for (int a = 0; a < 3; a++) finite = finite && std::isfinite(vs[k][a]);
+        if (!finite) continue;
+        for (int k = 0; k < 3; k++)
+            for (int a = 0; a < 3; a++) box_lo[a] = std::min(box_lo[a], vs[k][a]), box_hi[a] = std::max(box_hi[a], vs[k][a]);
+    }
+}
 
 int upload_common(rt_ctx* ctx, const rt_sphere* spheres, uint32_t n_spheres, const rt_light* lights, uint32_t n_lights,
                   const rt_vertex* vertices, uint32_t n_vertices, const std::vector<rt_triangle>& tris,
@@ -268,65 +396,19 @@ int upload_common(rt_ctx* ctx, const rt_sphere* spheres, uint32_t n_spheres, con
         bt[i].material_id = t.material_id;
         bt[i].prim_id = prim_ids.empty() ? (uint32_t)i : prim_ids[i];
     }
-    rt::BvhBuild bvh;
-    rt::BvhBuildOptions opt;
-    if (const char* e = std::getenv("RT_BVH_COST_TRAVERSE")) opt.cost_traverse = (float)std::atof(e); // tuning knobs (development)
-    if (const char* e = std::getenv("RT_BVH_MAX_LEAF")) opt.max_leaf = (uint32_t)std::atoi(e);
-    if (const char* e = std::getenv("RT_BVH8_COST_TRAVERSE")) opt.cost_traverse8 = (float)std::atof(e);
-    if (const char* e = std::getenv("RT_BUILD_METHOD")) opt.method = std::atoi(e);
-    if (const char* e = std::getenv("RT_BUILD_REINSERT")) opt.reinsert = std::atoi(e) != 0;
-    if (const char* e = std::getenv("RT_PLOC_RADIUS")) opt.ploc_radius = (uint32_t)std::atoi(e);
-    // Where the tree is built.  Default (method 2): ON the device (device_build.hip: Morton sort + PLOC + collapse + emission,
-    // a few milliseconds), as soon as the scene is large enough for that to matter; the host builders remain for tiny scenes, as
-    // the fallback when a device-built tree would be deeper than the kernels' stacks allow (degenerate inputs; the host build
-    // bounds its depth), and on request: RT_BUILD_METHOD=0 binned SAH + insertion-based optimisation (1 % faster frames, 0.35 s
-    // per 262 k triangles), 1 PLOC on the host (the statement the device build is checked against).
-    int method = 2;
-    if (const char* e = std::getenv("RT_BUILD_METHOD")) method = std::atoi(e);
-    if (method == 2 && bt.size() < RT_DEVICE_BUILD_MIN_TRIS) method = 0;
-    opt.method = method == 1 ? 1 : 0;
-    std::vector<rt::DeviceBuild> dbuilds;
-    uint32_t tree_nodes = 0, tree_tris = 0, tree_depth = 0;
-    if (method == 2) {
-        if (ctx->fail_upload_at == 0) {
-            ctx->fail_upload_at = -1;
-            ctx->uploaded = false;
-            ctx->frame_valid = false;
-            ctx->scene_counts = DevScene{};
-            for (auto& d : ctx->devs) free_scene(d);
-            return ctx->fail(RT_ERR_OOM, "rt_upload: allocation failure injected by rt_debug_fail_upload");
-        }
-        dbuilds.resize(ctx->devs.size());
-        bool ok = true;
-        for (size_t j = 0; j < ctx->devs.size() && ok; j++) {
-            DeviceState& d = ctx->devs[j];
-            HIPCHK(ctx, hipSetDevice(d.device));
-            const hipError_t e = rt::device_build(bt.data(), bt.size(), opt, d.stream, &dbuilds[j]);
-            ok = e == hipSuccess && dbuilds[j].depth <= RT_DEV_MAX_BVH_DEPTH && dbuilds[j].n_nodes <= RT_DEV_MAX_NODES &&
-                 dbuilds[j].n_nodes == dbuilds[0].n_nodes && dbuilds[j].n_tris == dbuilds[0].n_tris;
-        }
-        if (!ok) { // fall back to the host build (depth bound, or the device ran out of memory for the temporaries)
-            for (size_t j = 0; j < dbuilds.size(); j++) {
-                (void)hipSetDevice(ctx->devs[j].device);
-                (void)hipFree(dbuilds[j].nodes);
-                (void)hipFree(dbuilds[j].tris);
-            }
-            dbuilds.clear();
-            method = 0;
-        } else {
-            tree_nodes = dbuilds[0].n_nodes;
-            tree_tris = dbuilds[0].n_tris;
-            tree_depth = dbuilds[0].depth;
-        }
+    int method = tree_method(bt.size());
+    if (method == 2 && ctx->fail_upload_at == 0) {
+        ctx->fail_upload_at = -1;
+        ctx->uploaded = false;
+        ctx->frame_valid = false;
+        ctx->scene_counts = DevScene{};
+        for (auto& d : ctx->devs) free_scene(d);
+        return ctx->fail(RT_ERR_OOM, "rt_upload: allocation failure injected by rt_debug_fail_upload");
     }
-    if (method != 2) {
-        rt::build_bvh(bt.data(), bt.size(), opt, bvh);
-        if (bvh.depth > RT_DEV_MAX_BVH_DEPTH) return ctx->fail(RT_ERR_INTERNAL, "BVH depth %u exceeds the bound %d", bvh.depth, RT_DEV_MAX_BVH_DEPTH);
-        if (bvh.nodes.size() > RT_DEV_MAX_NODES) return ctx->fail(RT_ERR_BAD_ARG, "scene needs %zu BVH nodes > %u", bvh.nodes.size(), RT_DEV_MAX_NODES);
-        tree_nodes = (uint32_t)bvh.nodes.size();
-        tree_tris = (uint32_t)bvh.tris.size();
-        tree_depth = bvh.depth;
-    }
+    TreeBuild tb;
+    if (int rc = build_tree(ctx, bt, method, tb)) return rc;
+    method = tb.method;
+    const uint32_t tree_nodes = tb.nodes, tree_tris = tb.tris, tree_depth = tb.depth;
     ctx->n_input_tris = (uint32_t)bt.size();
     ctx->build_method = method;
 
@@ -372,16 +454,8 @@ int upload_common(rt_ctx* ctx, const rt_sphere* spheres, uint32_t n_spheres, con
     ctx->frame_valid = false;
     ctx->scene_counts = DevScene{};
     for (auto& d : ctx->devs) free_scene(d);
-    float box_lo[3] = {INFINITY, INFINITY, INFINITY}, box_hi[3] = {-INFINITY, -INFINITY, -INFINITY}; // of the triangles with finite vertices
-    for (const rt::BuildTri& t : bt) {
-        const float* vs[3] = {t.v0, t.v1, t.v2};
-        bool finite = true;
-        for (int k = 0; k < 3; k++)
-            for (int a = 0; a < 3; a++) finite = finite && std::isfinite(vs[k][a]);
-        if (!finite) continue;
-        for (int k = 0; k < 3; k++)
-            for (int a = 0; a < 3; a++) box_lo[a] = std::min(box_lo[a], vs[k][a]), box_hi[a] = std::max(box_hi[a], vs[k][a]);
-    }
+    float box_lo[3], box_hi[3]; // of the triangles with finite vertices
+    finite_box(bt, box_lo, box_hi);
     auto upload_all = [&](DeviceState& d) -> int {
         HIPCHK(ctx, hipSetDevice(d.device));
         int rc;
@@ -389,15 +463,9 @@ int upload_common(rt_ctx* ctx, const rt_sphere* spheres, uint32_t n_spheres, con
         auto hook = [&]() { return ctx->fail_upload_at >= 0 && ctx->fail_upload_at == k++; }; // test hook (rt_debug_fail_upload)
         const size_t j = (size_t)(&d - ctx->devs.data());
         if (hook()) return ctx->fail(RT_ERR_OOM, "rt_upload: allocation failure injected by rt_debug_fail_upload");
-        if (!dbuilds.empty()) { // the tree was built on this device: take the arrays over
-            d.nodes = dbuilds[j].nodes;
-            dbuilds[j].nodes = nullptr;
-        } else if ((rc = upload_array(ctx, &d.nodes, bvh.nodes)) != RT_OK) return rc;
+        if ((rc = take_nodes(ctx, j, tb, &d.nodes)) != RT_OK) return rc; // a device-built tree's arrays are taken over
         if (hook()) return ctx->fail(RT_ERR_OOM, "rt_upload: allocation failure injected by rt_debug_fail_upload");
-        if (!dbuilds.empty()) {
-            d.tris = dbuilds[j].tris;
-            dbuilds[j].tris = nullptr;
-        } else if ((rc = upload_array(ctx, &d.tris, bvh.tris)) != RT_OK) return rc;
+        if ((rc = take_tris(ctx, j, tb, &d.tris)) != RT_OK) return rc;
         if (hook()) return ctx->fail(RT_ERR_OOM, "rt_upload: allocation failure injected by rt_debug_fail_upload");
         if ((rc = upload_array(ctx, &d.spheres, ds)) != RT_OK) return rc;
         if ((rc = upload_array(ctx, &d.lights, dl)) != RT_OK) return rc;
@@ -411,11 +479,7 @@ int upload_common(rt_ctx* ctx, const rt_sphere* spheres, uint32_t n_spheres, con
         if (rc != RT_OK) {
             ctx->fail_upload_at = -1;
             for (auto& e : ctx->devs) free_scene(e);
-            for (size_t j = 0; j < dbuilds.size(); j++) { // device-built arrays not yet handed to a device state
-                (void)hipSetDevice(ctx->devs[j].device);
-                (void)hipFree(dbuilds[j].nodes);
-                (void)hipFree(dbuilds[j].tris);
-            }
+            free_tree_build(ctx, tb); // device-built arrays not yet handed to a device state
             return rc;
         }
     }
@@ -441,6 +505,11 @@ int upload_common(rt_ctx* ctx, const rt_sphere* spheres, uint32_t n_spheres, con
     ctx->stats.n_textures = ctx->n_textures;
     ctx->stats.texture_bytes = ctx->texture_bytes;
     ctx->build_tris.swap(bt);
+    ctx->up_triangles = tris;
+    ctx->up_prim_ids = prim_ids;
+    ctx->up_vertices = n_vertices;
+    ctx->rf_ready = false;
+    ctx->host_geometry_stale = false;
     ctx->host_lights = dl; // the light grids of the extended mode's shadow stage are built when a frame first needs them (ensure_grids)
     for (int a = 0; a < 3; a++) ctx->box_lo[a] = box_lo[a], ctx->box_hi[a] = box_hi[a];
     ctx->uploaded = true;
@@ -456,6 +525,7 @@ int upload_common(rt_ctx* ctx, const rt_sphere* spheres, uint32_t n_spheres, con
 // RT_SHADOW_GRID=0 and the RT_SHADOW_GRID_* variables are development knobs only.
 int ensure_grids(rt_ctx* ctx, DeviceState& d) {
     if (d.grids_tried) return RT_OK;
+    if (int rc = sync_host_geometry(ctx)) return rc; // box_lo / box_hi of positions an update left on the device
     d.grids_tried = true;
     const uint32_t n_lights = (uint32_t)ctx->host_lights.size(), tree_tris = ctx->scene_counts.n_tris;
     bool grids_on = true;
@@ -1227,6 +1297,7 @@ uint32_t rt_debug_pick_window(uint32_t iterations, uint32_t per_lane) { return r
 // hits do not depend on the tree).  The light grids hold triangle records in leaf order: they go with the old tree and are built again on demand.
 static int prepare_quality_tree(rt_ctx* ctx) {
     if (ctx->build_method == 0 || ctx->build_tris.empty()) return RT_OK; // already the host builder's (tiny scenes, a fallback, an earlier call)
+    if (int rc = sync_host_geometry(ctx)) return rc; // positions an update left on the device
     for (auto& d : ctx->devs) {
         HIPCHK(ctx, hipSetDevice(d.device));
         HIPCHK(ctx, hipDeviceSynchronize());
@@ -1262,6 +1333,7 @@ static int prepare_quality_tree(rt_ctx* ctx) {
         (void)hipFree(d.tris);
         d.nodes = nn[j];
         d.tris = nt[j];
+        free_refit(d);
         for (void* p : d.grid_allocs) (void)hipFree(p);
         d.grid_allocs.clear();
         d.grid_info.clear();
@@ -1282,6 +1354,7 @@ static int prepare_quality_tree(rt_ctx* ctx) {
     ctx->stats.grid_build_ms = 0.0;
     ctx->stats.tree_build = 0;
     ctx->build_method = 0;
+    ctx->rf_ready = false;
     ctx->frame_valid = false;
     return RT_OK;
 }
@@ -1607,7 +1680,7 @@ struct QueryPtr {
 };
 
 // Where `p` lives.  Pageable memory the runtime has never seen may come back as an error or as unregistered: both are host memory.
-int classify_ptr(rt_ctx* ctx, const char* fn, const char* what, const void* p, QueryPtr& q) {
+int classify_ptr(rt_ctx* ctx, const char* fn, const char* what, const void* p, QueryPtr& q, uintptr_t align = 16) {
     q = QueryPtr{};
     hipPointerAttribute_t a{};
     if (hipPointerGetAttributes(&a, p) != hipSuccess) {
@@ -1617,8 +1690,8 @@ int classify_ptr(rt_ctx* ctx, const char* fn, const char* what, const void* p, Q
     if (a.type != hipMemoryTypeDevice || a.isManaged) return RT_OK; // pinned, managed, unregistered
     for (size_t j = 0; j < ctx->devs.size(); j++)
         if (ctx->devs[j].device == a.device) {
-            if (reinterpret_cast<uintptr_t>(p) & 15u)
-                return ctx->fail(RT_ERR_BAD_ARG, "%s: %s is device memory that is not 16-byte aligned (%p)", fn, what, p);
+            if (reinterpret_cast<uintptr_t>(p) & (align - 1))
+                return ctx->fail(RT_ERR_BAD_ARG, "%s: %s is device memory that is not %u-byte aligned (%p)", fn, what, (unsigned)align, p);
             q.device = true;
             q.dev = j;
             return RT_OK;
@@ -1785,6 +1858,334 @@ int rt_camera_rays(rt_ctx* ctx, const rt_camera* camera, uint32_t width, uint32_
         }
     }
     HIPCHK(ctx, hipStreamSynchronize(d.stream));
+    return RT_OK;
+}
+
+} // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// rt_update_geometry: new positions for the uploaded scene's vertices and spheres.  The tree in use is refitted (refit.hip: the
+// triangle records and the node boxes follow the positions, the topology stays) or, on request or when a triangle the tree has no
+// record of became finite, rebuilt through the upload's own build and hand-over (build_tree / take_nodes / take_tris).
+// ---------------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// build_tris and the finite box from positions in host memory (3 floats per vertex), through the upload's triangles.
+void gather_positions(rt_ctx* ctx, const float* verts) {
+    for (size_t i = 0; i < ctx->up_triangles.size(); i++) {
+        const rt_triangle& t = ctx->up_triangles[i];
+        rt::BuildTri& b = ctx->build_tris[i];
+        std::memcpy(b.v0, verts + 3 * (size_t)t.v0_index, 12);
+        std::memcpy(b.v1, verts + 3 * (size_t)t.v1_index, 12);
+        std::memcpy(b.v2, verts + 3 * (size_t)t.v2_index, 12);
+    }
+    finite_box(ctx->build_tris, ctx->box_lo, ctx->box_hi);
+}
+
+int read_positions(rt_ctx* ctx, std::vector<float>& out) { // the positions of the last update, as the first device holds them
+    DeviceState& d = ctx->devs[0];
+    out.resize(3 * (size_t)ctx->up_vertices);
+    HIPCHK(ctx, hipSetDevice(d.device));
+    HIPCHK(ctx, hipStreamSynchronize(d.stream));
+    if (!out.empty()) HIPCHK(ctx, hipMemcpy(out.data(), d.rf_verts, out.size() * sizeof(float), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+// What the host side keeps of the scene (build_tris, box_lo / box_hi: rt_prepare RT_PREPARE_QUALITY_TREE and the light grids read
+// them) after an update from device memory: read back once, when one of them needs it.
+int sync_host_geometry(rt_ctx* ctx) {
+    if (!ctx->host_geometry_stale) return RT_OK;
+    std::vector<float> v;
+    if (int rc = read_positions(ctx, v)) return rc;
+    gather_positions(ctx, v.data());
+    ctx->host_geometry_stale = false;
+    return RT_OK;
+}
+
+// The refit's view of the current tree (made once per tree, from the first device's arrays; every device holds the same tree): the
+// tree levels, the vertex indices of every triangle record, and the triangles that have no record.
+int ensure_refit_view(rt_ctx* ctx) {
+    if (ctx->rf_ready) return RT_OK;
+    const uint32_t n_nodes = ctx->scene_counts.n_nodes, n_rec = ctx->scene_counts.n_tris;
+    std::vector<DevNode8> nodes(n_nodes);
+    std::vector<DevTri> recs(n_rec);
+    {
+        DeviceState& d = ctx->devs[0];
+        HIPCHK(ctx, hipSetDevice(d.device));
+        HIPCHK(ctx, hipStreamSynchronize(d.stream));
+        if (n_nodes) HIPCHK(ctx, hipMemcpy(nodes.data(), d.nodes, nodes.size() * sizeof(DevNode8), hipMemcpyDeviceToHost));
+        if (n_rec) HIPCHK(ctx, hipMemcpy(recs.data(), d.tris, recs.size() * sizeof(DevTri), hipMemcpyDeviceToHost));
+    }
+    const size_t n_in = ctx->up_triangles.size();
+    std::vector<uint32_t> index_of; // prim id -> upload index (identity unless the upload was packed)
+    if (!ctx->up_prim_ids.empty()) {
+        index_of.assign((size_t)*std::max_element(ctx->up_prim_ids.begin(), ctx->up_prim_ids.end()) + 1, 0xFFFFFFFFu);
+        for (size_t i = 0; i < n_in; i++) index_of[ctx->up_prim_ids[i]] = (uint32_t)i;
+    }
+    std::vector<uint32_t> vidx(3 * (size_t)n_rec, RT_REFIT_NO_RECORD), order, level_first;
+    std::vector<uint8_t> has_record(n_in, 0), visited(n_nodes, 0);
+    auto bad = [&](const char* what, uint32_t node) { return ctx->fail(RT_ERR_INTERNAL, "rt_update_geometry: node %u: %s", node, what); };
+    if (n_nodes) {
+        order.push_back(0);
+        visited[0] = 1;
+    }
+    for (size_t begin = 0; begin < order.size();) { // breadth first: one level per pass
+        const size_t end = order.size();
+        level_first.push_back((uint32_t)begin);
+        if (level_first.size() > RT_DEV_MAX_BVH_DEPTH) return bad("the tree is deeper than the depth bound", order[begin]);
+        for (size_t k = begin; k < end; k++) {
+            const uint32_t node = order[k];
+            const DevNode8& n = nodes[node];
+            const uint32_t imask = n.ex_imask >> 24, lmask = n.lmask & 0xFFu;
+            for (uint32_t sl = 0; sl < 8; sl++) {
+                const uint32_t bit = 1u << sl, below = bit - 1u;
+                if (imask & bit) {
+                    const uint64_t c = (uint64_t)n.child_base + (uint32_t)__builtin_popcount(imask & below);
+                    if (c >= n_nodes || visited[c]) return bad("inner child out of range or reached twice", node);
+                    visited[c] = 1;
+                    order.push_back((uint32_t)c);
+                } else if (lmask & bit) {
+                    const uint64_t first = (uint64_t)n.tri_base + RT_DEV_LEAF_STRIDE * (uint32_t)__builtin_popcount(lmask & below);
+                    if (first + RT_DEV_LEAF_STRIDE > n_rec || recs[first].leaf_count > RT_DEV_LEAF_STRIDE) return bad("leaf out of range", node);
+                    for (uint32_t r = 0; r < recs[first].leaf_count; r++) {
+                        const uint32_t prim = recs[first + r].prim_id;
+                        const uint32_t i = index_of.empty() ? prim : (prim < index_of.size() ? index_of[prim] : 0xFFFFFFFFu);
+                        if (i >= n_in) return bad("record with an unknown prim id", node);
+                        const rt_triangle& t = ctx->up_triangles[i];
+                        vidx[3 * (first + r)] = t.v0_index;
+                        vidx[3 * (first + r) + 1] = t.v1_index;
+                        vidx[3 * (first + r) + 2] = t.v2_index;
+                        has_record[i] = 1;
+                    }
+                }
+            }
+        }
+        begin = end;
+    }
+    level_first.push_back((uint32_t)order.size());
+    std::vector<uint32_t> dropped;
+    for (size_t i = 0; i < n_in; i++)
+        if (!has_record[i]) {
+            const rt_triangle& t = ctx->up_triangles[i];
+            dropped.insert(dropped.end(), {t.v0_index, t.v1_index, t.v2_index});
+        }
+    for (auto& d : ctx->devs) {
+        free_refit(d);
+        HIPCHK(ctx, hipSetDevice(d.device));
+        int rc;
+        if ((rc = upload_array(ctx, &d.rf_vidx, vidx)) != RT_OK || (rc = upload_array(ctx, &d.rf_order, order)) != RT_OK ||
+            (rc = upload_array(ctx, &d.rf_dropped, dropped)) != RT_OK)
+            return rc;
+        HIPCHK(ctx, hipMalloc((void**)&d.rf_boxes, std::max<size_t>(1, 2 * (size_t)n_nodes) * sizeof(float4)));
+        HIPCHK(ctx, hipMalloc((void**)&d.rf_flag, sizeof(uint32_t)));
+    }
+    ctx->rf_level_first = level_first;
+    ctx->rf_n_dropped = (uint32_t)(dropped.size() / 3);
+    ctx->rf_ready = true;
+    return RT_OK;
+}
+
+void drop_grids(rt_ctx* ctx) { // the light grids hold the old triangles: built again when a frame or rt_prepare needs them
+    for (auto& d : ctx->devs) {
+        (void)hipSetDevice(d.device);
+        for (void* p : d.grid_allocs) (void)hipFree(p);
+        d.grid_allocs.clear();
+        d.grid_info.clear();
+        d.grids = nullptr;
+        d.grids_tried = false;
+        d.grids_partial = false;
+    }
+    ctx->stats.grid_bytes = 0;
+    ctx->stats.grid_build_ms = 0.0;
+}
+
+// A new tree from build_tris (already holding the new positions), built and handed over as rt_upload_scene* does it.
+int rebuild_tree(rt_ctx* ctx) {
+    TreeBuild tb;
+    if (int rc = build_tree(ctx, ctx->build_tris, tree_method(ctx->build_tris.size()), tb)) {
+        free_tree_build(ctx, tb);
+        return rc;
+    }
+    const uint64_t old_bytes = (uint64_t)ctx->stats.bvh_nodes * sizeof(DevNode8) + (uint64_t)ctx->tree_tris_uploaded * sizeof(DevTri);
+    for (size_t j = 0; j < ctx->devs.size(); j++) {
+        DeviceState& d = ctx->devs[j];
+        HIPCHK(ctx, hipSetDevice(d.device));
+        HIPCHK(ctx, hipDeviceSynchronize());
+        (void)hipFree(d.nodes);
+        (void)hipFree(d.tris);
+        d.nodes = nullptr;
+        d.tris = nullptr;
+        free_refit(d);
+        int rc;
+        if ((rc = take_nodes(ctx, j, tb, &d.nodes)) != RT_OK || (rc = take_tris(ctx, j, tb, &d.tris)) != RT_OK) {
+            free_tree_build(ctx, tb);
+            return rc;
+        }
+        HIPCHK(ctx, hipDeviceSynchronize()); // upload_array copies on the null stream
+    }
+    DevScene& sc = ctx->scene_counts;
+    sc.n_nodes = tb.nodes;
+    sc.n_tris = tb.tris;
+    sc.stack_entries = 2u * tb.depth + 2u;
+    ctx->stats.scene_bytes += (uint64_t)tb.nodes * sizeof(DevNode8) + (uint64_t)tb.tris * sizeof(DevTri) - old_bytes;
+    ctx->stats.bvh_nodes = tb.nodes;
+    ctx->stats.bvh_depth = tb.depth;
+    ctx->stats.tree_build = (uint32_t)tb.method;
+    ctx->tree_tris_uploaded = tb.tris;
+    ctx->build_method = tb.method;
+    ctx->rf_ready = false;
+    return RT_OK;
+}
+
+// Everything after the argument checks; a failure here leaves the context "not uploaded" (rt_update_geometry).
+int update_geometry(rt_ctx* ctx, const rt_vertex* vertices, const QueryPtr& pv, const rt_sphere* spheres, uint32_t n_spheres, const QueryPtr& ps,
+                    bool rebuild, uint32_t* stat_flags, double* kernel_ms) {
+    const size_t nd = ctx->devs.size();
+    // spheres: rt_sphere (20 B) -> the first 20 B of each DevSphere (32 B, padding stays zero): one strided copy, no kernel
+    if (spheres && n_spheres) {
+        std::vector<rt_sphere> staged;
+        const void* src = spheres;
+        if (ps.device && nd > 1) { // device input for several devices: through the host
+            staged.resize(n_spheres);
+            HIPCHK(ctx, hipSetDevice(ctx->devs[ps.dev].device));
+            HIPCHK(ctx, hipMemcpy(staged.data(), spheres, n_spheres * sizeof(rt_sphere), hipMemcpyDeviceToHost));
+            src = staged.data();
+        }
+        for (auto& d : ctx->devs) {
+            HIPCHK(ctx, hipSetDevice(d.device));
+            HIPCHK(ctx, hipMemcpy2DAsync(d.spheres, sizeof(DevSphere), src, sizeof(rt_sphere), sizeof(rt_sphere), n_spheres, hipMemcpyDefault, d.stream));
+            HIPCHK(ctx, hipStreamSynchronize(d.stream));
+        }
+    }
+    if (!vertices || ctx->up_vertices == 0) return RT_OK;
+    // vertices: a copy on every device (the refit reads it; after device input it is also what a later readback reads)
+    const size_t vbytes = (size_t)ctx->up_vertices * sizeof(rt_vertex);
+    for (auto& d : ctx->devs)
+        if (!d.rf_verts) {
+            HIPCHK(ctx, hipSetDevice(d.device));
+            HIPCHK(ctx, hipMalloc((void**)&d.rf_verts, vbytes));
+        }
+    if (!pv.device) {
+        for (auto& d : ctx->devs) {
+            HIPCHK(ctx, hipSetDevice(d.device));
+            HIPCHK(ctx, hipMemcpyAsync(d.rf_verts, vertices, vbytes, hipMemcpyHostToDevice, d.stream));
+        }
+    } else {
+        DeviceState& s = ctx->devs[pv.dev];
+        HIPCHK(ctx, hipSetDevice(s.device));
+        HIPCHK(ctx, hipMemcpyAsync(s.rf_verts, vertices, vbytes, hipMemcpyDeviceToDevice, s.stream));
+        HIPCHK(ctx, hipStreamSynchronize(s.stream));
+        std::vector<float> staged;
+        for (size_t j = 0; j < nd; j++) {
+            if (j == pv.dev) continue;
+            DeviceState& d = ctx->devs[j];
+            HIPCHK(ctx, hipSetDevice(d.device));
+            if (staged.empty() && hipMemcpyPeer(d.rf_verts, d.device, s.rf_verts, s.device, vbytes) == hipSuccess) continue;
+            (void)hipGetLastError(); // no peer copy between these two: through the host
+            if (staged.empty()) {
+                staged.resize(3 * (size_t)ctx->up_vertices);
+                HIPCHK(ctx, hipSetDevice(s.device));
+                HIPCHK(ctx, hipMemcpy(staged.data(), s.rf_verts, vbytes, hipMemcpyDeviceToHost));
+                HIPCHK(ctx, hipSetDevice(d.device));
+            }
+            HIPCHK(ctx, hipMemcpy(d.rf_verts, staged.data(), vbytes, hipMemcpyHostToDevice));
+        }
+    }
+    drop_grids(ctx);
+    if (!rebuild) {
+        if (int rc = ensure_refit_view(ctx)) return rc;
+        if (ctx->rf_n_dropped) { // a triangle the tree has no record of may have become finite: then only a new tree places it
+            DeviceState& d = ctx->devs[0];
+            uint32_t flag = 0;
+            HIPCHK(ctx, hipSetDevice(d.device));
+            HIPCHK(ctx, hipMemsetAsync(d.rf_flag, 0, sizeof(uint32_t), d.stream));
+            HIPCHK(ctx, rt::launch_refit_any_finite(d.rf_dropped, ctx->rf_n_dropped, d.rf_verts, d.rf_flag, d.stream));
+            HIPCHK(ctx, hipMemcpyAsync(&flag, d.rf_flag, sizeof flag, hipMemcpyDeviceToHost, d.stream));
+            HIPCHK(ctx, hipStreamSynchronize(d.stream));
+            rebuild = flag != 0;
+        }
+    }
+    if (rebuild) {
+        std::vector<float> staged;
+        const float* hv = reinterpret_cast<const float*>(vertices);
+        if (pv.device) {
+            if (int rc = read_positions(ctx, staged)) return rc;
+            hv = staged.data();
+        }
+        gather_positions(ctx, hv);
+        ctx->host_geometry_stale = false;
+        if (int rc = rebuild_tree(ctx)) return rc;
+        *stat_flags = RT_STAT_REBUILT;
+        return RT_OK;
+    }
+    // the refit: every device's launches are queued before any is waited for
+    const std::vector<uint32_t>& lv = ctx->rf_level_first;
+    for (auto& d : ctx->devs) {
+        HIPCHK(ctx, hipSetDevice(d.device));
+        HIPCHK(ctx, hipEventRecord(d.ev0, d.stream));
+        HIPCHK(ctx, rt::launch_refit_tris(d.tris, d.rf_vidx, d.rf_verts, ctx->scene_counts.n_tris, d.stream));
+        for (size_t l = lv.size() - 1; l-- > 0;) // deepest level first
+            HIPCHK(ctx, rt::launch_refit_nodes(d.nodes, d.rf_boxes, d.tris, d.rf_vidx, d.rf_verts, d.rf_order + lv[l], lv[l + 1] - lv[l], d.stream));
+        HIPCHK(ctx, hipEventRecord(d.ev1, d.stream));
+    }
+    for (auto& d : ctx->devs) {
+        HIPCHK(ctx, hipSetDevice(d.device));
+        HIPCHK(ctx, hipStreamSynchronize(d.stream));
+        float ms = 0.0f;
+        HIPCHK(ctx, hipEventElapsedTime(&ms, d.ev0, d.ev1));
+        *kernel_ms = std::max(*kernel_ms, (double)ms);
+    }
+    if (pv.device) ctx->host_geometry_stale = true; // read back when rt_prepare or the light grids need it
+    else {
+        gather_positions(ctx, reinterpret_cast<const float*>(vertices));
+        ctx->host_geometry_stale = false;
+    }
+    *stat_flags = RT_STAT_REFIT;
+    return RT_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int rt_update_geometry(rt_ctx* ctx, const rt_vertex* vertices, uint32_t n_vertices, const rt_sphere* spheres, uint32_t n_spheres, uint32_t flags) {
+    const double w0 = now_ms();
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (flags & ~RT_UPDATE_REBUILD) return ctx->fail(RT_ERR_BAD_ARG, "rt_update_geometry: unknown flag bits 0x%x", flags & ~RT_UPDATE_REBUILD);
+    if (!ctx->uploaded) return ctx->fail(RT_ERR_NOT_UPLOADED, "rt_update_geometry: no scene uploaded");
+    if (!vertices && n_vertices) return ctx->fail(RT_ERR_BAD_ARG, "rt_update_geometry: vertices is NULL with n_vertices = %u", n_vertices);
+    if (!spheres && n_spheres) return ctx->fail(RT_ERR_BAD_ARG, "rt_update_geometry: spheres is NULL with n_spheres = %u", n_spheres);
+    if (vertices && n_vertices != ctx->up_vertices)
+        return ctx->fail(RT_ERR_BAD_ARG, "rt_update_geometry: %u vertices, the scene was uploaded with %u", n_vertices, ctx->up_vertices);
+    if (spheres && n_spheres != ctx->scene_counts.n_spheres)
+        return ctx->fail(RT_ERR_BAD_ARG, "rt_update_geometry: %u spheres, the scene was uploaded with %u", n_spheres, ctx->scene_counts.n_spheres);
+    if (int rcp = sync_pending(ctx)) return rcp; // a dispatch in flight still reads the old positions
+    QueryPtr pv, ps;
+    if (vertices && n_vertices)
+        if (int rc = classify_ptr(ctx, "rt_update_geometry", "vertices", vertices, pv, 4)) return rc;
+    if (spheres && n_spheres)
+        if (int rc = classify_ptr(ctx, "rt_update_geometry", "spheres", spheres, ps, 4)) return rc;
+    uint32_t stat_flags = 0;
+    double kernel_ms = 0.0;
+    const int rc = update_geometry(ctx, n_vertices ? vertices : nullptr, pv, spheres, n_spheres, ps, (flags & RT_UPDATE_REBUILD) != 0, &stat_flags, &kernel_ms);
+    if (rc != RT_OK) { // as a failed upload: nothing is left pointing at half-written arrays (the last frame stays readable)
+        for (auto& d : ctx->devs) {
+            (void)hipSetDevice(d.device);
+            (void)hipDeviceSynchronize();
+            free_scene(d);
+        }
+        ctx->uploaded = false;
+        ctx->scene_counts = DevScene{};
+        ctx->rf_ready = false;
+        ctx->host_geometry_stale = false;
+        return rc;
+    }
+    rt_stats& st = ctx->stats;
+    st.rays = st.primary_rays = st.continuation_rays = st.shadow_rays = st.pixels = 0;
+    st.node_visits = st.tri_tests = 0;
+    st.flags = stat_flags;
+    st.kernel_ms = kernel_ms;
+    st.wall_ms = now_ms() - w0;
     return RT_OK;
 }
 

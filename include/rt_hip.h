@@ -123,6 +123,9 @@ typedef struct rt_stats {
 #define RT_STAT_SINGLE_PASS 2u /* extended mode: primary rays only (max_bounces 0) over a tiny tree: rendered by the one-pass kernel that
                                   keeps a pixel's samples in registers and stores it once (same image as the pipeline, several times faster) */
 
+#define RT_STAT_REFIT 4u   /* rt_update_geometry: the tree in use was refitted to the new positions (topology kept)                     */
+#define RT_STAT_REBUILT 8u /* rt_update_geometry: a new tree was built from the new positions (RT_UPDATE_REBUILD, or the fallback below) */
+
 #define RT_MAX_BOUNCES 255u /* extended mode: bounce depths travel in 8 bits, as in pack_flags (shared/src/lib.rs:1154-1179) */
 
 /* Create a context on `n_devices` HIP devices (ids in device_ids; NULL = device 0..n-1).
@@ -265,6 +268,40 @@ int rt_occluded(rt_ctx* ctx, const rt_ray* rays, size_t n, uint8_t* occluded, ui
  * Row-major, y down, tmin = RT_MIN_RAY_DISTANCE, tmax = FLT_MAX.  `out` (width * height records) may be host or
  * device memory, classified as for the queries.  Needs no scene.  Synchronous. */
 int rt_camera_rays(rt_ctx* ctx, const rt_camera* camera, uint32_t width, uint32_t height, uint32_t mode, rt_ray* out);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Geometry updates: new positions for the uploaded scene, in place (no reference counterpart; Embree's refit build,
+ * RTC_BUILD_QUALITY_REFIT, is the model).
+ *
+ * What changes: positions only - the vertex positions, and each sphere's centre, radius and material.  Triangles (their
+ * vertex indices and material ids), materials, lights and textures stay as uploaded; moving lights or changing the
+ * topology needs rt_upload_scene*.  A non-NULL array must hold exactly the count of the last upload (for
+ * rt_upload_scene_packed: offsets->vertices_count / spheres_count), else RT_ERR_BAD_ARG.  NULL with count 0: unchanged.
+ * Where the input may live: each pointer is classified as for the ray queries.  Host memory of any kind is accepted, and
+ * device memory of one of the context's devices (4-byte alignment is enough); on a context with several devices, device
+ * input is copied to the others (peer copy, or through the host).  Device-resident input must be complete before the call.
+ * Result: afterwards every frame mode, rt_dispatch_tile, rt_intersect, rt_occluded and rt_read_hits give exactly the bits a
+ * fresh rt_upload_scene of the moved scene gives, refitted or rebuilt, whichever tree was in use (device build, host build,
+ * RT_PREPARE_QUALITY_TREE).  By default the tree in use is REFITTED: its triangle records and node boxes follow the new
+ * positions, its topology stays, so a tree refitted across large motions gets slower to trace (not less exact);
+ * RT_UPDATE_REBUILD builds a new one instead, as rt_upload_scene* would.  A triangle with a non-finite vertex is never hit
+ * (the builders leave it out; a refit keeps its record, which no ray accepts).  A triangle that had a non-finite vertex at
+ * upload and is finite now has no record to refit: the call then rebuilds by itself.
+ * Derived state: a vertex update drops the light grids of the extended mode (rebuilt by the next frame that needs them, or
+ * rt_prepare); a sphere-only update keeps them.  rt_prepare(RT_PREPARE_QUALITY_TREE) afterwards builds from the new positions.
+ * Synchronous; first waits for an rt_dispatch_tile still in flight.  rt_read_* still return the last frame.
+ * Statistics: kernel_ms (HIP events around the refit kernels, max over devices; 0 for a rebuild), wall_ms, flags =
+ * RT_STAT_REFIT or RT_STAT_REBUILT (0 for a sphere-only update); bvh_nodes, bvh_depth, tree_build and scene_bytes describe
+ * the tree in use afterwards; rays and the other counts are 0.
+ * Errors: unknown flag bits and wrong counts are RT_ERR_BAD_ARG, a call before any upload RT_ERR_NOT_UPLOADED; these leave the
+ * scene untouched.  A HIP or allocation failure part way leaves the context "not uploaded", as a failed upload does.
+ * --------------------------------------------------------------------------------------------------------------- */
+#define RT_UPDATE_REBUILD 1u /* build a new tree from the new positions instead of refitting the current one */
+
+int rt_update_geometry(rt_ctx* ctx,
+                       const rt_vertex* vertices, uint32_t n_vertices, /* NULL: vertices unchanged */
+                       const rt_sphere* spheres, uint32_t n_spheres,   /* NULL: spheres unchanged  */
+                       uint32_t flags);
 
 /* Last error text of this context (or of the failed rt_create when ctx is NULL). */
 const char* rt_last_error(rt_ctx* ctx);
