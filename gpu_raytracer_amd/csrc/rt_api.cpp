@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/rt_hip.h"
@@ -61,7 +62,6 @@ struct DeviceState {
     std::vector<void*> grid_allocs;
     std::vector<rt::ShadowGridBuild> grid_info;
     bool grids_tried = false;                              // the light grids of the current scene were built (or refused) on this device
-    bool grids_partial = false;                            // ... and a light that has triangles to cast shadows was left without one: then no light keeps its grid
     rt::WfBuffers wf{};                                    // wavefront pipeline state (extended mode)
     rt::WfBuffers wf2{};                                   // ... of the second lane (its own path state, queues and counters; the pixel sums are shared)
     std::vector<void*> wf2_allocs;
@@ -100,8 +100,6 @@ struct rt_ctx {
     double stage_ms[2] = {0.0, 0.0};       // RT_FLAG_STAGE_TIMES: [0] sum of the k_wf_shadow_grid launch durations of the last frame (device 0), [1] launches
     int fail_upload_at = -1;          // test hook: the next scene upload fails before its k-th device array (rt_debug_fail_upload)
     uint32_t n_input_tris = 0;        // triangles handed to the last scene upload (prim ids are < this)
-    int build_method = 0;             // how its tree was built: 0 host SAH, 1 host PLOC, 2 device PLOC
-    uint32_t tree_tris_uploaded = 0;  // triangle records of the tree the devices hold (scene_bytes accounting across rt_prepare)
     std::vector<rt::BuildTri> build_tris; // the triangles of the last upload as the builders take them (rt_prepare RT_PREPARE_QUALITY_TREE rebuilds from them)
     std::vector<DevLight> host_lights; // what the lazy light-grid build needs of the last upload: the lights, ...
     float box_lo[3] = {0, 0, 0}, box_hi[3] = {0, 0, 0}; // ... the box of the triangles with finite vertices
@@ -152,16 +150,20 @@ void free_refit(DeviceState& d) { // the refit's view of a tree goes with the tr
     d.rf_boxes = nullptr;
 }
 
-void free_scene(DeviceState& d) {
+void free_grids(DeviceState& d) { // the light grids hold triangle records of one tree: built again when a frame or rt_prepare needs them
     (void)hipSetDevice(d.device);
-    (void)hipFree(d.nodes); (void)hipFree(d.tris); (void)hipFree(d.spheres); (void)hipFree(d.lights); (void)hipFree(d.materials);
-    d.nodes = nullptr; d.tris = nullptr; d.spheres = nullptr; d.lights = nullptr; d.materials = nullptr;
     for (void* p : d.grid_allocs) (void)hipFree(p);
     d.grid_allocs.clear();
     d.grid_info.clear();
     d.grids = nullptr;
     d.grids_tried = false;
-    d.grids_partial = false;
+}
+
+void free_scene(DeviceState& d) {
+    (void)hipSetDevice(d.device);
+    (void)hipFree(d.nodes); (void)hipFree(d.tris); (void)hipFree(d.spheres); (void)hipFree(d.lights); (void)hipFree(d.materials);
+    d.nodes = nullptr; d.tris = nullptr; d.spheres = nullptr; d.lights = nullptr; d.materials = nullptr;
+    free_grids(d);
     // the staging of the ray queries goes with the scene it was used for (released by the next upload and by rt_destroy)
     (void)hipFree(d.rq_in);
     (void)hipFree(d.rq_out);
@@ -289,35 +291,47 @@ int tree_method(size_t n_tris) {
     return method;
 }
 
-// A tree built for every device of the context, not yet handed over: per-device arrays of the device build, or the host build's.
-struct TreeBuild {
-    int method = 0; // as built: 2 device, 0 / 1 host (the device build falls back to 0)
-    std::vector<rt::DeviceBuild> dbuilds;
-    rt::BvhBuild bvh;
-    uint32_t nodes = 0, tris = 0, depth = 0;
-};
-
-void free_tree_build(rt_ctx* ctx, TreeBuild& tb) { // device-built arrays not (yet) handed to a device state
-    for (size_t j = 0; j < tb.dbuilds.size(); j++) {
-        (void)hipSetDevice(ctx->devs[j].device);
-        (void)hipFree(tb.dbuilds[j].nodes);
-        (void)hipFree(tb.dbuilds[j].tris);
-        tb.dbuilds[j].nodes = nullptr;
-        tb.dbuilds[j].tris = nullptr;
-    }
-}
-
-// The build part of a scene upload (and of rt_update_geometry's rebuild): `method` from tree_method.
-int build_tree(rt_ctx* ctx, const std::vector<rt::BuildTri>& bt, int method, TreeBuild& tb) {
+// The tuning knobs of the tree an upload or a rebuild makes (development).
+rt::BvhBuildOptions knob_build_options() {
     rt::BvhBuildOptions opt;
-    if (const char* e = std::getenv("RT_BVH_COST_TRAVERSE")) opt.cost_traverse = (float)std::atof(e); // tuning knobs (development)
+    if (const char* e = std::getenv("RT_BVH_COST_TRAVERSE")) opt.cost_traverse = (float)std::atof(e);
     if (const char* e = std::getenv("RT_BVH_MAX_LEAF")) opt.max_leaf = (uint32_t)std::atoi(e);
     if (const char* e = std::getenv("RT_BVH8_COST_TRAVERSE")) opt.cost_traverse8 = (float)std::atof(e);
-    if (const char* e = std::getenv("RT_BUILD_METHOD")) opt.method = std::atoi(e);
     if (const char* e = std::getenv("RT_BUILD_REINSERT")) opt.reinsert = std::atoi(e) != 0;
     if (const char* e = std::getenv("RT_PLOC_RADIUS")) opt.ploc_radius = (uint32_t)std::atoi(e);
+    return opt;
+}
+
+// A tree built for every device of the context, not yet handed over (install_tree).  Per device, `dev` holds the arrays of the
+// device build, or the host build's once install_tree has copied them there; whatever was not handed over is freed with it.
+struct TreeBuild {
+    int method = 0; // as built: 2 device, 0 / 1 host (the device build falls back to 0)
+    std::vector<int> device_ids; // of the context, in order
+    std::vector<rt::DeviceBuild> dev;
+    rt::BvhBuild bvh;
+    uint32_t nodes = 0, tris = 0, depth = 0;
+
+    explicit TreeBuild(const rt_ctx* ctx) {
+        for (const DeviceState& d : ctx->devs) device_ids.push_back(d.device);
+    }
+    TreeBuild(const TreeBuild&) = delete;
+    TreeBuild& operator=(const TreeBuild&) = delete;
+    ~TreeBuild() { free_dev(); }
+    void free_dev() {
+        for (size_t j = 0; j < dev.size(); j++) {
+            (void)hipSetDevice(device_ids[j]);
+            (void)hipFree(dev[j].nodes);
+            (void)hipFree(dev[j].tris);
+        }
+        dev.clear();
+    }
+};
+
+// The build part of a scene upload, of rt_update_geometry's rebuild (`method` from tree_method, `opt` from knob_build_options) and
+// of rt_prepare's quality tree (method 0, default options).
+int build_tree(rt_ctx* ctx, const std::vector<rt::BuildTri>& bt, int method, rt::BvhBuildOptions opt, TreeBuild& tb) {
     opt.method = method == 1 ? 1 : 0;
-    std::vector<rt::DeviceBuild>& dbuilds = tb.dbuilds;
+    std::vector<rt::DeviceBuild>& dbuilds = tb.dev;
     rt::BvhBuild& bvh = tb.bvh;
     if (method == 2) {
         dbuilds.resize(ctx->devs.size());
@@ -330,8 +344,7 @@ int build_tree(rt_ctx* ctx, const std::vector<rt::BuildTri>& bt, int method, Tre
                  dbuilds[j].n_nodes == dbuilds[0].n_nodes && dbuilds[j].n_tris == dbuilds[0].n_tris;
         }
         if (!ok) { // fall back to the host build (depth bound, or the device ran out of memory for the temporaries)
-            free_tree_build(ctx, tb);
-            dbuilds.clear();
+            tb.free_dev();
             method = 0;
         } else {
             tb.nodes = dbuilds[0].n_nodes;
@@ -351,17 +364,69 @@ int build_tree(rt_ctx* ctx, const std::vector<rt::BuildTri>& bt, int method, Tre
     return RT_OK;
 }
 
-// The hand-over part: device j's node / triangle arrays of a built tree (taken over from the device build, or uploaded).
-int take_nodes(rt_ctx* ctx, size_t j, TreeBuild& tb, DevNode8** dst) {
-    if (tb.dbuilds.empty()) return upload_array(ctx, dst, tb.bvh.nodes);
-    *dst = tb.dbuilds[j].nodes;
-    tb.dbuilds[j].nodes = nullptr;
-    return RT_OK;
+uint64_t scene_bytes(const DevScene& s) { // rt_stats.scene_bytes of the arrays the counts describe
+    return (uint64_t)s.n_nodes * sizeof(DevNode8) + (uint64_t)s.n_tris * sizeof(DevTri) + (uint64_t)s.n_spheres * sizeof(DevSphere) +
+           (uint64_t)s.n_lights * sizeof(DevLight) + (uint64_t)s.n_materials * sizeof(DevMaterial);
 }
-int take_tris(rt_ctx* ctx, size_t j, TreeBuild& tb, DevTri** dst) {
-    if (tb.dbuilds.empty()) return upload_array(ctx, dst, tb.bvh.tris);
-    *dst = tb.dbuilds[j].tris;
-    tb.dbuilds[j].tris = nullptr;
+
+void drop_grids(rt_ctx* ctx) {
+    for (auto& d : ctx->devs) free_grids(d);
+    ctx->stats.grid_bytes = 0;
+    ctx->stats.grid_build_ms = 0.0;
+}
+
+// The context holds no scene: what a failed upload or update leaves, and where an upload starts.  The caller decides about frame_valid.
+void drop_scene(rt_ctx* ctx) {
+    for (auto& d : ctx->devs) {
+        (void)hipSetDevice(d.device);
+        (void)hipDeviceSynchronize(); // launches in flight may still read the scene
+        free_scene(d);
+    }
+    ctx->uploaded = false;
+    ctx->scene_counts = DevScene{};
+    ctx->rf_ready = false;
+    ctx->host_geometry_stale = false;
+}
+
+int injected_oom(rt_ctx* ctx) { return ctx->fail(RT_ERR_OOM, "rt_upload: allocation failure injected by rt_debug_fail_upload"); }
+
+// The one way a tree goes onto the devices (scene uploads, rt_prepare's quality tree, rt_update_geometry's rebuild).  Every device
+// gets its new arrays before any old ones are freed, so a failure leaves the old tree in place on every device.  The light grids and
+// the refit's view go with the old tree.  `fail_at`: the upload's test hook (rt_debug_fail_upload), 0 before the first device's node
+// array, 1 before its triangle array.
+int install_tree(rt_ctx* ctx, TreeBuild& tb, int fail_at = -1) {
+    const bool copy = tb.dev.empty(); // a host build: copied to every device
+    if (copy) tb.dev.resize(ctx->devs.size());
+    for (size_t j = 0; j < ctx->devs.size(); j++) {
+        HIPCHK(ctx, hipSetDevice(ctx->devs[j].device));
+        if (j == 0 && fail_at == 0) return injected_oom(ctx);
+        if (copy)
+            if (int rc = upload_array(ctx, &tb.dev[j].nodes, tb.bvh.nodes)) return rc;
+        if (j == 0 && fail_at == 1) return injected_oom(ctx);
+        if (copy)
+            if (int rc = upload_array(ctx, &tb.dev[j].tris, tb.bvh.tris)) return rc;
+        // the copies went through the null stream and d.stream is non-blocking; launches in flight may still read the old tree
+        HIPCHK(ctx, hipDeviceSynchronize());
+    }
+    drop_grids(ctx);
+    for (size_t j = 0; j < ctx->devs.size(); j++) {
+        DeviceState& d = ctx->devs[j];
+        (void)hipSetDevice(d.device);
+        (void)hipFree(d.nodes);
+        (void)hipFree(d.tris);
+        d.nodes = std::exchange(tb.dev[j].nodes, nullptr);
+        d.tris = std::exchange(tb.dev[j].tris, nullptr);
+        free_refit(d);
+    }
+    DevScene& sc = ctx->scene_counts;
+    sc.n_nodes = tb.nodes;
+    sc.n_tris = tb.tris;
+    sc.stack_entries = 2u * tb.depth + 2u; // a visit parks at most two groups
+    ctx->stats.scene_bytes = scene_bytes(sc);
+    ctx->stats.bvh_nodes = tb.nodes;
+    ctx->stats.bvh_depth = tb.depth;
+    ctx->stats.tree_build = (uint32_t)tb.method;
+    ctx->rf_ready = false;
     return RT_OK;
 }
 
@@ -396,21 +461,8 @@ int upload_common(rt_ctx* ctx, const rt_sphere* spheres, uint32_t n_spheres, con
         bt[i].material_id = t.material_id;
         bt[i].prim_id = prim_ids.empty() ? (uint32_t)i : prim_ids[i];
     }
-    int method = tree_method(bt.size());
-    if (method == 2 && ctx->fail_upload_at == 0) {
-        ctx->fail_upload_at = -1;
-        ctx->uploaded = false;
-        ctx->frame_valid = false;
-        ctx->scene_counts = DevScene{};
-        for (auto& d : ctx->devs) free_scene(d);
-        return ctx->fail(RT_ERR_OOM, "rt_upload: allocation failure injected by rt_debug_fail_upload");
-    }
-    TreeBuild tb;
-    if (int rc = build_tree(ctx, bt, method, tb)) return rc;
-    method = tb.method;
-    const uint32_t tree_nodes = tb.nodes, tree_tris = tb.tris, tree_depth = tb.depth;
-    ctx->n_input_tris = (uint32_t)bt.size();
-    ctx->build_method = method;
+    TreeBuild tb(ctx);
+    if (int rc = build_tree(ctx, bt, tree_method(bt.size()), knob_build_options(), tb)) return rc;
 
     std::vector<DevSphere> ds(n_spheres);
     for (uint32_t i = 0; i < n_spheres; i++) {
@@ -450,23 +502,24 @@ int upload_common(rt_ctx* ctx, const rt_sphere* spheres, uint32_t n_spheres, con
     // From here on the old scene is gone: the context counts as "nothing uploaded" until EVERY device holds the whole new
     // scene, so a failure half way (out of memory on the triangles, or on the second device) leaves no stale counts
     // pointing at freed or partly filled arrays - the next rt_render answers RT_ERR_NOT_UPLOADED.
-    ctx->uploaded = false;
+    const rt_stats kept = ctx->stats; // what a failed upload leaves in rt_stats
+    drop_scene(ctx);
     ctx->frame_valid = false;
-    ctx->scene_counts = DevScene{};
-    for (auto& d : ctx->devs) free_scene(d);
-    float box_lo[3], box_hi[3]; // of the triangles with finite vertices
-    finite_box(bt, box_lo, box_hi);
-    auto upload_all = [&](DeviceState& d) -> int {
+    DevScene& sc = ctx->scene_counts;
+    sc.n_spheres = n_spheres;
+    sc.n_lights = n_lights;
+    sc.n_materials = n_materials;
+    ctx->stats = rt_stats{};
+    ctx->stats.node_bytes = sizeof(DevNode8);
+    ctx->stats.tri_bytes = sizeof(DevTri);
+    ctx->stats.n_devices = (uint32_t)ctx->devs.size();
+    ctx->stats.n_textures = ctx->n_textures;
+    ctx->stats.texture_bytes = ctx->texture_bytes;
+    const int fail_at = std::exchange(ctx->fail_upload_at, -1); // the test hook is one-shot
+    auto upload_rest = [&](DeviceState& d) -> int {
         HIPCHK(ctx, hipSetDevice(d.device));
+        if (&d == &ctx->devs[0] && fail_at == 2) return injected_oom(ctx);
         int rc;
-        int k = 0;
-        auto hook = [&]() { return ctx->fail_upload_at >= 0 && ctx->fail_upload_at == k++; }; // test hook (rt_debug_fail_upload)
-        const size_t j = (size_t)(&d - ctx->devs.data());
-        if (hook()) return ctx->fail(RT_ERR_OOM, "rt_upload: allocation failure injected by rt_debug_fail_upload");
-        if ((rc = take_nodes(ctx, j, tb, &d.nodes)) != RT_OK) return rc; // a device-built tree's arrays are taken over
-        if (hook()) return ctx->fail(RT_ERR_OOM, "rt_upload: allocation failure injected by rt_debug_fail_upload");
-        if ((rc = take_tris(ctx, j, tb, &d.tris)) != RT_OK) return rc;
-        if (hook()) return ctx->fail(RT_ERR_OOM, "rt_upload: allocation failure injected by rt_debug_fail_upload");
         if ((rc = upload_array(ctx, &d.spheres, ds)) != RT_OK) return rc;
         if ((rc = upload_array(ctx, &d.lights, dl)) != RT_OK) return rc;
         if ((rc = upload_array(ctx, &d.materials, dm)) != RT_OK) return rc;
@@ -474,46 +527,22 @@ int upload_common(rt_ctx* ctx, const rt_sphere* spheres, uint32_t n_spheres, con
         HIPCHK(ctx, hipDeviceSynchronize());
         return RT_OK;
     };
-    for (auto& d : ctx->devs) {
-        const int rc = upload_all(d);
-        if (rc != RT_OK) {
-            ctx->fail_upload_at = -1;
-            for (auto& e : ctx->devs) free_scene(e);
-            free_tree_build(ctx, tb); // device-built arrays not yet handed to a device state
-            return rc;
-        }
+    int rc = install_tree(ctx, tb, fail_at);
+    for (auto& d : ctx->devs)
+        if (rc == RT_OK) rc = upload_rest(d);
+    if (rc != RT_OK) {
+        drop_scene(ctx);
+        ctx->stats = kept;
+        return rc;
     }
-    ctx->fail_upload_at = -1;
-    DevScene& sc = ctx->scene_counts;
-    sc = DevScene{};
-    sc.n_nodes = tree_nodes;
-    sc.n_tris = tree_tris;
-    sc.n_spheres = n_spheres;
-    sc.n_lights = n_lights;
-    sc.n_materials = n_materials;
-    sc.stack_entries = 2u * tree_depth + 2u; // a visit parks at most two groups
-    ctx->stats = rt_stats{};
-    ctx->stats.node_bytes = sizeof(DevNode8);
-    ctx->stats.tri_bytes = sizeof(DevTri);
-    ctx->stats.scene_bytes = (size_t)tree_nodes * sizeof(DevNode8) + (size_t)tree_tris * sizeof(DevTri) + ds.size() * sizeof(DevSphere) +
-                             dl.size() * sizeof(DevLight) + dm.size() * sizeof(DevMaterial);
-    ctx->stats.bvh_nodes = sc.n_nodes;
-    ctx->stats.bvh_depth = tree_depth;
-    ctx->stats.tree_build = (uint32_t)method;
-    ctx->tree_tris_uploaded = tree_tris;
-    ctx->stats.n_devices = (uint32_t)ctx->devs.size();
-    ctx->stats.n_textures = ctx->n_textures;
-    ctx->stats.texture_bytes = ctx->texture_bytes;
+    ctx->n_input_tris = (uint32_t)bt.size();
     ctx->build_tris.swap(bt);
     ctx->up_triangles = tris;
     ctx->up_prim_ids = prim_ids;
     ctx->up_vertices = n_vertices;
-    ctx->rf_ready = false;
-    ctx->host_geometry_stale = false;
     ctx->host_lights = dl; // the light grids of the extended mode's shadow stage are built when a frame first needs them (ensure_grids)
-    for (int a = 0; a < 3; a++) ctx->box_lo[a] = box_lo[a], ctx->box_hi[a] = box_hi[a];
+    finite_box(ctx->build_tris, ctx->box_lo, ctx->box_hi);
     ctx->uploaded = true;
-    ctx->frame_valid = false;
     return RT_OK;
 }
 
@@ -547,7 +576,14 @@ int ensure_grids(rt_ctx* ctx, DeviceState& d) {
     rt::ShadowGridOptions lopt = gopt;
     lopt.max_bytes = free_b / 4 / n_lights;
     lopt.max_entries = std::min<uint64_t>(gopt.max_entries, lopt.max_bytes / (RT_SG_ENTRY_QUADS * sizeof(uint4)));
+    // an error return below frees what was built; grids_tried stays set, so the following frames render without grids and do not try again
+    struct Guard {
+        DeviceState& d;
+        bool ok = false;
+        ~Guard() { if (!ok) { free_grids(d); d.grids_tried = true; } }
+    } guard{d};
     uint64_t bytes = 0;
+    bool partial = false; // a light that has triangles to cast shadows was left without a grid: then no light keeps its grid
     for (uint32_t i = 0; i < n_lights; i++) {
         rt::ShadowGridBuild gb;
         const hipError_t e = rt::shadow_grid_build(d.tris, tree_tris, ctx->host_lights[i], ctx->box_lo, ctx->box_hi, lopt, d.stream, &gb);
@@ -560,35 +596,33 @@ int ensure_grids(rt_ctx* ctx, DeviceState& d) {
         if (gb.overflow) d.grid_allocs.push_back(gb.overflow);
         if (gb.grid.kind != RT_SG_KIND_NONE) bytes += gb.bytes;
         any = any || gb.grid.kind != RT_SG_KIND_NONE;
-        if (gb.grid.kind == RT_SG_KIND_NONE && gb.n_entries != 0) d.grids_partial = true; // lists were counted and found too long (or too large): this light's segments walk the tree
+        if (gb.grid.kind == RT_SG_KIND_NONE && gb.n_entries != 0) partial = true; // lists were counted and found too long (or too large): this light's segments walk the tree
         d.grid_info.push_back(gb);
     }
-    if (any && d.grids_partial) {
+    if (any && partial) {
         // All lights or none.  The segments of a light without a grid are handed on one wave-load at a time, an atomic on the next queue's
         // counter each: a trickle when the lists leave 0.1 - 20 % to the tree, but with a whole light's segments it is millions of atomics
         // on one address per frame (bistro-like with one light of four on lists: 67 - 81 ms against 54 - 60 with no grids at all).
         HIPCHK(ctx, hipDeviceSynchronize());
-        for (void* p : d.grid_allocs) (void)hipFree(p);
-        d.grid_allocs.clear();
-        for (uint32_t i = 0; i < n_lights; i++) {
-            hg[i] = DevShadowGrid{};
-            d.grid_info[i].grid = DevShadowGrid{};
-            d.grid_info[i].blocks = d.grid_info[i].overflow = nullptr;
-            d.grid_info[i].bytes = 0;
-        }
+        std::vector<rt::ShadowGridBuild> info = std::move(d.grid_info); // what the lists looked like stays readable (rt_debug_shadow_grid)
+        free_grids(d);
+        d.grids_tried = true;
+        for (rt::ShadowGridBuild& g : info) g.grid = DevShadowGrid{}, g.blocks = g.overflow = nullptr, g.bytes = 0;
+        d.grid_info = std::move(info);
         any = false;
         bytes = 0;
     }
     if (any) {
-        int rc;
-        if ((rc = upload_array(ctx, &d.grids, hg)) != RT_OK) return rc;
-        d.grid_allocs.push_back(d.grids);
+        const int rc = upload_array(ctx, &d.grids, hg);
+        d.grid_allocs.push_back(d.grids); // (also when its copy failed)
+        if (rc != RT_OK) return rc;
         HIPCHK(ctx, hipDeviceSynchronize());
     }
     if (&d == &ctx->devs[0]) { // (every device holds the same grids)
         ctx->stats.grid_bytes = bytes;
         ctx->stats.grid_build_ms = now_ms() - t0;
     }
+    guard.ok = true;
     return RT_OK;
 }
 
@@ -1272,7 +1306,7 @@ int rt_debug_check_bvh(rt_ctx* ctx, uint32_t out[8]) {
         out[2] = b.depth;
         out[3] = real_depth;
         out[4] = once;
-        out[5] = (uint32_t)ctx->build_method;
+        out[5] = ctx->stats.tree_build;
         auto fnv = [](const void* p, size_t n) {
             uint32_t h = 2166136261u;
             const unsigned char* c = static_cast<const unsigned char*>(p);
@@ -1296,65 +1330,12 @@ uint32_t rt_debug_pick_window(uint32_t iterations, uint32_t per_lane) { return r
 // scenes that stay: 0.35 s per 262 k triangles, 4.8 s for 3.8 M; frames 2 % (sponza-like) to 9 % (bistro-like) faster, same images (closest
 // hits do not depend on the tree).  The light grids hold triangle records in leaf order: they go with the old tree and are built again on demand.
 static int prepare_quality_tree(rt_ctx* ctx) {
-    if (ctx->build_method == 0 || ctx->build_tris.empty()) return RT_OK; // already the host builder's (tiny scenes, a fallback, an earlier call)
+    if (ctx->stats.tree_build == 0 || ctx->build_tris.empty()) return RT_OK; // already the host builder's (tiny scenes, a fallback, an earlier call)
     if (int rc = sync_host_geometry(ctx)) return rc; // positions an update left on the device
-    for (auto& d : ctx->devs) {
-        HIPCHK(ctx, hipSetDevice(d.device));
-        HIPCHK(ctx, hipDeviceSynchronize());
-    }
-    rt::BvhBuild bvh;
-    rt::BvhBuildOptions opt;
-    opt.method = 0;
-    rt::build_bvh(ctx->build_tris.data(), ctx->build_tris.size(), opt, bvh);
-    if (bvh.depth > RT_DEV_MAX_BVH_DEPTH || bvh.nodes.size() > RT_DEV_MAX_NODES || bvh.nodes.empty())
-        return ctx->fail(RT_ERR_INTERNAL, "rt_prepare: the host build gave %zu nodes at depth %u (the device-built tree stays)", bvh.nodes.size(), bvh.depth);
-    // new arrays first, so that a failure leaves the old tree in place
-    std::vector<DevNode8*> nn(ctx->devs.size(), nullptr);
-    std::vector<DevTri*> nt(ctx->devs.size(), nullptr);
-    int rc = RT_OK;
-    for (size_t j = 0; j < ctx->devs.size() && rc == RT_OK; j++) {
-        if (hipSetDevice(ctx->devs[j].device) != hipSuccess) rc = ctx->fail(RT_ERR_HIP, "rt_prepare: hipSetDevice failed");
-        if (rc == RT_OK) rc = upload_array(ctx, &nn[j], bvh.nodes);
-        if (rc == RT_OK) rc = upload_array(ctx, &nt[j], bvh.tris);
-    }
-    if (rc != RT_OK) {
-        for (size_t j = 0; j < ctx->devs.size(); j++) {
-            (void)hipSetDevice(ctx->devs[j].device);
-            (void)hipFree(nn[j]);
-            (void)hipFree(nt[j]);
-        }
-        return rc;
-    }
-    for (size_t j = 0; j < ctx->devs.size(); j++) {
-        DeviceState& d = ctx->devs[j];
-        (void)hipSetDevice(d.device);
-        (void)hipDeviceSynchronize();
-        (void)hipFree(d.nodes);
-        (void)hipFree(d.tris);
-        d.nodes = nn[j];
-        d.tris = nt[j];
-        free_refit(d);
-        for (void* p : d.grid_allocs) (void)hipFree(p);
-        d.grid_allocs.clear();
-        d.grid_info.clear();
-        d.grids = nullptr;
-        d.grids_tried = false;
-        d.grids_partial = false;
-    }
-    DevScene& sc = ctx->scene_counts;
-    sc.n_nodes = (uint32_t)bvh.nodes.size();
-    sc.n_tris = (uint32_t)bvh.tris.size();
-    sc.stack_entries = 2u * bvh.depth + 2u;
-    ctx->stats.scene_bytes += (uint64_t)bvh.nodes.size() * sizeof(DevNode8) + (uint64_t)bvh.tris.size() * sizeof(DevTri) -
-                              ((uint64_t)ctx->stats.bvh_nodes * sizeof(DevNode8) + (uint64_t)ctx->tree_tris_uploaded * sizeof(DevTri));
-    ctx->tree_tris_uploaded = sc.n_tris;
-    ctx->stats.bvh_nodes = sc.n_nodes;
-    ctx->stats.bvh_depth = bvh.depth;
-    ctx->stats.grid_bytes = 0;
-    ctx->stats.grid_build_ms = 0.0;
-    ctx->stats.tree_build = 0;
-    ctx->build_method = 0;
-    ctx->rf_ready = false;
+    TreeBuild tb(ctx);
+    if (build_tree(ctx, ctx->build_tris, 0, rt::BvhBuildOptions{}, tb) != RT_OK || tb.bvh.nodes.empty())
+        return ctx->fail(RT_ERR_INTERNAL, "rt_prepare: the host build gave %zu nodes at depth %u (the device-built tree stays)", tb.bvh.nodes.size(), tb.bvh.depth);
+    if (int rc = install_tree(ctx, tb)) return rc;
     ctx->frame_valid = false;
     return RT_OK;
 }
@@ -1866,7 +1847,7 @@ int rt_camera_rays(rt_ctx* ctx, const rt_camera* camera, uint32_t width, uint32_
 // ---------------------------------------------------------------------------------------------------------------------------------
 // rt_update_geometry: new positions for the uploaded scene's vertices and spheres.  The tree in use is refitted (refit.hip: the
 // triangle records and the node boxes follow the positions, the topology stays) or, on request or when a triangle the tree has no
-// record of became finite, rebuilt through the upload's own build and hand-over (build_tree / take_nodes / take_tris).
+// record of became finite, rebuilt through the upload's own build and hand-over (build_tree / install_tree).
 // ---------------------------------------------------------------------------------------------------------------------------------
 namespace {
 
@@ -1985,58 +1966,6 @@ int ensure_refit_view(rt_ctx* ctx) {
     return RT_OK;
 }
 
-void drop_grids(rt_ctx* ctx) { // the light grids hold the old triangles: built again when a frame or rt_prepare needs them
-    for (auto& d : ctx->devs) {
-        (void)hipSetDevice(d.device);
-        for (void* p : d.grid_allocs) (void)hipFree(p);
-        d.grid_allocs.clear();
-        d.grid_info.clear();
-        d.grids = nullptr;
-        d.grids_tried = false;
-        d.grids_partial = false;
-    }
-    ctx->stats.grid_bytes = 0;
-    ctx->stats.grid_build_ms = 0.0;
-}
-
-// A new tree from build_tris (already holding the new positions), built and handed over as rt_upload_scene* does it.
-int rebuild_tree(rt_ctx* ctx) {
-    TreeBuild tb;
-    if (int rc = build_tree(ctx, ctx->build_tris, tree_method(ctx->build_tris.size()), tb)) {
-        free_tree_build(ctx, tb);
-        return rc;
-    }
-    const uint64_t old_bytes = (uint64_t)ctx->stats.bvh_nodes * sizeof(DevNode8) + (uint64_t)ctx->tree_tris_uploaded * sizeof(DevTri);
-    for (size_t j = 0; j < ctx->devs.size(); j++) {
-        DeviceState& d = ctx->devs[j];
-        HIPCHK(ctx, hipSetDevice(d.device));
-        HIPCHK(ctx, hipDeviceSynchronize());
-        (void)hipFree(d.nodes);
-        (void)hipFree(d.tris);
-        d.nodes = nullptr;
-        d.tris = nullptr;
-        free_refit(d);
-        int rc;
-        if ((rc = take_nodes(ctx, j, tb, &d.nodes)) != RT_OK || (rc = take_tris(ctx, j, tb, &d.tris)) != RT_OK) {
-            free_tree_build(ctx, tb);
-            return rc;
-        }
-        HIPCHK(ctx, hipDeviceSynchronize()); // upload_array copies on the null stream
-    }
-    DevScene& sc = ctx->scene_counts;
-    sc.n_nodes = tb.nodes;
-    sc.n_tris = tb.tris;
-    sc.stack_entries = 2u * tb.depth + 2u;
-    ctx->stats.scene_bytes += (uint64_t)tb.nodes * sizeof(DevNode8) + (uint64_t)tb.tris * sizeof(DevTri) - old_bytes;
-    ctx->stats.bvh_nodes = tb.nodes;
-    ctx->stats.bvh_depth = tb.depth;
-    ctx->stats.tree_build = (uint32_t)tb.method;
-    ctx->tree_tris_uploaded = tb.tris;
-    ctx->build_method = tb.method;
-    ctx->rf_ready = false;
-    return RT_OK;
-}
-
 // Everything after the argument checks; a failure here leaves the context "not uploaded" (rt_update_geometry).
 int update_geometry(rt_ctx* ctx, const rt_vertex* vertices, const QueryPtr& pv, const rt_sphere* spheres, uint32_t n_spheres, const QueryPtr& ps,
                     bool rebuild, uint32_t* stat_flags, double* kernel_ms) {
@@ -2114,7 +2043,9 @@ int update_geometry(rt_ctx* ctx, const rt_vertex* vertices, const QueryPtr& pv, 
         }
         gather_positions(ctx, hv);
         ctx->host_geometry_stale = false;
-        if (int rc = rebuild_tree(ctx)) return rc;
+        TreeBuild tb(ctx);
+        if (int rc = build_tree(ctx, ctx->build_tris, tree_method(ctx->build_tris.size()), knob_build_options(), tb)) return rc;
+        if (int rc = install_tree(ctx, tb)) return rc;
         *stat_flags = RT_STAT_REBUILT;
         return RT_OK;
     }
@@ -2169,15 +2100,7 @@ int rt_update_geometry(rt_ctx* ctx, const rt_vertex* vertices, uint32_t n_vertic
     double kernel_ms = 0.0;
     const int rc = update_geometry(ctx, n_vertices ? vertices : nullptr, pv, spheres, n_spheres, ps, (flags & RT_UPDATE_REBUILD) != 0, &stat_flags, &kernel_ms);
     if (rc != RT_OK) { // as a failed upload: nothing is left pointing at half-written arrays (the last frame stays readable)
-        for (auto& d : ctx->devs) {
-            (void)hipSetDevice(d.device);
-            (void)hipDeviceSynchronize();
-            free_scene(d);
-        }
-        ctx->uploaded = false;
-        ctx->scene_counts = DevScene{};
-        ctx->rf_ready = false;
-        ctx->host_geometry_stale = false;
+        drop_scene(ctx);
         return rc;
     }
     rt_stats& st = ctx->stats;

@@ -332,3 +332,24 @@ def test_context_with_several_devices(soup):
         with api.Context((0, 1)) as ref2:
             ref2.upload_scene(_moved(soup, dev.cpu().numpy()))
             _assert_same(ctx, ref2, _moved(soup, dev.cpu().numpy()))
+
+
+# 11 -----------------------------------------------------------------------------------------------------------------------
+def test_tree_stats_are_those_of_an_upload_of_that_tree(soup, monkeypatch):
+    """rt_prepare(RT_PREPARE_QUALITY_TREE) reports the tree it put in place as an upload that builds the same tree reports it
+    (scene_bytes included), and a fresh upload of the scene afterwards reports what the first upload did."""
+    keys = ("scene_bytes", "bvh_nodes", "bvh_depth", "tree_build", "grid_bytes", "grid_build_ms")
+    monkeypatch.setenv("RT_BUILD_METHOD", "0")  # the host builder's tree: the one rt_prepare builds
+    with _upload(soup) as host:
+        want = {k: host.stats()[k] for k in keys}
+        want_hash = _clean(host)["nodes_hash"]
+    monkeypatch.delenv("RT_BUILD_METHOD")
+    with _upload(soup) as ctx:
+        first = {k: ctx.stats()[k] for k in keys}
+        assert first["tree_build"] == 2
+        ctx.prepare(api.PREPARE_SHADOW_GRIDS)  # light grids, which go with the device-built tree
+        assert ctx.stats()["grid_bytes"] > 0
+        ctx.prepare(api.PREPARE_QUALITY_TREE)
+        assert {k: ctx.stats()[k] for k in keys} == want and _clean(ctx)["nodes_hash"] == want_hash
+        ctx.upload_scene(soup)
+        assert {k: ctx.stats()[k] for k in keys} == first
