@@ -6,7 +6,8 @@
 // presented frame until the progressive image is complete (src/compute.rs:12-251; TileHelper::calculate_tiles_per_frame
 // tiles per call, three colour-channel dispatches per tile) -> the display combine of main_fs (shader/src/lib.rs:383-388)
 // -> an image file (the reference has no image output; PLAN.md lists it as future), and prints the completion summary of
-// src/compute.rs:320-363.  With --spp/--bounces it renders the extended mode through rt_render instead.
+// src/compute.rs:320-363.  With --spp/--bounces it renders the extended mode through rt_render instead; --progressive N refines that
+// image over N accumulating calls (RT_FLAG_ACCUMULATE), the extended mode's counterpart of the progressive tile loop.
 //
 // Build (done by __graft_entry__.build()):
 //   g++ -std=c++17 -O2 examples/rt_render.cpp -Iinclude -Igpu_raytracer_amd/csrc -Lgpu_raytracer_amd -lrt_hip
@@ -34,10 +35,12 @@ static double now_ms() {
 
 static int usage(const char* argv0, int rc) {
     std::fprintf(rc ? stderr : stdout,
-                 "usage: %s [--gltf FILE.gltf|.glb] [--size WxH] [--out FILE.png|.ppm|.exr] [--spp N --bounces B] [--fly FRAMES] [--device D]\n"
+                 "usage: %s [--gltf FILE.gltf|.glb] [--size WxH] [--out FILE.png|.ppm|.exr] [--spp N --bounces B [--progressive C]] [--fly FRAMES] [--device D]\n"
                  "  without --gltf the reference's default scene (6 spheres, 2 triangles, 1 light) is rendered;\n"
                  "  without --spp the reference path runs: progressive 128x128 tiles, three channel dispatches per tile;\n"
                  "  with --spp N the extended mode (jittered samples, shadow rays, --bounces B, default 4) runs through rt_render;\n"
+                 "  with --progressive C as well, C accumulating calls of N spp each refine one image of C*N samples (the same image as\n"
+                 "  --spp C*N when C*N >= 2); each call's time and the running sample count are printed;\n"
                  "  with --fly FRAMES a scripted fly-through (CameraController deltas of src/input.rs) renders FRAMES whole frames with\n"
                  "  the reference semantics, reads each back and reports frames per second; the last frame is written.\n",
                  argv0);
@@ -46,7 +49,7 @@ static int usage(const char* argv0, int rc) {
 
 int main(int argc, char** argv) {
     std::string gltf, out = "out.png";
-    uint32_t width = 800, height = 600, spp = 0, bounces = 4, fly = 0;
+    uint32_t width = 800, height = 600, spp = 0, bounces = 4, fly = 0, progressive = 0;
     int device = 0;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -61,9 +64,11 @@ int main(int argc, char** argv) {
         } else if (a == "--spp") spp = (uint32_t)std::atoi(v);
         else if (a == "--bounces") bounces = (uint32_t)std::atoi(v);
         else if (a == "--fly") fly = (uint32_t)std::atoi(v);
+        else if (a == "--progressive") progressive = (uint32_t)std::atoi(v);
         else if (a == "--device") device = std::atoi(v);
         else return usage(argv[0], 2);
     }
+    if (progressive && !spp) return usage(argv[0], 2); // accumulation is the extended mode's
 
     // ---- scene (src/scene.rs) ----
     SceneState scene;
@@ -156,9 +161,24 @@ int main(int argc, char** argv) {
         p.max_bounces = bounces;
         p.mode = RT_MODE_EXTENDED;
         p.tile_world = 1;
-        rc = rt_render(ctx, &p);
-        if (rc != RT_OK) return fail("rt_render", rc);
         rt_stats st;
+        if (progressive) { // what a viewport does: show the image after every call, each call adds spp samples to it
+            p.flags = RT_FLAG_ACCUMULATE | RT_FLAG_ACCUMULATE_RESTART;
+            for (uint32_t c = 0; c < progressive; c++) {
+                const double c0 = now_ms();
+                rc = rt_render(ctx, &p);
+                if (rc != RT_OK) return fail("rt_render", rc);
+                const double call_ms = now_ms() - c0;
+                uint32_t samples = 0;
+                rt_accumulated_samples(ctx, &samples);
+                rt_get_stats(ctx, &st);
+                std::printf("progressive call %u: %.2f ms (%.2f ms on the device), %u samples accumulated\n", c + 1, call_ms, st.kernel_ms, samples);
+                p.flags = RT_FLAG_ACCUMULATE;
+            }
+        } else {
+            rc = rt_render(ctx, &p);
+            if (rc != RT_OK) return fail("rt_render", rc);
+        }
         rt_get_stats(ctx, &st);
         std::printf("extended mode: %u spp, %u bounces: %.2f ms on the device, %.1f M segments (%.1f camera, %.1f continuation, %.1f shadow), %.0f Mrays/s\n", spp,
                     bounces, st.kernel_ms, st.rays / 1e6, st.primary_rays / 1e6, st.continuation_rays / 1e6, st.shadow_rays / 1e6,

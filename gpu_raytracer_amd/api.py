@@ -26,6 +26,9 @@ FLAG_NO_SHADOW_GRID = 16
 FLAG_KERNEL_PIPELINE = 32
 FLAG_NO_BEAMS = 64
 FLAG_STAGE_TIMES = 128
+FLAG_ACCUMULATE = 256  # RT_FLAG_ACCUMULATE: add this call's samples to the context's running image (extended mode)
+FLAG_ACCUMULATE_RESTART = 512  # RT_FLAG_ACCUMULATE_RESTART: ... starting a new one at sample 0
+ACCUMULATE_MAX_SAMPLES = 1 << 24  # RT_ACCUMULATE_MAX_SAMPLES
 PREPARE_SHADOW_GRIDS = 1
 PREPARE_QUALITY_TREE = 2
 QUERY_COUNTERS = 1  # RT_QUERY_COUNTERS of rt_intersect / rt_occluded
@@ -43,6 +46,7 @@ ABI_SYMBOLS = [
     "rt_get_stats", "rt_last_error", "rt_destroy", "rt_version",
     "rt_intersect", "rt_occluded", "rt_camera_rays",
     "rt_update_geometry",
+    "rt_accumulated_samples",
 ]
 
 
@@ -263,15 +267,27 @@ class Context:
 
     # -- rendering -------------------------------------------------------------------
     def render(self, width, height, camera, mode=MODE_LEGACY, spp=1, max_bounces=4, frame_seed=0, tile_size=0,
-               tile_rank=0, tile_world=1, counters=False, no_shadows=False, kernel_v1=False, kernel_sm=False, no_shadow_grid=False, kernel_pipeline=False, no_beams=False, stage_times=False):
+               tile_rank=0, tile_world=1, counters=False, no_shadows=False, kernel_v1=False, kernel_sm=False, no_shadow_grid=False, kernel_pipeline=False, no_beams=False, stage_times=False,
+               accumulate=False, restart=False):
+        """rt_render.  accumulate=True (extended mode): add the spp samples to the context's running image and leave the mean over all of
+        them in the targets (accumulated_samples() tells how many); restart=True with it starts a new running image at sample 0."""
+        if restart and not accumulate:
+            raise ValueError("render: restart=True needs accumulate=True")
         p = np.zeros((), dtype=T.RENDER_PARAMS)
         p["camera"] = camera
         p["width"], p["height"], p["spp"], p["max_bounces"], p["mode"] = width, height, spp, max_bounces, mode
         p["frame_seed"], p["tile_size"], p["tile_rank"], p["tile_world"] = frame_seed, tile_size, tile_rank, tile_world
         p["flags"] = (FLAG_COUNTERS if counters else 0) | (FLAG_NO_SHADOWS if no_shadows else 0) | (FLAG_KERNEL_V1 if kernel_v1 else 0) | (FLAG_KERNEL_SM if kernel_sm else 0) | (FLAG_NO_SHADOW_GRID if no_shadow_grid else 0) | (FLAG_KERNEL_PIPELINE if kernel_pipeline else 0) | (FLAG_NO_BEAMS if no_beams else 0) | (FLAG_STAGE_TIMES if stage_times else 0)
+        p["flags"] |= (FLAG_ACCUMULATE if accumulate else 0) | (FLAG_ACCUMULATE_RESTART if restart else 0)
         self._check(self.lib.rt_render(self._h, _p(p)))
         self.width, self.height = width, height
         return self.stats()
+
+    def accumulated_samples(self):
+        """rt_accumulated_samples: samples in the running image of the accumulating renders (0: none)."""
+        n = C.c_uint32(0)
+        self._check(self.lib.rt_accumulated_samples(self._h, C.byref(n)))
+        return n.value
 
     def dispatch_tile(self, pc):
         pcb = np.ascontiguousarray(pc)

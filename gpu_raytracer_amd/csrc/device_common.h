@@ -516,6 +516,18 @@ __device__ __forceinline__ SimpleRng rng_for(uint32_t pixel_seed, uint32_t sampl
     return SimpleRng{h};
 }
 
+// Progressive accumulation (RT_FLAG_ACCUMULATE): a pixel's sum starts from the samples earlier calls left in
+// DevTargets::run_sum (zero for a closed frame or the first call of an accumulation) and goes back there with this launch's samples added,
+// in sample order, so that the image equals one frame of all the samples.
+__device__ __forceinline__ V3 run_sum_start(const DevFrame& fr, const DevTargets& tg, size_t pix) {
+    if (!tg.run_sum || fr.sample_base == 0) return v3(0.0f, 0.0f, 0.0f);
+    const float4 a = reinterpret_cast<const float4*>(tg.run_sum)[pix];
+    return v3(a.x, a.y, a.z);
+}
+__device__ __forceinline__ void run_sum_keep(const DevTargets& tg, size_t pix, V3 sum) {
+    if (tg.run_sum) reinterpret_cast<float4*>(tg.run_sum)[pix] = make_float4(sum.x, sum.y, sum.z, 0.0f);
+}
+
 // sin/cos(2*pi*u) as explicit-fma polynomials: identical bits on the host oracle and here.
 __device__ __forceinline__ void sincos_2pi(float u, float& s_out, float& c_out) {
     float f4 = u * 4.0f;

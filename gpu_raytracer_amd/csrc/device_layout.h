@@ -127,8 +127,12 @@ struct DevFrame {
     uint32_t mode;                                   // RT_MODE_*
     uint32_t channel_mask;                           // bit c set: write channel texture c (rt_dispatch_tile writes one)
     uint32_t cur_bounce, max_bounce;                 // mode 1 pass selection (shader/src/lib.rs:117-121)
-    uint32_t spp, frame_seed;
+    uint32_t spp, frame_seed;                        // spp: samples of THIS launch (loop length, batch sizing)
     uint32_t flags;                                  // RT_FLAG_* of rt_render_params
+    // extended mode: the samples of this launch are the global samples sample_base .. sample_base + spp - 1 (their seeds); the image is the
+    // running sum divided by n_total; jitter != 0: sub-pixel jitter, else the pixel centre.  A closed frame: 0, spp, spp > 1; an
+    // accumulating call (RT_FLAG_ACCUMULATE): the samples already in DevTargets::run_sum, their count + spp, 1
+    uint32_t sample_base, n_total, jitter;
     // when single_tile != 0 the launch covers exactly one tile given explicitly (rt_dispatch_tile)
     uint32_t single_tile, tile_off_x, tile_off_y, tile_w, tile_h;
 };
@@ -139,6 +143,8 @@ struct DevTargets {
     uint32_t* prim_id;   // per-pixel closest primitive (modes 0/1)
     float* hit_t;        // per-pixel hit distance       (modes 0/1)
     unsigned long long* counters; // RT_CNT_SLOTS words, DevCounterSlot
+    float* run_sum;      // RT_FLAG_ACCUMULATE frames only (else null): per pixel (width*height x 4 floats: r, g, b, 0) the running sum over the samples so far;
+                         // read at the start when DevFrame::sample_base > 0, written back with this launch's samples added
 };
 
 // Slots of DevTargets::counters (zeroed per frame and device; rt_intersect / rt_occluded zero the first three).  Written by k_render_reference,

@@ -92,9 +92,9 @@ __device__ __forceinline__ V3 ext_direct(const DevScene& sc, const DevMaterial& 
 template <bool COUNT>
 __device__ __forceinline__ V3 ext_trace_path(const DevScene& sc, const DevFrame& fr, uint32_t px, uint32_t py, uint32_t sample,
                                              uint2* stack, Counts& cnt, SegCounts& seg) {
-    SimpleRng rng = rng_for(fr.frame_seed + px + py * fr.width, sample);
+    SimpleRng rng = rng_for(fr.frame_seed + px + py * fr.width, sample); // sample: the global index (DevFrame::sample_base + k)
     float jx = 0.5f, jy = 0.5f;
-    if (fr.spp > 1) {
+    if (fr.jitter) {
         jx = rng.next_f32();
         jy = rng.next_f32();
     }
@@ -192,11 +192,12 @@ __global__ __launch_bounds__(WAVE) void k_render_extended(DevScene sc, DevFrame 
     Counts cnt = {0u, 0u};
     SegCounts seg = {0u, 0u, 0u};
     if (px.valid) {
-        V3 sum = v3(0.0f, 0.0f, 0.0f);
-        for (uint32_t s = 0; s < fr.spp; s++) sum = sum + ext_trace_path<COUNT>(sc, fr, px.x, px.y, s, stack, cnt, seg);
-        float n = (float)fr.spp;
-        V3 color = v3(sum.x / n, sum.y / n, sum.z / n);
         const size_t pix = (size_t)px.y * fr.width + px.x;
+        V3 sum = run_sum_start(fr, tg, pix);
+        for (uint32_t s = 0; s < fr.spp; s++) sum = sum + ext_trace_path<COUNT>(sc, fr, px.x, px.y, fr.sample_base + s, stack, cnt, seg);
+        run_sum_keep(tg, pix, sum);
+        float n = (float)fr.n_total;
+        V3 color = v3(sum.x / n, sum.y / n, sum.z / n);
         if (tg.rgba32f) reinterpret_cast<float4*>(tg.rgba32f)[pix] = make_float4(color.x, color.y, color.z, 1.0f);
         if (tg.chan[0]) reinterpret_cast<uint32_t*>(tg.chan[0])[pix] = unorm8(color.x) | 0xFF000000u;
         if (tg.chan[1]) reinterpret_cast<uint32_t*>(tg.chan[1])[pix] = (unorm8(color.y) << 8) | 0xFF000000u;
@@ -274,6 +275,7 @@ __global__ __launch_bounds__(WAVE, RT_SM_MIN_WAVES) void k_render_extended_sm(De
     uint32_t oct = 0;
     int sp = 0;
     bool anyhit = false;
+    if (px.valid) sum = run_sum_start(fr, tg, (size_t)px.y * fr.width + px.x); // the samples earlier calls of an accumulation left
 
     // start a segment: spheres are tested right away (wave-uniform loop), the BVH walk is deferred to the traversal phase
     auto begin_segment = [&](V3 so, V3 sd, float tmax, bool any) {
@@ -310,9 +312,10 @@ __global__ __launch_bounds__(WAVE, RT_SM_MIN_WAVES) void k_render_extended_sm(De
         while (state != ST_TRAVERSING && state != ST_DONE) {
             if (state == ST_NEW_SAMPLE) {
                 if (sample >= fr.spp) {
-                    float n = (float)fr.spp;
-                    V3 color = v3(sum.x / n, sum.y / n, sum.z / n);
                     const size_t pix = (size_t)px.y * fr.width + px.x;
+                    run_sum_keep(tg, pix, sum);
+                    float n = (float)fr.n_total;
+                    V3 color = v3(sum.x / n, sum.y / n, sum.z / n);
                     if (tg.rgba32f) reinterpret_cast<float4*>(tg.rgba32f)[pix] = make_float4(color.x, color.y, color.z, 1.0f);
                     if (tg.chan[0]) reinterpret_cast<uint32_t*>(tg.chan[0])[pix] = unorm8(color.x) | 0xFF000000u;
                     if (tg.chan[1]) reinterpret_cast<uint32_t*>(tg.chan[1])[pix] = (unorm8(color.y) << 8) | 0xFF000000u;
@@ -320,9 +323,9 @@ __global__ __launch_bounds__(WAVE, RT_SM_MIN_WAVES) void k_render_extended_sm(De
                     state = ST_DONE;
                     break;
                 }
-                rng = rng_for(fr.frame_seed + px.x + px.y * fr.width, sample);
+                rng = rng_for(fr.frame_seed + px.x + px.y * fr.width, fr.sample_base + sample);
                 float jx = 0.5f, jy = 0.5f;
-                if (fr.spp > 1) {
+                if (fr.jitter) {
                     jx = rng.next_f32();
                     jy = rng.next_f32();
                 }

@@ -82,6 +82,18 @@ struct DeviceState {
     uint32_t* rf_dropped = nullptr; // vertex indices of the triangles the tree has no record of (non-finite at upload)
     uint32_t* rf_flag = nullptr;
     float* rf_verts = nullptr;     // the positions of the last update (3 floats per vertex)
+    // RT_FLAG_ACCUMULATE: the running sum of the context's accumulation over this device's pixels (DevTargets::run_sum), frame-pixel layout,
+    // run_sum_w x run_sum_h x 16 bytes.  Outlives the pipeline's WfBuffers (re-sized with the batch); made by the first accumulating call, freed
+    // with the scene
+    float* run_sum = nullptr;
+    uint32_t run_sum_w = 0, run_sum_h = 0;
+};
+
+// What an accumulating rt_render must share with the previous one to continue its running image (rt_hip.h, RT_FLAG_ACCUMULATE): the
+// parameters that change the bits of a sample.  Compared bytewise (all 4-byte fields, no padding): the camera bit for bit.
+struct AccumKey {
+    rt_camera camera;
+    uint32_t width, height, max_bounces, frame_seed, tile_size, tile_rank, tile_world, no_shadows;
 };
 
 } // namespace
@@ -112,6 +124,8 @@ struct rt_ctx {
     bool host_geometry_stale = false;      // build_tris / box_lo / box_hi lag behind device-resident positions in devs[0].rf_verts
     uint32_t n_textures = 0;          // bindings 6-7 as last handed over (rt_upload_textures); never sampled, like the reference
     uint64_t texture_bytes = 0;
+    AccumKey acc_key{};               // RT_FLAG_ACCUMULATE: the parameters of the running image ...
+    uint32_t acc_samples = 0;         // ... and its sample count (0: none; the next accumulating call starts at sample 0)
 
     int fail(int code, const char* fmt, ...) {
         char buf[512];
@@ -172,6 +186,9 @@ void free_scene(DeviceState& d) {
     free_refit(d);
     (void)hipFree(d.rf_verts);
     d.rf_verts = nullptr;
+    (void)hipFree(d.run_sum); // the running image of an accumulation ends with the scene it was rendered from
+    d.run_sum = nullptr;
+    d.run_sum_w = d.run_sum_h = 0;
 }
 void free_targets(DeviceState& d) {
     (void)hipSetDevice(d.device);
@@ -266,14 +283,36 @@ DevScene scene_for(const rt_ctx* ctx, const DeviceState& d) {
     return s;
 }
 
-DevTargets targets_for(const DeviceState& d) {
+DevTargets targets_for(const DeviceState& d, const DevFrame& f) {
     DevTargets t;
     t.rgba32f = d.rgba32f;
     for (int c = 0; c < 3; c++) t.chan[c] = d.chan[c];
     t.prim_id = d.prim_id;
     t.hit_t = d.hit_t;
     t.counters = d.counters;
+    t.run_sum = (f.flags & RT_FLAG_ACCUMULATE) ? d.run_sum : nullptr;
     return t;
+}
+
+// The context's running image ends: the next accumulating rt_render starts at sample 0 (its buffers stay for it).  Called by the scene's
+// owners (drop_scene, rt_update_geometry), by every frame or dispatch that is not an accumulating one, and by an accumulating call before
+// its launches, so that a call that fails part way never leaves a half-added sum counted.
+void end_accumulation(rt_ctx* ctx) { ctx->acc_samples = 0; }
+
+// The running sums of an accumulating frame of width x height, one per device (its share of the pixels is written, the rest never read).
+int ensure_run_sums(rt_ctx* ctx, uint32_t w, uint32_t h) {
+    for (auto& d : ctx->devs) {
+        if (d.run_sum && d.run_sum_w == w && d.run_sum_h == h) continue;
+        HIPCHK(ctx, hipSetDevice(d.device));
+        if (d.stream) HIPCHK(ctx, hipStreamSynchronize(d.stream));
+        (void)hipFree(d.run_sum);
+        d.run_sum = nullptr;
+        d.run_sum_w = d.run_sum_h = 0;
+        HIPCHK(ctx, hipMalloc((void**)&d.run_sum, (size_t)w * h * 16)); // not cleared: a first call (sample_base 0) reads none of it
+        d.run_sum_w = w;
+        d.run_sum_h = h;
+    }
+    return RT_OK;
 }
 
 int sync_pending(rt_ctx* ctx);
@@ -386,6 +425,7 @@ void drop_scene(rt_ctx* ctx) {
     ctx->scene_counts = DevScene{};
     ctx->rf_ready = false;
     ctx->host_geometry_stale = false;
+    end_accumulation(ctx);
 }
 
 int injected_oom(rt_ctx* ctx) { return ctx->fail(RT_ERR_OOM, "rt_upload: allocation failure injected by rt_debug_fail_upload"); }
@@ -904,7 +944,7 @@ int wf_step_bounce(rt_ctx* ctx, DeviceState& d, WfRun& r, const WfLane& l, bool 
 int wf_step_resolve(rt_ctx* ctx, DeviceState& d, WfRun& r, const WfLane& l) {
     const uint32_t n = batch_samples(r);
     if (r.two && r.j > 0) HIPCHK(ctx, hipStreamWaitEvent(l.st, d.ev_res[(r.j - 1u) & 1u], 0));
-    HIPCHK(ctx, rt::wf_resolve(r.f, l.w, targets_for(d), n, r.first == 0, r.first + n >= r.f.spp, l.st));
+    HIPCHK(ctx, rt::wf_resolve(r.f, l.w, targets_for(d, r.f), n, r.first == 0, r.first + n >= r.f.spp, l.st));
     if (r.two) HIPCHK(ctx, hipEventRecord(d.ev_res[r.j & 1u], l.st));
     r.first += r.batch;
     r.j++;
@@ -1046,8 +1086,8 @@ int run_frame(rt_ctx* ctx, DevFrame fr, bool counters, uint32_t world, uint32_t 
             if (int rc = setup_pipeline(ctx, j, f, runs[j])) return rc;
             continue;
         }
-        if (k.kernel == rt::FrameKernel::REFERENCE) HIPCHK(ctx, rt::launch_render_reference(scene_for(ctx, d), f, targets_for(d), counters, d.stream));
-        else HIPCHK(ctx, rt::launch_render_extended(scene_for(ctx, d), f, targets_for(d), k.kernel, counters, d.stream));
+        if (k.kernel == rt::FrameKernel::REFERENCE) HIPCHK(ctx, rt::launch_render_reference(scene_for(ctx, d), f, targets_for(d, f), counters, d.stream));
+        else HIPCHK(ctx, rt::launch_render_extended(scene_for(ctx, d), f, targets_for(d, f), k.kernel, counters, d.stream));
         HIPCHK(ctx, hipEventRecord(d.ev1, d.stream));
     }
     // The pipeline's launches: every device advances by one step (a batch's generation, one bounce, a batch's resolve) in turn, so that
@@ -1361,6 +1401,11 @@ int rt_render(rt_ctx* ctx, const rt_render_params* p) {
     if (p->width == 0 || p->height == 0 || p->width > 65535u * 8u || p->height > 65535u * 8u)
         return ctx->fail(RT_ERR_BAD_ARG, "rt_render: bad resolution %ux%u", p->width, p->height);
     if (p->mode > RT_MODE_EXTENDED) return ctx->fail(RT_ERR_BAD_ARG, "rt_render: mode %u not supported", p->mode);
+    const bool accumulate = (p->flags & RT_FLAG_ACCUMULATE) != 0;
+    if ((p->flags & RT_FLAG_ACCUMULATE_RESTART) && !accumulate)
+        return ctx->fail(RT_ERR_BAD_ARG, "rt_render: RT_FLAG_ACCUMULATE_RESTART without RT_FLAG_ACCUMULATE");
+    if (accumulate && p->mode != RT_MODE_EXTENDED)
+        return ctx->fail(RT_ERR_BAD_ARG, "rt_render: RT_FLAG_ACCUMULATE needs the extended mode (mode %u has no samples)", p->mode);
     if (p->mode == RT_MODE_EXTENDED && (p->spp == 0 || p->spp > 65536u))
         return ctx->fail(RT_ERR_BAD_ARG, "rt_render: spp %u out of range", p->spp);
     // bounce depths travel in 8 bits in the reference (pack_flags, shared/src/lib.rs:1154-1179); modes 0/1 mask as the
@@ -1384,8 +1429,30 @@ int rt_render(rt_ctx* ctx, const rt_render_params* p) {
     fr.flags = p->flags;
     fr.frame_seed = p->frame_seed;
     fr.cam = make_camera(p->camera, (float)p->width, (float)p->height, p->mode != RT_MODE_LEGACY);
+    fr.n_total = fr.spp; // a closed frame: samples 0 .. spp-1, jittered when there are several
+    fr.jitter = fr.spp > 1 ? 1u : 0u;
+    AccumKey key{};
+    if (accumulate) {
+        key.camera = p->camera;
+        key.width = p->width, key.height = p->height, key.max_bounces = p->max_bounces, key.frame_seed = p->frame_seed;
+        key.tile_size = fr.tile_size, key.tile_rank = rank, key.tile_world = world, key.no_shadows = p->flags & RT_FLAG_NO_SHADOWS;
+        const bool cont = ctx->acc_samples && !(p->flags & RT_FLAG_ACCUMULATE_RESTART) && std::memcmp(&key, &ctx->acc_key, sizeof key) == 0;
+        const uint32_t base = cont ? ctx->acc_samples : 0u;
+        if ((uint64_t)base + fr.spp > RT_ACCUMULATE_MAX_SAMPLES)
+            return ctx->fail(RT_ERR_BAD_ARG, "rt_render: %u + %u samples would pass the accumulation limit of %u", base, fr.spp, RT_ACCUMULATE_MAX_SAMPLES);
+        fr.sample_base = base; // this call traces samples base .. base + spp - 1 and divides by all of them; every sample is jittered
+        fr.n_total = base + fr.spp;
+        fr.jitter = 1u;
+    }
+    end_accumulation(ctx); // counted again below once the frame has completed
+    if (accumulate)
+        if (int rc = ensure_run_sums(ctx, fr.width, fr.height)) return rc;
     int rc = run_frame(ctx, fr, (p->flags & RT_FLAG_COUNTERS) != 0, world, rank, false);
     if (rc != RT_OK) return rc;
+    if (accumulate) {
+        ctx->acc_key = key;
+        ctx->acc_samples = fr.n_total;
+    }
     ctx->frame_w = fr.width;
     ctx->frame_h = fr.height;
     ctx->frame_tile = fr.tile_size;
@@ -1426,6 +1493,7 @@ int rt_dispatch_tile(rt_ctx* ctx, const rt_push_constants* pc) {
     // Only texture `channel` receives texels (the other two keep theirs, as separate bind groups do);
     // the float and hit targets of the tile are refreshed as a by-product.
     DeviceState& d = ctx->devs[0];
+    end_accumulation(ctx);
     int rc = consolidate_on_first_device(ctx, w, h);
     if (rc != RT_OK) return rc;
     rc = run_frame(ctx, fr, false, 1, 0, true);
@@ -1637,6 +1705,13 @@ int rt_debug_shadow_grid(rt_ctx* ctx, uint32_t light, unsigned long long out[8])
     out[4] = g.longest;
     out[5] = g.heavy_cells;
     out[6] = g.filled_cells;
+    return RT_OK;
+}
+
+int rt_accumulated_samples(rt_ctx* ctx, uint32_t* samples) {
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (!samples) return ctx->fail(RT_ERR_BAD_ARG, "rt_accumulated_samples: null output");
+    *samples = ctx->acc_samples;
     return RT_OK;
 }
 
@@ -2098,6 +2173,7 @@ int rt_update_geometry(rt_ctx* ctx, const rt_vertex* vertices, uint32_t n_vertic
         if (int rc = classify_ptr(ctx, "rt_update_geometry", "spheres", spheres, ps, 4)) return rc;
     uint32_t stat_flags = 0;
     double kernel_ms = 0.0;
+    end_accumulation(ctx); // moved geometry: the samples so far are of another scene
     const int rc = update_geometry(ctx, n_vertices ? vertices : nullptr, pv, spheres, n_spheres, ps, (flags & RT_UPDATE_REBUILD) != 0, &stat_flags, &kernel_ms);
     if (rc != RT_OK) { // as a failed upload: nothing is left pointing at half-written arrays (the last frame stays readable)
         drop_scene(ctx);

@@ -147,9 +147,9 @@ __global__ __launch_bounds__(256) void k_wf_generate(DevFrame fr, rt::WfBuffers 
         const PixelCoord px = block_pixel_at(fr, b, lane);
         const uint32_t p = sb * WAVE + lane;
         if (px.valid) {
-            SimpleRng rng = rng_for(fr.frame_seed + px.x + px.y * fr.width, first_sample + k);
+            SimpleRng rng = rng_for(fr.frame_seed + px.x + px.y * fr.width, fr.sample_base + first_sample + k);
             float jx = 0.5f, jy = 0.5f;
-            if (fr.spp > 1) {
+            if (fr.jitter) {
                 jx = rng.next_f32();
                 jy = rng.next_f32();
             }
@@ -1315,22 +1315,29 @@ __global__ __launch_bounds__(256, RT_WF_SHADE_WAVES) void k_wf_finish(DevScene s
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// resolve: add the batch's samples to each pixel's running sum IN SAMPLE ORDER; write the image on the last batch
+// resolve: add the batch's samples to each pixel's running sum IN SAMPLE ORDER; write the image on the last batch.  The sum of a batch
+// lives per pixel slot (WfBuffers::accum); an accumulating call (DevTargets::run_sum) starts it from the earlier calls' sum in its first
+// batch and hands it back in its last.
 // ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(WAVE) void k_wf_resolve(DevFrame fr, rt::WfBuffers wb, DevTargets tg, uint32_t n_samples, uint32_t first_batch,
                                                      uint32_t last_batch) {
     const uint32_t lane = threadIdx.x, b = blockIdx.x;
     const uint32_t q = b * WAVE + lane;
-    float4 acc = first_batch ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : wb.accum[q];
-    V3 sum = f4v(acc);
+    V3 sum;
+    if (!first_batch) sum = f4v(wb.accum[q]);
+    else if (tg.run_sum && fr.sample_base) { // (wave-uniform)
+        const PixelCoord px = block_pixel_at(fr, b, lane);
+        sum = px.valid ? run_sum_start(fr, tg, (size_t)px.y * fr.width + px.x) : v3(0.0f, 0.0f, 0.0f);
+    } else sum = v3(0.0f, 0.0f, 0.0f);
     for (uint32_t k = 0; k < n_samples; k++) sum = sum + f4v(wb.sample_rad[(size_t)(RT_WF_BLOCK_MAJOR ? b * n_samples + k : k * wb.n_blocks + b) * WAVE + lane]);
     wb.accum[q] = make_float4(sum.x, sum.y, sum.z, 0.0f);
     if (!last_batch) return;
     const PixelCoord px = block_pixel_at(fr, b, lane);
     if (!px.valid) return;
-    const float n = (float)fr.spp;
-    const V3 color = v3(sum.x / n, sum.y / n, sum.z / n);
     const size_t pix = (size_t)px.y * fr.width + px.x;
+    run_sum_keep(tg, pix, sum);
+    const float n = (float)fr.n_total;
+    const V3 color = v3(sum.x / n, sum.y / n, sum.z / n);
     if (tg.rgba32f) reinterpret_cast<float4*>(tg.rgba32f)[pix] = make_float4(color.x, color.y, color.z, 1.0f);
     if (tg.chan[0]) reinterpret_cast<uint32_t*>(tg.chan[0])[pix] = unorm8(color.x) | 0xFF000000u;
     if (tg.chan[1]) reinterpret_cast<uint32_t*>(tg.chan[1])[pix] = (unorm8(color.y) << 8) | 0xFF000000u;

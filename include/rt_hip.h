@@ -71,6 +71,11 @@ extern "C" {
 #define RT_FLAG_STAGE_TIMES 128u /* extended mode only: time every launch of the frame's dominant stage kernel with HIP events on its stream  */
                               /* (bench.py's roofline of that kernel; read with rt_debug_stage_times)                                   */
 
+#define RT_FLAG_ACCUMULATE 256u /* extended mode only (RT_ERR_BAD_ARG with modes 0/1): progressive rendering - this call adds its spp samples to */
+                              /* the context's running image; rt_read_* then return the mean over all its samples.  See "Progressive       */
+                              /* accumulation" below                                                                                       */
+#define RT_FLAG_ACCUMULATE_RESTART 512u /* with RT_FLAG_ACCUMULATE only (RT_ERR_BAD_ARG otherwise): start a new running image at sample 0 */
+
 typedef struct rt_ctx rt_ctx;
 
 typedef struct rt_render_params {
@@ -204,6 +209,31 @@ int rt_read_rgba8_combined(rt_ctx* ctx, uint8_t* out, size_t n_bytes);
 int rt_read_hits(rt_ctx* ctx, uint32_t* prim_ids, float* t, size_t n_pixels);
 
 int rt_get_stats(rt_ctx* ctx, rt_stats* out);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Progressive accumulation (RT_FLAG_ACCUMULATE; Cycles' viewport and the reference's ProgressiveState, src/renderer.rs:821-855,
+ * are the model): many short rt_render calls refine one image.
+ *
+ * An accumulating call traces the samples n .. n+spp-1 of every pixel of its share, n being the samples already accumulated, adds them
+ * to the running sums in sample order and writes the mean over all n+spp samples to the targets rt_read_rgb32f / rt_read_rgba8_* read.
+ * Every sample of an accumulation is jittered (a closed frame jitters only when spp > 1), so an accumulation of N >= 2 samples gives
+ * exactly the bits of ONE closed frame of N spp with the same parameters, however the N samples were split over calls and whichever
+ * kernel (RT_FLAG_KERNEL_*) rendered each call.  An accumulation of exactly 1 sample is a jittered 1-spp image, which no closed frame gives.
+ * The running image continues only while camera (bitwise), width, height, max_bounces, frame_seed, tile_size, tile_rank, tile_world
+ * (0 read as 1, tile_size 0 as RT_TILE_SIZE) and RT_FLAG_NO_SHADOWS equal those of the previous accumulating call; otherwise the call starts
+ * a new one at sample 0 by itself, as RT_FLAG_ACCUMULATE_RESTART does.  The other RT_FLAG_* bits change no bits and may differ.
+ * The running image ends (the next accumulating call starts at 0) with rt_upload_scene*, rt_update_geometry, rt_dispatch_tile, any
+ * rt_render without RT_FLAG_ACCUMULATE and an accumulating call that fails once it has passed its argument checks.  It survives rt_prepare,
+ * rt_upload_textures, the ray queries, rt_camera_rays, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
+ * Limit: RT_ACCUMULATE_MAX_SAMPLES samples (where the float sample count stops being exact); a call that would pass it is RT_ERR_BAD_ARG
+ * and leaves the running image as it was.  rt_stats describes the call alone (its segments, pixels, kernel_ms).
+ * A context over several devices, and a tile_rank / tile_world share, accumulates its own share of the pixels.
+ * --------------------------------------------------------------------------------------------------------------- */
+#define RT_ACCUMULATE_MAX_SAMPLES 16777216u /* 2^24 */
+
+/* Samples in the context's running image (0 when there is none).  After an accumulating call, a count equal to that call's spp means
+ * it started a new running image. */
+int rt_accumulated_samples(rt_ctx* ctx, uint32_t* samples);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Ray queries: closest hit and occlusion for caller-supplied rays (no reference counterpart; Embree's rtcIntersect /
