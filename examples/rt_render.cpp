@@ -7,13 +7,15 @@
 // tiles per call, three colour-channel dispatches per tile) -> the display combine of main_fs (shader/src/lib.rs:383-388)
 // -> an image file (the reference has no image output; PLAN.md lists it as future), and prints the completion summary of
 // src/compute.rs:320-363.  With --spp/--bounces it renders the extended mode through rt_render instead; --progressive N refines that
-// image over N accumulating calls (RT_FLAG_ACCUMULATE), the extended mode's counterpart of the progressive tile loop.
+// image over N accumulating calls (RT_FLAG_ACCUMULATE), the extended mode's counterpart of the progressive tile loop; --denoise then
+// filters the finished image with the a-trous denoiser, guided by the first-hit feature buffers of its samples (rt_aovs, rt_denoise).
 //
 // Build (done by __graft_entry__.build()):
 //   g++ -std=c++17 -O2 examples/rt_render.cpp -Iinclude -Igpu_raytracer_amd/csrc -Lgpu_raytracer_amd -lrt_hip
 //       -Wl,-rpath,'$ORIGIN/../gpu_raytracer_amd' -o build/rt_render
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -35,12 +37,14 @@ static double now_ms() {
 
 static int usage(const char* argv0, int rc) {
     std::fprintf(rc ? stderr : stdout,
-                 "usage: %s [--gltf FILE.gltf|.glb] [--size WxH] [--out FILE.png|.ppm|.exr] [--spp N --bounces B [--progressive C]] [--fly FRAMES] [--device D]\n"
+                 "usage: %s [--gltf FILE.gltf|.glb] [--size WxH] [--out FILE.png|.ppm|.exr] [--spp N --bounces B [--progressive C] [--denoise]] [--fly FRAMES] [--device D]\n"
                  "  without --gltf the reference's default scene (6 spheres, 2 triangles, 1 light) is rendered;\n"
                  "  without --spp the reference path runs: progressive 128x128 tiles, three channel dispatches per tile;\n"
                  "  with --spp N the extended mode (jittered samples, shadow rays, --bounces B, default 4) runs through rt_render;\n"
                  "  with --progressive C as well, C accumulating calls of N spp each refine one image of C*N samples (the same image as\n"
                  "  --spp C*N when C*N >= 2); each call's time and the running sample count are printed;\n"
+                 "  with --denoise as well, the image (after the last call) is denoised with the default parameters, guided by the\n"
+                 "  feature buffers of all its samples, and the denoised image is written;\n"
                  "  with --fly FRAMES a scripted fly-through (CameraController deltas of src/input.rs) renders FRAMES whole frames with\n"
                  "  the reference semantics, reads each back and reports frames per second; the last frame is written.\n",
                  argv0);
@@ -51,10 +55,15 @@ int main(int argc, char** argv) {
     std::string gltf, out = "out.png";
     uint32_t width = 800, height = 600, spp = 0, bounces = 4, fly = 0, progressive = 0;
     int device = 0;
+    bool denoise = false;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { return i + 1 < argc ? argv[++i] : nullptr; };
         if (a == "--help" || a == "-h") return usage(argv[0], 0);
+        if (a == "--denoise") {
+            denoise = true;
+            continue;
+        }
         const char* v = next();
         if (!v) return usage(argv[0], 2);
         if (a == "--gltf") gltf = v;
@@ -68,7 +77,7 @@ int main(int argc, char** argv) {
         else if (a == "--device") device = std::atoi(v);
         else return usage(argv[0], 2);
     }
-    if (progressive && !spp) return usage(argv[0], 2); // accumulation is the extended mode's
+    if ((progressive || denoise) && !spp) return usage(argv[0], 2); // accumulation and the denoiser's samples are the extended mode's
 
     // ---- scene (src/scene.rs) ----
     SceneState scene;
@@ -95,6 +104,7 @@ int main(int argc, char** argv) {
     };
     BufferManager buffers;
     std::vector<uint8_t> rgba8((size_t)width * height * 4);
+    std::vector<float> denoised; // --denoise: the filtered float image
 
     if (fly > 0) {
         // ---- scripted fly-through: what dragging the mouse and holding W/D does in the reference (src/main.rs:150-186 ->
@@ -185,6 +195,37 @@ int main(int argc, char** argv) {
                     st.rays / (st.kernel_ms * 1e3));
         rc = rt_read_rgba8_combined(ctx, rgba8.data(), rgba8.size());
         if (rc != RT_OK) return fail("rt_read_rgba8_combined", rc);
+        if (denoise) { // the feature buffers of exactly the image's samples, then the filter with the header's defaults
+            const size_t n = (size_t)width * height;
+            std::vector<rt_aov> aov(n);
+            denoised.resize(n * 3);
+            rc = rt_read_rgb32f(ctx, denoised.data(), denoised.size());
+            if (rc != RT_OK) return fail("rt_read_rgb32f", rc);
+            if (progressive) rt_accumulated_samples(ctx, &p.spp); // the running image's samples (RT_FLAG_ACCUMULATE is still set)
+            rc = rt_aovs(ctx, &p, aov.data());
+            if (rc != RT_OK) return fail("rt_aovs", rc);
+            rt_get_stats(ctx, &st);
+            std::printf("aovs: %u samples per pixel: %.2f ms on the device, %.2f ms wall\n", p.spp, st.kernel_ms, st.wall_ms);
+            rt_denoise_params dp;
+            std::memset(&dp, 0, sizeof dp);
+            dp.width = width;
+            dp.height = height;
+            dp.iterations = RT_DENOISE_DEFAULT_ITERATIONS;
+            dp.flags = RT_DENOISE_DEMODULATE;
+            dp.sigma_color = RT_DENOISE_DEFAULT_SIGMA_COLOR;
+            dp.sigma_normal = RT_DENOISE_DEFAULT_SIGMA_NORMAL;
+            dp.sigma_depth = RT_DENOISE_DEFAULT_SIGMA_DEPTH;
+            dp.sigma_albedo = RT_DENOISE_DEFAULT_SIGMA_ALBEDO;
+            rc = rt_denoise(ctx, &dp, denoised.data(), aov.data(), denoised.data());
+            if (rc != RT_OK) return fail("rt_denoise", rc);
+            rt_get_stats(ctx, &st);
+            std::printf("denoise: %u iterations: %.2f ms on the device, %.2f ms wall\n", dp.iterations, st.kernel_ms, st.wall_ms);
+            auto unorm8 = [](float v) -> uint8_t { return !(v > 0.0f) ? 0 : v >= 1.0f ? 255 : (uint8_t)std::floor(v * 255.0f + 0.5f); }; // as the targets
+            for (size_t i = 0; i < n; i++) {
+                for (int c = 0; c < 3; c++) rgba8[4 * i + c] = unorm8(denoised[3 * i + c]);
+                rgba8[4 * i + 3] = 255;
+            }
+        }
     }
 
     const bool ppm = out.size() > 4 && out.substr(out.size() - 4) == ".ppm";
@@ -192,8 +233,8 @@ int main(int argc, char** argv) {
     bool ok;
     if (exr) { // the float image, every bit of it
         std::vector<float> rgb((size_t)width * height * 3);
-        rc = rt_read_rgb32f(ctx, rgb.data(), rgb.size());
-        if (rc != RT_OK) return fail("rt_read_rgb32f", rc);
+        if (!denoised.empty()) rgb = denoised;
+        else if ((rc = rt_read_rgb32f(ctx, rgb.data(), rgb.size())) != RT_OK) return fail("rt_read_rgb32f", rc);
         ok = write_exr(out.c_str(), rgb.data(), width, height);
     } else
         ok = ppm ? write_ppm(out.c_str(), rgba8.data(), width, height) : write_png(out.c_str(), rgba8.data(), width, height);

@@ -34,6 +34,11 @@ PREPARE_QUALITY_TREE = 2
 QUERY_COUNTERS = 1  # RT_QUERY_COUNTERS of rt_intersect / rt_occluded
 QUERY_CHUNK = 4194304  # RT_QUERY_CHUNK: host batches are staged in chunks of at most this many rays
 UPDATE_REBUILD = 1  # RT_UPDATE_REBUILD of rt_update_geometry
+AOV_SAMPLES_PER_LAUNCH = T.AOV_SAMPLES_PER_LAUNCH  # RT_AOV_SAMPLES_PER_LAUNCH: rt_aovs traces at most this many samples per kernel
+DENOISE_DEMODULATE = T.DENOISE_DEMODULATE  # RT_DENOISE_DEMODULATE of rt_denoise_params.flags
+DENOISE_MAX_ITERATIONS = T.DENOISE_MAX_ITERATIONS
+DENOISE_DEFAULTS = dict(iterations=T.DENOISE_DEFAULT_ITERATIONS, sigma_color=T.DENOISE_DEFAULT_SIGMA_COLOR, sigma_normal=T.DENOISE_DEFAULT_SIGMA_NORMAL,
+                        sigma_depth=T.DENOISE_DEFAULT_SIGMA_DEPTH, sigma_albedo=T.DENOISE_DEFAULT_SIGMA_ALBEDO)  # RT_DENOISE_DEFAULT_*
 STAT_MEGAKERNEL_FALLBACK, STAT_SINGLE_PASS, STAT_REFIT, STAT_REBUILT = 1, 2, 4, 8  # RT_STAT_* (rt_stats.flags)
 PRIM_MISS = 0xFFFFFFFF
 PRIM_SPHERE_FLAG = 0x80000000
@@ -47,6 +52,7 @@ ABI_SYMBOLS = [
     "rt_intersect", "rt_occluded", "rt_camera_rays",
     "rt_update_geometry",
     "rt_accumulated_samples",
+    "rt_aovs", "rt_sample_rays", "rt_denoise",
 ]
 
 
@@ -160,6 +166,46 @@ def split_hits(hits):
     return hits[:, 0], hits[:, 1], hits[:, 2], np.ascontiguousarray(hits[:, 3]).view(np.uint32)
 
 
+def split_aovs(aovs):
+    """(..., 8) AOV records (rt_aov: albedo xyz, depth, normal xyz, coverage; numpy or torch) -> dict of views: albedo (..., 3),
+    depth (...), normal (..., 3), coverage (...)."""
+    return {"albedo": aovs[..., 0:3], "depth": aovs[..., 3], "normal": aovs[..., 4:7], "coverage": aovs[..., 7]}
+
+
+def _check_image(a, name, h, w, c):
+    """Raises unless `a` is a C-contiguous float32 (h, w, c) numpy array or torch tensor."""
+    if _is_torch(a):
+        import torch
+        if a.dtype != torch.float32:
+            raise TypeError(f"{name}: dtype {a.dtype}, expected torch.float32")
+        shape, contiguous = tuple(a.shape), a.is_contiguous()
+    elif isinstance(a, np.ndarray):
+        if a.dtype != np.float32:
+            raise TypeError(f"{name}: dtype {a.dtype}, expected float32")
+        shape, contiguous = a.shape, a.flags.c_contiguous
+    else:
+        raise TypeError(f"{name}: a numpy array or a torch tensor, not {type(a).__name__}")
+    if tuple(shape) != (h, w, c):
+        raise ValueError(f"{name}: shape {tuple(shape)}, expected {(h, w, c)}")
+    if not contiguous:
+        raise ValueError(f"{name}: not C-contiguous")
+
+
+def render_params(width, height, camera, mode=MODE_LEGACY, spp=1, max_bounces=4, frame_seed=0, tile_size=0, tile_rank=0, tile_world=1,
+                  counters=False, no_shadows=False, kernel_v1=False, kernel_sm=False, no_shadow_grid=False, kernel_pipeline=False, no_beams=False,
+                  stage_times=False, accumulate=False, restart=False):
+    """An rt_render_params record (types.RENDER_PARAMS) from the keyword arguments of Context.render."""
+    if restart and not accumulate:
+        raise ValueError("render: restart=True needs accumulate=True")
+    p = np.zeros((), dtype=T.RENDER_PARAMS)
+    p["camera"] = camera
+    p["width"], p["height"], p["spp"], p["max_bounces"], p["mode"] = width, height, spp, max_bounces, mode
+    p["frame_seed"], p["tile_size"], p["tile_rank"], p["tile_world"] = frame_seed, tile_size, tile_rank, tile_world
+    p["flags"] = (FLAG_COUNTERS if counters else 0) | (FLAG_NO_SHADOWS if no_shadows else 0) | (FLAG_KERNEL_V1 if kernel_v1 else 0) | (FLAG_KERNEL_SM if kernel_sm else 0) | (FLAG_NO_SHADOW_GRID if no_shadow_grid else 0) | (FLAG_KERNEL_PIPELINE if kernel_pipeline else 0) | (FLAG_NO_BEAMS if no_beams else 0) | (FLAG_STAGE_TIMES if stage_times else 0)
+    p["flags"] |= (FLAG_ACCUMULATE if accumulate else 0) | (FLAG_ACCUMULATE_RESTART if restart else 0)
+    return p
+
+
 def _init_torch_device_runtime():
     """torch ships its own HIP runtime.  In one process it has to come up before the library's: torch initialised after a
     context exists reports "No HIP GPUs are available".  Done only when the program has imported torch."""
@@ -271,14 +317,10 @@ class Context:
                accumulate=False, restart=False):
         """rt_render.  accumulate=True (extended mode): add the spp samples to the context's running image and leave the mean over all of
         them in the targets (accumulated_samples() tells how many); restart=True with it starts a new running image at sample 0."""
-        if restart and not accumulate:
-            raise ValueError("render: restart=True needs accumulate=True")
-        p = np.zeros((), dtype=T.RENDER_PARAMS)
-        p["camera"] = camera
-        p["width"], p["height"], p["spp"], p["max_bounces"], p["mode"] = width, height, spp, max_bounces, mode
-        p["frame_seed"], p["tile_size"], p["tile_rank"], p["tile_world"] = frame_seed, tile_size, tile_rank, tile_world
-        p["flags"] = (FLAG_COUNTERS if counters else 0) | (FLAG_NO_SHADOWS if no_shadows else 0) | (FLAG_KERNEL_V1 if kernel_v1 else 0) | (FLAG_KERNEL_SM if kernel_sm else 0) | (FLAG_NO_SHADOW_GRID if no_shadow_grid else 0) | (FLAG_KERNEL_PIPELINE if kernel_pipeline else 0) | (FLAG_NO_BEAMS if no_beams else 0) | (FLAG_STAGE_TIMES if stage_times else 0)
-        p["flags"] |= (FLAG_ACCUMULATE if accumulate else 0) | (FLAG_ACCUMULATE_RESTART if restart else 0)
+        p = render_params(width, height, camera, mode=mode, spp=spp, max_bounces=max_bounces, frame_seed=frame_seed, tile_size=tile_size,
+                          tile_rank=tile_rank, tile_world=tile_world, counters=counters, no_shadows=no_shadows, kernel_v1=kernel_v1,
+                          kernel_sm=kernel_sm, no_shadow_grid=no_shadow_grid, kernel_pipeline=kernel_pipeline, no_beams=no_beams,
+                          stage_times=stage_times, accumulate=accumulate, restart=restart)
         self._check(self.lib.rt_render(self._h, _p(p)))
         self.width, self.height = width, height
         return self.stats()
@@ -390,6 +432,59 @@ class Context:
             raise ValueError(f"out: {len(out)} rows for {n} pixels")
         _sync_torch(out)
         self._check(self.lib.rt_camera_rays(self._h, _p(cam), C.c_uint32(width), C.c_uint32(height), C.c_uint32(mode), _addr(out)))
+        return out
+
+    # -- feature buffers and denoising -----------------------------------------------------------------------------------
+    def aovs(self, width, height, camera, out=None, **render_kw):
+        """rt_aovs: the first-hit albedo, depth, normal and coverage of the frame the same arguments give Context.render (its keyword
+        arguments: mode, spp, frame_seed, tile_*, accumulate, ...) -> (height, width, 8) float32 records (split_aovs; a numpy array
+        views as types.AOV).  `out` (optional): a numpy array or torch tensor (CPU or device) of that shape to write them to."""
+        p = render_params(width, height, camera, **render_kw)
+        if out is None:
+            out = np.empty((height, width, 8), np.float32)
+        else:
+            _check_image(out, "out", height, width, 8)
+        _sync_torch(out)
+        self._check(self.lib.rt_aovs(self._h, _p(p), _addr(out)))
+        return out
+
+    def sample_rays(self, width, height, camera, sample, out=None, **render_kw):
+        """rt_sample_rays: the extended mode's camera rays of global sample `sample` of the frame the arguments describe (mode=2 is
+        implied; spp and accumulate decide the jitter as in a frame) as a (width * height, 8) batch for intersect()."""
+        render_kw.setdefault("mode", MODE_EXTENDED)
+        p = render_params(width, height, camera, **render_kw)
+        n = width * height
+        if out is None:
+            out = np.empty((n, 8), np.float32)
+        elif _check_batch(out, "out", 8, "float32") != n:
+            raise ValueError(f"out: {len(out)} rows for {n} pixels")
+        _sync_torch(out)
+        self._check(self.lib.rt_sample_rays(self._h, _p(p), C.c_uint32(sample), _addr(out)))
+        return out
+
+    def denoise(self, rgb, aovs, out=None, iterations=DENOISE_DEFAULTS["iterations"], sigma_color=DENOISE_DEFAULTS["sigma_color"],
+                sigma_normal=DENOISE_DEFAULTS["sigma_normal"], sigma_depth=DENOISE_DEFAULTS["sigma_depth"],
+                sigma_albedo=DENOISE_DEFAULTS["sigma_albedo"], demodulate=True):
+        """rt_denoise: the edge-avoiding a-trous filter of an (h, w, 3) float32 image guided by its (h, w, 8) AOV records (aovs()).
+        Both numpy, or both torch tensors on the CPU or on one device of the context; the result (`out`, or a new array of the same
+        kind and device) is (h, w, 3).  out may be rgb (in place)."""
+        if _is_torch(rgb) != _is_torch(aovs):
+            raise TypeError("aovs: must be the same kind (numpy / torch) as rgb")
+        h, w = (tuple(getattr(rgb, "shape", ())) + (0, 0))[:2]
+        _check_image(rgb, "rgb", h, w, 3)
+        _check_image(aovs, "aovs", h, w, 8)
+        if out is None:
+            out = _empty_like_batch(rgb, (h, w, 3), "float32")
+        else:
+            if _is_torch(out) != _is_torch(rgb):
+                raise TypeError("out: must be the same kind (numpy / torch) as rgb")
+            _check_image(out, "out", h, w, 3)
+        dp = np.zeros((), dtype=T.DENOISE_PARAMS)
+        dp["width"], dp["height"], dp["iterations"] = w, h, iterations
+        dp["flags"] = DENOISE_DEMODULATE if demodulate else 0
+        dp["sigma_color"], dp["sigma_normal"], dp["sigma_depth"], dp["sigma_albedo"] = sigma_color, sigma_normal, sigma_depth, sigma_albedo
+        _sync_torch(rgb, aovs, out)
+        self._check(self.lib.rt_denoise(self._h, _p(dp), _addr(rgb), _addr(aovs), _addr(out)))
         return out
 
     def stats(self):

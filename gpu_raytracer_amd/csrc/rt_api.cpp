@@ -19,6 +19,7 @@
 #include "../../include/rt_hip.h"
 #include "bvh_builder.h"
 #include "bvh_check.h"
+#include "denoise.h"
 #include "device_build.h"
 #include "device_layout.h"
 #include "half.h"
@@ -87,6 +88,12 @@ struct DeviceState {
     // with the scene
     float* run_sum = nullptr;
     uint32_t run_sum_w = 0, run_sum_h = 0;
+    // rt_aovs / rt_denoise (denoise.h), grown on demand, kept until rt_destroy (they do not depend on the scene): the records of the
+    // device's share when they cannot be written in place, the staging of host rgb, and the two colour planes of the a-trous iterations
+    void* dn_aov = nullptr;
+    void* dn_rgb = nullptr;
+    void* dn_plane[2] = {nullptr, nullptr};
+    size_t dn_aov_bytes = 0, dn_rgb_bytes = 0, dn_plane_bytes[2] = {0, 0};
 };
 
 // What an accumulating rt_render must share with the previous one to continue its running image (rt_hip.h, RT_FLAG_ACCUMULATE): the
@@ -199,6 +206,13 @@ void free_targets(DeviceState& d) {
     if (d.readback_host) (void)hipHostFree(d.readback_host);
     d.readback_dev = d.readback_host = nullptr;
     d.readback_bytes = 0;
+}
+
+void free_denoise(DeviceState& d) {
+    (void)hipSetDevice(d.device);
+    for (void* p : {d.dn_aov, d.dn_rgb, d.dn_plane[0], d.dn_plane[1]}) (void)hipFree(p);
+    d.dn_aov = d.dn_rgb = d.dn_plane[0] = d.dn_plane[1] = nullptr;
+    d.dn_aov_bytes = d.dn_rgb_bytes = d.dn_plane_bytes[0] = d.dn_plane_bytes[1] = 0;
 }
 
 void free_wavefront(DeviceState& d) {
@@ -796,11 +810,18 @@ int sync_pending(rt_ctx* ctx) {
 
 // The tiles device j (of nd) takes of a frame: the context owns the tiles i with i % world == rank (rt_hip.h); its device j takes every
 // nd-th of those.
-void assign_tiles(DevFrame& f, DeviceState& d, uint32_t world, uint32_t rank, size_t nd, size_t j) {
+void frame_share(DevFrame& f, uint32_t world, uint32_t rank, size_t nd, size_t j) {
     const uint32_t total_tiles = f.tiles_x * f.tiles_y, stride = world * (uint32_t)nd, first = rank + world * (uint32_t)j;
-    f.tile_first = d.tile_first = first;
-    f.tile_stride = d.tile_stride = stride;
-    f.n_owned_tiles = d.n_owned = first < total_tiles ? (total_tiles - first + stride - 1) / stride : 0;
+    f.tile_first = first;
+    f.tile_stride = stride;
+    f.n_owned_tiles = first < total_tiles ? (total_tiles - first + stride - 1) / stride : 0;
+}
+// ... and records it as the device's share of the last rt_render (what rt_read_* gather).
+void assign_tiles(DevFrame& f, DeviceState& d, uint32_t world, uint32_t rank, size_t nd, size_t j) {
+    frame_share(f, world, rank, nd, j);
+    d.tile_first = f.tile_first;
+    d.tile_stride = f.tile_stride;
+    d.n_owned = f.n_owned_tiles;
 }
 
 struct KernelChoice {
@@ -997,15 +1018,18 @@ int add_totals(rt_ctx* ctx, FrameTotals& t, const unsigned long long (&w)[rt::WF
 }
 
 // Pixels of device d's share of frame fr: the explicit tile of a dispatch, or the tiles the device owns.
-uint64_t share_pixels(const DevFrame& fr, const DeviceState& d) {
-    if (fr.single_tile)
-        return (uint64_t)std::min(fr.tile_w, fr.width - std::min(fr.width, fr.tile_off_x)) * std::min(fr.tile_h, fr.height - std::min(fr.height, fr.tile_off_y));
+uint64_t owned_pixels(const DevFrame& fr, uint32_t first, uint32_t stride, uint32_t n_owned) {
     uint64_t pixels = 0;
-    for (uint32_t k = 0; k < d.n_owned; k++) {
-        const uint32_t tile = d.tile_first + k * d.tile_stride, ty = tile / fr.tiles_x, tx = tile % fr.tiles_x;
+    for (uint32_t k = 0; k < n_owned; k++) {
+        const uint32_t tile = first + k * stride, ty = tile / fr.tiles_x, tx = tile % fr.tiles_x;
         pixels += (uint64_t)std::min(fr.tile_size, fr.width - tx * fr.tile_size) * std::min(fr.tile_size, fr.height - ty * fr.tile_size);
     }
     return pixels;
+}
+uint64_t share_pixels(const DevFrame& fr, const DeviceState& d) {
+    if (fr.single_tile)
+        return (uint64_t)std::min(fr.tile_w, fr.width - std::min(fr.width, fr.tile_off_x)) * std::min(fr.tile_h, fr.height - std::min(fr.height, fr.tile_off_y));
+    return owned_pixels(fr, d.tile_first, d.tile_stride, d.n_owned);
 }
 
 // Waits for device j's share of a frame and adds its kernel time, stage times, counters and pixels to `t`.
@@ -1168,6 +1192,45 @@ int consolidate_on_first_device(rt_ctx* ctx, uint32_t w, uint32_t h) {
     return RT_OK;
 }
 
+// The argument rules of rt_render (rt_hip.h), shared by rt_aovs and rt_sample_rays (`fn` names the call in the error text): the frame p
+// describes, as a closed frame (without its tile share), and the tile_world / tile_rank share.
+int frame_of_params(rt_ctx* ctx, const char* fn, const rt_render_params* p, DevFrame& fr, uint32_t& world, uint32_t& rank) {
+    if (p->width == 0 || p->height == 0 || p->width > 65535u * 8u || p->height > 65535u * 8u)
+        return ctx->fail(RT_ERR_BAD_ARG, "%s: bad resolution %ux%u", fn, p->width, p->height);
+    if (p->mode > RT_MODE_EXTENDED) return ctx->fail(RT_ERR_BAD_ARG, "%s: mode %u not supported", fn, p->mode);
+    const bool accumulate = (p->flags & RT_FLAG_ACCUMULATE) != 0;
+    if ((p->flags & RT_FLAG_ACCUMULATE_RESTART) && !accumulate)
+        return ctx->fail(RT_ERR_BAD_ARG, "%s: RT_FLAG_ACCUMULATE_RESTART without RT_FLAG_ACCUMULATE", fn);
+    if (accumulate && p->mode != RT_MODE_EXTENDED)
+        return ctx->fail(RT_ERR_BAD_ARG, "%s: RT_FLAG_ACCUMULATE needs the extended mode (mode %u has no samples)", fn, p->mode);
+    if (p->mode == RT_MODE_EXTENDED && (p->spp == 0 || p->spp > 65536u))
+        return ctx->fail(RT_ERR_BAD_ARG, "%s: spp %u out of range", fn, p->spp);
+    // bounce depths travel in 8 bits in the reference (pack_flags, shared/src/lib.rs:1154-1179); modes 0/1 mask as the
+    // reference does, the extended mode refuses what it cannot represent rather than looping 2^32 times
+    if (p->mode == RT_MODE_EXTENDED && p->max_bounces > RT_MAX_BOUNCES)
+        return ctx->fail(RT_ERR_BAD_ARG, "%s: max_bounces %u > %u", fn, p->max_bounces, RT_MAX_BOUNCES);
+    world = p->tile_world ? p->tile_world : 1, rank = p->tile_rank;
+    if (rank >= world) return ctx->fail(RT_ERR_BAD_ARG, "%s: tile_rank %u >= tile_world %u", fn, rank, world);
+    fr = DevFrame{};
+    fr.width = p->width;
+    fr.height = p->height;
+    fr.tile_size = p->tile_size ? p->tile_size : RT_TILE_SIZE;
+    if (fr.tile_size > 4096) return ctx->fail(RT_ERR_BAD_ARG, "%s: tile_size %u too large", fn, fr.tile_size);
+    fr.tiles_x = (fr.width + fr.tile_size - 1) / fr.tile_size; // TileHelper::calculate_tile_count, shared/src/lib.rs:1187-1191
+    fr.tiles_y = (fr.height + fr.tile_size - 1) / fr.tile_size;
+    fr.mode = p->mode;
+    fr.channel_mask = 7u;
+    fr.cur_bounce = 0; // the bounce-0 pass of src/compute.rs:413-479 (later passes redraw the same pixels)
+    fr.max_bounce = p->mode == RT_MODE_EXTENDED ? p->max_bounces : (p->max_bounces & 0xFF);
+    fr.spp = p->mode == RT_MODE_EXTENDED ? p->spp : 1;
+    fr.flags = p->flags;
+    fr.frame_seed = p->frame_seed;
+    fr.cam = make_camera(p->camera, (float)p->width, (float)p->height, p->mode != RT_MODE_LEGACY);
+    fr.n_total = fr.spp; // a closed frame: samples 0 .. spp-1, jittered when there are several (DESIGN.md section 5)
+    fr.jitter = fr.spp > 1 ? 1u : 0u;
+    return RT_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -1222,6 +1285,7 @@ void rt_destroy(rt_ctx* ctx) {
         free_scene(d);
         free_targets(d);
         free_wavefront(d);
+        free_denoise(d);
         (void)hipFree(d.counters);
         if (d.ev0) (void)hipEventDestroy(d.ev0);
         if (d.ev1) (void)hipEventDestroy(d.ev1);
@@ -1398,39 +1462,10 @@ int rt_render(rt_ctx* ctx, const rt_render_params* p) {
     if (!ctx) return RT_ERR_BAD_ARG;
     if (!p) return ctx->fail(RT_ERR_BAD_ARG, "rt_render: null params");
     if (!ctx->uploaded) return ctx->fail(RT_ERR_NOT_UPLOADED, "rt_render: no scene uploaded");
-    if (p->width == 0 || p->height == 0 || p->width > 65535u * 8u || p->height > 65535u * 8u)
-        return ctx->fail(RT_ERR_BAD_ARG, "rt_render: bad resolution %ux%u", p->width, p->height);
-    if (p->mode > RT_MODE_EXTENDED) return ctx->fail(RT_ERR_BAD_ARG, "rt_render: mode %u not supported", p->mode);
-    const bool accumulate = (p->flags & RT_FLAG_ACCUMULATE) != 0;
-    if ((p->flags & RT_FLAG_ACCUMULATE_RESTART) && !accumulate)
-        return ctx->fail(RT_ERR_BAD_ARG, "rt_render: RT_FLAG_ACCUMULATE_RESTART without RT_FLAG_ACCUMULATE");
-    if (accumulate && p->mode != RT_MODE_EXTENDED)
-        return ctx->fail(RT_ERR_BAD_ARG, "rt_render: RT_FLAG_ACCUMULATE needs the extended mode (mode %u has no samples)", p->mode);
-    if (p->mode == RT_MODE_EXTENDED && (p->spp == 0 || p->spp > 65536u))
-        return ctx->fail(RT_ERR_BAD_ARG, "rt_render: spp %u out of range", p->spp);
-    // bounce depths travel in 8 bits in the reference (pack_flags, shared/src/lib.rs:1154-1179); modes 0/1 mask as the
-    // reference does, the extended mode refuses what it cannot represent rather than looping 2^32 times
-    if (p->mode == RT_MODE_EXTENDED && p->max_bounces > RT_MAX_BOUNCES)
-        return ctx->fail(RT_ERR_BAD_ARG, "rt_render: max_bounces %u > %u", p->max_bounces, RT_MAX_BOUNCES);
-    uint32_t world = p->tile_world ? p->tile_world : 1, rank = p->tile_rank;
-    if (rank >= world) return ctx->fail(RT_ERR_BAD_ARG, "rt_render: tile_rank %u >= tile_world %u", rank, world);
+    uint32_t world = 1, rank = 0;
     DevFrame fr{};
-    fr.width = p->width;
-    fr.height = p->height;
-    fr.tile_size = p->tile_size ? p->tile_size : RT_TILE_SIZE;
-    if (fr.tile_size > 4096) return ctx->fail(RT_ERR_BAD_ARG, "rt_render: tile_size %u too large", fr.tile_size);
-    fr.tiles_x = (fr.width + fr.tile_size - 1) / fr.tile_size; // TileHelper::calculate_tile_count, shared/src/lib.rs:1187-1191
-    fr.tiles_y = (fr.height + fr.tile_size - 1) / fr.tile_size;
-    fr.mode = p->mode;
-    fr.channel_mask = 7u;
-    fr.cur_bounce = 0; // the bounce-0 pass of src/compute.rs:413-479 (later passes redraw the same pixels)
-    fr.max_bounce = p->mode == RT_MODE_EXTENDED ? p->max_bounces : (p->max_bounces & 0xFF);
-    fr.spp = p->mode == RT_MODE_EXTENDED ? p->spp : 1;
-    fr.flags = p->flags;
-    fr.frame_seed = p->frame_seed;
-    fr.cam = make_camera(p->camera, (float)p->width, (float)p->height, p->mode != RT_MODE_LEGACY);
-    fr.n_total = fr.spp; // a closed frame: samples 0 .. spp-1, jittered when there are several (DESIGN.md section 5)
-    fr.jitter = fr.spp > 1 ? 1u : 0u;
+    if (int rc = frame_of_params(ctx, "rt_render", p, fr, world, rank)) return rc;
+    const bool accumulate = (p->flags & RT_FLAG_ACCUMULATE) != 0;
     AccumKey key{};
     if (accumulate) {
         key.camera = p->camera;
@@ -1512,8 +1547,21 @@ int rt_dispatch_tile(rt_ctx* ctx, const rt_push_constants* pc) {
     return RT_OK;
 }
 
-// Copy `elem` bytes per pixel of every device's owned tiles into `out` (full frame, row-major).
+// Copy `elem` bytes per pixel of the tiles first, first + stride, ... (n_owned of them) of a w x h frame of tile_size tiles, tiles_x
+// per row, from `src` to `dst` (both full frames, row-major).
 namespace {
+void copy_share(uint8_t* dst, const uint8_t* src, size_t elem, uint32_t w, uint32_t h, uint32_t ts, uint32_t tiles_x, uint32_t first, uint32_t stride,
+                uint32_t n_owned) {
+    for (uint32_t k = 0; k < n_owned; k++) {
+        uint32_t tile = first + k * stride;
+        uint32_t ty = tile / tiles_x, tx = tile % tiles_x;
+        uint32_t x0 = tx * ts, y0 = ty * ts, tw = std::min(ts, w - x0), th = std::min(ts, h - y0);
+        for (uint32_t y = y0; y < y0 + th; y++)
+            std::memcpy(dst + ((size_t)y * w + x0) * elem, src + ((size_t)y * w + x0) * elem, (size_t)tw * elem);
+    }
+}
+
+// Copy `elem` bytes per pixel of every device's owned tiles into `out` (full frame, row-major).
 int gather(rt_ctx* ctx, uint8_t* out, size_t elem, int which /*0 rgba32f, 1..3 chan, 4 prim, 5 t*/) {
     uint32_t w = ctx->frame_w, h = ctx->frame_h;
     size_t n = (size_t)w * h;
@@ -1530,14 +1578,7 @@ int gather(rt_ctx* ctx, uint8_t* out, size_t elem, int which /*0 rgba32f, 1..3 c
         }
         tmp.resize(n * elem);
         HIPCHK(ctx, hipMemcpy(tmp.data(), src, n * elem, hipMemcpyDeviceToHost));
-        uint32_t ts = ctx->frame_tile;
-        for (uint32_t k = 0; k < d.n_owned; k++) {
-            uint32_t tile = d.tile_first + k * d.tile_stride;
-            uint32_t ty = tile / ctx->frame_tiles_x, tx = tile % ctx->frame_tiles_x;
-            uint32_t x0 = tx * ts, y0 = ty * ts, tw = std::min(ts, w - x0), th = std::min(ts, h - y0);
-            for (uint32_t y = y0; y < y0 + th; y++)
-                std::memcpy(out + ((size_t)y * w + x0) * elem, tmp.data() + ((size_t)y * w + x0) * elem, (size_t)tw * elem);
-        }
+        copy_share(out, tmp.data(), elem, w, h, ctx->frame_tile, ctx->frame_tiles_x, d.tile_first, d.tile_stride, d.n_owned);
     }
     return RT_OK;
 }
@@ -2186,6 +2227,241 @@ int rt_update_geometry(rt_ctx* ctx, const rt_vertex* vertices, uint32_t n_vertic
     st.kernel_ms = kernel_ms;
     st.wall_ms = now_ms() - w0;
     return RT_OK;
+}
+
+} // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Feature buffers and denoising (rt_hip.h "Feature buffers (AOVs) and denoising"): rt_aovs, rt_sample_rays, rt_denoise.  Kernels in
+// denoise.hip.  None of them touches the frame targets, the tile shares rt_read_* gather, or the running image of an accumulation.
+// ---------------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// The jitter rule of the frames: a closed frame jitters when it has several samples (frame_of_params), an accumulation always.
+void sample_jitter(DevFrame& fr, uint32_t flags) {
+    if (flags & RT_FLAG_ACCUMULATE) fr.jitter = 1u;
+}
+
+void drain_streams(rt_ctx* ctx) { // after a failure: nothing of the call is left writing into the caller's memory
+    for (auto& d : ctx->devs) {
+        (void)hipSetDevice(d.device);
+        (void)hipStreamSynchronize(d.stream);
+    }
+}
+
+// One device's share of rt_aovs, enqueued: zero the frame's records (the pixels outside the share stay zero), then the samples in runs of
+// at most RT_AOV_SAMPLES_PER_LAUNCH, between the device's query event pair.
+int enqueue_aovs(rt_ctx* ctx, DeviceState& d, const DevFrame& f, void* acc, size_t bytes) {
+    HIPCHK(ctx, hipSetDevice(d.device));
+    if (int rc = ensure_query_events(ctx, d, 2)) return rc;
+    HIPCHK(ctx, hipMemsetAsync(acc, 0, bytes, d.stream));
+    HIPCHK(ctx, hipEventRecord(d.rq_events[0], d.stream));
+    const DevScene sc = scene_for(ctx, d);
+    for (uint32_t s0 = 0; s0 < f.n_total; s0 += RT_AOV_SAMPLES_PER_LAUNCH)
+        HIPCHK(ctx, rt::launch_aov_samples(sc, f, s0, std::min(RT_AOV_SAMPLES_PER_LAUNCH, f.n_total - s0), acc, d.stream));
+    HIPCHK(ctx, hipEventRecord(d.rq_events[1], d.stream));
+    return RT_OK;
+}
+
+int aovs(rt_ctx* ctx, const rt_render_params* p, rt_aov* out) {
+    const double w0 = now_ms();
+    uint32_t world = 1, rank = 0;
+    DevFrame fr{};
+    if (int rc = frame_of_params(ctx, "rt_aovs", p, fr, world, rank)) return rc;
+    if (!out) return ctx->fail(RT_ERR_BAD_ARG, "rt_aovs: out is NULL");
+    if (int rcp = sync_pending(ctx)) return rcp;
+    QueryPtr po;
+    if (int rc = classify_ptr(ctx, "rt_aovs", "out", out, po)) return rc;
+    sample_jitter(fr, p->flags);
+    const size_t n = (size_t)fr.width * fr.height, bytes = n * sizeof(rt_aov);
+    const size_t nd = ctx->devs.size();
+    const bool in_place = po.device && nd == 1; // else every device works on its own records and the shares are put together here
+    std::vector<DevFrame> share(nd, fr);
+    for (size_t j = 0; j < nd; j++) {
+        DeviceState& d = ctx->devs[j];
+        frame_share(share[j], world, rank, nd, j);
+        HIPCHK(ctx, hipSetDevice(d.device));
+        if (!in_place)
+            if (int rc = ensure_buffer(ctx, &d.dn_aov, &d.dn_aov_bytes, bytes)) return rc;
+        if (int rc = enqueue_aovs(ctx, d, share[j], in_place ? (void*)out : d.dn_aov, bytes)) {
+            drain_streams(ctx);
+            return rc;
+        }
+    }
+    double kernel_ms = 0.0;
+    uint64_t pixels = 0;
+    for (size_t j = 0; j < nd; j++) {
+        DeviceState& d = ctx->devs[j];
+        hipError_t e = hipSetDevice(d.device);
+        if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
+        if (e != hipSuccess) {
+            drain_streams(ctx);
+            return ctx->fail(RT_ERR_HIP, "rt_aovs: device %d: %s", d.device, hipGetErrorString(e));
+        }
+        float ms = 0.0f;
+        HIPCHK(ctx, hipEventElapsedTime(&ms, d.rq_events[0], d.rq_events[1]));
+        kernel_ms = std::max(kernel_ms, (double)ms);
+        pixels += owned_pixels(share[j], share[j].tile_first, share[j].tile_stride, share[j].n_owned_tiles);
+    }
+    if (!in_place && nd == 1) {
+        HIPCHK(ctx, hipSetDevice(ctx->devs[0].device));
+        HIPCHK(ctx, hipMemcpy(out, ctx->devs[0].dn_aov, bytes, hipMemcpyDeviceToHost));
+    } else if (!in_place) { // several devices: each holds its own tiles; zeros elsewhere, as rt_read_rgb32f gives them
+        std::vector<uint8_t> whole(bytes, 0), tmp(bytes);
+        for (size_t j = 0; j < nd; j++) {
+            const DeviceState& d = ctx->devs[j];
+            const DevFrame& f = share[j];
+            if (f.n_owned_tiles == 0) continue;
+            HIPCHK(ctx, hipSetDevice(d.device));
+            HIPCHK(ctx, hipMemcpy(tmp.data(), d.dn_aov, bytes, hipMemcpyDeviceToHost));
+            copy_share(whole.data(), tmp.data(), sizeof(rt_aov), f.width, f.height, f.tile_size, f.tiles_x, f.tile_first, f.tile_stride, f.n_owned_tiles);
+        }
+        if (po.device) {
+            HIPCHK(ctx, hipSetDevice(ctx->devs[po.dev].device));
+            HIPCHK(ctx, hipMemcpy(out, whole.data(), bytes, hipMemcpyHostToDevice));
+        } else {
+            std::memcpy(out, whole.data(), bytes);
+        }
+    }
+    rt_stats& st = ctx->stats;
+    st.pixels = pixels;
+    st.rays = st.primary_rays = pixels * fr.n_total;
+    st.continuation_rays = st.shadow_rays = st.node_visits = st.tri_tests = 0;
+    st.kernel_ms = kernel_ms;
+    st.wall_ms = now_ms() - w0;
+    return RT_OK;
+}
+
+int check_sigma(rt_ctx* ctx, const char* name, float s) {
+    if (!(s > 0.0f) || !std::isfinite(s)) return ctx->fail(RT_ERR_BAD_ARG, "rt_denoise: %s %g (finite and > 0)", name, (double)s);
+    return RT_OK;
+}
+
+int denoise(rt_ctx* ctx, const rt_denoise_params* dp, const float* rgb, const rt_aov* aov, float* out) {
+    const double w0 = now_ms();
+    if (!dp || !rgb || !aov || !out)
+        return ctx->fail(RT_ERR_BAD_ARG, "rt_denoise: %s is NULL", !dp ? "params" : !rgb ? "rgb" : !aov ? "aov" : "out");
+    if (dp->width == 0 || dp->height == 0 || dp->width > 65535u * 8u || dp->height > 65535u * 8u)
+        return ctx->fail(RT_ERR_BAD_ARG, "rt_denoise: bad resolution %ux%u", dp->width, dp->height);
+    if (dp->iterations < 1 || dp->iterations > RT_DENOISE_MAX_ITERATIONS)
+        return ctx->fail(RT_ERR_BAD_ARG, "rt_denoise: iterations %u (1 .. %u)", dp->iterations, RT_DENOISE_MAX_ITERATIONS);
+    if (dp->flags & ~RT_DENOISE_DEMODULATE) return ctx->fail(RT_ERR_BAD_ARG, "rt_denoise: unknown flag bits 0x%x", dp->flags & ~RT_DENOISE_DEMODULATE);
+    if (int rc = check_sigma(ctx, "sigma_color", dp->sigma_color)) return rc;
+    if (int rc = check_sigma(ctx, "sigma_normal", dp->sigma_normal)) return rc;
+    if (int rc = check_sigma(ctx, "sigma_depth", dp->sigma_depth)) return rc;
+    if (int rc = check_sigma(ctx, "sigma_albedo", dp->sigma_albedo)) return rc;
+    if (int rcp = sync_pending(ctx)) return rcp;
+    QueryPtr pr, pa, po;
+    if (int rc = classify_ptr(ctx, "rt_denoise", "rgb", rgb, pr, 4)) return rc;
+    if (int rc = classify_ptr(ctx, "rt_denoise", "aov", aov, pa, 16)) return rc;
+    if (int rc = classify_ptr(ctx, "rt_denoise", "out", out, po, 4)) return rc;
+    if (pr.device != pa.device || pr.device != po.device || pr.dev != pa.dev || pr.dev != po.dev)
+        return ctx->fail(RT_ERR_BAD_ARG, "rt_denoise: rgb, aov and out must all be host memory or all device memory of the same device");
+    const bool device = pr.device;
+    DeviceState& d = ctx->devs[pr.dev]; // host buffers: the first device
+    const uint32_t n = dp->width * dp->height;
+    if ((size_t)dp->width * dp->height > 0xFFFFFFFFull) return ctx->fail(RT_ERR_BAD_ARG, "rt_denoise: %ux%u pixels", dp->width, dp->height);
+    HIPCHK(ctx, hipSetDevice(d.device));
+    for (int k = 0; k < 2; k++)
+        if (int rc = ensure_buffer(ctx, &d.dn_plane[k], &d.dn_plane_bytes[k], (size_t)n * 16)) return rc;
+    if (!device) {
+        if (int rc = ensure_buffer(ctx, &d.dn_rgb, &d.dn_rgb_bytes, (size_t)n * 12)) return rc;
+        if (int rc = ensure_buffer(ctx, &d.dn_aov, &d.dn_aov_bytes, (size_t)n * sizeof(rt_aov))) return rc;
+    }
+    if (int rc = ensure_query_events(ctx, d, 2)) return rc;
+    const float* c_rgb = device ? rgb : (const float*)d.dn_rgb;
+    const void* c_aov = device ? (const void*)aov : d.dn_aov;
+    float* c_out = device ? out : (float*)d.dn_rgb; // the pack has read the staged rgb before the last iteration writes over it
+    float4* plane[2] = {(float4*)d.dn_plane[0], (float4*)d.dn_plane[1]};
+    const bool demod = (dp->flags & RT_DENOISE_DEMODULATE) != 0;
+    auto enqueue = [&]() -> hipError_t {
+        hipError_t e = hipSuccess;
+        if (!device) {
+            if ((e = hipMemcpyAsync(d.dn_rgb, rgb, (size_t)n * 12, hipMemcpyHostToDevice, d.stream)) != hipSuccess) return e;
+            if ((e = hipMemcpyAsync(d.dn_aov, aov, (size_t)n * sizeof(rt_aov), hipMemcpyHostToDevice, d.stream)) != hipSuccess) return e;
+        }
+        if ((e = hipEventRecord(d.rq_events[0], d.stream)) != hipSuccess) return e;
+        if ((e = rt::launch_denoise_pack(c_rgb, c_aov, plane[0], n, demod, d.stream)) != hipSuccess) return e;
+        for (uint32_t i = 0; i < dp->iterations; i++) {
+            rt::AtrousParams ap;
+            ap.width = dp->width, ap.height = dp->height, ap.iter = i;
+            const float sc = dp->sigma_color * std::ldexp(1.0f, -(int)i); // sigma_color * 2^-i
+            ap.inv_sc2 = 1.0f / (sc * sc);
+            ap.inv_sn2 = 1.0f / (dp->sigma_normal * dp->sigma_normal);
+            ap.sigma_depth = dp->sigma_depth;
+            ap.inv_sa2 = 1.0f / (dp->sigma_albedo * dp->sigma_albedo);
+            ap.demodulate = demod;
+            const bool last = i + 1 == dp->iterations;
+            if ((e = rt::launch_denoise_atrous(ap, plane[i & 1], c_aov, plane[(i + 1) & 1], c_out, last, d.stream)) != hipSuccess) return e;
+        }
+        if ((e = hipEventRecord(d.rq_events[1], d.stream)) != hipSuccess) return e;
+        if (!device) e = hipMemcpyAsync(out, d.dn_rgb, (size_t)n * 12, hipMemcpyDeviceToHost, d.stream);
+        return e;
+    };
+    hipError_t e = enqueue();
+    if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
+    if (e != hipSuccess) {
+        drain_streams(ctx);
+        return ctx->fail(e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP, "rt_denoise: %s", hipGetErrorString(e));
+    }
+    float ms = 0.0f;
+    HIPCHK(ctx, hipEventElapsedTime(&ms, d.rq_events[0], d.rq_events[1]));
+    rt_stats& st = ctx->stats;
+    st.rays = st.primary_rays = st.continuation_rays = st.shadow_rays = st.node_visits = st.tri_tests = 0;
+    st.pixels = n;
+    st.kernel_ms = ms;
+    st.wall_ms = now_ms() - w0;
+    return RT_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int rt_aovs(rt_ctx* ctx, const rt_render_params* p, rt_aov* out) {
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (!p) return ctx->fail(RT_ERR_BAD_ARG, "rt_aovs: null params");
+    if (!ctx->uploaded) return ctx->fail(RT_ERR_NOT_UPLOADED, "rt_aovs: no scene uploaded");
+    return aovs(ctx, p, out);
+}
+
+int rt_sample_rays(rt_ctx* ctx, const rt_render_params* p, uint32_t sample, rt_ray* out) {
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (!p) return ctx->fail(RT_ERR_BAD_ARG, "rt_sample_rays: null params");
+    if (p->mode != RT_MODE_EXTENDED) return ctx->fail(RT_ERR_BAD_ARG, "rt_sample_rays: mode %u (the extended mode's samples only)", p->mode);
+    rt_render_params q = *p;
+    q.tile_size = q.tile_rank = q.tile_world = 0; // ignored
+    uint32_t world = 1, rank = 0;
+    DevFrame fr{};
+    if (int rc = frame_of_params(ctx, "rt_sample_rays", &q, fr, world, rank)) return rc;
+    if (!out) return ctx->fail(RT_ERR_BAD_ARG, "rt_sample_rays: out is NULL");
+    if (int rcp = sync_pending(ctx)) return rcp;
+    QueryPtr po;
+    if (int rc = classify_ptr(ctx, "rt_sample_rays", "out", out, po)) return rc;
+    sample_jitter(fr, p->flags);
+    const size_t n = (size_t)fr.width * fr.height;
+    DeviceState& d = ctx->devs[po.dev];
+    HIPCHK(ctx, hipSetDevice(d.device));
+    if (!po.device)
+        if (int rc = ensure_buffer(ctx, &d.rq_in, &d.rq_in_bytes, std::min<size_t>(n, RT_QUERY_CHUNK) * sizeof(rt_ray))) return rc;
+    uint8_t* dst = reinterpret_cast<uint8_t*>(out);
+    for (size_t off = 0; off < n; off += RT_QUERY_CHUNK) { // as rt_camera_rays
+        const size_t m = std::min<size_t>(RT_QUERY_CHUNK, n - off);
+        void* res = po.device ? (void*)(dst + off * sizeof(rt_ray)) : d.rq_in;
+        hipError_t e = rt::launch_sample_rays(fr, sample, res, off, (uint32_t)m, d.stream);
+        if (e == hipSuccess && !po.device) e = hipMemcpyAsync(dst + off * sizeof(rt_ray), d.rq_in, m * sizeof(rt_ray), hipMemcpyDeviceToHost, d.stream);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(d.stream);
+            return ctx->fail(RT_ERR_HIP, "rt_sample_rays: %s", hipGetErrorString(e));
+        }
+    }
+    HIPCHK(ctx, hipStreamSynchronize(d.stream));
+    return RT_OK;
+}
+
+int rt_denoise(rt_ctx* ctx, const rt_denoise_params* dp, const float* rgb, const rt_aov* aov, float* out) {
+    if (!ctx) return RT_ERR_BAD_ARG;
+    return denoise(ctx, dp, rgb, aov, out);
 }
 
 } // extern "C"

@@ -69,6 +69,19 @@ STATS = np.dtype([
     ("texture_bytes", np.uint64), ("n_textures", u32), ("tree_build", u32),
     ("grid_bytes", np.uint64), ("grid_build_ms", np.float64),
 ])
+AOV = np.dtype([("albedo", f32, 3), ("depth", f32), ("normal", f32, 3), ("coverage", f32)])  # rt_aov
+DENOISE_PARAMS = np.dtype([
+    ("width", u32), ("height", u32), ("iterations", u32), ("flags", u32),
+    ("sigma_color", f32), ("sigma_normal", f32), ("sigma_depth", f32), ("sigma_albedo", f32),
+])
+AOV_SAMPLES_PER_LAUNCH = 64  # RT_AOV_SAMPLES_PER_LAUNCH
+DENOISE_DEMODULATE = 1  # RT_DENOISE_DEMODULATE
+DENOISE_MAX_ITERATIONS = 10
+DENOISE_DEFAULT_ITERATIONS = 2  # RT_DENOISE_DEFAULT_*: DESIGN.md section 4, the sweep they were chosen by
+DENOISE_DEFAULT_SIGMA_COLOR = 4.0
+DENOISE_DEFAULT_SIGMA_NORMAL = 1.0
+DENOISE_DEFAULT_SIGMA_DEPTH = 0.1
+DENOISE_DEFAULT_SIGMA_ALBEDO = 0.3
 STAT_MEGAKERNEL_FALLBACK = 1
 STAT_SINGLE_PASS = 2
 PREPARE_SHADOW_GRIDS = 1
@@ -78,7 +91,7 @@ MAX_BOUNCES = 255
 EXPECTED_SIZES = {
     "CAMERA": 40, "MATERIAL": 128, "LIGHT": 52, "TEXTURE_INFO": 32, "SPHERE": 20, "VERTEX": 12,
     "TRIANGLE": 16, "AABB": 32, "BVH_NODE": 48, "WAVEFRONT_RAY": 76, "WAVEFRONT_COUNTERS": 60,
-    "SCENE_METADATA_OFFSETS": 40, "PUSH_CONSTANTS": 128,
+    "SCENE_METADATA_OFFSETS": 40, "PUSH_CONSTANTS": 128, "AOV": 32, "DENOISE_PARAMS": 32,
 }
 for _name, _size in EXPECTED_SIZES.items():
     assert globals()[_name].itemsize == _size, (_name, globals()[_name].itemsize, _size)

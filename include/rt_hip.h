@@ -224,7 +224,7 @@ int rt_get_stats(rt_ctx* ctx, rt_stats* out);
  * a new one at sample 0 by itself, as RT_FLAG_ACCUMULATE_RESTART does.  The other RT_FLAG_* bits change no bits and may differ.
  * The running image ends (the next accumulating call starts at 0) with rt_upload_scene*, rt_update_geometry, rt_dispatch_tile, any
  * rt_render without RT_FLAG_ACCUMULATE and an accumulating call that fails once it has passed its argument checks.  It survives rt_prepare,
- * rt_upload_textures, the ray queries, rt_camera_rays, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
+ * rt_upload_textures, the ray queries, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
  * Limit: RT_ACCUMULATE_MAX_SAMPLES samples (where the float sample count stops being exact); a call that would pass it is RT_ERR_BAD_ARG
  * and leaves the running image as it was.  rt_stats describes the call alone (its segments, pixels, kernel_ms).
  * A context over several devices, and a tile_rank / tile_world share, accumulates its own share of the pixels.
@@ -332,6 +332,86 @@ int rt_update_geometry(rt_ctx* ctx,
                        const rt_vertex* vertices, uint32_t n_vertices, /* NULL: vertices unchanged */
                        const rt_sphere* spheres, uint32_t n_spheres,   /* NULL: spheres unchanged  */
                        uint32_t flags);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Feature buffers (AOVs) and denoising (no reference counterpart; Cycles' viewport denoising and the edge-avoiding a-trous
+ * wavelet filter of Dammertz, Sewtz, Hanika and Lensch, HPG 2010, are the model).  The statement is DESIGN.md section 4,
+ * "Feature buffers and the a-trous denoiser".
+ *
+ * rt_aovs: per pixel, what the first vertex of the frame `p` describes traces: albedo, geometric normal and depth of the first hit.
+ *   p is the struct rt_render takes, validated by the same rules (same errors).  The samples are those of a frame with p: mode 2
+ *   traces samples 0 .. spp-1 (rng_for(frame_seed + x + y * width, s), then the camera ray), jittered when spp > 1 or when
+ *   RT_FLAG_ACCUMULATE is set; so for a running image of N samples (rt_accumulated_samples) pass spp = N with RT_FLAG_ACCUMULATE.
+ *   Modes 0/1: the single pixel-centre ray of that mode; spp is ignored.  No other field or flag changes the result.
+ *   Per sample, the closest hit is the frames' (spheres first, the tie rule).  On a hit: albedo = the material's albedo (magenta
+ *   for an invalid material id), normal = the geometric normal face-forwarded against the ray, depth = t.  On a miss: albedo = the
+ *   colour the mode gives a miss (sky (0.1, 0.2, 0.3) in modes 1/2, black in mode 0), normal = 0.
+ *   Per pixel, f32 sums in sample order: albedo = sum albedo_s / spp; normal = sum over hits of normal_s / spp (not renormalised:
+ *   a silhouette pixel has a shorter normal); depth = sum over hits of t_s / hits, 0 without a hit; coverage = hits / spp.
+ *   The pixel set is the frame's: pixels outside the context's tile_rank / tile_world share are written as zero, a context over
+ *   several devices splits the tiles as rt_render does; the result does not depend on the device count, tile_size or the tree.
+ *   A launch traces at most RT_AOV_SAMPLES_PER_LAUNCH samples; the partial sums stay on the device in sample order.
+ *   Statistics: rays = primary_rays = camera segments traced, pixels, kernel_ms (max over devices), wall_ms; the rest 0.
+ * rt_sample_rays: the width * height mode-2 camera rays of global sample `sample` of the frame p (jitter rule as above), row-major,
+ *   tmin = RT_MIN_RAY_DISTANCE, tmax = FLT_MAX.  Other modes are RT_ERR_BAD_ARG; the tile fields are ignored; needs no scene.  For a
+ *   closed 1-spp p these are the bits of rt_camera_rays(mode 1).  Statistics as rt_camera_rays (unchanged).
+ * rt_denoise: C = rgb (rt_read_rgb32f layout), A, N, Z = albedo, normal, depth of `aov`.
+ *   1. D = max(A, 1e-3) per channel with RT_DENOISE_DEMODULATE, else 1; c_0 = C / D.
+ *   2. For i = 0 .. iterations-1, h = 2^i, every pixel p: taps q = p + h * (dx, dy), dy outer, dx inner, each -2..2, kernel
+ *      k = {1/16, 1/4, 3/8, 1/4, 1/16}.  A tap outside the image or whose colour is not finite is skipped.
+ *      e = |c_i(p) - c_i(q)|^2 / (sigma_color * 2^-i)^2 + |N(p) - N(q)|^2 / sigma_normal^2 + e_z + |A(p) - A(q)|^2 / sigma_albedo^2,
+ *      e_z = ((Z(p) - Z(q)) / (sigma_depth * max(Z(p), Z(q))))^2, 0 when both depths are 0; w = k[dx] * k[dy] * expf(-e);
+ *      c_{i+1}(p) = sum w * c_i(q) / sum w.  A pixel whose own colour is not finite is passed through unchanged.
+ *   3. out = c_K * D.
+ *   Buffers are classified as for the ray queries: all three host memory (staged through the context's first device), or all
+ *   device memory of one of the context's devices (aov 16-byte aligned, rgb / out 4-byte aligned).  out may equal rgb.
+ *   Statistics: pixels, kernel_ms, wall_ms; the rest 0.  Needs no scene.
+ * Shared: all three are synchronous, first wait for an rt_dispatch_tile still in flight, and leave the last frame, rt_read_* and
+ * the running image of an accumulation alone.  rt_aovs before an upload is RT_ERR_NOT_UPLOADED; NULL pointers, bad sizes and bad
+ * parameters are RT_ERR_BAD_ARG and change nothing.
+ * --------------------------------------------------------------------------------------------------------------- */
+typedef struct rt_aov {
+    float albedo[3];
+    float depth;
+    float normal[3];
+    float coverage;
+} rt_aov; /* 32 bytes */
+
+RT_STATIC_ASSERT(sizeof(rt_aov) == 32, "rt_aov is 32 B");
+RT_STATIC_ASSERT(offsetof(rt_aov, depth) == 12 && offsetof(rt_aov, normal) == 16 && offsetof(rt_aov, coverage) == 28, "rt_aov offsets");
+
+#define RT_AOV_SAMPLES_PER_LAUNCH 64u /* rt_aovs: samples one kernel launch traces at most */
+
+#define RT_DENOISE_DEMODULATE 1u       /* rt_denoise_params.flags: filter C / max(albedo, 1e-3), multiply back afterwards */
+#define RT_DENOISE_MAX_ITERATIONS 10u
+
+/* Defaults (the sweep they were chosen by). */
+#define RT_DENOISE_DEFAULT_ITERATIONS 2u
+#define RT_DENOISE_DEFAULT_SIGMA_COLOR 4.0f
+#define RT_DENOISE_DEFAULT_SIGMA_NORMAL 1.0f
+#define RT_DENOISE_DEFAULT_SIGMA_DEPTH 0.1f
+#define RT_DENOISE_DEFAULT_SIGMA_ALBEDO 0.3f
+
+typedef struct rt_denoise_params {
+    uint32_t width, height;
+    uint32_t iterations; /* 1 .. RT_DENOISE_MAX_ITERATIONS */
+    uint32_t flags;      /* RT_DENOISE_DEMODULATE */
+    float sigma_color, sigma_normal, sigma_depth, sigma_albedo; /* > 0, finite */
+} rt_denoise_params; /* 32 bytes */
+
+RT_STATIC_ASSERT(sizeof(rt_denoise_params) == 32, "rt_denoise_params is 32 B");
+RT_STATIC_ASSERT(offsetof(rt_denoise_params, flags) == 12 && offsetof(rt_denoise_params, sigma_color) == 16 &&
+                     offsetof(rt_denoise_params, sigma_albedo) == 28,
+                 "rt_denoise_params offsets");
+
+/* First-hit feature buffers of the frame p: width * height records, row-major, y down. */
+int rt_aovs(rt_ctx* ctx, const rt_render_params* p, rt_aov* out);
+
+/* The frame p's mode-2 camera rays of global sample `sample`: width * height records. */
+int rt_sample_rays(rt_ctx* ctx, const rt_render_params* p, uint32_t sample, rt_ray* out);
+
+/* Edge-avoiding a-trous filter of rgb (width * height * 3 floats) guided by aov (width * height records) -> out (may equal rgb). */
+int rt_denoise(rt_ctx* ctx, const rt_denoise_params* dp, const float* rgb, const rt_aov* aov, float* out);
 
 /* Last error text of this context (or of the failed rt_create when ctx is NULL). */
 const char* rt_last_error(rt_ctx* ctx);
