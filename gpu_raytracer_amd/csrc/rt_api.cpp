@@ -705,19 +705,29 @@ int ensure_wavefront(rt_ctx* ctx, DeviceState& d, uint32_t n_blocks, uint32_t ba
     };
     rt::WfBuffers& w = lane ? d.wf2 : d.wf;
     const size_t P = capacity ? capacity : 64;
-    HIPCHK(ctx, alloc((void**)&w.ray_o, P * 16));
-    HIPCHK(ctx, alloc((void**)&w.ray_d, P * 16));
-    HIPCHK(ctx, alloc((void**)&w.hit, P * 16));
-    HIPCHK(ctx, alloc((void**)&w.thr, P * 16));
-    HIPCHK(ctx, alloc((void**)&w.rad, P * 16));
-    HIPCHK(ctx, alloc((void**)&w.vtx, P * 32));
-    HIPCHK(ctx, alloc((void**)&w.sample_rad, P * 16));
-    HIPCHK(ctx, alloc((void**)&w.pxy, P * 4));
     // producers reserve queue space in windows (wavefront.hip): wf_queue_slots is the bound on real entries + padding
     const uint32_t lights = std::max(1u, n_lights);
     const size_t ext_slots = rt::wf_queue_slots(P, 1), shadow_slots = rt::wf_queue_slots(P * (size_t)lights, lights);
     if (ext_slots > 0xFFFFFFFFull || shadow_slots > 0xFFFFFFFFull)
         return ctx->fail(RT_ERR_INTERNAL, "wavefront queues of %zu / %zu slots exceed 32-bit positions", ext_slots, shadow_slots);
+    // from depth 1 on a path's id is its extension queue position (k_wf_finish compacts): the arrays indexed by id hold S records, and
+    // ids must fit the 27 bits they share with a light index in shadow queue entries (wavefront_max_paths keeps P small enough)
+    const size_t S = std::min(rt::wf_state_slots(P), ext_slots);
+    if (S > (size_t)RT_WF_ID_MASK + 1)
+        return ctx->fail(RT_ERR_INTERNAL, "wavefront path ids of %zu slots exceed %u bits", S, 27u);
+    HIPCHK(ctx, alloc((void**)&w.ray_o, S * 16));
+    HIPCHK(ctx, alloc((void**)&w.ray_d, S * 16));
+    HIPCHK(ctx, alloc((void**)&w.thr, S * 16));
+    HIPCHK(ctx, alloc((void**)&w.rad, S * 16));
+    HIPCHK(ctx, alloc((void**)&w.next_o, S * 16));
+    HIPCHK(ctx, alloc((void**)&w.next_d, S * 16));
+    HIPCHK(ctx, alloc((void**)&w.next_thr, S * 16));
+    HIPCHK(ctx, alloc((void**)&w.next_rad, S * 16));
+    HIPCHK(ctx, alloc((void**)&w.hit, S * 16));
+    HIPCHK(ctx, alloc((void**)&w.vtx, S * 32));
+    HIPCHK(ctx, alloc((void**)&w.sample_rad, P * 16));
+    HIPCHK(ctx, alloc((void**)&w.pxy, P * 4));
+    w.state_cap = (uint32_t)S;
     HIPCHK(ctx, alloc((void**)&w.q_ext[0], ext_slots * 4));
     HIPCHK(ctx, alloc((void**)&w.q_ext[1], ext_slots * 4));
     HIPCHK(ctx, alloc((void**)&w.q_shadow, shadow_slots * 4));
@@ -751,14 +761,25 @@ int ensure_wavefront(rt_ctx* ctx, DeviceState& d, uint32_t n_blocks, uint32_t ba
 // Samples per pixel kept in flight by the wavefront pipeline.  Every stage of every bounce ends in a tail where
 // the persistent waves drain, and late bounces carry few paths, so batches should be as large as memory allows:
 // measured on the headline frame, 3 samples per batch (8 M paths) 4,640 Mrays/s, 32 per batch (71 M paths, 12 GB
-// of the 288 GB) 5,840.  Target 64 M paths, bounded by half the free device memory, the 27-bit path id of a shadow
+// of the 288 GB while the path state was updated in place; ~21 GB per lane with compaction: two state sets over ~1.65 id slots per
+// path slot) 5,840.  Target 64 M paths, bounded by half the free device memory, the 27-bit path id of a shadow
 // queue entry and the 32-bit queue positions; the samples are then spread evenly over the batches.
 // RT_WF_BATCH (samples per batch) / RT_WF_TARGET_PATHS override.
-// Largest number of path slots the wavefront pipeline can address: 27-bit path ids in shadow queue entries, 32-bit queue
-// positions with up to 4 slots per (path, light) plus per-wave slack (wf_queue_slots).
+// Largest number of path slots the wavefront pipeline can address: 27-bit path ids in shadow queue entries - compacted ids are queue
+// positions, padding included (wf_state_slots: ~88 M path slots on MI355X) - and 32-bit queue positions with up to 4 slots per
+// (path, light) plus per-wave slack (wf_queue_slots).
 uint64_t wavefront_max_paths(uint32_t n_lights) {
+    static const uint64_t by_ids = [] { // the most path slots whose compacted ids fit 27 bits (wf_state_slots grows with P)
+        uint64_t lo = 1, hi = (uint64_t)RT_WF_ID_MASK + 1;
+        while (lo < hi) {
+            const uint64_t mid = (lo + hi + 1) / 2;
+            if (rt::wf_state_slots((size_t)mid) <= (uint64_t)RT_WF_ID_MASK + 1) lo = mid;
+            else hi = mid - 1;
+        }
+        return lo;
+    }();
     const uint64_t lights = std::max(1u, n_lights);
-    return std::min<uint64_t>((uint64_t)RT_WF_ID_MASK + 1, (1ull << 29) / lights);
+    return std::min<uint64_t>(by_ids, (1ull << 29) / lights);
 }
 
 uint32_t wavefront_batch(uint32_t n_blocks, uint32_t spp, uint32_t n_lights, size_t free_bytes, bool two_lanes) {
@@ -771,7 +792,10 @@ uint32_t wavefront_batch(uint32_t n_blocks, uint32_t spp, uint32_t n_lights, siz
     uint64_t target_paths = 64ull << 20;
     if (const char* e = std::getenv("RT_WF_TARGET_PATHS")) target_paths = std::max<uint64_t>(1, std::strtoull(e, nullptr, 10));
     const uint64_t lights = std::max(1u, n_lights);
-    const uint64_t bytes_per_path = 8 * 16 + 4 + 2 * 16 + 16 * lights + 4 * lights; // path state, vis, pxy, two extension queues, shadow queue (4 slots per entry), the handed-on shadow queue (dense)
+    // path state indexed by id (two sets of ray_o / ray_d / thr / rad, hit, vtx: 176 bytes per record, wf_state_slots records = under 2 per path
+    // slot for batches large enough that memory bounds them), sample_rad, pxy, two extension queues, shadow queue (4 slots per entry), the
+    // handed-on shadow queue (dense)
+    const uint64_t bytes_per_path = 2 * 11 * 16 + 16 + 4 + 2 * 16 + 16 * lights + 4 * lights;
     target_paths = std::min<uint64_t>(target_paths, free_bytes / 2 / bytes_per_path);
     target_paths = std::min<uint64_t>(target_paths, wavefront_max_paths(n_lights));
     uint32_t max_batch = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(spp, target_paths / per_sample));
@@ -835,8 +859,9 @@ struct KernelChoice {
 // the nested-loop kernel loops the pixel's samples in registers, traces the closest hit and the per-light shadow segments inline and
 // stores the pixel once: 2.6 ms, same bits (the per-sample order is fixed by the CPU statement).  SURVEY 7 step 6, shader/src/lib.rs:86-88
 // (one write per pixel).  RT_FLAG_KERNEL_PIPELINE keeps the pipeline.  The pipeline needs one visibility bit per light and every path
-// slot of ONE sample per owned pixel block addressable; anything else (more than 32 lights, a single device's share beyond ~134 M
-// pixels) takes the state-machine megakernel.
+// slot of ONE sample per owned pixel block addressable (wavefront_max_paths: the compacted path ids of a one-sample batch must fit
+// 27 bits); anything else (more than 32 lights, a single device's share beyond ~88 M pixels, fewer with 7 or more lights) takes the
+// state-machine megakernel.
 KernelChoice choose_kernel(const rt_ctx* ctx, const DevFrame& f) {
     using rt::FrameKernel;
     const DevScene& sc = ctx->scene_counts;
@@ -1428,6 +1453,7 @@ unsigned long long rt_debug_queue_slots(unsigned long long max_entries, uint32_t
     return rt::wf_queue_slots_for((size_t)max_entries, per_lane, (size_t)waves);
 }
 uint32_t rt_debug_pick_window(uint32_t iterations, uint32_t per_lane) { return rt::wf_pick_window(iterations, per_lane); }
+unsigned long long rt_debug_state_slots(unsigned long long paths, unsigned long long waves) { return rt::wf_state_slots_for((size_t)paths, (size_t)waves); }
 
 // RT_PREPARE_QUALITY_TREE: the tree of the uploaded scene rebuilt by the host builder (bvh_builder.cpp method 0: multithreaded binned SAH +
 // insertion-based optimisation + the same 8-slot collapse) in place of the one rt_upload_scene* built on the device in milliseconds.  For

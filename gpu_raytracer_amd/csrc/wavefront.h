@@ -59,17 +59,24 @@ enum WfTotal : uint32_t {
 };
 
 struct WfBuffers {
-    // per path slot (P = samples_in_batch * n_blocks * 64)
-    float4* ray_o;       // xyz origin
-    float4* ray_d;       // xyz direction (also the incoming direction of the current vertex)
-    uint4* hit;          // xyz = hit point bits, w = RT_PRIM_MISS | RT_PRIM_SPHERE_FLAG + sphere index | triangle slot
-    float4* thr;         // xyz throughput, w = bits: hero channel | depth << 8
-    float4* rad;         // xyz radiance of the sample so far, w = bits: rng state
-    float4* vtx;         // two per path, always used together, so one 32-byte record = one cache line per gather:
+    // Path ids.  At depth 0 a path's id is its path slot p (P = samples_in_batch * n_blocks * 64 of them), its ORIGIN.  From depth 1 on
+    // it is the path's position in the extension queue: k_wf_finish writes a continuing path's record at the queue slot it reserves
+    // (compaction), so every stage reads the live paths densely.  Positions include window padding: the arrays indexed by id hold
+    // state_cap (wf_state_slots) records, those indexed by origin P.
+    float4* ray_o;       // [id] xyz origin (the current bounce's state; wf_bounce selects one of the two sets by bounce parity)
+    float4* ray_d;       // [id] xyz direction (also the incoming direction of the current vertex), w = bits: origin slot of the path
+    uint4* hit;          // [id] xyz = hit point bits, w = RT_PRIM_MISS | RT_PRIM_SPHERE_FLAG + sphere index | triangle slot
+    float4* thr;         // [id] xyz throughput, w = bits: hero channel | depth << 8
+    float4* rad;         // [id] xyz radiance of the sample so far, w = bits: rng state
+    float4* next_o;      // [queue position] the same four records of the paths that continue, written by k_wf_finish
+    float4* next_d;
+    float4* next_thr;
+    float4* next_rad;
+    float4* vtx;         // [id] two per path, always used together, so one 32-byte record = one cache line per gather:
                          //   [2 id]     xyz vertex position, w = bits: material id
                          //   [2 id + 1] xyz geometric normal, w = bits: the lights with a shadow segment from the current vertex (k_wf_shade), less those the shadow stage found occluded
-    float4* sample_rad;  // xyz final radiance of the sample (written when the path ends)
-    uint32_t* pxy;       // x | y << 16, 0xFFFFFFFF = no pixel (tile edge)
+    float4* sample_rad;  // [origin] xyz final radiance of the sample (written when the path ends)
+    uint32_t* pxy;       // [origin] x | y << 16, 0xFFFFFFFF = no pixel (tile edge)
     // queues
     uint32_t* q_ext[2];  // path ids to extend (double buffered)
     uint32_t* q_shadow;  // path id | light << 27 (frames without light grids; with them the shadow stage goes by vertex, over q_ext)
@@ -80,6 +87,7 @@ struct WfBuffers {
     float4* accum;       // per owned pixel slot: running sum over samples (in sample order)
     uint32_t q_ext_cap;  // slots allocated for each extension queue / the shadow queue: a window reservation that would
     uint32_t q_shadow_cap; // end beyond it raises totals[WF_TOTAL_ERROR] instead of writing (window_reserve)
+    uint32_t state_cap;  // records of the arrays indexed by id (>= P, <= q_ext_cap, <= RT_WF_ID_MASK + 1): k_wf_finish reserves below it
     uint32_t* stack_ovf; // global overflow part of the traversal stacks: [persistent wave][entry][lane], 64-bit entries
     uint32_t ovf_entries; // entries per lane in it
     uint32_t n_blocks;   // 8x8 pixel blocks owned by this device
@@ -104,6 +112,8 @@ struct WfBuffers {
 #define RT_WF_ID_MASK 0x07FFFFFFu
 
 uint32_t wf_shading_blocks(); // grid size (256-thread blocks) of the generate / shade / finish kernels
+size_t wf_state_slots(size_t paths); // records of the arrays indexed by a compacted path id (queue positions k_wf_finish can reach), for `paths` path slots
+size_t wf_state_slots_for(size_t paths, size_t producing_waves); // the same for a given number of producing waves (host-only arithmetic)
 size_t wf_queue_slots(size_t max_entries, uint32_t per_lane); // allocation bound of a queue holding up to max_entries real entries, written with up to per_lane entries per lane and iteration
 size_t wf_queue_slots_for(size_t max_entries, uint32_t per_lane, size_t producing_waves); // the same for a given number of producing waves (host-only arithmetic, unit-tested)
 uint32_t wf_pick_window(uint32_t iterations, uint32_t per_lane); // the reservation window a producing wave uses (host copy of the device rule, unit-tested)
