@@ -9,6 +9,7 @@
 // src/compute.rs:320-363.  With --spp/--bounces it renders the extended mode through rt_render instead; --progressive N refines that
 // image over N accumulating calls (RT_FLAG_ACCUMULATE), the extended mode's counterpart of the progressive tile loop; --denoise then
 // filters the finished image with the a-trous denoiser, guided by the first-hit feature buffers of its samples (rt_aovs, rt_denoise).
+// --adaptive T makes the progressive calls adaptive (rt_render_adaptive): pixels whose error fell below T stop taking samples.
 //
 // Build (done by __graft_entry__.build()):
 //   g++ -std=c++17 -O2 examples/rt_render.cpp -Iinclude -Igpu_raytracer_amd/csrc -Lgpu_raytracer_amd -lrt_hip
@@ -37,12 +38,14 @@ static double now_ms() {
 
 static int usage(const char* argv0, int rc) {
     std::fprintf(rc ? stderr : stdout,
-                 "usage: %s [--gltf FILE.gltf|.glb] [--size WxH] [--out FILE.png|.ppm|.exr] [--spp N --bounces B [--progressive C] [--denoise]] [--fly FRAMES] [--device D]\n"
+                 "usage: %s [--gltf FILE.gltf|.glb] [--size WxH] [--out FILE.png|.ppm|.exr] [--spp N --bounces B [--progressive C [--adaptive T [--min-samples M]]] [--denoise]] [--fly FRAMES] [--device D]\n"
                  "  without --gltf the reference's default scene (6 spheres, 2 triangles, 1 light) is rendered;\n"
                  "  without --spp the reference path runs: progressive 128x128 tiles, three channel dispatches per tile;\n"
                  "  with --spp N the extended mode (jittered samples, shadow rays, --bounces B, default 4) runs through rt_render;\n"
                  "  with --progressive C as well, C accumulating calls of N spp each refine one image of C*N samples (the same image as\n"
                  "  --spp C*N when C*N >= 2); each call's time and the running sample count are printed;\n"
+                 "  with --adaptive T as well, the C calls are adaptive (rt_render_adaptive, threshold T, every pixel gets at least M\n"
+                 "  samples, default 4): converged pixels stop sampling; each call's time, active pixels and samples are printed;\n"
                  "  with --denoise as well, the image (after the last call) is denoised with the default parameters, guided by the\n"
                  "  feature buffers of all its samples, and the denoised image is written;\n"
                  "  with --fly FRAMES a scripted fly-through (CameraController deltas of src/input.rs) renders FRAMES whole frames with\n"
@@ -55,7 +58,9 @@ int main(int argc, char** argv) {
     std::string gltf, out = "out.png";
     uint32_t width = 800, height = 600, spp = 0, bounces = 4, fly = 0, progressive = 0;
     int device = 0;
-    bool denoise = false;
+    bool denoise = false, adaptive = false;
+    float threshold = 0.0f;
+    uint32_t min_samples = 4;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { return i + 1 < argc ? argv[++i] : nullptr; };
@@ -74,10 +79,15 @@ int main(int argc, char** argv) {
         else if (a == "--bounces") bounces = (uint32_t)std::atoi(v);
         else if (a == "--fly") fly = (uint32_t)std::atoi(v);
         else if (a == "--progressive") progressive = (uint32_t)std::atoi(v);
+        else if (a == "--adaptive") {
+            adaptive = true;
+            threshold = (float)std::atof(v);
+        } else if (a == "--min-samples") min_samples = (uint32_t)std::atoi(v);
         else if (a == "--device") device = std::atoi(v);
         else return usage(argv[0], 2);
     }
     if ((progressive || denoise) && !spp) return usage(argv[0], 2); // accumulation and the denoiser's samples are the extended mode's
+    if (adaptive && !progressive) return usage(argv[0], 2);          // adaptive sampling refines a progressive image
 
     // ---- scene (src/scene.rs) ----
     SceneState scene;
@@ -174,15 +184,23 @@ int main(int argc, char** argv) {
         rt_stats st;
         if (progressive) { // what a viewport does: show the image after every call, each call adds spp samples to it
             p.flags = RT_FLAG_ACCUMULATE | RT_FLAG_ACCUMULATE_RESTART;
+            rt_adaptive_params ap;
+            std::memset(&ap, 0, sizeof ap);
+            ap.threshold = threshold;
+            ap.min_samples = min_samples;
             for (uint32_t c = 0; c < progressive; c++) {
                 const double c0 = now_ms();
-                rc = rt_render(ctx, &p);
-                if (rc != RT_OK) return fail("rt_render", rc);
+                rc = adaptive ? rt_render_adaptive(ctx, &p, &ap) : rt_render(ctx, &p);
+                if (rc != RT_OK) return fail(adaptive ? "rt_render_adaptive" : "rt_render", rc);
                 const double call_ms = now_ms() - c0;
                 uint32_t samples = 0;
                 rt_accumulated_samples(ctx, &samples);
                 rt_get_stats(ctx, &st);
-                std::printf("progressive call %u: %.2f ms (%.2f ms on the device), %u samples accumulated\n", c + 1, call_ms, st.kernel_ms, samples);
+                if (adaptive)
+                    std::printf("adaptive call %u: %.2f ms (%.2f ms on the device), %llu active pixels, %llu samples traced, %u samples at most\n", c + 1,
+                                call_ms, st.kernel_ms, (unsigned long long)st.pixels, (unsigned long long)st.primary_rays, samples);
+                else
+                    std::printf("progressive call %u: %.2f ms (%.2f ms on the device), %u samples accumulated\n", c + 1, call_ms, st.kernel_ms, samples);
                 p.flags = RT_FLAG_ACCUMULATE;
             }
         } else {

@@ -53,6 +53,7 @@ ABI_SYMBOLS = [
     "rt_update_geometry",
     "rt_accumulated_samples",
     "rt_aovs", "rt_sample_rays", "rt_denoise",
+    "rt_render_adaptive", "rt_read_adaptive",
 ]
 
 
@@ -170,6 +171,12 @@ def split_aovs(aovs):
     """(..., 8) AOV records (rt_aov: albedo xyz, depth, normal xyz, coverage; numpy or torch) -> dict of views: albedo (..., 3),
     depth (...), normal (..., 3), coverage (...)."""
     return {"albedo": aovs[..., 0:3], "depth": aovs[..., 3], "normal": aovs[..., 4:7], "coverage": aovs[..., 7]}
+
+
+def split_adaptive(records):
+    """(..., 8) adaptive-sampling records (rt_adaptive_pixel: S xyz, n, H xyz, error; numpy or torch) -> dict of views: sum (..., 3),
+    samples (...), odd (..., 3), error (...)."""
+    return {"sum": records[..., 0:3], "samples": records[..., 3], "odd": records[..., 4:7], "error": records[..., 7]}
 
 
 def _check_image(a, name, h, w, c):
@@ -330,6 +337,25 @@ class Context:
         n = C.c_uint32(0)
         self._check(self.lib.rt_accumulated_samples(self._h, C.byref(n)))
         return n.value
+
+    def render_adaptive(self, width, height, camera, spp, threshold, min_samples=4, restart=False, **render_kw):
+        """rt_render_adaptive: an accumulating extended-mode call (mode=2 and accumulate=True are implied) that traces spp samples only
+        for the pixels the convergence rule leaves active (rt_hip.h "Adaptive sampling"); the other keyword arguments are Context.render's.
+        Returns the call's stats (pixels: the pixels that received samples)."""
+        render_kw.setdefault("mode", MODE_EXTENDED)
+        p = render_params(width, height, camera, spp=spp, accumulate=True, restart=restart, **render_kw)
+        ap = np.zeros((), dtype=T.ADAPTIVE_PARAMS)
+        ap["threshold"], ap["min_samples"] = threshold, min_samples
+        self._check(self.lib.rt_render_adaptive(self._h, _p(p), _p(ap)))
+        self.width, self.height = width, height
+        return self.stats()
+
+    def read_adaptive(self):
+        """rt_read_adaptive: the (height, width, 8) float32 records S, n, H, error of the adaptive running image (split_adaptive; a numpy
+        array views as types.ADAPTIVE_PIXEL)."""
+        out = np.zeros((self.height, self.width, 8), np.float32)
+        self._check(self.lib.rt_read_adaptive(self._h, _p(out), C.c_size_t(self.height * self.width)))
+        return out
 
     def dispatch_tile(self, pc):
         pcb = np.ascontiguousarray(pc)

@@ -528,6 +528,52 @@ __device__ __forceinline__ void run_sum_keep(const DevTargets& tg, size_t pix, V
     if (tg.run_sum) reinterpret_cast<float4*>(tg.run_sum)[pix] = make_float4(sum.x, sum.y, sum.z, 0.0f);
 }
 
+// The image of a pixel from its sum over n samples: the float target and the three rgba8 channel textures.  Every kernel that ends a
+// pixel's samples stores through this one function (the frame kernels, k_wf_resolve, k_ad_image), so their bits cannot drift apart.
+__device__ __forceinline__ void store_image(const DevTargets& tg, size_t pix, V3 sum, float n) {
+    const V3 color = v3(sum.x / n, sum.y / n, sum.z / n);
+    if (tg.rgba32f) reinterpret_cast<float4*>(tg.rgba32f)[pix] = make_float4(color.x, color.y, color.z, 1.0f);
+    if (tg.chan[0]) reinterpret_cast<uint32_t*>(tg.chan[0])[pix] = unorm8(color.x) | 0xFF000000u;
+    if (tg.chan[1]) reinterpret_cast<uint32_t*>(tg.chan[1])[pix] = (unorm8(color.y) << 8) | 0xFF000000u;
+    if (tg.chan[2]) reinterpret_cast<uint32_t*>(tg.chan[2])[pix] = (unorm8(color.z) << 16) | 0xFF000000u;
+}
+
+// Adaptive sampling (rt_render_adaptive).  A pixel of an adaptive running image keeps n (its samples, run_sum w), S
+// (their sum, run_sum xyz) and H (the sum of its odd-indexed samples, run_odd xyz).  A new image (DevFrame::sample_base 0) has none.
+struct AdPixel {
+    V3 s, h;
+    uint32_t n;
+};
+__device__ __forceinline__ AdPixel ad_load(const DevFrame& fr, const DevTargets& tg, size_t pix) {
+    AdPixel a;
+    a.s = a.h = v3(0.0f, 0.0f, 0.0f);
+    a.n = 0u;
+    if (fr.sample_base == 0u) return a;
+    const float4 s = reinterpret_cast<const float4*>(tg.run_sum)[pix], h = reinterpret_cast<const float4*>(tg.run_odd)[pix];
+    a.s = v3(s.x, s.y, s.z);
+    a.h = v3(h.x, h.y, h.z);
+    a.n = (uint32_t)s.w;
+    return a;
+}
+__device__ __forceinline__ void ad_keep(const DevTargets& tg, size_t pix, V3 s, V3 h, uint32_t n) {
+    reinterpret_cast<float4*>(tg.run_sum)[pix] = make_float4(s.x, s.y, s.z, (float)n);
+    reinterpret_cast<float4*>(tg.run_odd)[pix] = make_float4(h.x, h.y, h.z, 0.0f);
+}
+// The rule's error, in exactly this order (rt_hip.h): I = S / n, A = (H + H) / n, d = |I - A| summed r, g, b, e = d / (1e-4 + sqrt(I.r + I.g + I.b)).
+__device__ __forceinline__ float ad_error(V3 s, V3 h, uint32_t n_samples) {
+    const float n = (float)n_samples;
+    const V3 i = v3(s.x / n, s.y / n, s.z / n);
+    const V3 a = v3((h.x + h.x) / n, (h.y + h.y) / n, (h.z + h.z) / n);
+    const float d = fabsf(i.x - a.x) + fabsf(i.y - a.y) + fabsf(i.z - a.z);
+    return d / (1e-4f + sqrtf(i.x + i.y + i.z));
+}
+// Whether the pixel takes samples this call: too few samples so far, or an error at or above the threshold (a NaN error: converged).
+__device__ __forceinline__ bool ad_active(const AdPixel& a, float threshold, uint32_t min_samples) {
+    return a.n < min_samples || ad_error(a.s, a.h, a.n) >= threshold;
+}
+// Whether lane `lane` of owned block `block` takes samples this call (k_ad_select's mask).
+__device__ __forceinline__ bool ad_lane_active(const DevFrame& fr, uint32_t block, uint32_t lane) { return (fr.ad_mask[block] >> lane) & 1ull; }
+
 // sin/cos(2*pi*u) as explicit-fma polynomials: identical bits on the host oracle and here.
 __device__ __forceinline__ void sincos_2pi(float u, float& s_out, float& c_out) {
     float f4 = u * 4.0f;

@@ -133,6 +133,13 @@ struct DevFrame {
     // running sum divided by n_total; jitter != 0: sub-pixel jitter, else the pixel centre.  A closed frame: 0, spp, spp > 1; an
     // accumulating call (RT_FLAG_ACCUMULATE): the samples already in DevTargets::run_sum, their count + spp, 1
     uint32_t sample_base, n_total, jitter;
+    // rt_render_adaptive (null / 0 for every other frame): per owned 8x8 block the mask of its lanes that take samples
+    // this call (k_ad_select), and the blocks with any, in block order (k_ad_compact): block b of the pipeline is owned block ad_blocks[b].
+    // Each pixel's own count n (DevTargets::run_sum w) is its sample base; sample_base is the count of a pixel that never stopped (0: a new image)
+    const unsigned long long* ad_mask;
+    const uint32_t* ad_blocks;
+    float ad_threshold;
+    uint32_t ad_min_samples, adaptive;
     // when single_tile != 0 the launch covers exactly one tile given explicitly (rt_dispatch_tile)
     uint32_t single_tile, tile_off_x, tile_off_y, tile_w, tile_h;
 };
@@ -145,6 +152,7 @@ struct DevTargets {
     unsigned long long* counters; // RT_CNT_SLOTS words, DevCounterSlot
     float* run_sum;      // RT_FLAG_ACCUMULATE frames only (else null): per pixel (width*height x 4 floats: r, g, b, 0) the running sum over the samples so far;
                          // read at the start when DevFrame::sample_base > 0, written back with this launch's samples added
+    float* run_odd;      // rt_render_adaptive frames only (else null): per pixel (r, g, b, 0) the running sum over the odd-indexed samples
 };
 
 // Slots of DevTargets::counters (zeroed per frame and device; rt_intersect / rt_occluded zero the first three).  Written by k_render_reference,

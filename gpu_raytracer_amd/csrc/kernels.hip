@@ -184,24 +184,32 @@ __device__ __forceinline__ V3 ext_trace_path(const DevScene& sc, const DevFrame&
     return radiance;
 }
 
-template <bool COUNT>
+// AD: the adaptive variant (rt_render_adaptive): a lane whose pixel k_ad_select left out behaves like a pixel outside the image; the
+// others trace their own samples n .. n+spp-1 and add them to S (and the odd-indexed ones to H); k_ad_image writes the targets.
+template <bool COUNT, bool AD>
 __global__ __launch_bounds__(WAVE) void k_render_extended(DevScene sc, DevFrame fr, DevTargets tg) {
     extern __shared__ uint2 s_stack[]; // DevScene::stack_entries * 64 64-bit entries
     PixelCoord px = block_pixel(fr);
+    if (AD) px.valid = px.valid && ad_lane_active(fr, blockIdx.x, threadIdx.x);
     uint2* stack = s_stack + threadIdx.x;
     Counts cnt = {0u, 0u};
     SegCounts seg = {0u, 0u, 0u};
-    if (px.valid) {
+    if (px.valid && AD) {
+        const size_t pix = (size_t)px.y * fr.width + px.x;
+        AdPixel a = ad_load(fr, tg, pix);
+        for (uint32_t s = 0; s < fr.spp; s++) {
+            const uint32_t g = a.n + s;
+            const V3 x = ext_trace_path<COUNT>(sc, fr, px.x, px.y, g, stack, cnt, seg);
+            a.s = a.s + x;
+            if (g & 1u) a.h = a.h + x;
+        }
+        ad_keep(tg, pix, a.s, a.h, a.n + fr.spp);
+    } else if (px.valid) {
         const size_t pix = (size_t)px.y * fr.width + px.x;
         V3 sum = run_sum_start(fr, tg, pix);
         for (uint32_t s = 0; s < fr.spp; s++) sum = sum + ext_trace_path<COUNT>(sc, fr, px.x, px.y, fr.sample_base + s, stack, cnt, seg);
         run_sum_keep(tg, pix, sum);
-        float n = (float)fr.n_total;
-        V3 color = v3(sum.x / n, sum.y / n, sum.z / n);
-        if (tg.rgba32f) reinterpret_cast<float4*>(tg.rgba32f)[pix] = make_float4(color.x, color.y, color.z, 1.0f);
-        if (tg.chan[0]) reinterpret_cast<uint32_t*>(tg.chan[0])[pix] = unorm8(color.x) | 0xFF000000u;
-        if (tg.chan[1]) reinterpret_cast<uint32_t*>(tg.chan[1])[pix] = (unorm8(color.y) << 8) | 0xFF000000u;
-        if (tg.chan[2]) reinterpret_cast<uint32_t*>(tg.chan[2])[pix] = (unorm8(color.z) << 16) | 0xFF000000u;
+        store_image(tg, pix, sum, (float)fr.n_total);
     }
     // segment counts are part of the result (rt_stats.rays): one atomic per wave and counter
     unsigned long long c0 = wave_sum(seg.camera), c1 = wave_sum(seg.continuation), c2 = wave_sum(seg.shadow);
@@ -244,10 +252,11 @@ __global__ __launch_bounds__(WAVE) void k_render_extended(DevScene sc, DevFrame 
 
 enum : uint32_t { ST_NEW_SAMPLE = 0, ST_CLOSEST_DONE = 1, ST_SHADOW_DONE = 2, ST_LIGHTS = 3, ST_TRAVERSING = 4, ST_DONE = 5 };
 
-template <bool COUNT>
+template <bool COUNT, bool AD> // AD: the adaptive variant, as k_render_extended's
 __global__ __launch_bounds__(WAVE, RT_SM_MIN_WAVES) void k_render_extended_sm(DevScene sc, DevFrame fr, DevTargets tg) {
     extern __shared__ uint2 s_stack[]; // DevScene::stack_entries * 64 64-bit entries
-    const PixelCoord px = block_pixel(fr);
+    PixelCoord px = block_pixel(fr);
+    if (AD) px.valid = px.valid && ad_lane_active(fr, blockIdx.x, threadIdx.x);
     uint2* __restrict__ stack = s_stack + threadIdx.x;
     const uint4* __restrict__ nodes = reinterpret_cast<const uint4*>(sc.nodes);
     Counts cnt = {0u, 0u};
@@ -276,6 +285,14 @@ __global__ __launch_bounds__(WAVE, RT_SM_MIN_WAVES) void k_render_extended_sm(De
     int sp = 0;
     bool anyhit = false;
     if (px.valid) sum = run_sum_start(fr, tg, (size_t)px.y * fr.width + px.x); // the samples earlier calls of an accumulation left
+    V3 odd = v3(0.0f, 0.0f, 0.0f);
+    uint32_t base = fr.sample_base; // the pixel's first global sample of this launch
+    if (AD && px.valid) {
+        const AdPixel a = ad_load(fr, tg, (size_t)px.y * fr.width + px.x);
+        sum = a.s;
+        odd = a.h;
+        base = a.n;
+    }
 
     // start a segment: spheres are tested right away (wave-uniform loop), the BVH walk is deferred to the traversal phase
     auto begin_segment = [&](V3 so, V3 sd, float tmax, bool any) {
@@ -313,17 +330,16 @@ __global__ __launch_bounds__(WAVE, RT_SM_MIN_WAVES) void k_render_extended_sm(De
             if (state == ST_NEW_SAMPLE) {
                 if (sample >= fr.spp) {
                     const size_t pix = (size_t)px.y * fr.width + px.x;
-                    run_sum_keep(tg, pix, sum);
-                    float n = (float)fr.n_total;
-                    V3 color = v3(sum.x / n, sum.y / n, sum.z / n);
-                    if (tg.rgba32f) reinterpret_cast<float4*>(tg.rgba32f)[pix] = make_float4(color.x, color.y, color.z, 1.0f);
-                    if (tg.chan[0]) reinterpret_cast<uint32_t*>(tg.chan[0])[pix] = unorm8(color.x) | 0xFF000000u;
-                    if (tg.chan[1]) reinterpret_cast<uint32_t*>(tg.chan[1])[pix] = (unorm8(color.y) << 8) | 0xFF000000u;
-                    if (tg.chan[2]) reinterpret_cast<uint32_t*>(tg.chan[2])[pix] = (unorm8(color.z) << 16) | 0xFF000000u;
+                    if (AD) {
+                        ad_keep(tg, pix, sum, odd, base + fr.spp);
+                    } else {
+                        run_sum_keep(tg, pix, sum);
+                        store_image(tg, pix, sum, (float)fr.n_total);
+                    }
                     state = ST_DONE;
                     break;
                 }
-                rng = rng_for(fr.frame_seed + px.x + px.y * fr.width, fr.sample_base + sample);
+                rng = rng_for(fr.frame_seed + px.x + px.y * fr.width, (AD ? base : fr.sample_base) + sample);
                 float jx = 0.5f, jy = 0.5f;
                 if (fr.jitter) {
                     jx = rng.next_f32();
@@ -451,6 +467,7 @@ __global__ __launch_bounds__(WAVE, RT_SM_MIN_WAVES) void k_render_extended_sm(De
             }
             if (end_sample) {
                 sum = sum + radiance;
+                if (AD && ((base + sample) & 1u)) odd = odd + radiance;
                 sample++;
                 state = ST_NEW_SAMPLE;
             }
@@ -616,15 +633,23 @@ hipError_t launch_render_extended(const DevScene& sc, const DevFrame& fr, const 
     if (n_tiles == 0) return hipSuccess;
     dim3 grid(n_tiles * blocks_per_tile(fr.tile_size)), block(WAVE);
     if (kernel != FrameKernel::MEGAKERNEL_SM) { // the nested loops (also the one-pass kernel)
-        if (counters)
-            hipLaunchKernelGGL(k_render_extended<true>, grid, block, lds_bytes(sc), stream, sc, fr, tg);
+        if (fr.adaptive && counters)
+            hipLaunchKernelGGL((k_render_extended<true, true>), grid, block, lds_bytes(sc), stream, sc, fr, tg);
+        else if (fr.adaptive)
+            hipLaunchKernelGGL((k_render_extended<false, true>), grid, block, lds_bytes(sc), stream, sc, fr, tg);
+        else if (counters)
+            hipLaunchKernelGGL((k_render_extended<true, false>), grid, block, lds_bytes(sc), stream, sc, fr, tg);
         else
-            hipLaunchKernelGGL(k_render_extended<false>, grid, block, lds_bytes(sc), stream, sc, fr, tg);
+            hipLaunchKernelGGL((k_render_extended<false, false>), grid, block, lds_bytes(sc), stream, sc, fr, tg);
     } else {
-        if (counters)
-            hipLaunchKernelGGL(k_render_extended_sm<true>, grid, block, lds_bytes(sc), stream, sc, fr, tg);
+        if (fr.adaptive && counters)
+            hipLaunchKernelGGL((k_render_extended_sm<true, true>), grid, block, lds_bytes(sc), stream, sc, fr, tg);
+        else if (fr.adaptive)
+            hipLaunchKernelGGL((k_render_extended_sm<false, true>), grid, block, lds_bytes(sc), stream, sc, fr, tg);
+        else if (counters)
+            hipLaunchKernelGGL((k_render_extended_sm<true, false>), grid, block, lds_bytes(sc), stream, sc, fr, tg);
         else
-            hipLaunchKernelGGL(k_render_extended_sm<false>, grid, block, lds_bytes(sc), stream, sc, fr, tg);
+            hipLaunchKernelGGL((k_render_extended_sm<false, false>), grid, block, lds_bytes(sc), stream, sc, fr, tg);
     }
     return hipGetLastError();
 }

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/rt_hip.h"
+#include "adaptive.h"
 #include "bvh_builder.h"
 #include "bvh_check.h"
 #include "denoise.h"
@@ -88,6 +89,16 @@ struct DeviceState {
     // with the scene
     float* run_sum = nullptr;
     uint32_t run_sum_w = 0, run_sum_h = 0;
+    // rt_render_adaptive: the running sum over the odd-indexed samples (DevTargets::run_odd, same layout; made by the first adaptive call, freed
+    // with run_sum), and the selection of a call (adaptive.h): per owned block its mask of pixels that take samples, the list of the blocks
+    // with any (ad_cap entries each), the two counts k_ad_compact leaves on the device, and what the host read of them for the last call
+    float* run_odd = nullptr;
+    unsigned long long* ad_mask = nullptr;
+    uint32_t* ad_blocks = nullptr;
+    unsigned long long* ad_counts = nullptr;
+    uint32_t ad_cap = 0;
+    uint32_t ad_live_blocks = 0;
+    uint64_t ad_pixels = 0;
     // rt_aovs / rt_denoise (denoise.h), grown on demand, kept until rt_destroy (they do not depend on the scene): the records of the
     // device's share when they cannot be written in place, the staging of host rgb, and the two colour planes of the a-trous iterations
     void* dn_aov = nullptr;
@@ -101,6 +112,7 @@ struct DeviceState {
 struct AccumKey {
     rt_camera camera;
     uint32_t width, height, max_bounces, frame_seed, tile_size, tile_rank, tile_world, no_shadows;
+    uint32_t adaptive; // the running image of rt_render_adaptive (per-pixel counts) is not continued by plain accumulating calls, nor the reverse
 };
 
 } // namespace
@@ -194,8 +206,14 @@ void free_scene(DeviceState& d) {
     (void)hipFree(d.rf_verts);
     d.rf_verts = nullptr;
     (void)hipFree(d.run_sum); // the running image of an accumulation ends with the scene it was rendered from
-    d.run_sum = nullptr;
+    (void)hipFree(d.run_odd);
+    d.run_sum = d.run_odd = nullptr;
     d.run_sum_w = d.run_sum_h = 0;
+    for (void* p : {(void*)d.ad_mask, (void*)d.ad_blocks, (void*)d.ad_counts}) (void)hipFree(p);
+    d.ad_mask = nullptr;
+    d.ad_blocks = nullptr;
+    d.ad_counts = nullptr;
+    d.ad_cap = 0;
 }
 void free_targets(DeviceState& d) {
     (void)hipSetDevice(d.device);
@@ -305,6 +323,7 @@ DevTargets targets_for(const DeviceState& d, const DevFrame& f) {
     t.hit_t = d.hit_t;
     t.counters = d.counters;
     t.run_sum = (f.flags & RT_FLAG_ACCUMULATE) ? d.run_sum : nullptr;
+    t.run_odd = f.adaptive ? d.run_odd : nullptr;
     return t;
 }
 
@@ -313,18 +332,39 @@ DevTargets targets_for(const DeviceState& d, const DevFrame& f) {
 // its launches, so that a call that fails part way never leaves a half-added sum counted.
 void end_accumulation(rt_ctx* ctx) { ctx->acc_samples = 0; }
 
-// The running sums of an accumulating frame of width x height, one per device (its share of the pixels is written, the rest never read).
-int ensure_run_sums(rt_ctx* ctx, uint32_t w, uint32_t h) {
+// The running sums of an accumulating frame of width x height, one per device (its share of the pixels is written, the rest never read);
+// an adaptive one (rt_render_adaptive) also has the odd-sample sums and the selection buffers for every block of the frame's tiling.
+int ensure_run_sums(rt_ctx* ctx, const DevFrame& fr) {
+    const uint32_t w = fr.width, h = fr.height;
     for (auto& d : ctx->devs) {
-        if (d.run_sum && d.run_sum_w == w && d.run_sum_h == h) continue;
         HIPCHK(ctx, hipSetDevice(d.device));
-        if (d.stream) HIPCHK(ctx, hipStreamSynchronize(d.stream));
-        (void)hipFree(d.run_sum);
-        d.run_sum = nullptr;
-        d.run_sum_w = d.run_sum_h = 0;
-        HIPCHK(ctx, hipMalloc((void**)&d.run_sum, (size_t)w * h * 16)); // not cleared: a first call (sample_base 0) reads none of it
-        d.run_sum_w = w;
-        d.run_sum_h = h;
+        if (!(d.run_sum && d.run_sum_w == w && d.run_sum_h == h)) {
+            if (d.stream) HIPCHK(ctx, hipStreamSynchronize(d.stream));
+            (void)hipFree(d.run_sum);
+            (void)hipFree(d.run_odd);
+            d.run_sum = d.run_odd = nullptr;
+            d.run_sum_w = d.run_sum_h = 0;
+            HIPCHK(ctx, hipMalloc((void**)&d.run_sum, (size_t)w * h * 16)); // not cleared: a first call (sample_base 0) reads none of it
+            d.run_sum_w = w;
+            d.run_sum_h = h;
+        }
+        if (!fr.adaptive) continue;
+        if (!d.run_odd) HIPCHK(ctx, hipMalloc((void**)&d.run_odd, (size_t)w * h * 16)); // (as run_sum: read only once written)
+        const uint64_t all_blocks = (uint64_t)fr.tiles_x * fr.tiles_y * rt::blocks_per_tile(fr.tile_size); // a device owns at most all of them
+        if (all_blocks > 0xFFFFFFFFull) return ctx->fail(RT_ERR_BAD_ARG, "rt_render_adaptive: %llu pixel blocks exceed 32-bit block indices", (unsigned long long)all_blocks);
+        const uint32_t blocks = (uint32_t)all_blocks;
+        if (d.ad_cap < blocks || !d.ad_counts) {
+            if (d.stream) HIPCHK(ctx, hipStreamSynchronize(d.stream));
+            for (void* p : {(void*)d.ad_mask, (void*)d.ad_blocks, (void*)d.ad_counts}) (void)hipFree(p);
+            d.ad_mask = nullptr;
+            d.ad_blocks = nullptr;
+            d.ad_counts = nullptr;
+            d.ad_cap = 0;
+            HIPCHK(ctx, hipMalloc((void**)&d.ad_mask, (size_t)std::max(1u, blocks) * 8));
+            HIPCHK(ctx, hipMalloc((void**)&d.ad_blocks, (size_t)std::max(1u, blocks) * 4));
+            HIPCHK(ctx, hipMalloc((void**)&d.ad_counts, 2 * 8));
+            d.ad_cap = blocks;
+        }
     }
     return RT_OK;
 }
@@ -681,11 +721,14 @@ int ensure_grids(rt_ctx* ctx, DeviceState& d) {
 }
 
 // Path-state arrays and queues of the wavefront pipeline, sized for `batch` samples per owned pixel block.
-int ensure_wavefront(rt_ctx* ctx, DeviceState& d, uint32_t n_blocks, uint32_t batch, uint32_t n_lights, bool two_lanes) {
+// `shrink`: an adaptive call (rt_render_adaptive), whose live blocks change from call to call, also runs in an allocation made for more
+// blocks; it leaves the allocation's shape as it was (its lanes say how many blocks it covers, lane_of), so frames of that shape keep it.
+int ensure_wavefront(rt_ctx* ctx, DeviceState& d, uint32_t n_blocks, uint32_t batch, uint32_t n_lights, bool two_lanes, bool shrink = false) {
     const uint32_t capacity = n_blocks * batch * 64u;
     // overflow entries (64-bit) per lane beyond the LDS part of the stack
     const uint32_t ovf_entries = ctx->scene_counts.stack_entries + 2u > RT_WF8_LDS_STACK ? ctx->scene_counts.stack_entries + 2u - RT_WF8_LDS_STACK : 1u;
-    if (d.wf.capacity >= capacity && d.wf.n_blocks == n_blocks && d.wf.batch == batch && d.wf_lights >= n_lights && d.wf.counters &&
+    const bool same_shape = shrink ? d.wf.n_blocks >= n_blocks : (d.wf.n_blocks == n_blocks && d.wf.batch == batch);
+    if (d.wf.capacity >= capacity && same_shape && d.wf_lights >= n_lights && d.wf.counters &&
         d.wf.ovf_entries >= ovf_entries && d.wf.stack_ovf && (!two_lanes || (d.wf2.counters && d.wf2.capacity >= capacity && d.wf2.stack_ovf)))
         return RT_OK;
     free_wavefront(d);
@@ -882,6 +925,7 @@ struct WfRun {
     DevFrame f{};
     DevScene dsc{};
     uint32_t batch = 1, first = 0, j = 0, it = 0, alive = 0; // samples per batch, first sample and number of the batch, bounce, live paths
+    uint32_t n_blocks = 0; // pixel blocks the walk covers (an adaptive call: the live ones, f.ad_blocks)
     bool two = false;   // batches alternate between the device's two lanes
     bool beams = false; // camera segments test their block's beam list (else they walk the tree)
     hipStream_t poll_stream = nullptr;
@@ -895,7 +939,8 @@ int setup_pipeline(rt_ctx* ctx, size_t j, const DevFrame& f, WfRun& r) {
     const uint32_t n_lights = ctx->scene_counts.n_lights;
     if (!(f.flags & (RT_FLAG_NO_SHADOW_GRID | RT_FLAG_NO_SHADOWS))) // the first frame that traces shadow segments through the pipeline builds the light grids
         if (int rc = ensure_grids(ctx, d)) return rc;
-    const uint32_t n_blocks = f.n_owned_tiles * rt::blocks_per_tile(f.tile_size);
+    // an adaptive call's pipeline covers the blocks k_ad_select listed (f.ad_blocks): path slots, queues and launches scale with the live pixels
+    const uint32_t n_blocks = f.adaptive ? d.ad_live_blocks : f.n_owned_tiles * rt::blocks_per_tile(f.tile_size);
     size_t free_b = 0, total_b = 0;
     HIPCHK(ctx, hipMemGetInfo(&free_b, &total_b));
     const char* lanes_env = std::getenv("RT_WF_LANES"); // (read per frame: tests and A/B runs switch it)
@@ -914,13 +959,18 @@ int setup_pipeline(rt_ctx* ctx, size_t j, const DevFrame& f, WfRun& r) {
     // traversal (bound by VALU issue).  The pixel sums are added in batch order: a resolve waits for the previous batch's.
     const uint32_t n_batches = (f.spp + batch - 1) / batch;
     const bool two = two_lanes_on && n_batches >= 2 && d.stream2;
-    if (int rc = ensure_wavefront(ctx, d, n_blocks, batch, n_lights, two)) return rc;
+    if (int rc = ensure_wavefront(ctx, d, n_blocks, batch, n_lights, two, f.adaptive != 0)) return rc;
     HIPCHK(ctx, hipMemsetAsync(d.wf.totals, 0, rt::WF_N_TOTALS * sizeof(unsigned long long), d.stream));
-    HIPCHK(ctx, hipEventRecord(d.ev0, d.stream)); // re-record: allocation above is not part of the kernel time
+    if (!f.adaptive) HIPCHK(ctx, hipEventRecord(d.ev0, d.stream)); // re-record: allocation above is not part of the kernel time (an adaptive call's selection is)
     // camera beams: on by default, RT_WF_BEAMS=0 (development knob) or RT_FLAG_NO_BEAMS walks the tree for every camera segment
     const char* be = std::getenv("RT_WF_BEAMS");
     const bool beams = !(f.flags & RT_FLAG_NO_BEAMS) && (be ? std::atoi(be) != 0 : true);
-    if (beams) HIPCHK(ctx, rt::wf_beams(scene_for(ctx, d), f, d.wf, d.stream));
+    if (beams) {
+        rt::WfBuffers wb = d.wf;
+        wb.n_blocks = n_blocks; // (an adaptive call may run in an allocation made for more blocks)
+        wb.batch = batch;
+        HIPCHK(ctx, rt::wf_beams(scene_for(ctx, d), f, wb, d.stream));
+    }
     if (two) {
         HIPCHK(ctx, hipEventRecord(d.ev_start, d.stream));
         HIPCHK(ctx, hipStreamWaitEvent(d.stream2, d.ev_start, 0));
@@ -937,6 +987,7 @@ int setup_pipeline(rt_ctx* ctx, size_t j, const DevFrame& f, WfRun& r) {
     r.f = f;
     r.dsc = scene_for(ctx, d);
     r.batch = batch;
+    r.n_blocks = n_blocks;
     r.two = two;
     r.beams = beams;
     return RT_OK;
@@ -948,14 +999,16 @@ WfLane lane_of(const DeviceState& d, const WfRun& r) {
     const bool second = r.two && (r.j & 1u);
     WfLane l{second ? d.wf2 : d.wf, second ? d.stream2 : d.stream};
     if (!r.beams) l.w.beam_count = nullptr;
+    l.w.n_blocks = r.n_blocks; // (the allocation's own unless the walk is an adaptive call's)
+    l.w.batch = r.batch;
     return l;
 }
 uint32_t batch_samples(const WfRun& r) { return std::min(r.batch, r.f.spp - r.first); }
 
 // One step per phase of a pipeline walk, on the lane `l` of its current batch (the caller has made r's device current).
 // GENERATE: the paths of the current batch.
-int wf_step_generate(rt_ctx* ctx, WfRun& r, const WfLane& l) {
-    HIPCHK(ctx, rt::wf_generate(r.dsc, r.f, l.w, r.first, batch_samples(r), l.st));
+int wf_step_generate(rt_ctx* ctx, DeviceState& d, WfRun& r, const WfLane& l) {
+    HIPCHK(ctx, rt::wf_generate(r.dsc, r.f, l.w, targets_for(d, r.f), r.first, batch_samples(r), l.st));
     r.it = 0;
     r.phase = WfRun::BOUNCE;
     return RT_OK;
@@ -990,7 +1043,7 @@ int wf_step_bounce(rt_ctx* ctx, DeviceState& d, WfRun& r, const WfLane& l, bool 
 int wf_step_resolve(rt_ctx* ctx, DeviceState& d, WfRun& r, const WfLane& l) {
     const uint32_t n = batch_samples(r);
     if (r.two && r.j > 0) HIPCHK(ctx, hipStreamWaitEvent(l.st, d.ev_res[(r.j - 1u) & 1u], 0));
-    HIPCHK(ctx, rt::wf_resolve(r.f, l.w, targets_for(d, r.f), n, r.first == 0, r.first + n >= r.f.spp, l.st));
+    HIPCHK(ctx, rt::wf_resolve(r.f, l.w, targets_for(d, r.f), n, r.first, r.first == 0, r.first + n >= r.f.spp, l.st));
     if (r.two) HIPCHK(ctx, hipEventRecord(d.ev_res[r.j & 1u], l.st));
     r.first += r.batch;
     r.j++;
@@ -1002,6 +1055,7 @@ int wf_step_resolve(rt_ctx* ctx, DeviceState& d, WfRun& r, const WfLane& l) {
         HIPCHK(ctx, hipEventRecord(d.ev_join, d.stream2));
         HIPCHK(ctx, hipStreamWaitEvent(d.stream, d.ev_join, 0));
     }
+    if (r.f.adaptive) HIPCHK(ctx, rt::launch_ad_image(r.f, targets_for(d, r.f), d.stream));
     HIPCHK(ctx, hipEventRecord(d.ev1, d.stream));
     r.phase = WfRun::DONE;
     return RT_OK;
@@ -1088,7 +1142,7 @@ int collect_device(rt_ctx* ctx, size_t j, const DevFrame& fr, bool counters, con
         HIPCHK(ctx, hipMemcpy(c, d.counters, sizeof c, hipMemcpyDeviceToHost));
         add_counters(t, c);
     }
-    t.pixels += share_pixels(fr, d);
+    t.pixels += fr.adaptive ? d.ad_pixels : share_pixels(fr, d); // (an adaptive call: the pixels that received samples)
     return RT_OK;
 }
 
@@ -1129,6 +1183,21 @@ int run_frame(rt_ctx* ctx, DevFrame fr, bool counters, uint32_t world, uint32_t 
         if (!single_tile) assign_tiles(f, d, world, rank, nd, j);
         HIPCHK(ctx, hipMemsetAsync(d.counters, 0, RT_CNT_SLOTS * sizeof(unsigned long long), d.stream));
         HIPCHK(ctx, hipEventRecord(d.ev0, d.stream));
+        if (f.adaptive) { // rt_render_adaptive: which pixels take samples, read back once per call and device to size what follows
+            f.ad_mask = d.ad_mask;
+            f.ad_blocks = d.ad_blocks;
+            unsigned long long counts[2] = {0, 0};
+            HIPCHK(ctx, rt::launch_ad_select(f, targets_for(d, f), d.ad_mask, d.ad_blocks, d.ad_counts, d.stream));
+            HIPCHK(ctx, hipMemcpyAsync(counts, d.ad_counts, sizeof counts, hipMemcpyDeviceToHost, d.stream));
+            HIPCHK(ctx, hipStreamSynchronize(d.stream));
+            d.ad_live_blocks = (uint32_t)counts[0];
+            d.ad_pixels = counts[1];
+            if (d.ad_live_blocks == 0) { // every pixel of the share has stopped: nothing to trace
+                HIPCHK(ctx, rt::launch_ad_image(f, targets_for(d, f), d.stream));
+                HIPCHK(ctx, hipEventRecord(d.ev1, d.stream));
+                continue;
+            }
+        }
         const KernelChoice k = choose_kernel(ctx, f);
         stat_flags |= (k.fallback ? RT_STAT_MEGAKERNEL_FALLBACK : 0u) | (k.kernel == rt::FrameKernel::SINGLE_PASS ? RT_STAT_SINGLE_PASS : 0u);
         if (k.kernel == rt::FrameKernel::PIPELINE) {
@@ -1137,6 +1206,7 @@ int run_frame(rt_ctx* ctx, DevFrame fr, bool counters, uint32_t world, uint32_t 
         }
         if (k.kernel == rt::FrameKernel::REFERENCE) HIPCHK(ctx, rt::launch_render_reference(scene_for(ctx, d), f, targets_for(d, f), counters, d.stream));
         else HIPCHK(ctx, rt::launch_render_extended(scene_for(ctx, d), f, targets_for(d, f), k.kernel, counters, d.stream));
+        if (f.adaptive) HIPCHK(ctx, rt::launch_ad_image(f, targets_for(d, f), d.stream));
         HIPCHK(ctx, hipEventRecord(d.ev1, d.stream));
     }
     // The pipeline's launches: every device advances by one step (a batch's generation, one bounce, a batch's resolve) in turn, so that
@@ -1151,7 +1221,7 @@ int run_frame(rt_ctx* ctx, DevFrame fr, bool counters, uint32_t world, uint32_t 
             DeviceState& d = ctx->devs[r.dev];
             HIPCHK(ctx, hipSetDevice(d.device));
             const WfLane l = lane_of(d, r);
-            const int rc = r.phase == WfRun::GENERATE ? wf_step_generate(ctx, r, l) : r.phase == WfRun::BOUNCE ? wf_step_bounce(ctx, d, r, l, counters, polls) : wf_step_resolve(ctx, d, r, l);
+            const int rc = r.phase == WfRun::GENERATE ? wf_step_generate(ctx, d, r, l) : r.phase == WfRun::BOUNCE ? wf_step_bounce(ctx, d, r, l, counters, polls) : wf_step_resolve(ctx, d, r, l);
             if (rc != RT_OK) return rc;
         }
         for (WfRun* r : polls) {
@@ -1178,7 +1248,7 @@ int run_frame(rt_ctx* ctx, DevFrame fr, bool counters, uint32_t world, uint32_t 
     return RT_OK;
 }
 
-int gather(rt_ctx* ctx, uint8_t* out, size_t elem, int which);
+int gather(rt_ctx* ctx, uint8_t* out, size_t elem, int which, void* const* per_device = nullptr);
 
 // A dispatch sequence runs on the context's first device and starts from the textures as they are (tiles that are
 // not dispatched keep their texels, like the reference's storage textures).  After an rt_render that was split over
@@ -1484,31 +1554,34 @@ int rt_prepare(rt_ctx* ctx, uint32_t what) {
     return RT_OK;
 }
 
-int rt_render(rt_ctx* ctx, const rt_render_params* p) {
-    if (!ctx) return RT_ERR_BAD_ARG;
-    if (!p) return ctx->fail(RT_ERR_BAD_ARG, "rt_render: null params");
-    if (!ctx->uploaded) return ctx->fail(RT_ERR_NOT_UPLOADED, "rt_render: no scene uploaded");
-    uint32_t world = 1, rank = 0;
-    DevFrame fr{};
-    if (int rc = frame_of_params(ctx, "rt_render", p, fr, world, rank)) return rc;
-    const bool accumulate = (p->flags & RT_FLAG_ACCUMULATE) != 0;
-    AccumKey key{};
-    if (accumulate) {
-        key.camera = p->camera;
-        key.width = p->width, key.height = p->height, key.max_bounces = p->max_bounces, key.frame_seed = p->frame_seed;
-        key.tile_size = fr.tile_size, key.tile_rank = rank, key.tile_world = world, key.no_shadows = p->flags & RT_FLAG_NO_SHADOWS;
-        const bool cont = ctx->acc_samples && !(p->flags & RT_FLAG_ACCUMULATE_RESTART) && std::memcmp(&key, &ctx->acc_key, sizeof key) == 0;
-        const uint32_t base = cont ? ctx->acc_samples : 0u;
-        if ((uint64_t)base + fr.spp > RT_ACCUMULATE_MAX_SAMPLES)
-            return ctx->fail(RT_ERR_BAD_ARG, "rt_render: %u + %u samples would pass the accumulation limit of %u", base, fr.spp, RT_ACCUMULATE_MAX_SAMPLES);
-        fr.sample_base = base; // this call traces samples base .. base + spp - 1 and divides by all of them; every sample is jittered
-        fr.n_total = base + fr.spp;
-        fr.jitter = 1u;
-    }
+} // extern "C"
+
+namespace {
+
+// The running image an accumulating call (rt_render with RT_FLAG_ACCUMULATE, rt_render_adaptive) continues or starts: its key, and fr's
+// sample base and count.  Fails, changing nothing, when the call would pass RT_ACCUMULATE_MAX_SAMPLES.
+int accumulation_of(rt_ctx* ctx, const char* fn, const rt_render_params* p, uint32_t world, uint32_t rank, bool adaptive, DevFrame& fr, AccumKey& key) {
+    key = AccumKey{};
+    key.camera = p->camera;
+    key.width = p->width, key.height = p->height, key.max_bounces = p->max_bounces, key.frame_seed = p->frame_seed;
+    key.tile_size = fr.tile_size, key.tile_rank = rank, key.tile_world = world, key.no_shadows = p->flags & RT_FLAG_NO_SHADOWS;
+    key.adaptive = adaptive ? 1u : 0u;
+    const bool cont = ctx->acc_samples && !(p->flags & RT_FLAG_ACCUMULATE_RESTART) && std::memcmp(&key, &ctx->acc_key, sizeof key) == 0;
+    const uint32_t base = cont ? ctx->acc_samples : 0u;
+    if ((uint64_t)base + fr.spp > RT_ACCUMULATE_MAX_SAMPLES)
+        return ctx->fail(RT_ERR_BAD_ARG, "%s: %u + %u samples would pass the accumulation limit of %u", fn, base, fr.spp, RT_ACCUMULATE_MAX_SAMPLES);
+    fr.sample_base = base; // this call traces samples base .. base + spp - 1 and divides by all of them; every sample is jittered
+    fr.n_total = base + fr.spp; // (adaptive: the count of a pixel that never stopped; each pixel has its own)
+    fr.jitter = 1u;
+    return RT_OK;
+}
+
+// An rt_render or rt_render_adaptive call whose arguments have been checked: the frame fr, and with `accumulate` the running image `key`.
+int render_call(rt_ctx* ctx, const DevFrame& fr, bool counters, uint32_t world, uint32_t rank, bool accumulate, const AccumKey& key) {
     end_accumulation(ctx); // counted again below once the frame has completed
     if (accumulate)
-        if (int rc = ensure_run_sums(ctx, fr.width, fr.height)) return rc;
-    int rc = run_frame(ctx, fr, (p->flags & RT_FLAG_COUNTERS) != 0, world, rank, false);
+        if (int rc = ensure_run_sums(ctx, fr)) return rc;
+    int rc = run_frame(ctx, fr, counters, world, rank, false);
     if (rc != RT_OK) return rc;
     if (accumulate) {
         ctx->acc_key = key;
@@ -1521,6 +1594,46 @@ int rt_render(rt_ctx* ctx, const rt_render_params* p) {
     ctx->frame_tiles_y = fr.tiles_y;
     ctx->frame_valid = true;
     return RT_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int rt_render(rt_ctx* ctx, const rt_render_params* p) {
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (!p) return ctx->fail(RT_ERR_BAD_ARG, "rt_render: null params");
+    if (!ctx->uploaded) return ctx->fail(RT_ERR_NOT_UPLOADED, "rt_render: no scene uploaded");
+    uint32_t world = 1, rank = 0;
+    DevFrame fr{};
+    if (int rc = frame_of_params(ctx, "rt_render", p, fr, world, rank)) return rc;
+    const bool accumulate = (p->flags & RT_FLAG_ACCUMULATE) != 0;
+    AccumKey key{};
+    if (accumulate)
+        if (int rc = accumulation_of(ctx, "rt_render", p, world, rank, false, fr, key)) return rc;
+    return render_call(ctx, fr, (p->flags & RT_FLAG_COUNTERS) != 0, world, rank, accumulate, key);
+}
+
+int rt_render_adaptive(rt_ctx* ctx, const rt_render_params* p, const rt_adaptive_params* ap) {
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (!p || !ap) return ctx->fail(RT_ERR_BAD_ARG, "rt_render_adaptive: null params");
+    if (!ctx->uploaded) return ctx->fail(RT_ERR_NOT_UPLOADED, "rt_render_adaptive: no scene uploaded");
+    uint32_t world = 1, rank = 0;
+    DevFrame fr{};
+    if (int rc = frame_of_params(ctx, "rt_render_adaptive", p, fr, world, rank)) return rc;
+    if (p->mode != RT_MODE_EXTENDED || !(p->flags & RT_FLAG_ACCUMULATE))
+        return ctx->fail(RT_ERR_BAD_ARG, "rt_render_adaptive: needs the extended mode with RT_FLAG_ACCUMULATE (mode %u, flags 0x%x)", p->mode, p->flags);
+    if (!std::isfinite(ap->threshold) || !(ap->threshold >= 0.0f))
+        return ctx->fail(RT_ERR_BAD_ARG, "rt_render_adaptive: threshold %g is not finite and >= 0", (double)ap->threshold);
+    if (ap->min_samples < 2u || ap->min_samples > RT_ACCUMULATE_MAX_SAMPLES)
+        return ctx->fail(RT_ERR_BAD_ARG, "rt_render_adaptive: min_samples %u outside [2, %u]", ap->min_samples, RT_ACCUMULATE_MAX_SAMPLES);
+    if (ap->flags != 0u) return ctx->fail(RT_ERR_BAD_ARG, "rt_render_adaptive: flags 0x%x reserved", ap->flags);
+    AccumKey key{};
+    if (int rc = accumulation_of(ctx, "rt_render_adaptive", p, world, rank, true, fr, key)) return rc;
+    fr.adaptive = 1u;
+    fr.ad_threshold = ap->threshold;
+    fr.ad_min_samples = ap->min_samples;
+    return render_call(ctx, fr, (p->flags & RT_FLAG_COUNTERS) != 0, world, rank, true, key);
 }
 
 int rt_dispatch_tile(rt_ctx* ctx, const rt_push_constants* pc) {
@@ -1587,8 +1700,9 @@ void copy_share(uint8_t* dst, const uint8_t* src, size_t elem, uint32_t w, uint3
     }
 }
 
-// Copy `elem` bytes per pixel of every device's owned tiles into `out` (full frame, row-major).
-int gather(rt_ctx* ctx, uint8_t* out, size_t elem, int which /*0 rgba32f, 1..3 chan, 4 prim, 5 t*/) {
+// Copy `elem` bytes per pixel of every device's owned tiles into `out` (full frame, row-major), from the target `which` or, with
+// `per_device`, from a full-frame buffer per device.
+int gather(rt_ctx* ctx, uint8_t* out, size_t elem, int which /*0 rgba32f, 1..3 chan, 4 prim, 5 t*/, void* const* per_device) {
     uint32_t w = ctx->frame_w, h = ctx->frame_h;
     size_t n = (size_t)w * h;
     std::vector<uint8_t> tmp;
@@ -1596,6 +1710,8 @@ int gather(rt_ctx* ctx, uint8_t* out, size_t elem, int which /*0 rgba32f, 1..3 c
         DeviceState& d = ctx->devs[j];
         if (d.fb_w != w || d.fb_h != h || d.n_owned == 0) continue;
         const void* src = which == 0 ? (const void*)d.rgba32f : which <= 3 ? (const void*)d.chan[which - 1] : which == 4 ? (const void*)d.prim_id : (const void*)d.hit_t;
+        if (per_device && !per_device[j]) continue;
+        if (per_device) src = per_device[j];
         HIPCHK(ctx, hipSetDevice(d.device));
         bool all = d.tile_stride == 1 && d.tile_first == 0;
         if (all) {
@@ -1610,13 +1726,8 @@ int gather(rt_ctx* ctx, uint8_t* out, size_t elem, int which /*0 rgba32f, 1..3 c
 }
 } // namespace
 
-// Whole frame on one device: run the epilogue there and bring the result back through pinned staging
-// (`which` 0: packed rgb32f, 1: combined rgba8).  Returns RT_OK, an error, or 1 when the caller must use the gather path.
-static int read_epilogue(rt_ctx* ctx, int which, void* out, size_t bytes) {
-    if (ctx->devs.size() != 1) return 1;
-    DeviceState& d = ctx->devs[0];
-    if (d.fb_w != ctx->frame_w || d.fb_h != ctx->frame_h || !(d.tile_stride == 1 && d.tile_first == 0)) return 1;
-    HIPCHK(ctx, hipSetDevice(d.device));
+// The read-back staging of device d (current): at least `bytes` on the device and pinned on the host.
+static int ensure_readback(rt_ctx* ctx, DeviceState& d, size_t bytes) {
     if (d.readback_bytes < bytes) {
         (void)hipFree(d.readback_dev);
         if (d.readback_host) (void)hipHostFree(d.readback_host);
@@ -1626,6 +1737,17 @@ static int read_epilogue(rt_ctx* ctx, int which, void* out, size_t bytes) {
         HIPCHK(ctx, hipHostMalloc(&d.readback_host, bytes, hipHostMallocDefault));
         d.readback_bytes = bytes;
     }
+    return RT_OK;
+}
+
+// Whole frame on one device: run the epilogue there and bring the result back through pinned staging
+// (`which` 0: packed rgb32f, 1: combined rgba8).  Returns RT_OK, an error, or 1 when the caller must use the gather path.
+static int read_epilogue(rt_ctx* ctx, int which, void* out, size_t bytes) {
+    if (ctx->devs.size() != 1) return 1;
+    DeviceState& d = ctx->devs[0];
+    if (d.fb_w != ctx->frame_w || d.fb_h != ctx->frame_h || !(d.tile_stride == 1 && d.tile_first == 0)) return 1;
+    HIPCHK(ctx, hipSetDevice(d.device));
+    if (int rc = ensure_readback(ctx, d, bytes)) return rc;
     const size_t n = (size_t)ctx->frame_w * ctx->frame_h;
     if (which == 0) HIPCHK(ctx, rt::launch_pack_rgb32f(d.rgba32f, (float*)d.readback_dev, n, d.stream));
     else HIPCHK(ctx, rt::launch_combine_rgba8(d.chan[0], d.chan[1], d.chan[2], (uint8_t*)d.readback_dev, n, d.stream));
@@ -1773,6 +1895,28 @@ int rt_debug_shadow_grid(rt_ctx* ctx, uint32_t light, unsigned long long out[8])
     out[5] = g.heavy_cells;
     out[6] = g.filled_cells;
     return RT_OK;
+}
+
+int rt_read_adaptive(rt_ctx* ctx, rt_adaptive_pixel* out, size_t n_pixels) {
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (int rcp = sync_pending(ctx)) return rcp;
+    if (!ctx->acc_samples || !ctx->acc_key.adaptive) return ctx->fail(RT_ERR_BAD_ARG, "rt_read_adaptive: the context has no adaptive running image");
+    const size_t n = (size_t)ctx->frame_w * ctx->frame_h;
+    if (!out || n_pixels != n) return ctx->fail(RT_ERR_BAD_ARG, "rt_read_adaptive: expected %zu records, got %zu", n, n_pixels);
+    static_assert(sizeof(rt_adaptive_pixel) == 32, "two float4 per record (k_ad_records)");
+    // every device's records of the whole frame (those outside its share are never copied), then its share of them into `out`
+    std::vector<void*> src(ctx->devs.size(), nullptr);
+    for (size_t j = 0; j < ctx->devs.size(); j++) {
+        DeviceState& d = ctx->devs[j];
+        if (d.fb_w != ctx->frame_w || d.fb_h != ctx->frame_h || d.n_owned == 0 || !d.run_sum || !d.run_odd) continue;
+        HIPCHK(ctx, hipSetDevice(d.device));
+        if (int rc = ensure_readback(ctx, d, n * sizeof(rt_adaptive_pixel))) return rc;
+        HIPCHK(ctx, rt::launch_ad_records(d.run_sum, d.run_odd, d.readback_dev, n, d.stream));
+        HIPCHK(ctx, hipStreamSynchronize(d.stream));
+        src[j] = d.readback_dev;
+    }
+    std::memset(out, 0, n * sizeof(rt_adaptive_pixel));
+    return gather(ctx, reinterpret_cast<uint8_t*>(out), sizeof(rt_adaptive_pixel), 0, src.data());
 }
 
 int rt_accumulated_samples(rt_ctx* ctx, uint32_t* samples) {

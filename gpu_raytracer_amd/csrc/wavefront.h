@@ -119,12 +119,15 @@ size_t wf_queue_slots_for(size_t max_entries, uint32_t per_lane, size_t producin
 uint32_t wf_pick_window(uint32_t iterations, uint32_t per_lane); // the reservation window a producing wave uses (host copy of the device rule, unit-tested)
 uint32_t wf_persistent_waves(); // grid size (in 64-lane blocks) of the persistent traversal kernels on the current device
 hipError_t wf_beams(const DevScene& sc, const DevFrame& fr, const WfBuffers& wb, hipStream_t s); // once per frame and device, before the batches
-hipError_t wf_generate(const DevScene& sc, const DevFrame& fr, const WfBuffers& wb, uint32_t first_sample, uint32_t n_samples, hipStream_t s);
+// tg: read by the adaptive variant only (each pixel's own sample count, rt_render_adaptive)
+hipError_t wf_generate(const DevScene& sc, const DevFrame& fr, const WfBuffers& wb, const DevTargets& tg, uint32_t first_sample, uint32_t n_samples, hipStream_t s);
 // Whether wf_bounce launches k_wf_shadow_grid, and so records the grid_events around it: the frame traces shadow segments and has light grids.
 inline bool wf_runs_shadow_grid(const DevFrame& fr, const WfBuffers& wb) { return !(fr.flags & RT_FLAG_NO_SHADOWS) && wb.grids; }
 hipError_t wf_bounce(const DevScene& sc, const DevFrame& fr, const WfBuffers& wb, uint32_t iteration, uint32_t n_samples, bool counters, hipStream_t s,
                      hipEvent_t* grid_events = nullptr); // n_samples: samples per pixel in this batch (iteration 0); grid_events: two events recorded around the k_wf_shadow_grid launch
-hipError_t wf_resolve(const DevFrame& fr, const WfBuffers& wb, const DevTargets& tg, uint32_t n_samples, bool first_batch, bool last_batch, hipStream_t s);
+// first_sample: the batch's first sample of the launch (the adaptive variant keeps H, the sum over the odd-indexed samples, from it)
+hipError_t wf_resolve(const DevFrame& fr, const WfBuffers& wb, const DevTargets& tg, uint32_t n_samples, uint32_t first_sample, bool first_batch, bool last_batch,
+                      hipStream_t s);
 
 } // namespace rt
 #endif

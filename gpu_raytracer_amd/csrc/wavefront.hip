@@ -125,9 +125,11 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// generation: one lane per path slot (sample k of pixel (block b, lane l))
+// generation: one lane per path slot (sample k of pixel (block b, lane l)).  AD: the adaptive variant (rt_render_adaptive): block b is
+// owned block fr.ad_blocks[b], a lane k_ad_select left out behaves like a lane outside the image, and a pixel's samples start at its own n.
 // ---------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_wf_generate(DevFrame fr, rt::WfBuffers wb, uint32_t first_sample, uint32_t n_slots_blocks) {
+template <bool AD>
+__global__ __launch_bounds__(256) void k_wf_generate(DevFrame fr, rt::WfBuffers wb, DevTargets tg, uint32_t first_sample, uint32_t n_slots_blocks) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t n_waves = gridDim.x * 4u, wave = blockIdx.x * 4u + (threadIdx.x >> 6);
     OutWindow win = {0u, 0u};
@@ -146,10 +148,15 @@ __global__ __launch_bounds__(256) void k_wf_generate(DevFrame fr, rt::WfBuffers 
 #else
         const uint32_t k = sb / wb.n_blocks, b = sb - k * wb.n_blocks; // sb = k * n_blocks + b
 #endif
-        const PixelCoord px = block_pixel_at(fr, b, lane);
+        PixelCoord px = block_pixel_at(fr, AD ? fr.ad_blocks[b] : b, lane);
+        uint32_t base = fr.sample_base;
+        if (AD) {
+            px.valid = px.valid && ad_lane_active(fr, fr.ad_blocks[b], lane);
+            if (px.valid) base = ad_load(fr, tg, (size_t)px.y * fr.width + px.x).n;
+        }
         const uint32_t p = sb * WAVE + lane;
         if (px.valid) {
-            SimpleRng rng = rng_for(fr.frame_seed + px.x + px.y * fr.width, fr.sample_base + first_sample + k);
+            SimpleRng rng = rng_for(fr.frame_seed + px.x + px.y * fr.width, base + first_sample + k);
             float jx = 0.5f, jy = 0.5f;
             if (fr.jitter) {
                 jx = rng.next_f32();
@@ -507,13 +514,14 @@ __device__ __forceinline__ float beam_box_distance(const V3 o, const float lo[3]
     const float dx = fmaxf(fmaxf(lo[0] - o.x, o.x - hi[0]), 0.0f), dy = fmaxf(fmaxf(lo[1] - o.y, o.y - hi[1]), 0.0f), dz = fmaxf(fmaxf(lo[2] - o.z, o.z - hi[2]), 0.0f);
     return sqrtf(dx * dx + dy * dy + dz * dz) * RT_BEAM_DIST_SCALE;
 }
+template <bool AD> // AD: block b is owned block fr.ad_blocks[b] (rt_render_adaptive)
 __global__ __launch_bounds__(WAVE) void k_wf_beams(DevScene sc, DevFrame fr, rt::WfBuffers wb) {
     __shared__ uint32_t s_nodes[RT_BEAM_STACK];
     __shared__ uint32_t s_leaf[RT_BEAM_LEAVES];
     __shared__ uint32_t s_ref[RT_BEAM_CAP];
     __shared__ float s_dist[RT_BEAM_CAP];
     const uint32_t lane = threadIdx.x, b = blockIdx.x;
-    const PixelCoord p0 = block_pixel_at(fr, b, 0); // the block's first pixel (defined also when it lies outside the image)
+    const PixelCoord p0 = block_pixel_at(fr, AD ? fr.ad_blocks[b] : b, 0); // the block's first pixel (defined also when it lies outside the image)
     const float x0 = (float)p0.x - RT_BEAM_MARGIN_PX, x1 = (float)p0.x + 8.0f + RT_BEAM_MARGIN_PX;
     const float y0 = (float)p0.y - RT_BEAM_MARGIN_PX, y1 = (float)p0.y + 8.0f + RT_BEAM_MARGIN_PX;
     const DevCamera& cam = fr.cam;
@@ -1329,12 +1337,35 @@ __global__ __launch_bounds__(256, RT_WF_SHADE_WAVES) void k_wf_finish(DevScene s
 // ---------------------------------------------------------------------------------------------------------
 // resolve: add the batch's samples to each pixel's running sum IN SAMPLE ORDER; write the image on the last batch.  The sum of a batch
 // lives per pixel slot (WfBuffers::accum); an accumulating call (DevTargets::run_sum) starts it from the earlier calls' sum in its first
-// batch and hands it back in its last.
+// batch and hands it back in its last.  AD: the adaptive variant: every batch adds to S and H in DevTargets::run_sum / run_odd directly
+// (the pixel's count n stays in run_sum w, where k_wf_generate reads it, until the last batch adds spp to it); no targets are written.
 // ---------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(WAVE) void k_wf_resolve(DevFrame fr, rt::WfBuffers wb, DevTargets tg, uint32_t n_samples, uint32_t first_batch,
+template <bool AD>
+__global__ __launch_bounds__(WAVE) void k_wf_resolve(DevFrame fr, rt::WfBuffers wb, DevTargets tg, uint32_t n_samples, uint32_t first_sample, uint32_t first_batch,
                                                      uint32_t last_batch) {
     const uint32_t lane = threadIdx.x, b = blockIdx.x;
     const uint32_t q = b * WAVE + lane;
+    if (AD) {
+        const uint32_t ob = fr.ad_blocks[b];
+        const PixelCoord px = block_pixel_at(fr, ob, lane);
+        if (!px.valid || !ad_lane_active(fr, ob, lane)) return;
+        const size_t pix = (size_t)px.y * fr.width + px.x;
+        AdPixel a;
+        if (first_batch) a = ad_load(fr, tg, pix);
+        else {
+            const float4 s = reinterpret_cast<const float4*>(tg.run_sum)[pix], h = reinterpret_cast<const float4*>(tg.run_odd)[pix];
+            a.s = f4v(s);
+            a.h = f4v(h);
+            a.n = (uint32_t)s.w;
+        }
+        for (uint32_t k = 0; k < n_samples; k++) {
+            const V3 x = f4v(wb.sample_rad[(size_t)(RT_WF_BLOCK_MAJOR ? b * n_samples + k : k * wb.n_blocks + b) * WAVE + lane]);
+            a.s = a.s + x;
+            if ((a.n + first_sample + k) & 1u) a.h = a.h + x;
+        }
+        ad_keep(tg, pix, a.s, a.h, last_batch ? a.n + fr.spp : a.n);
+        return;
+    }
     V3 sum;
     if (!first_batch) sum = f4v(wb.accum[q]);
     else if (tg.run_sum && fr.sample_base) { // (wave-uniform)
@@ -1348,12 +1379,7 @@ __global__ __launch_bounds__(WAVE) void k_wf_resolve(DevFrame fr, rt::WfBuffers 
     if (!px.valid) return;
     const size_t pix = (size_t)px.y * fr.width + px.x;
     run_sum_keep(tg, pix, sum);
-    const float n = (float)fr.n_total;
-    const V3 color = v3(sum.x / n, sum.y / n, sum.z / n);
-    if (tg.rgba32f) reinterpret_cast<float4*>(tg.rgba32f)[pix] = make_float4(color.x, color.y, color.z, 1.0f);
-    if (tg.chan[0]) reinterpret_cast<uint32_t*>(tg.chan[0])[pix] = unorm8(color.x) | 0xFF000000u;
-    if (tg.chan[1]) reinterpret_cast<uint32_t*>(tg.chan[1])[pix] = (unorm8(color.y) << 8) | 0xFF000000u;
-    if (tg.chan[2]) reinterpret_cast<uint32_t*>(tg.chan[2])[pix] = (unorm8(color.z) << 16) | 0xFF000000u;
+    store_image(tg, pix, sum, (float)fr.n_total);
 }
 
 int g_cu_count = 0;
@@ -1438,15 +1464,17 @@ hipError_t wf_beams(const DevScene& sc, const DevFrame& fr, const WfBuffers& wb,
     if (!wb.beam_count || wb.n_blocks == 0) return hipSuccess;
     const hipError_t e = hipMemsetAsync(wb.beam_count + wb.n_blocks, 0, sizeof(uint32_t), s); // blocks without a list so far
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_wf_beams, dim3(wb.n_blocks), dim3(WAVE), 0, s, sc, fr, wb);
+    if (fr.adaptive) hipLaunchKernelGGL(k_wf_beams<true>, dim3(wb.n_blocks), dim3(WAVE), 0, s, sc, fr, wb);
+    else hipLaunchKernelGGL(k_wf_beams<false>, dim3(wb.n_blocks), dim3(WAVE), 0, s, sc, fr, wb);
     return hipGetLastError();
 }
 
-hipError_t wf_generate(const DevScene&, const DevFrame& fr, const WfBuffers& wb, uint32_t first_sample, uint32_t n_samples, hipStream_t s) {
+hipError_t wf_generate(const DevScene&, const DevFrame& fr, const WfBuffers& wb, const DevTargets& tg, uint32_t first_sample, uint32_t n_samples, hipStream_t s) {
     hipError_t e = hipMemsetAsync(wb.counters, 0, WF_N_COUNTERS * sizeof(uint32_t), s);
     if (e != hipSuccess) return e;
     if (wb.n_blocks == 0 || n_samples == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_wf_generate, dim3(wf_shading_blocks()), dim3(256), 0, s, fr, wb, first_sample, n_samples * wb.n_blocks);
+    if (fr.adaptive) hipLaunchKernelGGL(k_wf_generate<true>, dim3(wf_shading_blocks()), dim3(256), 0, s, fr, wb, tg, first_sample, n_samples * wb.n_blocks);
+    else hipLaunchKernelGGL(k_wf_generate<false>, dim3(wf_shading_blocks()), dim3(256), 0, s, fr, wb, tg, first_sample, n_samples * wb.n_blocks);
     return hipGetLastError();
 }
 
@@ -1500,9 +1528,13 @@ hipError_t wf_bounce(const DevScene& sc, const DevFrame& fr, const WfBuffers& wb
     return hipGetLastError();
 }
 
-hipError_t wf_resolve(const DevFrame& fr, const WfBuffers& wb, const DevTargets& tg, uint32_t n_samples, bool first_batch, bool last_batch, hipStream_t s) {
+hipError_t wf_resolve(const DevFrame& fr, const WfBuffers& wb, const DevTargets& tg, uint32_t n_samples, uint32_t first_sample, bool first_batch, bool last_batch,
+                      hipStream_t s) {
     if (wb.n_blocks == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_wf_resolve, dim3(wb.n_blocks), dim3(WAVE), 0, s, fr, wb, tg, n_samples, first_batch ? 1u : 0u, last_batch ? 1u : 0u);
+    if (fr.adaptive)
+        hipLaunchKernelGGL(k_wf_resolve<true>, dim3(wb.n_blocks), dim3(WAVE), 0, s, fr, wb, tg, n_samples, first_sample, first_batch ? 1u : 0u, last_batch ? 1u : 0u);
+    else
+        hipLaunchKernelGGL(k_wf_resolve<false>, dim3(wb.n_blocks), dim3(WAVE), 0, s, fr, wb, tg, n_samples, first_sample, first_batch ? 1u : 0u, last_batch ? 1u : 0u);
     return hipGetLastError();
 }
 

@@ -236,6 +236,56 @@ int rt_get_stats(rt_ctx* ctx, rt_stats* out);
 int rt_accumulated_samples(rt_ctx* ctx, uint32_t* samples);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Adaptive sampling (Cycles' adaptive sampling and Dammertz et al. 2010, "A hierarchical automatic stopping condition for Monte
+ * Carlo global illumination", are the model): progressive accumulation that stops spending samples on pixels that have converged.
+ *
+ * Every owned pixel of an adaptive running image keeps n (its samples so far), S (the sum of its samples x_0 .. x_{n-1} in sample
+ * order) and H (the sum of its odd-indexed samples x_1, x_3, ... in sample order).  At the start of every call each pixel's error is
+ * evaluated from them in f32, in exactly this order:
+ *     I = S / n,  A = (H + H) / n                      (per channel)
+ *     d = |I.r - A.r| + |I.g - A.g| + |I.b - A.b|      (left to right)
+ *     e = d / (1e-4f + sqrtf(I.r + I.g + I.b))
+ * and the pixel is active when n < min_samples or e >= threshold (a NaN error counts as converged; n == 0 is always active).  An
+ * active pixel traces its global samples n .. n+spp-1 (all jittered), adds them to S, the odd-indexed ones to H, and n += spp; an
+ * inactive one traces nothing.  Every owned pixel's targets then hold S / (float)n: a pixel that stopped at n samples holds exactly
+ * the bits of the closed n-spp frame (n >= 2) at that pixel, whichever kernel rendered each call.  There is no exchange between
+ * neighbours: a pixel's fate depends on its own samples only, so tile shares and devices stay independent.
+ *
+ * p follows rt_render's rules and must be mode 2 with RT_FLAG_ACCUMULATE (RT_FLAG_ACCUMULATE_RESTART allowed); ap needs a finite
+ * threshold >= 0 (0: no pixel with a finite error stops, i.e. plain accumulation), 2 <= min_samples <= RT_ACCUMULATE_MAX_SAMPLES and
+ * flags == 0.  Anything else is RT_ERR_BAD_ARG and changes nothing.
+ * The running image continues under the key of RT_FLAG_ACCUMULATE and is marked adaptive: a plain accumulating rt_render after
+ * adaptive calls starts a new running image, and so does the reverse.  threshold and min_samples are not part of the key: a tighter
+ * threshold on a later call wakes stopped pixels up.  Everything else that ends an accumulation ends this one.
+ * rt_accumulated_samples returns the count of a pixel that never stopped (the sum of the spp of the image's calls); a call that could
+ * take a pixel past RT_ACCUMULATE_MAX_SAMPLES is RT_ERR_BAD_ARG.  rt_stats of the call: rays / primary_rays / continuation_rays /
+ * shadow_rays count what was traced, pixels the pixels that received samples, kernel_ms includes the selection and image passes.
+ * --------------------------------------------------------------------------------------------------------------- */
+typedef struct rt_adaptive_params {
+    float threshold;       /* e at or above which a pixel keeps sampling; 0 = never stop (plain accumulation) */
+    uint32_t min_samples;  /* samples every pixel gets before it may stop; >= 2 */
+    uint32_t flags;        /* reserved, 0 */
+    uint32_t _pad;
+} rt_adaptive_params;      /* 16 B */
+
+typedef struct rt_adaptive_pixel {
+    float sum[3];  float samples;   /* S, n (as float: exact below RT_ACCUMULATE_MAX_SAMPLES) */
+    float odd[3];  float error;     /* H, e by the rule above (0 when n == 0) */
+} rt_adaptive_pixel;       /* 32 B */
+
+RT_STATIC_ASSERT(sizeof(rt_adaptive_params) == 16, "rt_adaptive_params is 16 B");
+RT_STATIC_ASSERT(offsetof(rt_adaptive_params, min_samples) == 4 && offsetof(rt_adaptive_params, flags) == 8, "rt_adaptive_params offsets");
+RT_STATIC_ASSERT(sizeof(rt_adaptive_pixel) == 32, "rt_adaptive_pixel is 32 B");
+RT_STATIC_ASSERT(offsetof(rt_adaptive_pixel, samples) == 12 && offsetof(rt_adaptive_pixel, odd) == 16 && offsetof(rt_adaptive_pixel, error) == 28,
+                 "rt_adaptive_pixel offsets");
+
+int rt_render_adaptive(rt_ctx* ctx, const rt_render_params* p, const rt_adaptive_params* ap);
+
+/* One record per pixel (n_pixels == width*height of the running image), gathered over devices and tile shares as rt_read_rgb32f
+ * does; pixels outside the share read as zeros.  RT_ERR_BAD_ARG when the context has no adaptive running image. */
+int rt_read_adaptive(rt_ctx* ctx, rt_adaptive_pixel* out, size_t n_pixels);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Ray queries: closest hit and occlusion for caller-supplied rays (no reference counterpart; Embree's rtcIntersect /
  * rtcOccluded are the model).  They trace the uploaded scene with the frames' rules and leave the last frame alone.
  *

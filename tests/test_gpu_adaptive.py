@@ -1,0 +1,363 @@
+"""Adaptive sampling (rt_render_adaptive) on the GPU: a pixel that stopped at n samples holds exactly the bits of the closed n-spp frame
+(and the CPU statement's); the rule is the one rt_hip.h states, restated here in numpy float32; threshold 0 is plain accumulation; the
+same call sequence gives the same bits and counts on every kernel path, with and without light grids and beams, over tile shares, a
+device listed twice and small batches; the running image starts, continues and ends when rt_hip.h says it does, and bad arguments
+change nothing."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from gpu_raytracer_amd import scenes
+from gpu_raytracer_amd import types as T
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+W, H, B = 96, 64, 3
+MIN = 4
+SEQ = [2, 2, 2, 2, 2]  # spp of the calls of the standard sequence (the first two sample every pixel: n < MIN)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def _assert_equal(a, b, msg=""):
+    np.testing.assert_array_equal(_bits(a), _bits(b), err_msg=msg)
+
+
+def _images(ctx):
+    return ctx.read_rgb32f(), ctx.read_rgba8_combined()
+
+
+def _frame(rt_api, scene, n, bounces=B, w=W, h=H, **kw):
+    """The closed n-spp frame in a fresh context: images and stats."""
+    with rt_api.Context() as ctx:
+        ctx.upload_scene(scene)
+        st = ctx.render(w, h, scene.camera, mode=2, spp=n, max_bounces=bounces, **kw)
+        return _images(ctx), st
+
+
+def np_error(rec):
+    """The rule's error from (S, n, H), in numpy float32 and in rt_hip.h's order (0 where n == 0)."""
+    s, n, hh = rec[..., 0:3], rec[..., 3], rec[..., 4:7]
+    with np.errstate(all="ignore"):
+        i = s / n[..., None]
+        a = (hh + hh) / n[..., None]
+        d = np.abs(i[..., 0] - a[..., 0]) + np.abs(i[..., 1] - a[..., 1]) + np.abs(i[..., 2] - a[..., 2])
+        e = d / (np.float32(1e-4) + np.sqrt(i[..., 0] + i[..., 1] + i[..., 2]))
+    return np.where(n == 0, np.float32(0), e).astype(np.float32)
+
+
+def np_active(rec, threshold, min_samples):
+    e = np_error(rec)
+    with np.errstate(invalid="ignore"):
+        return (rec[..., 3] < min_samples) | (e >= np.float32(threshold))
+
+
+def _run(ctx, scene, seq, thresholds, bounces=B, w=W, h=H, restart=True, **kw):
+    """The adaptive calls seq[i] spp with thresholds[i]: per-call stats, the records and images after the last."""
+    stats = []
+    for i, (n, t) in enumerate(zip(seq, thresholds)):
+        stats.append(ctx.render_adaptive(w, h, scene.camera, n, t, min_samples=MIN, max_bounces=bounces, restart=restart and i == 0, **kw))
+    return stats, ctx.read_adaptive(), _images(ctx)
+
+
+def _threshold(rt_api, scene, q=0.6, bounces=B, **kw):
+    """A threshold that stops some pixels after the first MIN samples and leaves others running: a quantile of their non-zero errors
+    (a pixel whose samples are all equal, such as the sky's, has error 0 and stops at any positive threshold)."""
+    with rt_api.Context() as ctx:
+        ctx.upload_scene(scene)
+        _, rec, _ = _run(ctx, scene, [2, 2], [0.0, 0.0], bounces=bounces, **kw)
+    e = np_error(rec)
+    e = e[np.isfinite(e) & (e > 0)]
+    assert e.size > 0
+    return float(np.quantile(e, q))
+
+
+def _check_identity(rt_api, scene, rec, images, bounces=B, min_counts=3, oracle=None, **kw):
+    """Every pixel holds the bits of the closed frame of its own count; returns the counts."""
+    counts = rec[..., 3].astype(np.int64)
+    distinct = sorted(set(counts.ravel().tolist()))
+    assert len(distinct) >= min_counts, distinct
+    for n in distinct:
+        want, _ = _frame(rt_api, scene, n, bounces, **kw)
+        m = counts == n
+        _assert_equal(images[0][m], want[0][m], f"rgb32f of the pixels with {n} samples")
+        np.testing.assert_array_equal(images[1][m], want[1][m], err_msg=f"rgba8 of the pixels with {n} samples")
+        if oracle is not None and n == distinct[0]:
+            ref = oracle.render_extended(oracle.PackedScene(scene, use_bvh=False), W, H, n, bounces)
+            _assert_equal(want[0], ref["rgb"], "closed frame against the oracle")
+    return counts
+
+
+# 1 + 2 --------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["cornell12", "default"])
+def test_stopped_pixels_hold_their_closed_frame_and_the_rule_holds(rt_api, oracle_mod, name):
+    scene = scenes.SCENES[name]()
+    t = _threshold(rt_api, scene)
+    total = 0
+    with rt_api.Context() as ctx:
+        ctx.upload_scene(scene)
+        prev = None
+        camera_segments = 0
+        for i, n in enumerate(SEQ):
+            st = ctx.render_adaptive(W, H, scene.camera, n, t, min_samples=MIN, max_bounces=B, restart=i == 0)
+            total += n
+            assert ctx.accumulated_samples() == total
+            rec = ctx.read_adaptive()
+            rgb, comb = _images(ctx)
+            grew = rec[..., 3] > (prev[..., 3] if prev is not None else 0)
+            if prev is not None:
+                np.testing.assert_array_equal(grew, np_active(prev, t, MIN), err_msg=f"call {i}: active set")
+                assert np.array_equal(rec[..., 3][~grew], prev[..., 3][~grew])
+                _assert_equal(rec[~grew], prev[~grew], f"call {i}: stopped pixels keep their sums")
+            np.testing.assert_array_equal(rec[..., 3][grew], (prev[..., 3][grew] if prev is not None else 0) + n)
+            assert st["primary_rays"] == int(grew.sum()) * n and st["pixels"] == int(grew.sum())
+            camera_segments += st["primary_rays"]
+            _assert_equal(rec[..., 7], np_error(rec), f"call {i}: the error")
+            _assert_equal(rgb, rec[..., 0:3] / rec[..., 3:4], f"call {i}: the image is S / n")
+            prev = rec
+        assert camera_segments == int(rec[..., 3].sum())
+        counts = _check_identity(rt_api, scene, rec, (rgb, comb), oracle=oracle_mod)
+    assert counts.min() == MIN and counts.max() == total  # some pixels stopped as early as allowed, some never did
+    assert (counts < total).any() and (counts == total).any()
+
+
+# 3 ------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("path,bounces,kw", [("pipeline", B, {}), ("kernel_sm", B, {"kernel_sm": True}), ("kernel_v1", B, {"kernel_v1": True}),
+                                             ("one_pass", 0, {})])
+def test_threshold_zero_is_plain_accumulation(rt_api, path, bounces, kw):
+    scene = scenes.cornell12()
+    split = [2, 3, 1]
+    with rt_api.Context() as ctx:
+        ctx.upload_scene(scene)
+        plain = [ctx.render(W, H, scene.camera, mode=2, spp=n, max_bounces=bounces, accumulate=True, restart=i == 0, **kw) for i, n in enumerate(split)]
+        want = _images(ctx)
+    with rt_api.Context() as ctx:
+        ctx.upload_scene(scene)
+        stats, rec, got = _run(ctx, scene, split, [0.0] * len(split), bounces=bounces, **kw)
+    _assert_equal(got[0], want[0], path)
+    np.testing.assert_array_equal(got[1], want[1], err_msg=path)
+    assert (rec[..., 3] == sum(split)).all()
+    for a, b in zip(stats, plain):
+        assert (a["primary_rays"], a["continuation_rays"], a["shadow_rays"], a["pixels"]) == \
+               (b["primary_rays"], b["continuation_rays"], b["shadow_rays"], b["pixels"]), path
+        if path == "one_pass":
+            assert a["flags"] & rt_api.STAT_SINGLE_PASS
+        else:
+            assert not a["flags"] & rt_api.STAT_SINGLE_PASS
+
+
+# 4 ------------------------------------------------------------------------------------------------------------------------------
+def _owned(w, h, tile, world, rank):
+    tx = (w + tile - 1) // tile
+    ys, xs = np.mgrid[0:h, 0:w]
+    return ((ys // tile) * tx + xs // tile) % world == rank
+
+
+def _totals(stats):
+    return tuple(sum(s[k] for s in stats) for k in ("primary_rays", "continuation_rays", "shadow_rays", "pixels"))
+
+
+@pytest.mark.parametrize("bounces", [B, 0])
+def test_same_sequence_same_bits_everywhere(rt_api, monkeypatch, bounces):
+    scene = scenes.cornell12()
+    tile = 32
+    t = _threshold(rt_api, scene, bounces=bounces, tile_size=tile)
+    thr = [t] * len(SEQ)
+    monkeypatch.delenv("RT_WF_BATCH", raising=False)
+
+    def run(devices=(0,), **kw):
+        with rt_api.Context(devices) as ctx:
+            ctx.upload_scene(scene)
+            stats, rec, img = _run(ctx, scene, SEQ, thr, bounces=bounces, tile_size=tile, **kw)
+        return stats, rec, img
+
+    base_stats, base_rec, base_img = run()
+    assert len(set(base_rec[..., 3].ravel().tolist())) >= 2
+    variants = {"kernel_sm": {"kernel_sm": True}, "kernel_v1": {"kernel_v1": True}, "pipeline": {"kernel_pipeline": True},
+                "no_shadow_grid": {"no_shadow_grid": True}, "no_beams": {"no_beams": True}}
+    for name, kw in variants.items():
+        stats, rec, img = run(**kw)
+        _assert_equal(rec, base_rec, name)
+        _assert_equal(img[0], base_img[0], name)
+        np.testing.assert_array_equal(img[1], base_img[1], err_msg=name)
+        assert _totals(stats) == _totals(base_stats), name
+    stats, rec, img = run(devices=(0, 0))
+    _assert_equal(rec, base_rec, "one device listed twice")
+    _assert_equal(img[0], base_img[0], "one device listed twice")
+    assert _totals(stats) == _totals(base_stats)
+    monkeypatch.setenv("RT_WF_BATCH", "1")
+    stats, rec, img = run(kernel_pipeline=True)
+    monkeypatch.delenv("RT_WF_BATCH")
+    _assert_equal(rec, base_rec, "one sample per batch")
+    _assert_equal(img[0], base_img[0], "one sample per batch")
+    assert _totals(stats) == _totals(base_stats)
+    for world in (2, 3):
+        rec, rgb, comb, tot = np.zeros_like(base_rec), np.zeros_like(base_img[0]), np.zeros_like(base_img[1]), np.zeros(4, np.int64)
+        for rank in range(world):
+            stats, r, img = run(tile_world=world, tile_rank=rank)
+            m = _owned(W, H, tile, world, rank)
+            assert not r[~m].any()  # pixels outside the share read as zeros
+            rec[m], rgb[m], comb[m] = r[m], img[0][m], img[1][m]
+            tot += np.array(_totals(stats))
+        _assert_equal(rec, base_rec, f"world {world}")
+        _assert_equal(rgb, base_img[0], f"world {world}")
+        np.testing.assert_array_equal(comb, base_img[1], err_msg=f"world {world}")
+        assert tuple(tot.tolist()) == _totals(base_stats)
+
+
+def test_small_batches_on_sponza_like(rt_api, monkeypatch):
+    """Several batches (RT_WF_BATCH=1) and the pipeline's two lanes over a larger frame whose live blocks shrink from call to call."""
+    scene = scenes.sponza_like()
+    w, h = 256, 144
+    t = _threshold(rt_api, scene, w=w, h=h)
+    seq, thr = [2, 2, 3, 3], [t] * 4
+
+    def run():
+        with rt_api.Context() as ctx:
+            ctx.upload_scene(scene)
+            return _run(ctx, scene, seq, thr, w=w, h=h)
+
+    monkeypatch.delenv("RT_WF_BATCH", raising=False)
+    s0, r0, i0 = run()
+    monkeypatch.setenv("RT_WF_BATCH", "1")
+    s1, r1, i1 = run()
+    _assert_equal(r1, r0)
+    _assert_equal(i1[0], i0[0])
+    assert _totals(s1) == _totals(s0)
+    assert s0[-1]["pixels"] < w * h
+    monkeypatch.delenv("RT_WF_BATCH")
+    counts = r0[..., 3].astype(np.int64)
+    for n in sorted(set(counts.ravel().tolist())):
+        want, _ = _frame(rt_api, scene, n, B, w=w, h=h)
+        _assert_equal(i0[0][counts == n], want[0][counts == n], f"{n} samples")
+
+
+# 5 ------------------------------------------------------------------------------------------------------------------------------
+def _bad_arg(fn):
+    with pytest.raises(Exception) as ei:
+        fn()
+    assert "BAD_ARG" in str(ei.value), str(ei.value)
+
+
+def test_life_cycle(rt_api):
+    scene = scenes.cornell12()
+    t = _threshold(rt_api, scene)
+    with rt_api.Context() as ctx:
+        ctx.upload_scene(scene)
+        _bad_arg(ctx.read_adaptive)  # nothing rendered
+        _run(ctx, scene, SEQ, [t] * len(SEQ))
+        assert ctx.accumulated_samples() == sum(SEQ)
+        # plain accumulation after adaptive calls: a new image; and the reverse
+        ctx.render(W, H, scene.camera, mode=2, spp=3, max_bounces=B, accumulate=True)
+        assert ctx.accumulated_samples() == 3
+        _bad_arg(ctx.read_adaptive)
+        ctx.render_adaptive(W, H, scene.camera, 2, t, min_samples=MIN, max_bounces=B)
+        assert ctx.accumulated_samples() == 2
+        assert (ctx.read_adaptive()[..., 3] == 2).all()
+        ctx.render_adaptive(W, H, scene.camera, 2, t, min_samples=MIN, max_bounces=B)
+        assert ctx.accumulated_samples() == 4
+        # restart
+        ctx.render_adaptive(W, H, scene.camera, 3, t, min_samples=MIN, max_bounces=B, restart=True)
+        assert ctx.accumulated_samples() == 3 and (ctx.read_adaptive()[..., 3] == 3).all()
+        # upload and geometry updates end the image
+        ctx.upload_scene(scene)
+        assert ctx.accumulated_samples() == 0
+        _bad_arg(ctx.read_adaptive)
+        ctx.render_adaptive(W, H, scene.camera, 2, t, min_samples=MIN, max_bounces=B)
+        assert ctx.accumulated_samples() == 2
+        ctx.update_geometry(np.ascontiguousarray(scene.vertices["position"], dtype=np.float32))
+        assert ctx.accumulated_samples() == 0
+        _bad_arg(ctx.read_adaptive)
+        # a closed frame ends it too
+        ctx.render_adaptive(W, H, scene.camera, 2, t, min_samples=MIN, max_bounces=B)
+        ctx.render(W, H, scene.camera, mode=2, spp=2, max_bounces=B)
+        assert ctx.accumulated_samples() == 0
+        _bad_arg(ctx.read_adaptive)
+
+
+def test_tighter_threshold_wakes_stopped_pixels(rt_api, oracle_mod):
+    scene = scenes.cornell12()
+    t = _threshold(rt_api, scene, q=0.5)
+    with rt_api.Context() as ctx:
+        ctx.upload_scene(scene)
+        _, before, _ = _run(ctx, scene, SEQ, [t] * len(SEQ))
+        st = ctx.render_adaptive(W, H, scene.camera, 2, t / 4, min_samples=MIN, max_bounces=B)
+        rec = ctx.read_adaptive()
+        images = _images(ctx)
+    total = sum(SEQ) + 2
+    assert st["pixels"] == int(np_active(before, t / 4, MIN).sum())
+    woke = (rec[..., 3] > before[..., 3]) & (before[..., 3] < sum(SEQ))
+    assert woke.any() and rec[..., 3].max() == total
+    _check_identity(rt_api, scene, rec, images)
+
+
+def test_bad_arguments_change_nothing(rt_api):
+    scene = scenes.cornell12()
+    t = _threshold(rt_api, scene)
+    lib = rt_api.load()
+    with rt_api.Context() as ctx:
+        ctx.upload_scene(scene)
+        _run(ctx, scene, SEQ, [t] * len(SEQ))
+        rec0, img0, n0 = ctx.read_adaptive(), _images(ctx), ctx.accumulated_samples()
+
+        def call(flags=rt_api.FLAG_ACCUMULATE, mode=2, threshold=t, min_samples=MIN, aflags=0):
+            p = rt_api.render_params(W, H, scene.camera, mode=mode, spp=2, max_bounces=B)
+            p["flags"] = flags
+            ap = np.zeros((), T.ADAPTIVE_PARAMS)
+            ap["threshold"], ap["min_samples"], ap["flags"] = threshold, min_samples, aflags
+            return lib.rt_render_adaptive(ctx._h, C.c_void_p(p.ctypes.data), C.c_void_p(ap.ctypes.data))
+
+        for bad in ({"flags": 0}, {"flags": rt_api.FLAG_ACCUMULATE_RESTART}, {"mode": 1}, {"min_samples": 1}, {"min_samples": 0},
+                    {"min_samples": rt_api.ACCUMULATE_MAX_SAMPLES + 1}, {"threshold": -1e-3}, {"threshold": float("nan")},
+                    {"threshold": float("inf")}, {"aflags": 1}):
+            assert call(**bad) == -1, bad
+            assert ctx.accumulated_samples() == n0, bad
+            _assert_equal(ctx.read_adaptive(), rec0, str(bad))
+            _assert_equal(ctx.read_rgb32f(), img0[0], str(bad))
+        assert lib.rt_render_adaptive(ctx._h, C.c_void_p(0), C.c_void_p(0)) == -1
+        out = np.zeros((H, W, 8), np.float32)
+        assert lib.rt_read_adaptive(ctx._h, C.c_void_p(out.ctypes.data), C.c_size_t(W * H + 1)) == -1
+        assert call() == 0  # the image goes on
+        assert ctx.accumulated_samples() == n0 + 2
+
+
+def test_sample_limit(rt_api):
+    """2^24 samples: 256 calls of 65536 reach the limit (threshold 0: every pixel keeps sampling), the next call is refused."""
+    scene = scenes.empty_scene()
+    with rt_api.Context() as ctx:
+        ctx.upload_scene(scene)
+        for i in range(256):
+            ctx.render_adaptive(8, 8, scene.camera, 65536, 0.0, max_bounces=0)
+        assert ctx.accumulated_samples() == rt_api.ACCUMULATE_MAX_SAMPLES
+        rec = ctx.read_adaptive()
+        assert (rec[..., 3] == rt_api.ACCUMULATE_MAX_SAMPLES).all()
+        _bad_arg(lambda: ctx.render_adaptive(8, 8, scene.camera, 1, 0.0, max_bounces=0))
+        assert ctx.accumulated_samples() == rt_api.ACCUMULATE_MAX_SAMPLES
+        _assert_equal(ctx.read_adaptive(), rec)
+        ctx.render_adaptive(8, 8, scene.camera, 2, 0.0, max_bounces=0, restart=True)
+        assert ctx.accumulated_samples() == 2
+
+
+# 6 ------------------------------------------------------------------------------------------------------------------------------
+def test_front_end_adaptive(tmp_path):
+    exe = os.path.join(ROOT, "build", "rt_render")
+    a, b, c = str(tmp_path / "a.png"), str(tmp_path / "b.png"), str(tmp_path / "c.png")
+    common = ["--size", "160x96", "--spp", "2", "--progressive", "4"]
+    out = subprocess.run([exe] + common + ["--adaptive", "0", "--out", a], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr
+    assert out.stdout.count("adaptive call") == 4
+    out = subprocess.run([exe] + common + ["--out", b], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr
+    assert open(a, "rb").read() == open(b, "rb").read()
+    out = subprocess.run([exe] + common + ["--adaptive", "0.02", "--min-samples", "2", "--out", c], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr
+    active = [int(x) for x in re.findall(r"(\d+) active pixels", out.stdout)]
+    assert len(active) == 4 and active[0] == 160 * 96
+    assert active[-1] < active[0], out.stdout
