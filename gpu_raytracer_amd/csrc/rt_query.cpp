@@ -1,0 +1,402 @@
+// rt_query.cpp — calls that trace or filter outside a frame: ray queries (rt_hip.h "Ray queries": rt_intersect, rt_occluded,
+// rt_camera_rays) and the image passes ("Feature buffers (AOVs) and denoising": rt_aovs, rt_sample_rays, rt_denoise; kernels in
+// denoise.hip).  None of them touches the frame targets, the tile shares rt_read_* gather, or the running image of an accumulation.
+#include "rt_internal.h"
+
+namespace rti {
+// Where `p` lives.  Pageable memory the runtime has never seen may come back as an error or as unregistered: both are host memory.
+int classify_ptr(rt_ctx* ctx, const char* fn, const char* what, const void* p, QueryPtr& q, uintptr_t align) {
+    q = QueryPtr{};
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return RT_OK;
+    }
+    if (a.type != hipMemoryTypeDevice || a.isManaged) return RT_OK; // pinned, managed, unregistered
+    for (size_t j = 0; j < ctx->devs.size(); j++)
+        if (ctx->devs[j].device == a.device) {
+            if (reinterpret_cast<uintptr_t>(p) & (align - 1))
+                return ctx->fail(RT_ERR_BAD_ARG, "%s: %s is device memory that is not %u-byte aligned (%p)", fn, what, (unsigned)align, p);
+            q.device = true;
+            q.dev = j;
+            return RT_OK;
+        }
+    return ctx->fail(RT_ERR_BAD_ARG, "%s: %s is device memory of HIP device %d, which is not a device of this context", fn, what, a.device);
+}
+
+namespace {
+
+int ensure_query_events(rt_ctx* ctx, DeviceState& d, size_t n) {
+    while (d.rq_events.size() < n) {
+        hipEvent_t e = nullptr;
+        HIPCHK(ctx, hipEventCreate(&e));
+        d.rq_events.push_back(e);
+    }
+    return RT_OK;
+}
+
+void drain_streams(rt_ctx* ctx) { // after a failure: nothing of the call is left writing into the caller's memory
+    for (auto& d : ctx->devs) {
+        (void)hipSetDevice(d.device);
+        (void)hipStreamSynchronize(d.stream);
+    }
+}
+
+// Both query kinds: out_elem = 16 (rt_hit) or 1 (occluded byte).
+int run_query(rt_ctx* ctx, const char* fn, const rt_ray* rays, size_t n, void* out, size_t out_elem, uint32_t flags) {
+    const double w0 = now_ms();
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (n == 0) return RT_OK;
+    const char* out_name = out_elem == 1 ? "occluded" : "hits";
+    if (!rays || !out) return ctx->fail(RT_ERR_BAD_ARG, "%s: %s is NULL with n = %zu", fn, !rays ? "rays" : out_name, n);
+    if (flags & ~RT_QUERY_COUNTERS) return ctx->fail(RT_ERR_BAD_ARG, "%s: unknown flag bits 0x%x", fn, flags & ~RT_QUERY_COUNTERS);
+    if (!ctx->uploaded) return ctx->fail(RT_ERR_NOT_UPLOADED, "%s: no scene uploaded", fn);
+    if (int rcp = sync_pending(ctx)) return rcp;
+    QueryPtr pin, pout;
+    if (int rc = classify_ptr(ctx, fn, "rays", rays, pin)) return rc;
+    if (int rc = classify_ptr(ctx, fn, out_name, out, pout)) return rc;
+    if (pin.device != pout.device || pin.dev != pout.dev)
+        return ctx->fail(RT_ERR_BAD_ARG, "%s: rays (%s %zu) and %s (%s %zu) must both be host memory or both device memory of the same device", fn,
+                         pin.device ? "device memory of context device" : "host memory", pin.device ? pin.dev : (size_t)0, out_name,
+                         pout.device ? "device memory of context device" : "host memory", pout.device ? pout.dev : (size_t)0);
+    const bool counters = (flags & RT_QUERY_COUNTERS) != 0;
+    const size_t nd = ctx->devs.size();
+    std::vector<size_t> first(nd, 0), count(nd, 0);
+    if (pin.device) count[pin.dev] = n; // a device batch runs where it lives
+    else
+        for (size_t j = 0; j < nd; j++) first[j] = n * j / nd, count[j] = n * (j + 1) / nd - first[j]; // contiguous ranges, one per device
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(rays);
+    uint8_t* dst = reinterpret_cast<uint8_t*>(out);
+    // every device's range is enqueued before any is waited for
+    auto enqueue = [&](size_t j) -> int {
+        DeviceState& d = ctx->devs[j];
+        HIPCHK(ctx, hipSetDevice(d.device));
+        const DevScene sc = scene_for(ctx, d);
+        const size_t chunks = (count[j] + RT_QUERY_CHUNK - 1) / RT_QUERY_CHUNK;
+        if (int rc = ensure_query_events(ctx, d, 2 * chunks)) return rc;
+        if (!pin.device) {
+            const size_t m = std::min<size_t>(count[j], RT_QUERY_CHUNK);
+            HIPCHK(ctx, d.rq.in.reserve(m * sizeof(rt_ray)));
+            HIPCHK(ctx, d.rq.out.reserve(m * out_elem));
+        }
+        if (counters) HIPCHK(ctx, hipMemsetAsync(d.counters.get(), 0, (RT_CNT_TRI_TESTS + 1) * sizeof(unsigned long long), d.stream));
+        for (size_t c = 0; c < chunks; c++) {
+            const size_t off = first[j] + c * RT_QUERY_CHUNK, m = std::min<size_t>(RT_QUERY_CHUNK, first[j] + count[j] - off);
+            const void* in = src + off * sizeof(rt_ray);
+            void* res = dst + off * out_elem;
+            if (!pin.device) {
+                HIPCHK(ctx, hipMemcpyAsync(d.rq.in.get(), in, m * sizeof(rt_ray), hipMemcpyHostToDevice, d.stream));
+                in = d.rq.in.get();
+                res = d.rq.out.get();
+            }
+            HIPCHK(ctx, hipEventRecord(d.rq_events[2 * c], d.stream));
+            HIPCHK(ctx, rt::launch_ray_query(sc, in, res, (uint32_t)m, out_elem == 1, counters ? d.counters.get() : nullptr, d.stream));
+            HIPCHK(ctx, hipEventRecord(d.rq_events[2 * c + 1], d.stream));
+            if (!pin.device) HIPCHK(ctx, hipMemcpyAsync(dst + off * out_elem, d.rq.out.get(), m * out_elem, hipMemcpyDeviceToHost, d.stream));
+        }
+        return RT_OK;
+    };
+    for (size_t j = 0; j < nd; j++)
+        if (count[j] > 0)
+            if (int rc = enqueue(j)) {
+                drain_streams(ctx);
+                return rc;
+            }
+    double kernel_ms = 0.0;
+    unsigned long long nodes = 0, tris = 0;
+    for (size_t j = 0; j < nd; j++) {
+        if (count[j] == 0) continue;
+        DeviceState& d = ctx->devs[j];
+        hipError_t e = hipSetDevice(d.device);
+        if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
+        if (e != hipSuccess) {
+            drain_streams(ctx);
+            return ctx->fail(RT_ERR_HIP, "%s: device %d: %s", fn, d.device, hipGetErrorString(e));
+        }
+        double ms = 0.0;
+        for (size_t c = 0; 2 * c + 1 < d.rq_events.size() && c * RT_QUERY_CHUNK < count[j]; c++) {
+            float cm = 0.0f;
+            HIPCHK(ctx, hipEventElapsedTime(&cm, d.rq_events[2 * c], d.rq_events[2 * c + 1]));
+            ms += cm;
+        }
+        kernel_ms = std::max(kernel_ms, ms);
+        if (counters) {
+            unsigned long long cn[RT_CNT_TRI_TESTS + 1];
+            HIPCHK(ctx, hipMemcpy(cn, d.counters.get(), sizeof cn, hipMemcpyDeviceToHost));
+            nodes += cn[RT_CNT_NODE_VISITS];
+            tris += cn[RT_CNT_TRI_TESTS];
+        }
+    }
+    rt_stats& st = ctx->stats;
+    st.rays = n;
+    st.primary_rays = st.continuation_rays = st.shadow_rays = st.pixels = 0;
+    st.node_visits = counters ? nodes : 0;
+    st.tri_tests = counters ? tris : 0;
+    st.kernel_ms = kernel_ms;
+    st.wall_ms = now_ms() - w0;
+    return RT_OK;
+}
+
+// The jitter rule of the frames: a closed frame jitters when it has several samples (frame_of_params), an accumulation always.
+void sample_jitter(DevFrame& fr, uint32_t flags) {
+    if (flags & RT_FLAG_ACCUMULATE) fr.jitter = 1u;
+}
+
+// One device's share of rt_aovs, enqueued: zero the frame's records (the pixels outside the share stay zero), then the samples in runs of
+// at most RT_AOV_SAMPLES_PER_LAUNCH, between the device's query event pair.
+int enqueue_aovs(rt_ctx* ctx, DeviceState& d, const DevFrame& f, void* acc, size_t bytes) {
+    HIPCHK(ctx, hipSetDevice(d.device));
+    if (int rc = ensure_query_events(ctx, d, 2)) return rc;
+    HIPCHK(ctx, hipMemsetAsync(acc, 0, bytes, d.stream));
+    HIPCHK(ctx, hipEventRecord(d.rq_events[0], d.stream));
+    const DevScene sc = scene_for(ctx, d);
+    for (uint32_t s0 = 0; s0 < f.n_total; s0 += RT_AOV_SAMPLES_PER_LAUNCH)
+        HIPCHK(ctx, rt::launch_aov_samples(sc, f, s0, std::min(RT_AOV_SAMPLES_PER_LAUNCH, f.n_total - s0), acc, d.stream));
+    HIPCHK(ctx, hipEventRecord(d.rq_events[1], d.stream));
+    return RT_OK;
+}
+
+int aovs(rt_ctx* ctx, const rt_render_params* p, rt_aov* out) {
+    const double w0 = now_ms();
+    uint32_t world = 1, rank = 0;
+    DevFrame fr{};
+    if (int rc = frame_of_params(ctx, "rt_aovs", p, fr, world, rank)) return rc;
+    if (!out) return ctx->fail(RT_ERR_BAD_ARG, "rt_aovs: out is NULL");
+    if (int rcp = sync_pending(ctx)) return rcp;
+    QueryPtr po;
+    if (int rc = classify_ptr(ctx, "rt_aovs", "out", out, po)) return rc;
+    sample_jitter(fr, p->flags);
+    const size_t n = (size_t)fr.width * fr.height, bytes = n * sizeof(rt_aov);
+    const size_t nd = ctx->devs.size();
+    const bool in_place = po.device && nd == 1; // else every device works on its own records and the shares are put together here
+    std::vector<DevFrame> share(nd, fr);
+    for (size_t j = 0; j < nd; j++) {
+        DeviceState& d = ctx->devs[j];
+        frame_share(share[j], world, rank, nd, j);
+        HIPCHK(ctx, hipSetDevice(d.device));
+        if (!in_place)
+            HIPCHK(ctx, d.dn.aov.reserve(bytes));
+        if (int rc = enqueue_aovs(ctx, d, share[j], in_place ? (void*)out : d.dn.aov.get(), bytes)) {
+            drain_streams(ctx);
+            return rc;
+        }
+    }
+    double kernel_ms = 0.0;
+    uint64_t pixels = 0;
+    for (size_t j = 0; j < nd; j++) {
+        DeviceState& d = ctx->devs[j];
+        hipError_t e = hipSetDevice(d.device);
+        if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
+        if (e != hipSuccess) {
+            drain_streams(ctx);
+            return ctx->fail(RT_ERR_HIP, "rt_aovs: device %d: %s", d.device, hipGetErrorString(e));
+        }
+        float ms = 0.0f;
+        HIPCHK(ctx, hipEventElapsedTime(&ms, d.rq_events[0], d.rq_events[1]));
+        kernel_ms = std::max(kernel_ms, (double)ms);
+        pixels += owned_pixels(share[j], share[j].tile_first, share[j].tile_stride, share[j].n_owned_tiles);
+    }
+    if (!in_place && nd == 1) {
+        HIPCHK(ctx, hipSetDevice(ctx->devs[0].device));
+        HIPCHK(ctx, hipMemcpy(out, ctx->devs[0].dn.aov.get(), bytes, hipMemcpyDeviceToHost));
+    } else if (!in_place) { // several devices: each holds its own tiles; zeros elsewhere, as rt_read_rgb32f gives them
+        std::vector<uint8_t> whole(bytes, 0), tmp(bytes);
+        for (size_t j = 0; j < nd; j++) {
+            const DeviceState& d = ctx->devs[j];
+            const DevFrame& f = share[j];
+            if (f.n_owned_tiles == 0) continue;
+            HIPCHK(ctx, hipSetDevice(d.device));
+            HIPCHK(ctx, hipMemcpy(tmp.data(), d.dn.aov.get(), bytes, hipMemcpyDeviceToHost));
+            copy_share(whole.data(), tmp.data(), sizeof(rt_aov), f.width, f.height, f.tile_size, f.tiles_x, f.tile_first, f.tile_stride, f.n_owned_tiles);
+        }
+        if (po.device) {
+            HIPCHK(ctx, hipSetDevice(ctx->devs[po.dev].device));
+            HIPCHK(ctx, hipMemcpy(out, whole.data(), bytes, hipMemcpyHostToDevice));
+        } else {
+            std::memcpy(out, whole.data(), bytes);
+        }
+    }
+    rt_stats& st = ctx->stats;
+    st.pixels = pixels;
+    st.rays = st.primary_rays = pixels * fr.n_total;
+    st.continuation_rays = st.shadow_rays = st.node_visits = st.tri_tests = 0;
+    st.kernel_ms = kernel_ms;
+    st.wall_ms = now_ms() - w0;
+    return RT_OK;
+}
+
+int check_sigma(rt_ctx* ctx, const char* name, float s) {
+    if (!(s > 0.0f) || !std::isfinite(s)) return ctx->fail(RT_ERR_BAD_ARG, "rt_denoise: %s %g (finite and > 0)", name, (double)s);
+    return RT_OK;
+}
+
+int denoise(rt_ctx* ctx, const rt_denoise_params* dp, const float* rgb, const rt_aov* aov, float* out) {
+    const double w0 = now_ms();
+    if (!dp || !rgb || !aov || !out)
+        return ctx->fail(RT_ERR_BAD_ARG, "rt_denoise: %s is NULL", !dp ? "params" : !rgb ? "rgb" : !aov ? "aov" : "out");
+    if (dp->width == 0 || dp->height == 0 || dp->width > 65535u * 8u || dp->height > 65535u * 8u)
+        return ctx->fail(RT_ERR_BAD_ARG, "rt_denoise: bad resolution %ux%u", dp->width, dp->height);
+    if (dp->iterations < 1 || dp->iterations > RT_DENOISE_MAX_ITERATIONS)
+        return ctx->fail(RT_ERR_BAD_ARG, "rt_denoise: iterations %u (1 .. %u)", dp->iterations, RT_DENOISE_MAX_ITERATIONS);
+    if (dp->flags & ~RT_DENOISE_DEMODULATE) return ctx->fail(RT_ERR_BAD_ARG, "rt_denoise: unknown flag bits 0x%x", dp->flags & ~RT_DENOISE_DEMODULATE);
+    if (int rc = check_sigma(ctx, "sigma_color", dp->sigma_color)) return rc;
+    if (int rc = check_sigma(ctx, "sigma_normal", dp->sigma_normal)) return rc;
+    if (int rc = check_sigma(ctx, "sigma_depth", dp->sigma_depth)) return rc;
+    if (int rc = check_sigma(ctx, "sigma_albedo", dp->sigma_albedo)) return rc;
+    if (int rcp = sync_pending(ctx)) return rcp;
+    QueryPtr pr, pa, po;
+    if (int rc = classify_ptr(ctx, "rt_denoise", "rgb", rgb, pr, 4)) return rc;
+    if (int rc = classify_ptr(ctx, "rt_denoise", "aov", aov, pa, 16)) return rc;
+    if (int rc = classify_ptr(ctx, "rt_denoise", "out", out, po, 4)) return rc;
+    if (pr.device != pa.device || pr.device != po.device || pr.dev != pa.dev || pr.dev != po.dev)
+        return ctx->fail(RT_ERR_BAD_ARG, "rt_denoise: rgb, aov and out must all be host memory or all device memory of the same device");
+    const bool device = pr.device;
+    DeviceState& d = ctx->devs[pr.dev]; // host buffers: the first device
+    const uint32_t n = dp->width * dp->height;
+    if ((size_t)dp->width * dp->height > 0xFFFFFFFFull) return ctx->fail(RT_ERR_BAD_ARG, "rt_denoise: %ux%u pixels", dp->width, dp->height);
+    HIPCHK(ctx, hipSetDevice(d.device));
+    for (int k = 0; k < 2; k++)
+        HIPCHK(ctx, d.dn.plane[k].reserve((size_t)n * 16));
+    if (!device) {
+        HIPCHK(ctx, d.dn.rgb.reserve((size_t)n * 12));
+        HIPCHK(ctx, d.dn.aov.reserve((size_t)n * sizeof(rt_aov)));
+    }
+    if (int rc = ensure_query_events(ctx, d, 2)) return rc;
+    const float* c_rgb = device ? rgb : (const float*)d.dn.rgb.get();
+    const void* c_aov = device ? (const void*)aov : d.dn.aov.get();
+    float* c_out = device ? out : (float*)d.dn.rgb.get(); // the pack has read the staged rgb before the last iteration writes over it
+    float4* plane[2] = {d.dn.plane[0].get(), d.dn.plane[1].get()};
+    const bool demod = (dp->flags & RT_DENOISE_DEMODULATE) != 0;
+    auto enqueue = [&]() -> hipError_t {
+        hipError_t e = hipSuccess;
+        if (!device) {
+            if ((e = hipMemcpyAsync(d.dn.rgb.get(), rgb, (size_t)n * 12, hipMemcpyHostToDevice, d.stream)) != hipSuccess) return e;
+            if ((e = hipMemcpyAsync(d.dn.aov.get(), aov, (size_t)n * sizeof(rt_aov), hipMemcpyHostToDevice, d.stream)) != hipSuccess) return e;
+        }
+        if ((e = hipEventRecord(d.rq_events[0], d.stream)) != hipSuccess) return e;
+        if ((e = rt::launch_denoise_pack(c_rgb, c_aov, plane[0], n, demod, d.stream)) != hipSuccess) return e;
+        for (uint32_t i = 0; i < dp->iterations; i++) {
+            rt::AtrousParams ap;
+            ap.width = dp->width, ap.height = dp->height, ap.iter = i;
+            const float sc = dp->sigma_color * std::ldexp(1.0f, -(int)i); // sigma_color * 2^-i
+            ap.inv_sc2 = 1.0f / (sc * sc);
+            ap.inv_sn2 = 1.0f / (dp->sigma_normal * dp->sigma_normal);
+            ap.sigma_depth = dp->sigma_depth;
+            ap.inv_sa2 = 1.0f / (dp->sigma_albedo * dp->sigma_albedo);
+            ap.demodulate = demod;
+            const bool last = i + 1 == dp->iterations;
+            if ((e = rt::launch_denoise_atrous(ap, plane[i & 1], c_aov, plane[(i + 1) & 1], c_out, last, d.stream)) != hipSuccess) return e;
+        }
+        if ((e = hipEventRecord(d.rq_events[1], d.stream)) != hipSuccess) return e;
+        if (!device) e = hipMemcpyAsync(out, d.dn.rgb.get(), (size_t)n * 12, hipMemcpyDeviceToHost, d.stream);
+        return e;
+    };
+    hipError_t e = enqueue();
+    if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
+    if (e != hipSuccess) {
+        drain_streams(ctx);
+        return ctx->fail(e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP, "rt_denoise: %s", hipGetErrorString(e));
+    }
+    float ms = 0.0f;
+    HIPCHK(ctx, hipEventElapsedTime(&ms, d.rq_events[0], d.rq_events[1]));
+    rt_stats& st = ctx->stats;
+    st.rays = st.primary_rays = st.continuation_rays = st.shadow_rays = st.node_visits = st.tri_tests = 0;
+    st.pixels = n;
+    st.kernel_ms = ms;
+    st.wall_ms = now_ms() - w0;
+    return RT_OK;
+}
+
+} // namespace
+
+} // namespace rti
+
+using namespace rti;
+
+extern "C" {
+
+int rt_intersect(rt_ctx* ctx, const rt_ray* rays, size_t n, rt_hit* hits, uint32_t flags) {
+    return run_query(ctx, "rt_intersect", rays, n, hits, sizeof(rt_hit), flags);
+}
+
+int rt_occluded(rt_ctx* ctx, const rt_ray* rays, size_t n, uint8_t* occluded, uint32_t flags) {
+    return run_query(ctx, "rt_occluded", rays, n, occluded, 1, flags);
+}
+
+int rt_camera_rays(rt_ctx* ctx, const rt_camera* camera, uint32_t width, uint32_t height, uint32_t mode, rt_ray* out) {
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (mode != RT_MODE_LEGACY && mode != RT_MODE_WAVEFRONT) return ctx->fail(RT_ERR_BAD_ARG, "rt_camera_rays: mode %u (0 or 1)", mode);
+    const size_t n = (size_t)width * height;
+    if (n == 0) return RT_OK;
+    if (!camera || !out) return ctx->fail(RT_ERR_BAD_ARG, "rt_camera_rays: %s is NULL", !camera ? "camera" : "out");
+    if (int rcp = sync_pending(ctx)) return rcp;
+    QueryPtr po;
+    if (int rc = classify_ptr(ctx, "rt_camera_rays", "out", out, po)) return rc;
+    DeviceState& d = ctx->devs[po.dev];
+    HIPCHK(ctx, hipSetDevice(d.device));
+    if (!po.device)
+        HIPCHK(ctx, d.rq.in.reserve(std::min<size_t>(n, RT_QUERY_CHUNK) * sizeof(rt_ray)));
+    // the frames' camera constants (make_camera) and ray generation (camera_ray): the rays are those rt_render traces
+    const DevCamera cam = make_camera(*camera, (float)width, (float)height, mode != RT_MODE_LEGACY);
+    uint8_t* dst = reinterpret_cast<uint8_t*>(out);
+    for (size_t off = 0; off < n; off += RT_QUERY_CHUNK) {
+        const size_t m = std::min<size_t>(RT_QUERY_CHUNK, n - off);
+        void* res = po.device ? (void*)(dst + off * sizeof(rt_ray)) : d.rq.in.get();
+        hipError_t e = rt::launch_camera_rays(cam, width, mode != RT_MODE_LEGACY, res, off, (uint32_t)m, d.stream);
+        if (e == hipSuccess && !po.device) e = hipMemcpyAsync(dst + off * sizeof(rt_ray), d.rq.in.get(), m * sizeof(rt_ray), hipMemcpyDeviceToHost, d.stream);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(d.stream);
+            return ctx->fail(RT_ERR_HIP, "rt_camera_rays: %s", hipGetErrorString(e));
+        }
+    }
+    HIPCHK(ctx, hipStreamSynchronize(d.stream));
+    return RT_OK;
+}
+
+int rt_aovs(rt_ctx* ctx, const rt_render_params* p, rt_aov* out) {
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (!p) return ctx->fail(RT_ERR_BAD_ARG, "rt_aovs: null params");
+    if (!ctx->uploaded) return ctx->fail(RT_ERR_NOT_UPLOADED, "rt_aovs: no scene uploaded");
+    return aovs(ctx, p, out);
+}
+
+int rt_sample_rays(rt_ctx* ctx, const rt_render_params* p, uint32_t sample, rt_ray* out) {
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (!p) return ctx->fail(RT_ERR_BAD_ARG, "rt_sample_rays: null params");
+    if (p->mode != RT_MODE_EXTENDED) return ctx->fail(RT_ERR_BAD_ARG, "rt_sample_rays: mode %u (the extended mode's samples only)", p->mode);
+    rt_render_params q = *p;
+    q.tile_size = q.tile_rank = q.tile_world = 0; // ignored
+    uint32_t world = 1, rank = 0;
+    DevFrame fr{};
+    if (int rc = frame_of_params(ctx, "rt_sample_rays", &q, fr, world, rank)) return rc;
+    if (!out) return ctx->fail(RT_ERR_BAD_ARG, "rt_sample_rays: out is NULL");
+    if (int rcp = sync_pending(ctx)) return rcp;
+    QueryPtr po;
+    if (int rc = classify_ptr(ctx, "rt_sample_rays", "out", out, po)) return rc;
+    sample_jitter(fr, p->flags);
+    const size_t n = (size_t)fr.width * fr.height;
+    DeviceState& d = ctx->devs[po.dev];
+    HIPCHK(ctx, hipSetDevice(d.device));
+    if (!po.device)
+        HIPCHK(ctx, d.rq.in.reserve(std::min<size_t>(n, RT_QUERY_CHUNK) * sizeof(rt_ray)));
+    uint8_t* dst = reinterpret_cast<uint8_t*>(out);
+    for (size_t off = 0; off < n; off += RT_QUERY_CHUNK) { // as rt_camera_rays
+        const size_t m = std::min<size_t>(RT_QUERY_CHUNK, n - off);
+        void* res = po.device ? (void*)(dst + off * sizeof(rt_ray)) : d.rq.in.get();
+        hipError_t e = rt::launch_sample_rays(fr, sample, res, off, (uint32_t)m, d.stream);
+        if (e == hipSuccess && !po.device) e = hipMemcpyAsync(dst + off * sizeof(rt_ray), d.rq.in.get(), m * sizeof(rt_ray), hipMemcpyDeviceToHost, d.stream);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(d.stream);
+            return ctx->fail(RT_ERR_HIP, "rt_sample_rays: %s", hipGetErrorString(e));
+        }
+    }
+    HIPCHK(ctx, hipStreamSynchronize(d.stream));
+    return RT_OK;
+}
+
+int rt_denoise(rt_ctx* ctx, const rt_denoise_params* dp, const float* rgb, const rt_aov* aov, float* out) {
+    if (!ctx) return RT_ERR_BAD_ARG;
+    return denoise(ctx, dp, rgb, aov, out);
+}
+
+} // extern "C"
