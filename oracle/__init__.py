@@ -57,6 +57,7 @@ def lib():
         _lib.oracle_f32_to_f16.argtypes = [C.c_float]
         _lib.oracle_f16_to_f32.restype = C.c_float
         _lib.oracle_f16_to_f32.argtypes = [C.c_uint16]
+        _lib.oracle_unit_vectors.restype = None
     return _lib
 
 
@@ -164,6 +165,19 @@ def render_frame(packed, width, height, camera=None, mode=0, cur_bounce=0, max_b
         comb[..., 0], comb[..., 1], comb[..., 2], comb[..., 3] = chans[0][..., 0], chans[1][..., 1], chans[2][..., 2], 255
         out["combined"] = comb
     return out
+
+
+def unit_vectors(u1, u2):
+    """The extended mode's unit_vector(u1, u2) and sincos_2pi(u2) for float32 arrays of equal length
+    -> (xyz (n, 3), sincos (n, 2): sin, cos), float32."""
+    u1 = np.ascontiguousarray(u1, np.float32).ravel()
+    u2 = np.ascontiguousarray(u2, np.float32).ravel()
+    if u1.size != u2.size:
+        raise ValueError("unit_vectors: u1 and u2 differ in length")
+    xyz = np.zeros((u1.size, 3), np.float32)
+    sc = np.zeros((u1.size, 2), np.float32)
+    lib().oracle_unit_vectors(_ptr(u1), _ptr(u2), C.c_uint64(u1.size), _ptr(xyz), _ptr(sc))
+    return xyz, sc
 
 
 EXT_NO_SHADOWS = 2

@@ -920,6 +920,18 @@ extern "C" {
 uint16_t oracle_f32_to_f16(float v) { return f32_to_f16(v); }
 float oracle_f16_to_f32(uint16_t h) { return f16_to_f32(h); }
 
+void oracle_unit_vectors(const float* u1, const float* u2, uint64_t n, float* xyz, float* sincos) {
+    for (uint64_t i = 0; i < n; i++) {
+        if (xyz) {
+            V3 v = unit_vector(u1[i], u2[i]);
+            xyz[i * 3 + 0] = v.x;
+            xyz[i * 3 + 1] = v.y;
+            xyz[i * 3 + 2] = v.z;
+        }
+        if (sincos) sincos_2pi(u2[i], &sincos[i * 2 + 0], &sincos[i * 2 + 1]);
+    }
+}
+
 int oracle_dispatch(const oracle_bindings* b, const rt_push_constants* pc, uint8_t* image, uint32_t img_w, uint32_t img_h,
                     oracle_counters* counters) {
     if (!b || !pc || !image) return -1;

@@ -109,6 +109,10 @@ void oracle_set_fast_traversal(int on);
 uint16_t oracle_f32_to_f16(float v);
 float oracle_f16_to_f32(uint16_t h);
 
+/* The extended mode's direction sampler, exposed for tests: for i < n, xyz[3i..] = unit_vector(u1[i], u2[i]) and
+ * sincos[2i..] = (sin, cos) of 2*pi*u2[i] as sincos_2pi computes them.  Either output may be NULL. */
+void oracle_unit_vectors(const float* u1, const float* u2, uint64_t n, float* xyz, float* sincos);
+
 #ifdef __cplusplus
 }
 #endif
