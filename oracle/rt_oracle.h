@@ -15,8 +15,8 @@
  * contract (restated in tests/test_contract.py) and (b) hand-derived
  * known-answer tests K1-K7 of SURVEY.md §8c (tests/test_oracle_kat.py).
  * For ray-gen / traversal / intersection / shading there are no reference
- * vectors: that part is "parity unpinned by reference vectors, pinned by
- * source reading".
+ * vectors: that part is pinned by a second, independent reading of the source,
+ * the float64 statement of tests/reference_cases.py.
  */
 #ifndef RT_ORACLE_H
 #define RT_ORACLE_H
