@@ -1,7 +1,7 @@
 // denoise.hip — the kernels of rt_aovs, rt_sample_rays and rt_denoise (include/rt_hip.h, DESIGN.md "Feature buffers and the a-trous
 // denoiser").
 //
-// rt_aovs traces the camera samples of a frame with the frames' own first-vertex rules (device_common.h: rng_for, camera_ray,
+// rt_aovs traces the camera samples of a frame with the frames' own first-vertex rules (device_common.h: ext_sample_ray,
 // find_closest, hit_geometry) and reduces them per pixel in sample order.  One wave per 8x8 pixel block of an owned tile (block_pixel, as
 // the frames), the per-lane stack in LDS as in k_render_reference.  A launch takes a bounded run of samples and keeps the partial sums in
 // the output records, so that a large frame at many samples is many short kernels.
@@ -34,24 +34,18 @@ __global__ __launch_bounds__(WAVE) void k_aov_samples(DevScene sc, DevFrame fr, 
         b = acc[2 * pix + 1];
     }
     const bool wavefront = fr.mode != 0; // RT_MODE_LEGACY: the pixel-centre ray normalised twice
-    const V3 miss = wavefront ? v3(0.1f, 0.2f, 0.3f) : v3(0.0f, 0.0f, 0.0f); // the colour the mode gives a miss
+    const V3 miss = wavefront ? RT_SKY() : v3(0.0f, 0.0f, 0.0f); // the colour the mode gives a miss
     Counts cnt = {0u, 0u};
     for (uint32_t k = 0; k < ns; k++) {
-        float jx = 0.5f, jy = 0.5f;
-        if (fr.jitter) { // the frame's rule (ext_trace_path, k_wf_generate): the pixel's seed and the global sample index
-            SimpleRng rng = rng_for(fr.frame_seed + px.x + px.y * fr.width, s0 + k);
-            jx = rng.next_f32();
-            jy = rng.next_f32();
-        }
-        V3 o, d;
-        camera_ray(fr.cam, (float)px.x + jx, (float)px.y + jy, wavefront, o, d);
+        V3 o, d; // the frames' rule: the pixel's seed and the global sample index
+        ext_sample_ray(fr.cam, fr.width, fr.frame_seed, fr.jitter, px.x, px.y, s0 + k, wavefront, o, d);
         const Hit hit = find_closest<false>(sc, o, d, stack, cnt);
         V3 albedo = miss;
         if (hit.prim != RT_PRIM_MISS) {
             V3 point, normal;
             uint32_t material_id;
             hit_geometry(sc, hit, o, d, point, normal, material_id);
-            albedo = material_id < sc.n_materials ? ld3(sc.materials[material_id].albedo) : v3(1.0f, 0.0f, 1.0f); // magenta, as shade_hit
+            albedo = material_id < sc.n_materials ? ld3(sc.materials[material_id].albedo) : RT_MAGENTA(); // as shade_hit
             const V3 nf = dot(normal, d) < 0.0f ? normal : -normal; // face-forwarded, the continuation's nf
             b.x = b.x + nf.x;
             b.y = b.y + nf.y;
@@ -79,14 +73,8 @@ __global__ __launch_bounds__(256) void k_aov_sample_rays(DevCamera cam, uint32_t
     if (i >= n) return;
     const uint64_t pix = first + i;
     const uint32_t px = (uint32_t)(pix % width), py = (uint32_t)(pix / width);
-    float jx = 0.5f, jy = 0.5f;
-    if (jitter) {
-        SimpleRng rng = rng_for(frame_seed + px + py * width, sample);
-        jx = rng.next_f32();
-        jy = rng.next_f32();
-    }
     V3 o, d;
-    camera_ray(cam, (float)px + jx, (float)py + jy, true, o, d);
+    ext_sample_ray(cam, width, frame_seed, jitter, px, py, sample, true, o, d);
     out[2 * (size_t)i] = make_float4(o.x, o.y, o.z, RT_MIN_RAY_DISTANCE);
     out[2 * (size_t)i + 1] = make_float4(d.x, d.y, d.z, RT_F32_MAX);
 }

@@ -1,7 +1,8 @@
 // device_common.h — device-side building blocks shared by kernels.hip (megakernels) and wavefront.hip
 // (queue-based pipeline): vector math in the reference's operation order, ray generation, sphere and
 // Möller–Trumbore tests, the quantised 8-wide BVH visit and group walk, the reference's shading, and the extended mode's
-// RNG / sampling helpers.  Everything is __forceinline__; both translation units are compiled with
+// RNG / sampling helpers and the ONE statement of its path vertex (ext_sample_ray, ext_light_sum, ext_leave_vertex, ext_scatter)
+// that its three implementations call.  Everything is __forceinline__; both translation units are compiled with
 // -ffp-contract=off so the arithmetic that decides hits and colours is identical in all kernels.
 #ifndef RT_DEVICE_COMMON_H
 #define RT_DEVICE_COMMON_H
@@ -37,6 +38,11 @@ __device__ __forceinline__ V3 cross(V3 a, V3 b) {
 }
 __device__ __forceinline__ float length(V3 a) { return sqrtf(dot(a, a)); }
 __device__ __forceinline__ V3 normalize(V3 a) { return a * (1.0f / length(a)); }
+
+// The two colours every mode shares: what a segment that leaves the scene sees (process_wavefront_ray, wavefront.rs:146-151) and
+// what a hit with a material index out of range shows (lib.rs:307-309).
+__device__ __forceinline__ V3 RT_SKY() { return v3(0.1f, 0.2f, 0.3f); }
+__device__ __forceinline__ V3 RT_MAGENTA() { return v3(1.0f, 0.0f, 1.0f); }
 
 // IEEE half round trip, round-to-nearest-even (shader/src/lighting.rs:125-127)
 __device__ __forceinline__ float f16_round_trip(float v) {
@@ -442,7 +448,7 @@ __device__ __forceinline__ V3 shade_hit(const DevScene& sc, const Hit& hit, V3 o
     V3 point, normal;
     uint32_t material_id;
     hit_geometry(sc, hit, o, d, point, normal, material_id);
-    if (material_id >= sc.n_materials) return v3(1.0f, 0.0f, 1.0f); // magenta, lib.rs:307-309
+    if (material_id >= sc.n_materials) return RT_MAGENTA();
     const DevMaterial m = sc.materials[material_id];
     V3 lighting = calculate_lighting(sc, m, point, normal);
     float tf = fminf(fmaxf(m.transmission, 0.0f), 1.0f); // lib.rs:323
@@ -609,7 +615,12 @@ __device__ __forceinline__ V3 unit_vector(float u1, float u2) {
     return v3(r * cs, r * sn, z);
 }
 
-#define EXT_EPS 0.001f /* WavefrontRay::t_min (shared/src/lib.rs:854) as the origin offset */
+// ------------------------------------------------------------------------------------
+// The extended mode's path vertex, stated once for its three implementations: the queue pipeline
+// (wavefront.hip), the state-machine megakernel and the nested-loop megakernel (kernels.hip).  The tests hold the three to the same
+// bits and to the CPU statement, so every expression here, and the order of the rng draws, is part of the result.
+// ------------------------------------------------------------------------------------
+#define EXT_EPS 0.001f /* WavefrontRay::t_min (shared/src/lib.rs:854) as the origin offset of shadow and continuation segments */
 
 struct SegCounts {
     uint32_t camera, continuation, shadow;
@@ -621,6 +632,131 @@ __device__ __forceinline__ unsigned long long wave_sum(uint32_t v) {
     return s;
 }
 
+// The megakernels' epilogue.  Segment counts are part of the result (rt_stats.rays): one atomic per wave and counter.
+template <bool COUNT>
+__device__ __forceinline__ void flush_segment_counts(const DevTargets& tg, const SegCounts& seg, const Counts& cnt) {
+    unsigned long long c0 = wave_sum(seg.camera), c1 = wave_sum(seg.continuation), c2 = wave_sum(seg.shadow);
+    unsigned long long n0 = COUNT ? wave_sum(cnt.nodes) : 0ull, n1 = COUNT ? wave_sum(cnt.tris) : 0ull;
+    if (threadIdx.x == 0 && tg.counters) {
+        atomicAdd(&tg.counters[RT_CNT_SEGMENTS], c0 + c1 + c2);
+        atomicAdd(&tg.counters[RT_CNT_CAMERA], c0);
+        atomicAdd(&tg.counters[RT_CNT_CONTINUATION], c1);
+        atomicAdd(&tg.counters[RT_CNT_SHADOW], c2);
+        if (COUNT) {
+            atomicAdd(&tg.counters[RT_CNT_NODE_VISITS], n0);
+            atomicAdd(&tg.counters[RT_CNT_TRI_TESTS], n1);
+        }
+    }
+}
+
+// The camera ray of global sample `sample` (DevFrame::sample_base + k, or the pixel's own n + k in an adaptive call) of pixel (px, py):
+// the pixel's seed (lib.rs:103-105), two draws under `jitter`, else the pixel centre.  Returns the rng in the state the path continues
+// from; a caller that only wants the ray drops it, and the seed is then computed under `jitter` alone.
+__device__ __forceinline__ SimpleRng ext_sample_ray(const DevCamera& cam, uint32_t width, uint32_t frame_seed, uint32_t jitter, uint32_t px, uint32_t py,
+                                                    uint32_t sample, bool wavefront, V3& o, V3& d) {
+    SimpleRng rng = rng_for(frame_seed + px + py * width, sample);
+    float jx = 0.5f, jy = 0.5f;
+    if (jitter) {
+        jx = rng.next_f32();
+        jy = rng.next_f32();
+    }
+    camera_ray(cam, (float)px + jx, (float)py + jy, wavefront, o, d);
+    return rng;
+}
+
+// Step 2.  A light whose contribution is not zero is gated by a shadow segment.
+__device__ __forceinline__ bool needs_shadow_segment(V3 contrib) { return contrib.x != 0.0f || contrib.y != 0.0f || contrib.z != 0.0f; }
+// The ordered light sum: the 0.1 albedo ambient term at the terminal vertex only, the lights in index order (lighting.rs:33-43) with
+// the occluded ones skipped, emission last.  `visible(li, dir, dist)` is asked only about lights that need a segment, in that order.
+__device__ __forceinline__ V3 light_sum_begin(const DevMaterial& m, bool terminal) {
+    V3 total = v3(0.0f, 0.0f, 0.0f);
+    if (terminal) total = total + ld3(m.albedo) * 0.1f;
+    return total;
+}
+__device__ __forceinline__ V3 light_sum_end(V3 total, const DevMaterial& m) { return total + ld3(m.emission); }
+template <class Visible>
+__device__ __forceinline__ V3 ext_light_sum(const DevLight* lights, uint32_t n_lights, const DevMaterial& m, V3 point, V3 normal, bool terminal,
+                                            bool shadows, Visible visible) {
+    V3 total = light_sum_begin(m, terminal);
+    for (uint32_t li = 0; li < n_lights; li++) {
+        V3 sdir;
+        float sdist;
+        const V3 contrib = light_contribution(lights[li], m, point, normal, sdir, sdist);
+        if (needs_shadow_segment(contrib) && shadows && !visible(li, sdir, sdist)) continue;
+        total = total + contrib;
+    }
+    return light_sum_end(total, m);
+}
+
+// Step 3.  Leaving a vertex with its light sum: the terminal one adds the reference's calculate_shading (transmission mix included),
+// any other the part that is not transmitted.  Returns T = clamp(transmission, 0, 1), which the continuation draws against.
+__device__ __forceinline__ float ext_leave_vertex(const DevMaterial& m, V3 lighting, bool terminal, V3 throughput, V3& radiance) {
+    const float tf = fminf(fmaxf(m.transmission, 0.0f), 1.0f); // lib.rs:323
+    if (terminal) {
+        V3 out = lighting;
+        if (tf > 0.0f) out = transmission_mix(m, lighting, tf);
+        radiance = radiance + out * throughput;
+    } else {
+        radiance = radiance + (lighting * (1.0f - tf)) * throughput;
+    }
+    return tf;
+}
+
+// Steps 4 and 5.  The continuation from a non-terminal vertex at `point` (geometric normal `normal`, never flipped; `din` the incoming
+// direction; `depth` the vertex's index on the path).  Updates the rng, the hero channel (3: none yet) and the throughput, gives the
+// next segment, and returns false when the path is absorbed (rng, channel and throughput are then of no further use).
+// One exit with an `absorbed` flag, not early returns: with those k_wf_finish takes 89 VGPRs instead of 79 and loses a wave per SIMD.
+__device__ __forceinline__ bool ext_scatter(const DevMaterial& m, V3 point, V3 normal, V3 din, float tf, uint32_t depth, SimpleRng& rng,
+                                            uint32_t& channel, V3& throughput, V3& norigin, V3& ndir) {
+    const bool front = dot(normal, din) < 0.0f;
+    const V3 nf = front ? normal : -normal; // face-forwarded
+    bool transmit = false;
+    if (tf > 0.0f) transmit = rng.next_f32() < tf;
+    bool absorbed = false;
+    if (transmit) {
+        if (channel == 3) { // the hero channel, chosen once per path
+            const uint32_t c = (uint32_t)(rng.next_f32() * 3.0f);
+            channel = c < 2 ? c : 2;
+            throughput = v3(channel == 0 ? throughput.x * 3.0f : 0.0f, channel == 1 ? throughput.y * 3.0f : 0.0f,
+                            channel == 2 ? throughput.z * 3.0f : 0.0f);
+        }
+        const float offs = channel == 0 ? -0.018f : (channel == 1 ? 0.0f : 0.035f); // dispersion, material.rs:47-52
+        const float ior_c = m.ior + offs;
+        const float eta = front ? (1.0f / ior_c) : ior_c;
+        const float cos_i = -dot(nf, din);
+        const float sin2_t = eta * eta * (1.0f - cos_i * cos_i);
+        if (sin2_t > 1.0f) { // total internal reflection: stays on the incoming side
+            ndir = din - nf * (2.0f * dot(din, nf));
+            norigin = point + nf * EXT_EPS;
+        } else {
+            const float cos_t = sqrtf(1.0f - sin2_t);
+            ndir = din * eta + nf * (eta * cos_i - cos_t);
+            norigin = point - nf * EXT_EPS;
+        }
+        ndir = normalize(ndir);
+        throughput = throughput * ld3(m.albedo);
+    } else if (m.metallic > 0.5f) {
+        const float u1 = rng.next_f32(), u2 = rng.next_f32();
+        const V3 r = din - nf * (2.0f * dot(din, nf));
+        ndir = normalize(r + unit_vector(u1, u2) * m.roughness);
+        absorbed = !(dot(ndir, nf) > 0.0f); // a lobe direction below the surface
+        norigin = point + nf * EXT_EPS;
+        if (!absorbed) throughput = throughput * ld3(m.albedo);
+    } else {
+        const float u1 = rng.next_f32(), u2 = rng.next_f32();
+        V3 w = nf + unit_vector(u1, u2); // cosine-weighted
+        if (dot(w, w) < 1e-12f) w = nf;
+        ndir = normalize(w);
+        norigin = point + nf * EXT_EPS;
+        throughput = throughput * ld3(m.albedo);
+    }
+    if (!absorbed && depth >= 2) { // apply_russian_roulette (shared/src/lib.rs:969-978) from the third vertex on
+        const float p = fminf(fmaxf(fmaxf(fmaxf(throughput.x, throughput.y), throughput.z), 0.05f), 1.0f);
+        if (rng.next_f32() > p) absorbed = true;
+        else throughput = v3(throughput.x / p, throughput.y / p, throughput.z / p);
+    }
+    return !absorbed;
+}
 
 // Direction and length of the shadow segment toward light L from `point`: the same expressions
 // light_contribution evaluates (lighting.rs:103, 120-122), so both produce the same bits.

@@ -12,6 +12,10 @@
 // sphere quadratic) and the shading keep the reference's f32 operation order; the file
 // is compiled with -ffp-contract=off so nothing is fused implicitly.  The boxes of the
 // 8-wide tree are a conservative filter (device_common.h); culling by the closest hit.
+//
+// The two extended-mode megakernels here own their control flow only (nested loops; a per-lane
+// state machine).  What a path vertex does - sample ray, light sum, leaving the vertex, scatter,
+// roulette - is stated once in device_common.h (ext_*), which the queue pipeline calls too.
 #include "kernels.h"
 
 #include <algorithm>
@@ -48,7 +52,7 @@ __global__ __launch_bounds__(WAVE) void k_render_reference(DevScene sc, DevFrame
         camera_ray(fr.cam, (float)px.x + 0.5f, (float)px.y + 0.5f, wavefront, o, d);
         hit = find_closest<COUNT>(sc, o, d, stack, cnt);
         if (hit.prim != RT_PRIM_MISS) color = shade_hit(sc, hit, o, d);
-        else if (wavefront) color = v3(0.1f, 0.2f, 0.3f);
+        else if (wavefront) color = RT_SKY();
     }
     const size_t pix = (size_t)px.y * fr.width + px.x;
     if (tg.rgba32f) reinterpret_cast<float4*>(tg.rgba32f)[pix] = make_float4(color.x, color.y, color.z, 1.0f);
@@ -67,39 +71,21 @@ __global__ __launch_bounds__(WAVE) void k_render_reference(DevScene sc, DevFrame
 }
 
 
+// The nested loops' light sum: a light that needs a shadow segment gets it traced on the spot.
 template <bool COUNT>
-__device__ __forceinline__ V3 ext_direct(const DevScene& sc, const DevMaterial& m, V3 point, V3 normal, bool ambient, bool shadows,
+__device__ __forceinline__ V3 ext_direct(const DevScene& sc, const DevMaterial& m, V3 point, V3 normal, bool terminal, bool shadows,
                                          uint2* stack, Counts& cnt, SegCounts& seg) {
-    V3 total = v3(0.0f, 0.0f, 0.0f);
-    if (ambient) total = total + ld3(m.albedo) * 0.1f;
-    for (uint32_t li = 0; li < sc.n_lights; li++) {
-        V3 sdir;
-        float sdist;
-        V3 contrib = light_contribution(sc.lights[li], m, point, normal, sdir, sdist);
-        if (!(contrib.x != 0.0f || contrib.y != 0.0f || contrib.z != 0.0f)) {
-            total = total + contrib;
-            continue;
-        }
-        if (shadows) {
-            seg.shadow++;
-            if (occluded<COUNT>(sc, point + normal * EXT_EPS, sdir, RT_MIN_RAY_DISTANCE, sdist, stack, cnt)) continue;
-        }
-        total = total + contrib;
-    }
-    return total + ld3(m.emission);
+    return ext_light_sum(sc.lights, sc.n_lights, m, point, normal, terminal, shadows, [&](uint32_t, V3 sdir, float sdist) {
+        seg.shadow++;
+        return !occluded<COUNT>(sc, point + normal * EXT_EPS, sdir, RT_MIN_RAY_DISTANCE, sdist, stack, cnt);
+    });
 }
 
 template <bool COUNT>
 __device__ __forceinline__ V3 ext_trace_path(const DevScene& sc, const DevFrame& fr, uint32_t px, uint32_t py, uint32_t sample,
                                              uint2* stack, Counts& cnt, SegCounts& seg) {
-    SimpleRng rng = rng_for(fr.frame_seed + px + py * fr.width, sample); // sample: the global index (DevFrame::sample_base + k)
-    float jx = 0.5f, jy = 0.5f;
-    if (fr.jitter) {
-        jx = rng.next_f32();
-        jy = rng.next_f32();
-    }
     V3 o, d;
-    camera_ray(fr.cam, (float)px + jx, (float)py + jy, true, o, d);
+    SimpleRng rng = ext_sample_ray(fr.cam, fr.width, fr.frame_seed, fr.jitter, px, py, sample, true, o, d);
     V3 radiance = v3(0.0f, 0.0f, 0.0f);
     V3 throughput = v3(1.0f, 1.0f, 1.0f);
     uint32_t channel = 3;
@@ -108,76 +94,23 @@ __device__ __forceinline__ V3 ext_trace_path(const DevScene& sc, const DevFrame&
         if (depth == 0) seg.camera++; else seg.continuation++;
         Hit hit = find_closest<COUNT>(sc, o, d, stack, cnt);
         if (hit.prim == RT_PRIM_MISS) {
-            radiance = radiance + v3(0.1f, 0.2f, 0.3f) * throughput;
+            radiance = radiance + RT_SKY() * throughput;
             break;
         }
         V3 point, normal;
         uint32_t material_id;
         hit_geometry(sc, hit, o, d, point, normal, material_id);
         if (material_id >= sc.n_materials) {
-            radiance = radiance + v3(1.0f, 0.0f, 1.0f) * throughput;
+            radiance = radiance + RT_MAGENTA() * throughput;
             break;
         }
         const DevMaterial m = sc.materials[material_id];
-        float tf = fminf(fmaxf(m.transmission, 0.0f), 1.0f);
-        bool terminal = depth >= fr.max_bounce;
-        V3 lighting = ext_direct<COUNT>(sc, m, point, normal, terminal, shadows, stack, cnt, seg);
-        if (terminal) {
-            V3 out = lighting;
-            if (tf > 0.0f) out = transmission_mix(m, lighting, tf);
-            radiance = radiance + out * throughput;
-            break;
-        }
-        radiance = radiance + (lighting * (1.0f - tf)) * throughput;
-
-        bool front = dot(normal, d) < 0.0f;
-        V3 nf = front ? normal : -normal;
-        bool transmit = false;
-        if (tf > 0.0f) transmit = rng.next_f32() < tf;
-        V3 ndir, norigin;
-        V3 albedo = ld3(m.albedo);
-        if (transmit) {
-            if (channel == 3) {
-                uint32_t c = (uint32_t)(rng.next_f32() * 3.0f);
-                channel = c < 2 ? c : 2;
-                throughput = v3(channel == 0 ? throughput.x * 3.0f : 0.0f, channel == 1 ? throughput.y * 3.0f : 0.0f,
-                                channel == 2 ? throughput.z * 3.0f : 0.0f);
-            }
-            float offs = channel == 0 ? -0.018f : (channel == 1 ? 0.0f : 0.035f); // material.rs:47-52
-            float ior_c = m.ior + offs;
-            float eta = front ? (1.0f / ior_c) : ior_c;
-            float cos_i = -dot(nf, d);
-            float sin2_t = eta * eta * (1.0f - cos_i * cos_i);
-            if (sin2_t > 1.0f) {
-                ndir = d - nf * (2.0f * dot(d, nf));
-                norigin = point + nf * EXT_EPS;
-            } else {
-                float cos_t = sqrtf(1.0f - sin2_t);
-                ndir = d * eta + nf * (eta * cos_i - cos_t);
-                norigin = point - nf * EXT_EPS;
-            }
-            ndir = normalize(ndir);
-            throughput = throughput * albedo;
-        } else if (m.metallic > 0.5f) {
-            float u1 = rng.next_f32(), u2 = rng.next_f32();
-            V3 r = d - nf * (2.0f * dot(d, nf));
-            ndir = normalize(r + unit_vector(u1, u2) * m.roughness);
-            if (!(dot(ndir, nf) > 0.0f)) break;
-            norigin = point + nf * EXT_EPS;
-            throughput = throughput * albedo;
-        } else {
-            float u1 = rng.next_f32(), u2 = rng.next_f32();
-            V3 w = nf + unit_vector(u1, u2);
-            if (dot(w, w) < 1e-12f) w = nf;
-            ndir = normalize(w);
-            norigin = point + nf * EXT_EPS;
-            throughput = throughput * albedo;
-        }
-        if (depth >= 2) {
-            float p = fminf(fmaxf(fmaxf(fmaxf(throughput.x, throughput.y), throughput.z), 0.05f), 1.0f);
-            if (rng.next_f32() > p) break;
-            throughput = v3(throughput.x / p, throughput.y / p, throughput.z / p);
-        }
+        const bool terminal = depth >= fr.max_bounce;
+        const V3 lighting = ext_direct<COUNT>(sc, m, point, normal, terminal, shadows, stack, cnt, seg);
+        const float tf = ext_leave_vertex(m, lighting, terminal, throughput, radiance);
+        if (terminal) break;
+        V3 norigin, ndir;
+        if (!ext_scatter(m, point, normal, d, tf, depth, rng, channel, throughput, norigin, ndir)) break;
         o = norigin;
         d = ndir;
     }
@@ -211,19 +144,7 @@ __global__ __launch_bounds__(WAVE) void k_render_extended(DevScene sc, DevFrame 
         run_sum_keep(tg, pix, sum);
         store_image(tg, pix, sum, (float)fr.n_total);
     }
-    // segment counts are part of the result (rt_stats.rays): one atomic per wave and counter
-    unsigned long long c0 = wave_sum(seg.camera), c1 = wave_sum(seg.continuation), c2 = wave_sum(seg.shadow);
-    unsigned long long n0 = COUNT ? wave_sum(cnt.nodes) : 0ull, n1 = COUNT ? wave_sum(cnt.tris) : 0ull;
-    if (threadIdx.x == 0 && tg.counters) {
-        atomicAdd(&tg.counters[RT_CNT_SEGMENTS], c0 + c1 + c2);
-        atomicAdd(&tg.counters[RT_CNT_CAMERA], c0);
-        atomicAdd(&tg.counters[RT_CNT_CONTINUATION], c1);
-        atomicAdd(&tg.counters[RT_CNT_SHADOW], c2);
-        if (COUNT) {
-            atomicAdd(&tg.counters[RT_CNT_NODE_VISITS], n0);
-            atomicAdd(&tg.counters[RT_CNT_TRI_TESTS], n1);
-        }
-    }
+    flush_segment_counts<COUNT>(tg, seg, cnt);
 }
 
 
@@ -339,14 +260,8 @@ __global__ __launch_bounds__(WAVE, RT_SM_MIN_WAVES) void k_render_extended_sm(De
                     state = ST_DONE;
                     break;
                 }
-                rng = rng_for(fr.frame_seed + px.x + px.y * fr.width, (AD ? base : fr.sample_base) + sample);
-                float jx = 0.5f, jy = 0.5f;
-                if (fr.jitter) {
-                    jx = rng.next_f32();
-                    jy = rng.next_f32();
-                }
                 V3 co, cd;
-                camera_ray(fr.cam, (float)px.x + jx, (float)px.y + jy, true, co, cd);
+                rng = ext_sample_ray(fr.cam, fr.width, fr.frame_seed, fr.jitter, px.x, px.y, (AD ? base : fr.sample_base) + sample, true, co, cd);
                 radiance = v3(0.0f, 0.0f, 0.0f);
                 throughput = v3(1.0f, 1.0f, 1.0f);
                 channel = 3;
@@ -358,18 +273,17 @@ __global__ __launch_bounds__(WAVE, RT_SM_MIN_WAVES) void k_render_extended_sm(De
             bool end_sample = false;
             if (state == ST_CLOSEST_DONE) {
                 if (hit.prim == RT_PRIM_MISS) {
-                    radiance = radiance + v3(0.1f, 0.2f, 0.3f) * throughput;
+                    radiance = radiance + RT_SKY() * throughput;
                     end_sample = true;
                 } else {
                     hit_geometry(sc, hit, o, d, point, normal, material_id);
                     din = d;
                     if (material_id >= sc.n_materials) {
-                        radiance = radiance + v3(1.0f, 0.0f, 1.0f) * throughput;
+                        radiance = radiance + RT_MAGENTA() * throughput;
                         end_sample = true;
                     } else {
                         terminal = depth >= fr.max_bounce;
-                        lighting = v3(0.0f, 0.0f, 0.0f);
-                        if (terminal) lighting = lighting + ld3(sc.materials[material_id].albedo) * 0.1f;
+                        lighting = light_sum_begin(sc.materials[material_id], terminal);
                         li = 0;
                         state = ST_LIGHTS;
                     }
@@ -386,7 +300,7 @@ __global__ __launch_bounds__(WAVE, RT_SM_MIN_WAVES) void k_render_extended_sm(De
                     V3 sdir;
                     float sdist;
                     V3 contrib = light_contribution(sc.lights[li], m, point, normal, sdir, sdist);
-                    if ((contrib.x != 0.0f || contrib.y != 0.0f || contrib.z != 0.0f) && shadows) {
+                    if (needs_shadow_segment(contrib) && shadows) {
                         pending = contrib;
                         seg.shadow++;
                         launched = true;
@@ -398,71 +312,15 @@ __global__ __launch_bounds__(WAVE, RT_SM_MIN_WAVES) void k_render_extended_sm(De
                 }
                 if (launched) continue;
                 // ---- all lights done: finish the vertex ----
-                lighting = lighting + ld3(m.emission);
-                float tf = fminf(fmaxf(m.transmission, 0.0f), 1.0f);
-                if (terminal) {
-                    V3 out = lighting;
-                    if (tf > 0.0f) out = transmission_mix(m, lighting, tf);
-                    radiance = radiance + out * throughput;
+                lighting = light_sum_end(lighting, m);
+                const float tf = ext_leave_vertex(m, lighting, terminal, throughput, radiance);
+                V3 norigin, ndir;
+                if (terminal || !ext_scatter(m, point, normal, din, tf, depth, rng, channel, throughput, norigin, ndir)) {
                     end_sample = true;
                 } else {
-                    radiance = radiance + (lighting * (1.0f - tf)) * throughput;
-                    bool front = dot(normal, din) < 0.0f;
-                    V3 nf = front ? normal : -normal;
-                    bool transmit = false;
-                    if (tf > 0.0f) transmit = rng.next_f32() < tf;
-                    V3 ndir, norigin;
-                    V3 albedo = ld3(m.albedo);
-                    bool absorbed = false;
-                    if (transmit) {
-                        if (channel == 3) {
-                            uint32_t c = (uint32_t)(rng.next_f32() * 3.0f);
-                            channel = c < 2 ? c : 2;
-                            throughput = v3(channel == 0 ? throughput.x * 3.0f : 0.0f, channel == 1 ? throughput.y * 3.0f : 0.0f,
-                                            channel == 2 ? throughput.z * 3.0f : 0.0f);
-                        }
-                        float offs = channel == 0 ? -0.018f : (channel == 1 ? 0.0f : 0.035f);
-                        float ior_c = m.ior + offs;
-                        float eta = front ? (1.0f / ior_c) : ior_c;
-                        float cos_i = -dot(nf, din);
-                        float sin2_t = eta * eta * (1.0f - cos_i * cos_i);
-                        if (sin2_t > 1.0f) {
-                            ndir = din - nf * (2.0f * dot(din, nf));
-                            norigin = point + nf * EXT_EPS;
-                        } else {
-                            float cos_t = sqrtf(1.0f - sin2_t);
-                            ndir = din * eta + nf * (eta * cos_i - cos_t);
-                            norigin = point - nf * EXT_EPS;
-                        }
-                        ndir = normalize(ndir);
-                        throughput = throughput * albedo;
-                    } else if (m.metallic > 0.5f) {
-                        float u1 = rng.next_f32(), u2 = rng.next_f32();
-                        V3 r = din - nf * (2.0f * dot(din, nf));
-                        ndir = normalize(r + unit_vector(u1, u2) * m.roughness);
-                        absorbed = !(dot(ndir, nf) > 0.0f);
-                        norigin = point + nf * EXT_EPS;
-                        if (!absorbed) throughput = throughput * albedo;
-                    } else {
-                        float u1 = rng.next_f32(), u2 = rng.next_f32();
-                        V3 w = nf + unit_vector(u1, u2);
-                        if (dot(w, w) < 1e-12f) w = nf;
-                        ndir = normalize(w);
-                        norigin = point + nf * EXT_EPS;
-                        throughput = throughput * albedo;
-                    }
-                    if (!absorbed && depth >= 2) {
-                        float p = fminf(fmaxf(fmaxf(fmaxf(throughput.x, throughput.y), throughput.z), 0.05f), 1.0f);
-                        if (rng.next_f32() > p) absorbed = true;
-                        else throughput = v3(throughput.x / p, throughput.y / p, throughput.z / p);
-                    }
-                    if (absorbed) {
-                        end_sample = true;
-                    } else {
-                        depth++;
-                        seg.continuation++;
-                        begin_segment(norigin, ndir, RT_F32_MAX, false);
-                    }
+                    depth++;
+                    seg.continuation++;
+                    begin_segment(norigin, ndir, RT_F32_MAX, false);
                 }
             }
             if (end_sample) {
@@ -553,25 +411,16 @@ __global__ __launch_bounds__(WAVE, RT_SM_MIN_WAVES) void k_render_extended_sm(De
         }
         if (COUNT) dg_cv += __builtin_readcyclecounter() - t_begin;
     }
-    unsigned long long c0 = wave_sum(seg.camera), c1 = wave_sum(seg.continuation), c2 = wave_sum(seg.shadow);
-    unsigned long long n0 = COUNT ? wave_sum(cnt.nodes) : 0ull, n1 = COUNT ? wave_sum(cnt.tris) : 0ull;
-    if (threadIdx.x == 0 && tg.counters) {
-        atomicAdd(&tg.counters[RT_CNT_SEGMENTS], c0 + c1 + c2);
-        atomicAdd(&tg.counters[RT_CNT_CAMERA], c0);
-        atomicAdd(&tg.counters[RT_CNT_CONTINUATION], c1);
-        atomicAdd(&tg.counters[RT_CNT_SHADOW], c2);
-        if (COUNT) {
-            atomicAdd(&tg.counters[RT_CNT_NODE_VISITS], n0);
-            atomicAdd(&tg.counters[RT_CNT_TRI_TESTS], n1);
-            atomicAdd(&tg.counters[RT_CNT_SM_TRANSITION_PASSES], dg_tp);
-            atomicAdd(&tg.counters[RT_CNT_SM_TRANSITION_LANES], dg_tl);
-            atomicAdd(&tg.counters[RT_CNT_SM_NODE_ITERS], dg_ni);
-            atomicAdd(&tg.counters[RT_CNT_SM_NODE_LANES], dg_nl);
-            atomicAdd(&tg.counters[RT_CNT_SM_LEAF_ITERS], dg_li);
-            atomicAdd(&tg.counters[RT_CNT_SM_LEAF_LANES], dg_ll);
-            atomicAdd(&tg.counters[RT_CNT_SM_CYCLES_TRANSITION], dg_ct);
-            atomicAdd(&tg.counters[RT_CNT_SM_CYCLES_TRAVERSAL], dg_cv);
-        }
+    flush_segment_counts<COUNT>(tg, seg, cnt);
+    if (COUNT && threadIdx.x == 0 && tg.counters) {
+        atomicAdd(&tg.counters[RT_CNT_SM_TRANSITION_PASSES], dg_tp);
+        atomicAdd(&tg.counters[RT_CNT_SM_TRANSITION_LANES], dg_tl);
+        atomicAdd(&tg.counters[RT_CNT_SM_NODE_ITERS], dg_ni);
+        atomicAdd(&tg.counters[RT_CNT_SM_NODE_LANES], dg_nl);
+        atomicAdd(&tg.counters[RT_CNT_SM_LEAF_ITERS], dg_li);
+        atomicAdd(&tg.counters[RT_CNT_SM_LEAF_LANES], dg_ll);
+        atomicAdd(&tg.counters[RT_CNT_SM_CYCLES_TRANSITION], dg_ct);
+        atomicAdd(&tg.counters[RT_CNT_SM_CYCLES_TRAVERSAL], dg_cv);
     }
 }
 

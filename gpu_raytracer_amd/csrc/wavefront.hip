@@ -156,14 +156,8 @@ __global__ __launch_bounds__(256) void k_wf_generate(DevFrame fr, rt::WfBuffers 
         }
         const uint32_t p = sb * WAVE + lane;
         if (px.valid) {
-            SimpleRng rng = rng_for(fr.frame_seed + px.x + px.y * fr.width, base + first_sample + k);
-            float jx = 0.5f, jy = 0.5f;
-            if (fr.jitter) {
-                jx = rng.next_f32();
-                jy = rng.next_f32();
-            }
             V3 o, d;
-            camera_ray(fr.cam, (float)px.x + jx, (float)px.y + jy, true, o, d);
+            const SimpleRng rng = ext_sample_ray(fr.cam, fr.width, fr.frame_seed, fr.jitter, px.x, px.y, base + first_sample + k, true, o, d);
             wb.ray_o[p] = make_float4(o.x, o.y, o.z, 0.0f);
             wb.ray_d[p] = make_float4(d.x, d.y, d.z, __uint_as_float(p)); // w: the origin slot, where the path's sample_rad goes
             wb.thr[p] = make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(3u)); // channel 3 (none), depth 0
@@ -1097,13 +1091,13 @@ __global__ __launch_bounds__(256, RT_WF_SHADE_WAVES) void k_wf_shade(DevScene sc
             asm volatile("" : "+v"(h.x), "+v"(h.y), "+v"(h.z), "+v"(h.w));
             // throughput / radiance / origin are only read where a path ends here (a quarter of this stage's read traffic otherwise)
             if (h.w == RT_PRIM_MISS) { // process_wavefront_ray, wavefront.rs:146-151
-                const V3 radiance = f4v(wb.rad[id]) + v3(0.1f, 0.2f, 0.3f) * f4v(wb.thr[id]);
+                const V3 radiance = f4v(wb.rad[id]) + RT_SKY() * f4v(wb.thr[id]);
                 wf_end_path(wb, wf_origin(wb, id), radiance);
             } else {
                 point = v3(__uint_as_float(h.x), __uint_as_float(h.y), __uint_as_float(h.z));
                 surface_at(sc, (h.w & RT_PRIM_SPHERE_FLAG) != 0, h.w & ~RT_PRIM_SPHERE_FLAG, point, normal, material_id);
                 if (material_id >= sc.n_materials) {
-                    const V3 radiance = f4v(wb.rad[id]) + v3(1.0f, 0.0f, 1.0f) * f4v(wb.thr[id]);
+                    const V3 radiance = f4v(wb.rad[id]) + RT_MAGENTA() * f4v(wb.thr[id]);
                     wf_end_path(wb, wf_origin(wb, id), radiance);
                 } else {
                     vertex = true;
@@ -1123,7 +1117,7 @@ __global__ __launch_bounds__(256, RT_WF_SHADE_WAVES) void k_wf_shade(DevScene sc
                     V3 sdir;
                     float sdist;
                     const V3 contrib = light_contribution(s_lights[li], m, point, normal, sdir, sdist);
-                    if (contrib.x != 0.0f || contrib.y != 0.0f || contrib.z != 0.0f) mask |= 1u << li;
+                    if (needs_shadow_segment(contrib)) mask |= 1u << li;
                 }
             }
             // the visibility word of the vertex record starts as this mask; the shadow stage clears the bits of occluded segments
@@ -1234,83 +1228,16 @@ __global__ __launch_bounds__(256, RT_WF_SHADE_WAVES) void k_wf_finish(DevScene s
             const uint32_t depth = tw >> 8;
             SimpleRng rng = {__float_as_uint(ra.w)};
             const bool terminal = depth >= fr.max_bounce;
-            // direct light: the reference's loop order (lighting.rs:33-43), occluded lights skipped
-            V3 lighting = v3(0.0f, 0.0f, 0.0f);
-            if (terminal) lighting = lighting + ld3(m.albedo) * 0.1f;
-            for (uint32_t li = 0; li < sc.n_lights; li++) {
-                V3 sdir;
-                float sdist;
-                const V3 contrib = light_contribution(s_lights[li], m, point, normal, sdir, sdist);
-                const bool nonzero = contrib.x != 0.0f || contrib.y != 0.0f || contrib.z != 0.0f;
-                if (nonzero && shadows && !((vis >> li) & 1u)) continue;
-                lighting = lighting + contrib;
-            }
-            lighting = lighting + ld3(m.emission);
-            const float tf = fminf(fmaxf(m.transmission, 0.0f), 1.0f);
-            if (terminal) {
-                V3 out = lighting;
-                if (tf > 0.0f) out = transmission_mix(m, lighting, tf);
-                radiance = radiance + out * throughput;
+            // the shadow stage has answered every light that needed a segment: its bit of `vis` is still set if nothing is in the way
+            const V3 lighting = ext_light_sum(s_lights, sc.n_lights, m, point, normal, terminal, shadows, [&](uint32_t li, V3, float) { return ((vis >> li) & 1u) != 0u; });
+            const float tf = ext_leave_vertex(m, lighting, terminal, throughput, radiance);
+            if (terminal || !ext_scatter(m, point, normal, f4v(rdin), tf, depth, rng, channel, throughput, norigin, ndir)) {
                 wf_end_path(wb, origin, radiance);
             } else {
-                radiance = radiance + (lighting * (1.0f - tf)) * throughput;
-                const V3 din = f4v(rdin);
-                const bool front = dot(normal, din) < 0.0f;
-                const V3 nf = front ? normal : -normal;
-                bool transmit = false;
-                if (tf > 0.0f) transmit = rng.next_f32() < tf;
-                const V3 albedo = ld3(m.albedo);
-                bool absorbed = false;
-                if (transmit) {
-                    if (channel == 3) {
-                        uint32_t c = (uint32_t)(rng.next_f32() * 3.0f);
-                        channel = c < 2 ? c : 2;
-                        throughput = v3(channel == 0 ? throughput.x * 3.0f : 0.0f, channel == 1 ? throughput.y * 3.0f : 0.0f,
-                                        channel == 2 ? throughput.z * 3.0f : 0.0f);
-                    }
-                    const float offs = channel == 0 ? -0.018f : (channel == 1 ? 0.0f : 0.035f);
-                    const float ior_c = m.ior + offs;
-                    const float eta = front ? (1.0f / ior_c) : ior_c;
-                    const float cos_i = -dot(nf, din);
-                    const float sin2_t = eta * eta * (1.0f - cos_i * cos_i);
-                    if (sin2_t > 1.0f) {
-                        ndir = din - nf * (2.0f * dot(din, nf));
-                        norigin = point + nf * EXT_EPS;
-                    } else {
-                        const float cos_t = sqrtf(1.0f - sin2_t);
-                        ndir = din * eta + nf * (eta * cos_i - cos_t);
-                        norigin = point - nf * EXT_EPS;
-                    }
-                    ndir = normalize(ndir);
-                    throughput = throughput * albedo;
-                } else if (m.metallic > 0.5f) {
-                    const float u1 = rng.next_f32(), u2 = rng.next_f32();
-                    const V3 r = din - nf * (2.0f * dot(din, nf));
-                    ndir = normalize(r + unit_vector(u1, u2) * m.roughness);
-                    absorbed = !(dot(ndir, nf) > 0.0f);
-                    norigin = point + nf * EXT_EPS;
-                    if (!absorbed) throughput = throughput * albedo;
-                } else {
-                    const float u1 = rng.next_f32(), u2 = rng.next_f32();
-                    V3 w = nf + unit_vector(u1, u2);
-                    if (dot(w, w) < 1e-12f) w = nf;
-                    ndir = normalize(w);
-                    norigin = point + nf * EXT_EPS;
-                    throughput = throughput * albedo;
-                }
-                if (!absorbed && depth >= 2) {
-                    const float p = fminf(fmaxf(fmaxf(fmaxf(throughput.x, throughput.y), throughput.z), 0.05f), 1.0f);
-                    if (rng.next_f32() > p) absorbed = true;
-                    else throughput = v3(throughput.x / p, throughput.y / p, throughput.z / p);
-                }
-                if (absorbed) {
-                    wf_end_path(wb, origin, radiance);
-                } else {
-                    cont = true;
-                    next_tw = channel | ((depth + 1u) << 8);
-                    rng_seed = rng.seed;
-                    ndir_origin = origin;
-                }
+                cont = true;
+                next_tw = channel | ((depth + 1u) << 8);
+                rng_seed = rng.seed;
+                ndir_origin = origin;
             }
         }
         // a continuing path moves to the slot it reserves in the next queue: from there on its id IS its queue position, and the next
