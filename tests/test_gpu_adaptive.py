@@ -4,6 +4,7 @@ same call sequence gives the same bits and counts on every kernel path, with and
 device listed twice and small batches; the running image starts, continues and ends when rt_hip.h says it does, and bad arguments
 change nothing."""
 import ctypes as C
+import dataclasses
 import os
 import re
 import subprocess
@@ -11,7 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from gpu_raytracer_amd import scenes
+from gpu_raytracer_amd import hostpack, scenes
 from gpu_raytracer_amd import types as T
 
 pytestmark = pytest.mark.gpu
@@ -237,6 +238,136 @@ def test_small_batches_on_sponza_like(rt_api, monkeypatch):
     for n in sorted(set(counts.ravel().tolist())):
         want, _ = _frame(rt_api, scene, n, B, w=w, h=h)
         _assert_equal(i0[0][counts == n], want[0][counts == n], f"{n} samples")
+
+
+# 4b: more than 1024 pixel blocks ---------------------------------------------------------------------------------------------------
+# k_ad_compact lists the live blocks in one workgroup of 1024 threads, 1024 block masks at a time, and carries the number listed so far
+# and the pixel count from one 1024 to the next; the host sizes the call's pipeline from what it returns.
+CHUNK = 1024   # block masks per pass of the compaction (adaptive.hip: AD_COMPACT_THREADS)
+BIG_TILE = 32
+
+
+def _block_table(active, w, h, tile, world=1, rank=0):
+    """Per owned 8x8 block, in the library's block order, (pixels inside the image, pixels of `active`) as an (n_blocks, 2) array.
+    The order, from rt_hip.h and DESIGN.md: a context owns the tiles whose row-major index % tile_world == tile_rank, in that order
+    (rt_render_params::tile_rank); one wave per 8x8 block of an owned tile, (ceil(tile_size / 8))^2 per tile whether inside the image
+    or not, row by row within the tile ('Adaptive sampling': 'in block order')."""
+    tx, ty, per_side = (w + tile - 1) // tile, (h + tile - 1) // tile, (tile + 7) // 8
+    rows = []
+    for t in range(rank, tx * ty, world):
+        oy, ox = (t // tx) * tile, (t % tx) * tile
+        for by in range(per_side):
+            for bx in range(per_side):
+                y0, x0 = oy + 8 * by, ox + 8 * bx
+                y1, x1 = min(y0 + 8, oy + tile, h), min(x0 + 8, ox + tile, w)
+                inside = max(0, y1 - y0) * max(0, x1 - x0)
+                rows.append((inside, int(active[y0:y1, x0:x1].sum()) if inside else 0))
+    return np.array(rows, np.int64)
+
+
+def _checked_sequence(rt_api, scene, w, h, t, bounces=2, **kw):
+    """The standard sequence with everything test_stopped_pixels_hold_their_closed_frame_and_the_rule_holds asserts per call; returns
+    the per-call stats, the records before the last call, the final records and images."""
+    total, camera_segments, prev, before_last, stats = 0, 0, None, None, []
+    with rt_api.Context() as ctx:
+        ctx.upload_scene(scene)
+        for i, n in enumerate(SEQ):
+            st = ctx.render_adaptive(w, h, scene.camera, n, t, min_samples=MIN, max_bounces=bounces, restart=i == 0, tile_size=BIG_TILE, **kw)
+            stats.append(st)
+            total += n
+            assert ctx.accumulated_samples() == total
+            rec = ctx.read_adaptive()
+            rgb, comb = _images(ctx)
+            grew = rec[..., 3] > (prev[..., 3] if prev is not None else 0)
+            if prev is not None:
+                np.testing.assert_array_equal(grew, np_active(prev, t, MIN), err_msg=f"call {i}: active set")
+                assert np.array_equal(rec[..., 3][~grew], prev[..., 3][~grew])
+                _assert_equal(rec[~grew], prev[~grew], f"call {i}: stopped pixels keep their sums")
+            np.testing.assert_array_equal(rec[..., 3][grew], (prev[..., 3][grew] if prev is not None else 0) + n)
+            assert st["primary_rays"] == int(grew.sum()) * n and st["pixels"] == int(grew.sum())
+            camera_segments += st["primary_rays"]
+            _assert_equal(rec[..., 7], np_error(rec), f"call {i}: the error")
+            _assert_equal(rgb, rec[..., 0:3] / rec[..., 3:4], f"call {i}: the image is S / n")
+            before_last, prev = prev, rec
+        assert camera_segments == int(rec[..., 3].sum())
+    return stats, before_last, rec, (rgb, comb)
+
+
+def test_more_than_1024_blocks_live_and_stopped_on_both_sides(rt_api, monkeypatch):
+    """328 x 264 at tile 32: 11 x 9 tiles of 16 blocks = 1584 owned blocks, the last column and row of tiles partly outside the image;
+    the last call's selection has live and fully stopped blocks below and above block 1024, so the list is written across the pass
+    boundary with a non-zero carry."""
+    monkeypatch.delenv("RT_WF_BATCH", raising=False)
+    scene, w, h, bounces = scenes.cornell12(), 328, 264, 2
+    t = _threshold(rt_api, scene, q=0.6, bounces=bounces, w=w, h=h, tile_size=BIG_TILE)
+    stats, before_last, rec, images = _checked_sequence(rt_api, scene, w, h, t, bounces)
+    table = _block_table(np_active(before_last, t, MIN), w, h, BIG_TILE)
+    assert len(table) == 11 * 9 * 16 == 1584 and int(table[:, 0].sum()) == w * h and int(table[:, 1].sum()) == stats[-1]["pixels"]
+    assert (table[:, 0] == 0).any()  # blocks outside the image are listed among the owned ones
+    for side, part in (("below", table[:CHUNK]), ("above", table[CHUNK:])):
+        live, stopped = int((part[:, 1] > 0).sum()), int(((part[:, 0] > 0) & (part[:, 1] == 0)).sum())
+        print(f"blocks {side} {CHUNK}: {live} live, {stopped} fully stopped, {int((part[:, 0] == 0).sum())} outside the image")
+        assert live > 0 and stopped > 0, side
+    counts = _check_identity(rt_api, scene, rec, images, bounces=bounces, w=w, h=h, tile_size=BIG_TILE)
+    assert counts.min() == MIN and counts.max() == sum(SEQ)
+    # the same records and totals over tile shares of 2, united, and on the state-machine megakernel
+    base = _totals(stats)
+    got_rec, rgb, tot = np.zeros_like(rec), np.zeros_like(images[0]), np.zeros(4, np.int64)
+    for rank in range(2):
+        with rt_api.Context() as ctx:
+            ctx.upload_scene(scene)
+            s, r, img = _run(ctx, scene, SEQ, [t] * len(SEQ), bounces=bounces, w=w, h=h, tile_size=BIG_TILE, tile_world=2, tile_rank=rank)
+        m = _owned(w, h, BIG_TILE, 2, rank)
+        assert not r[~m].any()
+        got_rec[m], rgb[m] = r[m], img[0][m]
+        tot += np.array(_totals(s))
+    _assert_equal(got_rec, rec, "tile shares of 2")
+    _assert_equal(rgb, images[0], "tile shares of 2")
+    assert tuple(tot.tolist()) == base
+    with rt_api.Context() as ctx:
+        ctx.upload_scene(scene)
+        s, r, img = _run(ctx, scene, SEQ, [t] * len(SEQ), bounces=bounces, w=w, h=h, tile_size=BIG_TILE, kernel_sm=True)
+    _assert_equal(r, rec, "kernel_sm")
+    _assert_equal(img[0], images[0], "kernel_sm")
+    np.testing.assert_array_equal(img[1], images[1], err_msg="kernel_sm")
+    assert _totals(s) == base
+    assert [x["pixels"] for x in s] == [x["pixels"] for x in stats]
+
+
+def test_exactly_1024_blocks(rt_api, monkeypatch):
+    """256 x 256 at tile 32: 64 tiles of 16 blocks, one full pass of the compaction and no second."""
+    monkeypatch.delenv("RT_WF_BATCH", raising=False)
+    scene, w, h, bounces = scenes.cornell12(), 256, 256, 2
+    t = _threshold(rt_api, scene, q=0.6, bounces=bounces, w=w, h=h, tile_size=BIG_TILE)
+    stats, before_last, rec, images = _checked_sequence(rt_api, scene, w, h, t, bounces)
+    table = _block_table(np_active(before_last, t, MIN), w, h, BIG_TILE)
+    assert len(table) == CHUNK and (table[:, 0] == 64).all()
+    live = int((table[:, 1] > 0).sum())
+    print(f"{live} of {CHUNK} blocks live in the last call")
+    assert live > 0 and stats[-1]["pixels"] == int(table[:, 1].sum())
+    _check_identity(rt_api, scene, rec, images, bounces=bounces, w=w, h=h, tile_size=BIG_TILE)
+
+
+def test_second_pass_with_nothing_to_list(rt_api, monkeypatch):
+    """256 x 264 at tile 32: 8 x 9 tiles = 1152 blocks.  Blocks 1024 .. 1151 are the last row of tiles, of which only the first block
+    row is inside the image; the camera is pitched down by 30 degrees, so those rows see past the box's floor into the sky, whose
+    samples are all equal: once they have min_samples they are fully stopped, and the second pass of the compaction adds nothing to a
+    list the first has filled."""
+    monkeypatch.delenv("RT_WF_BATCH", raising=False)
+    base = scenes.cornell12()
+    cam = hostpack.camera((0.0, 0.0, 3.4), (0.0, -0.5, -np.sqrt(0.75)), (0.0, 1.0, 0.0), 45.0)
+    scene = dataclasses.replace(base, camera=cam)
+    w, h, bounces = 256, 264, 2
+    t = _threshold(rt_api, scene, q=0.6, bounces=bounces, w=w, h=h, tile_size=BIG_TILE)
+    assert t > 0
+    stats, before_last, rec, images = _checked_sequence(rt_api, scene, w, h, t, bounces)
+    table = _block_table(np_active(before_last, t, MIN), w, h, BIG_TILE)
+    assert len(table) == 8 * 9 * 16 == 1152
+    assert (table[CHUNK:, 1] == 0).all() and (table[CHUNK:, 0] > 0).any() and (table[CHUNK:, 0] == 0).any()
+    assert (table[:CHUNK, 1] > 0).any()
+    assert stats[-1]["pixels"] == int(table[:CHUNK, 1].sum()) > 0
+    assert stats[0]["pixels"] == w * h  # the first calls sample every pixel: both passes list blocks there
+    _check_identity(rt_api, scene, rec, images, bounces=bounces, w=w, h=h, tile_size=BIG_TILE)
 
 
 # 5 ------------------------------------------------------------------------------------------------------------------------------

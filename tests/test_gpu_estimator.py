@@ -20,7 +20,7 @@ def _furnace(b):
     return (lambda: ec.furnace(b, w, h)), spp, ec.check_furnace
 
 
-CASES = {f"furnace_b{b}": _furnace(b) for b in range(9)}
+CASES = {f"furnace_b{b}": _furnace(b) for b in FURNACE_SPP}
 CASES.update({f"sky_{k}": ((lambda k=k: ec.sky_wall(k)), SKY_WALL_SPP, ec.check_sky_wall) for k in ec.WALL_LAYOUTS})
 CASES.update({f"glass_T{t}": ((lambda t=t: ec.glass_over_black_floor(t)), GLASS_SPP, ec.check_glass_black) for t in (0.25, 1.0)})
 CASES.update({"glass_hero": (ec.glass_over_emissive_floor, GLASS_SPP, ec.check_hero), "glass_slab": (ec.glass_slab, GLASS_SPP, ec.check_hero),
