@@ -1,12 +1,12 @@
 // bvh_builder.cpp — binned-SAH binary build (host, multi-threaded) collapsed into the 8-wide quantised layout, see bvh_builder.h.
 #include "bvh_builder.h"
+#include "bvh_rules.h"
 
 #include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <future>
 #include <limits>
 #include <numeric>
@@ -15,33 +15,6 @@
 
 namespace rt {
 namespace {
-
-struct Box {
-    float mn[3], mx[3];
-    void reset() {
-        for (int a = 0; a < 3; a++) {
-            mn[a] = std::numeric_limits<float>::infinity();
-            mx[a] = -std::numeric_limits<float>::infinity();
-        }
-    }
-    void grow(const Box& b) {
-        for (int a = 0; a < 3; a++) {
-            mn[a] = std::min(mn[a], b.mn[a]);
-            mx[a] = std::max(mx[a], b.mx[a]);
-        }
-    }
-    void grow(const float p[3]) {
-        for (int a = 0; a < 3; a++) {
-            mn[a] = std::min(mn[a], p[a]);
-            mx[a] = std::max(mx[a], p[a]);
-        }
-    }
-    float half_area() const {
-        float dx = mx[0] - mn[0], dy = mx[1] - mn[1], dz = mx[2] - mn[2];
-        if (!(dx >= 0.0f) || !(dy >= 0.0f) || !(dz >= 0.0f)) return 0.0f;
-        return dx * dy + dy * dz + dz * dx;
-    }
-};
 
 struct TmpNode {
     Box box;
@@ -333,44 +306,15 @@ static uint32_t reinsertion_optimize(std::vector<TmpNode>& nodes, uint32_t n_nod
 }
 #endif
 
-void put_tri(const BuildTri& t, DevTri* o) {
-    for (int a = 0; a < 3; a++) {
-        o->v0[a] = t.v0[a];
-        o->e1[a] = t.v1[a] - t.v0[a]; // shader/src/intersection.rs:104
-        o->e2[a] = t.v2[a] - t.v0[a]; // :105
-    }
-    o->material_id = t.material_id;
-    o->prim_id = t.prim_id;
-    o->leaf_count = 0;
-}
-
-// ---- PLOC (Meister, Bittner, "Parallel Locally-Ordered Clustering for Bounding Volume Hierarchy Construction", 2018): sort the
-// triangles along a Morton curve, then repeatedly merge every pair of clusters that are each other's nearest neighbour (by the
-// area of the union) within `radius` positions of the curve.  This host version is the executable statement of what the device
-// build does (csrc/device_build.hip); it fills `nodes` (leaves first: node i = the i-th triangle in Morton order) and returns the root.
-uint64_t morton21(float x) { // x in [0, 1]: 21 bits spread to every third bit (same expression in device_build.hip)
-    uint64_t v = (uint64_t)(uint32_t)std::min(std::max(x * 2097152.0f, 0.0f), 2097151.0f);
-    v = (v | v << 32) & 0x1f00000000ffffull;
-    v = (v | v << 16) & 0x1f0000ff0000ffull;
-    v = (v | v << 8) & 0x100f00f00f00f00full;
-    v = (v | v << 4) & 0x10c30c30c30c30c3ull;
-    v = (v | v << 2) & 0x1249249249249249ull;
-    return v;
-}
-
+// ---- PLOC on the host (bvh_rules.h rules 2 and 4, the rounds in sequence): what the device build (csrc/device_build.hip) does in
+// kernels.  It fills `nodes` (leaves first: node i = the i-th triangle in Morton order) and returns the root.
 uint32_t build_ploc(const std::vector<Box>& boxes, const std::vector<float>& cent, std::vector<uint32_t>& ids, std::vector<TmpNode>& nodes, uint32_t radius) {
     const size_t n = ids.size();
     Box cb;
     cb.reset();
     for (size_t i = 0; i < n; i++) cb.grow(&cent[3 * (size_t)ids[i]]);
-    float inv[3];
-    for (int a = 0; a < 3; a++) inv[a] = cb.mx[a] > cb.mn[a] ? 1.0f / (cb.mx[a] - cb.mn[a]) : 0.0f;
     std::vector<std::pair<uint64_t, uint32_t>> keyed(n);
-    for (size_t i = 0; i < n; i++) {
-        const float* c = &cent[3 * (size_t)ids[i]];
-        const uint64_t code = (morton21((c[0] - cb.mn[0]) * inv[0]) << 2) | (morton21((c[1] - cb.mn[1]) * inv[1]) << 1) | morton21((c[2] - cb.mn[2]) * inv[2]);
-        keyed[i] = {code, ids[i]};
-    }
+    for (size_t i = 0; i < n; i++) keyed[i] = {morton63(&cent[3 * (size_t)ids[i]], cb.mn, cb.mx), ids[i]};
     std::sort(keyed.begin(), keyed.end());
     for (size_t i = 0; i < n; i++) ids[i] = keyed[i].second;
     nodes.resize(2 * n);
@@ -382,143 +326,56 @@ uint32_t build_ploc(const std::vector<Box>& boxes, const std::vector<float>& cen
         nodes[i].count = 1;
         cl[i] = (uint32_t)i;
     }
-    uint32_t n_nodes = (uint32_t)n;
-    size_t m = n;
+    uint32_t n_nodes = (uint32_t)n, m = (uint32_t)n, level = 0;
     next.reserve(n);
-    // Degenerate input stalls the pairing: with coincident triangles every cluster's nearest neighbour is the first of its
-    // window, in a chain of growing triangles it is the predecessor - one mutual pair per round, and a tree as deep as the
-    // input is long.  A round that merges less than a sixteenth of the clusters therefore escalates, for the rest of the build:
-    // level 1 prefers position i ^ 1 among EQUAL areas (coincident triangles then pair up perfectly), level 2 pairs i and i ^ 1
-    // outright.  Ordinary scenes never leave level 0.  (Level 1's rule at level 0 was measured: +5 % node visits on the
-    // sponza-like scene, whose tessellated walls are full of exact ties.)
-    int level = 0;
     while (m > 1) {
-        for (size_t i = 0; i < m; i++) {
-            const size_t buddy = i ^ 1;
-            if (level == 2) {
-                nn[i] = (uint32_t)(buddy < m ? buddy : i);
-                continue;
-            }
-            const Box& bi = nodes[cl[i]].box;
-            auto union_area = [&](size_t j) {
-                Box u = bi;
+        for (uint32_t i = 0; i < m; i++)
+            nn[i] = ploc_nearest(i, m, radius, level, [&](uint32_t j) {
+                Box u = nodes[cl[i]].box;
                 u.grow(nodes[cl[j]].box);
                 return u.half_area();
-            };
-            float best = std::numeric_limits<float>::infinity();
-            uint32_t bj = (uint32_t)i;
-            if (level == 1 && buddy < m) best = union_area(buddy), bj = (uint32_t)buddy;
-            const size_t lo = i > radius ? i - radius : 0, hi = std::min(m - 1, i + radius);
-            for (size_t j = lo; j <= hi; j++) { // first best: the lower position wins ties
-                if (j == i) continue;
-                const float a = union_area(j);
-                if (a < best) best = a, bj = (uint32_t)j;
-            }
-            nn[i] = bj;
-        }
+            });
         next.clear();
         const uint32_t nodes_before = n_nodes;
-        for (size_t i = 0; i < m; i++) {
-            const uint32_t j = nn[i];
-            if (j != i && nn[j] == i) {
-                if (i < j) {
-                    TmpNode& p = nodes[n_nodes];
-                    p.box = nodes[cl[i]].box;
-                    p.box.grow(nodes[cl[j]].box);
-                    p.left = cl[i];
-                    p.right = cl[j];
-                    p.start = p.count = 0;
-                    next.push_back(n_nodes++);
-                }
-            } else {
-                next.push_back(cl[i]);
-            }
+        for (uint32_t i = 0; i < m; i++) {
+            const uint32_t role = ploc_role(nn.data(), i);
+            if (role == 0u) next.push_back(cl[i]);
+            if (role != 1u) continue;
+            TmpNode& p = nodes[n_nodes];
+            p.box = nodes[cl[i]].box;
+            p.box.grow(nodes[cl[nn[i]]].box);
+            p.left = cl[i];
+            p.right = cl[nn[i]];
+            p.start = p.count = 0;
+            next.push_back(n_nodes++);
         }
-        if ((n_nodes - nodes_before) < m / 16 && level < 2) level++;
-        m = next.size();
+        if (ploc_escalates(n_nodes - nodes_before, m, level)) level++;
+        m = (uint32_t)next.size();
         std::copy(next.begin(), next.end(), cl.begin());
     }
     nodes.resize(n_nodes);
     return cl[0];
 }
 
-// ---- 8-wide collapse (DevNode8).  Which binary nodes become wide nodes, which are absorbed, which subtrees become one leaf is
-// chosen by dynamic programming over the binary tree (minimum expected cost): c[k-1] = cheapest cost of a subtree when it may
-// occupy at most k child slots of its wide parent: k = 1: either one leaf (<= max_leaf triangles) or a wide node of its own,
-// area * cost_traverse8 + the best split of 8 slots between its two children; k > 1: the best split of k slots between its
-// children, or k - 1 slots.  (Round 1's 4-wide collapse used the same program with four slots; the greedy "open the child with
-// the largest area" rule it replaced was 0.8-1.5 % worse.)
-constexpr int W8 = 8;
-struct Dp8 {
-    float c[W8];
-    uint8_t split[W8]; // [k-1]: slots for the left child when k are distributed (0: use k - 1); [0]: the split of 8 when the node is a wide node
-    uint8_t leaf;
+// ---- 8-wide collapse (DevNode8): the program of bvh_rules.h over the binary tree, then the emission, depth first, appending.
+struct HostTree { // the binary tree as rules 6 and 9 read it
+    const std::vector<TmpNode>& nodes;
+    const std::vector<CollapseRec>& dp;
+    const std::vector<uint32_t>& ids;
+    bool inner(uint32_t n, uint32_t& l, uint32_t& r) const {
+        l = nodes[n].left, r = nodes[n].right;
+        return l != 0xFFFFFFFFu;
+    }
+    const CollapseRec& rec(uint32_t n) const { return dp[n]; }
+    uint32_t leaf_tris(uint32_t n, uint32_t* out, uint32_t ng) const {
+        for (uint32_t i = 0; i < nodes[n].count && ng < RT_DEV_LEAF_STRIDE; i++) out[ng++] = ids[nodes[n].start + i];
+        return ng;
+    }
 };
 
-void quantise_axis(const Box& parent, int a, float org, uint32_t& ex_out, double& scale_out) {
-    double extent = (double)parent.mx[a] - (double)parent.mn[a];
-    int e = 1;
-    if (extent > 0.0) {
-        int fe;
-        std::frexp(extent / 255.0, &fe);
-        e = fe + 127;
-        if (e < 1) e = 1;
-        if (e > 254) e = 254;
-    }
-    (void)org;
-    ex_out = (uint32_t)(e - 127) & 0xFFu;
-    scale_out = std::ldexp(1.0, e - 127);
-}
-
-void quantise_box(const Box& cb, int a, float org, double scale, uint32_t& qlo, uint32_t& qhi) {
-    double lo = std::floor(((double)cb.mn[a] - (double)org) / scale);
-    double hi = std::ceil(((double)cb.mx[a] - (double)org) / scale);
-    lo = std::min(std::max(lo, 0.0), 255.0);
-    hi = std::min(std::max(hi, 0.0), 255.0);
-    while (lo > 0.0 && (double)org + lo * scale > (double)cb.mn[a]) lo -= 1.0;
-    while (hi < 255.0 && (double)org + hi * scale < (double)cb.mx[a]) hi += 1.0;
-    qlo = (uint32_t)lo;
-    qhi = (uint32_t)hi;
-}
-
-void collapse8(std::vector<TmpNode>& nodes, std::vector<uint32_t>& ids, uint32_t n_nodes, uint32_t root, const BuildTri* tris_in, const BvhBuildOptions& opt,
+void collapse8(const std::vector<TmpNode>& nodes, const std::vector<uint32_t>& ids, uint32_t n_nodes, uint32_t root, const BuildTri* tris_in, const BvhBuildOptions& opt,
                uint32_t max_leaf, BvhBuild& out) {
-    auto is_leaf = [&](uint32_t t) { return nodes[t].left == 0xFFFFFFFFu; };
-    DevTri blank;
-    std::memset(&blank, 0, sizeof blank);
-    if (is_leaf(root)) { // the whole scene is one leaf: a root node with that one child in slot 0, so that every walk starts at node 0
-        const TmpNode& t = nodes[root];
-        out.nodes.emplace_back();
-        DevNode8& d = out.nodes[0];
-        uint32_t ex[3];
-        for (int a = 0; a < 3; a++) {
-            d.org[a] = t.box.mn[a];
-            double scale;
-            quantise_axis(t.box, a, d.org[a], ex[a], scale);
-            uint32_t qlo, qhi;
-            quantise_box(t.box, a, d.org[a], scale, qlo, qhi);
-            d.qlo[a][0] = qlo | 0xFFFFFF00u; // slots 1..7 empty: inverted
-            d.qhi[a][0] = qhi;
-            d.qlo[a][1] = 0xFFFFFFFFu;
-            d.qhi[a][1] = 0u;
-        }
-        d.ex_imask = ex[0] | (ex[1] << 8) | (ex[2] << 16);
-        d.child_base = 0;
-        d.tri_base = 0;
-        d.lmask = 1u;
-        d._pad = 0;
-        for (uint32_t i = 0; i < RT_DEV_LEAF_STRIDE; i++) {
-            out.tris.push_back(blank);
-            if (i < t.count) put_tri(tris_in[ids[t.start + i]], &out.tris[i]);
-        }
-        out.tris[0].leaf_count = t.count;
-        out.n_leaves = 1;
-        out.depth = 1;
-        return;
-    }
-    std::vector<Dp8> dp(n_nodes);
-    std::vector<uint32_t> sub_count(n_nodes, 0);
-    const float inf = std::numeric_limits<float>::infinity();
+    std::vector<CollapseRec> dp(n_nodes);
     {
         struct Frame {
             uint32_t node;
@@ -526,84 +383,24 @@ void collapse8(std::vector<TmpNode>& nodes, std::vector<uint32_t>& ids, uint32_t
         };
         std::vector<Frame> st;
         st.push_back({root, 0});
-        while (!st.empty()) {
+        while (!st.empty()) { // children before parents
             Frame f = st.back();
             st.pop_back();
             const TmpNode& t = nodes[f.node];
-            Dp8& d = dp[f.node];
             if (t.left == 0xFFFFFFFFu) {
-                const float lc = opt.cost_intersect * (float)t.count * t.box.half_area();
-                for (int k = 0; k < W8; k++) d.c[k] = lc, d.split[k] = 0;
-                d.leaf = 1;
-                sub_count[f.node] = t.count;
-                continue;
-            }
-            if (f.phase == 0) {
+                collapse_leaf(dp[f.node], opt.cost_intersect, t.count, t.box.half_area());
+            } else if (f.phase == 0) {
                 st.push_back({f.node, 1});
                 st.push_back({t.left, 0});
                 st.push_back({t.right, 0});
-                continue;
-            }
-            // triangles of the subtree (saturating well above max_leaf): a subtree of <= max_leaf triangles may become one leaf,
-            // whatever the order of its ids (the leaf gathers them)
-            sub_count[f.node] = std::min<uint32_t>(sub_count[t.left] + sub_count[t.right], 1u << 20);
-            const Dp8 &dl = dp[t.left], &dr = dp[t.right];
-            float dist[W8 + 1];
-            uint8_t arg[W8 + 1];
-            for (int k = 0; k <= W8; k++) dist[k] = inf, arg[k] = 0;
-            for (int k = 2; k <= W8; k++)
-                for (int i = 1; i < k; i++) {
-                    const float v = dl.c[i - 1] + dr.c[k - i - 1];
-                    if (v < dist[k]) dist[k] = v, arg[k] = (uint8_t)i;
-                }
-            const float area = t.box.half_area();
-            const float wide = opt.cost_traverse8 * area + dist[W8];
-            const uint32_t cnt = sub_count[f.node];
-            const float leafc = cnt && cnt <= max_leaf ? opt.cost_intersect * (float)cnt * area : inf;
-            // Finite coordinates whose box area overflows f32 (~1e19 and beyond) make every cost inf or NaN: no `v < dist` above
-            // succeeds and arg stays 0, which is not a split.  The rule then is explicit, the same in device_build.hip:
-            // a leaf only when the count allows it, else a wide node split 1 : 7 - a poor tree, but a valid one.
-            if (arg[W8] == 0) arg[W8] = 1;
-            d.leaf = (cnt && cnt <= max_leaf && !(wide < leafc)) ? 1 : 0;
-            d.c[0] = std::min(leafc, wide);
-            d.split[0] = arg[W8];
-            for (int k = 2; k <= W8; k++) {
-                if (dist[k] < d.c[k - 2]) d.c[k - 1] = dist[k], d.split[k - 1] = arg[k];
-                else d.c[k - 1] = d.c[k - 2], d.split[k - 1] = 0;
+            } else {
+                collapse_inner(dp[f.node], dp[t.left], dp[t.right], t.box.half_area(), opt.cost_traverse8, opt.cost_intersect, max_leaf);
             }
         }
     }
-    std::function<void(uint32_t, int, uint32_t*, int&)> expand = [&](uint32_t m, int k, uint32_t* ch, int& nch) {
-        TmpNode& t = nodes[m];
-        if (t.left != 0xFFFFFFFFu) {
-            while (k > 1 && dp[m].split[k - 1] == 0) k--;
-            if (k > 1) {
-                const int i = dp[m].split[k - 1];
-                expand(t.left, i, ch, nch);
-                expand(t.right, k - i, ch, nch);
-                return;
-            }
-            if (dp[m].leaf) { // the whole subtree as one leaf: gather its triangles (appended to ids), in index order
-                uint32_t gathered[RT_DEV_LEAF_STRIDE], ng = 0, todo[2 * RT_DEV_LEAF_STRIDE], nt = 0;
-                todo[nt++] = m;
-                while (nt) {
-                    const TmpNode& u = nodes[todo[--nt]];
-                    if (u.left == 0xFFFFFFFFu) {
-                        for (uint32_t i = 0; i < u.count && ng < RT_DEV_LEAF_STRIDE; i++) gathered[ng++] = ids[u.start + i];
-                    } else {
-                        todo[nt++] = u.left;
-                        todo[nt++] = u.right;
-                    }
-                }
-                std::sort(gathered, gathered + ng, [&](uint32_t x, uint32_t y) { return tris_in[x].prim_id < tris_in[y].prim_id; });
-                t.start = (uint32_t)ids.size();
-                t.count = ng;
-                ids.insert(ids.end(), gathered, gathered + ng);
-                t.left = t.right = 0xFFFFFFFFu;
-            }
-        }
-        ch[nch++] = m;
-    };
+    const HostTree tree{nodes, dp, ids};
+    // A scene whose binary tree is one leaf gets a root node with that one child (slot 0 by rule 7), so that every walk starts at node 0.
+    const bool one_leaf = nodes[root].left == 0xFFFFFFFFu;
     struct Item {
         uint32_t tmp, dev, depth;
     };
@@ -617,105 +414,43 @@ void collapse8(std::vector<TmpNode>& nodes, std::vector<uint32_t>& ids, uint32_t
         Item it = stack.back();
         stack.pop_back();
         out.depth = std::max(out.depth, it.depth);
-        const TmpNode t = nodes[it.tmp];
-        uint32_t ch[W8];
-        int nch = 0;
-        {
-            const int i = dp[it.tmp].split[0];
-            expand(t.left, i, ch, nch);
-            expand(t.right, W8 - i, ch, nch);
-        }
-        // Slot assignment: slot s lies toward the corner (s & 1 ? +x : -x, s & 2 ? +y : -y, s & 4 ? +z : -z) of the node.
-        // Greedy: repeatedly give the (child, slot) pair with the largest projection of the child's centre offset on
-        // the slot's diagonal.
-        float pc[3];
-        for (int a = 0; a < 3; a++) pc[a] = 0.5f * t.box.mn[a] + 0.5f * t.box.mx[a];
-        float score[W8][W8];
-        for (int c = 0; c < nch; c++) {
-            const Box& cb = nodes[ch[c]].box;
-            float off[3];
-            for (int a = 0; a < 3; a++) off[a] = (0.5f * cb.mn[a] + 0.5f * cb.mx[a]) - pc[a];
-            for (int sl = 0; sl < W8; sl++) score[c][sl] = (sl & 1 ? off[0] : -off[0]) + (sl & 2 ? off[1] : -off[1]) + (sl & 4 ? off[2] : -off[2]);
-        }
+        const TmpNode& t = nodes[it.tmp];
+        uint32_t ch[W8] = {root}, l, r;
+        const int nch = one_leaf ? 1 : wide_children(tree, it.tmp, ch);
+        Box cb[W8];
+        for (int c = 0; c < nch; c++) cb[c] = nodes[ch[c]].box;
         int slot_child[W8];
-        bool child_done[W8] = {false, false, false, false, false, false, false, false};
-        for (int sl = 0; sl < W8; sl++) slot_child[sl] = -1;
-        for (int round = 0; round < nch; round++) {
-            int bc = -1, bs = -1;
-            float best = -inf;
-            for (int c = 0; c < nch; c++) {
-                if (child_done[c]) continue;
-                for (int sl = 0; sl < W8; sl++)
-                    if (slot_child[sl] < 0 && score[c][sl] > best) best = score[c][sl], bc = c, bs = sl;
-            }
-            if (bc < 0) { // only NaN scores are left (degenerate boxes): any free slot
-                for (int c = 0; c < nch && bc < 0; c++)
-                    if (!child_done[c]) bc = c;
-                for (int sl = 0; sl < W8 && bs < 0; sl++)
-                    if (slot_child[sl] < 0) bs = sl;
-            }
-            slot_child[bs] = bc;
-            child_done[bc] = true;
-        }
+        assign_slots(t.box, cb, nch, slot_child);
         uint32_t imask = 0, lmask = 0;
         for (int sl = 0; sl < W8; sl++) {
             if (slot_child[sl] < 0) continue;
-            if (is_leaf(ch[slot_child[sl]])) lmask |= 1u << sl;
+            const uint32_t cn = ch[slot_child[sl]];
+            if (!tree.inner(cn, l, r) || dp[cn].leaf) lmask |= 1u << sl;
             else imask |= 1u << sl;
         }
         const uint32_t child_base = (uint32_t)out.nodes.size();
         const int n_inner = __builtin_popcount(imask);
         for (int c = 0; c < n_inner; c++) out.nodes.emplace_back();
         const uint32_t tri_base = (uint32_t)out.tris.size();
-        int inner_rank = 0;
-        std::vector<Item> pushes;
+        for (int sl = W8 - 1; sl >= 0; sl--) // inner children: visited in slot order
+            if (imask & (1u << sl)) stack.push_back({ch[slot_child[sl]], child_base + (uint32_t)__builtin_popcount(imask & ((1u << sl) - 1u)), it.depth + 1});
         for (int sl = 0; sl < W8; sl++) {
-            if (slot_child[sl] < 0) continue;
+            if (!(lmask & (1u << sl))) continue;
             const uint32_t cn = ch[slot_child[sl]];
-            if (imask & (1u << sl)) {
-                pushes.push_back({cn, child_base + (uint32_t)inner_rank, it.depth + 1});
-                inner_rank++;
-            } else {
-                const TmpNode& lf = nodes[cn];
-                const size_t first = out.tris.size();
-                for (uint32_t i = 0; i < RT_DEV_LEAF_STRIDE; i++) {
-                    out.tris.push_back(blank);
-                    if (i < lf.count) put_tri(tris_in[ids[lf.start + i]], &out.tris[first + i]);
-                }
-                out.tris[first].leaf_count = lf.count;
-                out.n_leaves++;
-                if (root_area > 0) cost += opt.cost_intersect * lf.count * lf.box.half_area() / root_area;
-            }
+            uint32_t gathered[RT_DEV_LEAF_STRIDE];
+            const uint32_t ng = gather_leaf(tree, cn, tris_in, gathered);
+            for (uint32_t x = 0; x < RT_DEV_LEAF_STRIDE; x++) out.tris.push_back(leaf_record(tris_in, gathered, ng, x));
+            out.n_leaves++;
+            if (root_area > 0) cost += opt.cost_intersect * ng * nodes[cn].box.half_area() / root_area;
         }
-        for (int c = (int)pushes.size() - 1; c >= 0; c--) stack.push_back(pushes[c]);
         if (root_area > 0) cost += opt.cost_traverse8 * t.box.half_area() / root_area;
         DevNode8& d = out.nodes[it.dev];
-        uint32_t ex[3];
-        for (int a = 0; a < 3; a++) {
-            d.org[a] = t.box.mn[a];
-            double scale;
-            quantise_axis(t.box, a, d.org[a], ex[a], scale);
-            for (int h = 0; h < 2; h++) {
-                uint32_t lo_word = 0, hi_word = 0;
-                for (int i = 0; i < 4; i++) {
-                    const int sl = 4 * h + i;
-                    uint32_t qlo = 255, qhi = 0; // empty slot: inverted, never entered
-                    if (slot_child[sl] >= 0) quantise_box(nodes[ch[slot_child[sl]]].box, a, d.org[a], scale, qlo, qhi);
-                    lo_word |= qlo << (8 * i);
-                    hi_word |= qhi << (8 * i);
-                }
-                d.qlo[a][h] = lo_word;
-                d.qhi[a][h] = hi_word;
-            }
-        }
-        d.ex_imask = ex[0] | (ex[1] << 8) | (ex[2] << 16) | (imask << 24);
-        d.child_base = child_base;
+        quantise_node(d, imask, t.box, [&](int sl) { return slot_child[sl] < 0 ? (const Box*)nullptr : &cb[slot_child[sl]]; });
+        d.child_base = one_leaf ? 0u : child_base;
         d.tri_base = tri_base;
         d.lmask = lmask;
         d._pad = 0;
     }
-    // An empty slot can only be entered when the float evaluation cannot tell 255 grid steps apart (degenerate node, ray
-    // origin ~1e8 grid steps away).  The traversal masks the hit bits with imask | lmask, so it is never followed.
     out.sah_cost = cost;
 }
 
@@ -736,21 +471,14 @@ void build_bvh(const BuildTri* tris_in, size_t n_in, const BvhBuildOptions& opt_
     b.cent.resize(3 * n_in);
     for (size_t i = 0; i < n_in; i++) {
         const BuildTri& t = tris_in[i];
-        bool finite = true;
-        for (int a = 0; a < 3; a++) finite = finite && std::isfinite(t.v0[a]) && std::isfinite(t.v1[a]) && std::isfinite(t.v2[a]);
-        if (!finite) continue;
-        Box bx;
-        bx.reset();
-        bx.grow(t.v0);
-        bx.grow(t.v1);
-        bx.grow(t.v2);
-        b.boxes[i] = bx;
-        for (int a = 0; a < 3; a++) b.cent[3 * i + a] = 0.5f * bx.mn[a] + 0.5f * bx.mx[a];
+        if (!tri_finite(t.v0, t.v1, t.v2)) continue;
+        b.boxes[i] = tri_box(t.v0, t.v1, t.v2);
+        for (int a = 0; a < 3; a++) b.cent[3 * i + a] = b.boxes[i].centre(a);
         b.ids.push_back((uint32_t)i);
     }
     size_t n = b.ids.size();
     if (n == 0) return;
-    if (opt_in.method == 1) { // PLOC on the host: the statement of the device build (quality / structure reference)
+    if (opt_in.method == 1) { // PLOC on the host: the tree the device build makes (quality / structure reference)
         std::vector<TmpNode> pn;
         const uint32_t proot = build_ploc(b.boxes, b.cent, b.ids, pn, opt_in.ploc_radius);
         collapse8(pn, b.ids, (uint32_t)pn.size(), proot, tris_in, b.opt, b.opt.max_leaf, out);

@@ -105,6 +105,16 @@ static void check_node(Ctx& c, uint32_t node, uint32_t depth, const double plo[3
     CHECK(present >= (node == 0 ? 1 : 2), "node %u has %d children", node, present);
 }
 
+// FNV-1a over the bytes of a node or triangle array (neither type has padding the builders leave unwritten): two trees with the same
+// hashes are the same arrays.  rt_debug_check_bvh and tests/check_bvh.cpp report it.
+static uint32_t hash_bytes(const void* p, size_t n) {
+    uint32_t h = 2166136261u;
+    const unsigned char* c = static_cast<const unsigned char*>(p);
+    for (size_t i = 0; i < n; i++) h = (h ^ c[i]) * 16777619u;
+    return h;
+}
+static uint32_t hash_nodes(const BvhBuild& b) { return hash_bytes(b.nodes.data(), b.nodes.size() * sizeof(DevNode8)); }
+static uint32_t hash_tris(const BvhBuild& b) { return hash_bytes(b.tris.data(), b.tris.size() * sizeof(DevTri)); }
 
 // Checks the whole tree; `seen` must hold one zero per caller triangle (prim id).  Returns the number of failures.
 static int check_tree(const BvhBuild& b, std::vector<uint32_t>& seen, uint32_t* real_depth, size_t* leaves) {

@@ -101,7 +101,7 @@ int rt_debug_fail_upload(rt_ctx* ctx, int k) {
 // Development aid (not part of rt_hip.h): download the tree the context holds on its first device and validate it the way the
 // kernels decode it (bvh_check.h: slots and masks, every finite triangle in exactly one leaf, conservative boxes, depth).
 // out[0] nodes, [1] leaves, [2] reported depth, [3] real depth, [4] triangles placed exactly once, [5] build method, [6] / [7] FNV-1a
-// hashes of the node and triangle arrays (the device build lays its tree out exactly as its host statement does); returns the number of failures.
+// hashes of the node and triangle arrays (the device build lays its tree out exactly as the host's PLOC build does; rtcheck::hash_nodes / hash_tris); returns the number of failures.
 int rt_debug_check_bvh(rt_ctx* ctx, uint32_t out[8]) {
     if (!ctx || !ctx->uploaded) return -1;
     DeviceState& d = ctx->devs[0];
@@ -131,14 +131,8 @@ int rt_debug_check_bvh(rt_ctx* ctx, uint32_t out[8]) {
         out[3] = real_depth;
         out[4] = once;
         out[5] = ctx->stats.tree_build;
-        auto fnv = [](const void* p, size_t n) {
-            uint32_t h = 2166136261u;
-            const unsigned char* c = static_cast<const unsigned char*>(p);
-            for (size_t i = 0; i < n; i++) h = (h ^ c[i]) * 16777619u;
-            return h;
-        };
-        out[6] = fnv(b.nodes.data(), b.nodes.size() * sizeof(DevNode8));
-        out[7] = fnv(b.tris.data(), b.tris.size() * sizeof(DevTri));
+        out[6] = rtcheck::hash_nodes(b);
+        out[7] = rtcheck::hash_tris(b);
     }
     return fails;
 }

@@ -55,7 +55,7 @@ int main(int argc, char** argv) {
     }
     BvhBuild b;
     BvhBuildOptions opt;
-    opt.method = argc > 4 ? std::atoi(argv[4]) : 0; // 0: binned SAH + insertion-based optimisation, 1: PLOC (the statement of the device build)
+    opt.method = argc > 4 ? std::atoi(argv[4]) : 0; // 0: binned SAH + insertion-based optimisation, 1: PLOC (the tree the device build makes)
     build_bvh(tris.data(), tris.size(), opt, b);
     std::vector<uint32_t> seen(n, 0);
     uint32_t real_depth = 0;
@@ -69,7 +69,7 @@ int main(int argc, char** argv) {
         CHECK(seen[i] == (finite ? 1u : 0u), "triangle %zu appears %u times", i, seen[i]);
         once += seen[i] == 1;
     }
-    std::printf("kind %d n %zu: %zu nodes, %zu leaves, depth %u (reported %u), %zu triangles placed, %d failures\n", kind, n, b.nodes.size(), leaves, real_depth,
-                b.depth, once, g_fail);
+    std::printf("kind %d n %zu: %zu nodes, %zu leaves, depth %u (reported %u), %zu triangles placed, %d failures, nodes_hash %08x tris_hash %08x\n", kind, n, b.nodes.size(),
+                leaves, real_depth, b.depth, once, g_fail, hash_nodes(b), hash_tris(b));
     return g_fail ? 1 : 0;
 }

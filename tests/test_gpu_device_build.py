@@ -3,8 +3,9 @@ program, emission) - the default for scenes of 1,024 triangles and more.
 
   * structure: the tree a context holds is downloaded and validated the way the kernels decode it (csrc/bvh_check.h, the checker
     the host builders run under ASan/UBSan): slots and masks, every finite triangle in exactly one leaf, conservative boxes, depth;
-  * the host statement: bvh_builder.cpp's PLOC (RT_BUILD_METHOD=1) is the same algorithm - same Morton codes, neighbour rule,
-    collapse program and depth-first layout - so the node and triangle arrays are BYTE-IDENTICAL (compared by hash);
+  * the host's PLOC build (bvh_builder.cpp, RT_BUILD_METHOD=1) calls the same rules (csrc/bvh_rules.h: Morton codes, neighbour rule,
+    collapse program, slots, quantisation) and appends in the depth-first layout the device computes - so the node and triangle
+    arrays are BYTE-IDENTICAL (compared by hash);
   * images: hits and colours are identical to those from a host-built (binned SAH) tree - closest hits do not depend on topology;
   * degenerate input (coincident triangles, a chain of growing triangles, non-finite vertices) stays logarithmic and shallow.
 """
@@ -111,6 +112,56 @@ def test_device_build_on_degenerate_input(rt_api, monkeypatch, kind):
     finally:
         dev.close()
         host.close()
+
+
+# Small trees: a wide node has fewer than eight children, a whole subtree becomes one leaf, the root's program is nearly a leaf.
+# An explicit RT_BUILD_METHOD=2 still leaves scenes under 1,024 triangles to the host builder (tree_method, rt_scene.cpp), so of
+# the sizes 9 / 37 / 300 / 1000 and the 1,000 coincident triangles none reaches the device build: they stay as the declined cases,
+# and the smallest sizes the device build accepts (1,024, one more, an odd one) and 1,024 coincident triangles are added to them.
+SMALL = [("soup", 9), ("soup", 37), ("soup", 300), ("soup", 1000), ("coincident", 1000),
+         ("soup", 1024), ("soup", 1025), ("soup", 1531), ("coincident", 1024)]
+
+
+def _small_scene(kind, n):
+    return scenes.random_soup(n, seed=11) if kind == "soup" else _degenerate(kind, n)
+
+
+@pytest.fixture(scope="module")
+def small_builds(rt_api):
+    """Every small case built once with RT_BUILD_METHOD=2 and once with =1: (device's check, host's check) per case."""
+    mp = pytest.MonkeyPatch()
+    out = {}
+    try:
+        for kind, n in SMALL:
+            scene = _small_scene(kind, n)
+            dev, _ = _upload(rt_api, mp, scene, 2)
+            host, _ = _upload(rt_api, mp, scene, 1)
+            try:
+                out[(kind, n)] = (dev.debug_check_bvh(), host.debug_check_bvh())
+            finally:
+                dev.close()
+                host.close()
+    finally:
+        mp.undo()
+    return out
+
+
+@pytest.mark.parametrize("kind,n", SMALL, ids=[f"{k}{n}" for k, n in SMALL])
+def test_small_device_builds_match_the_host(small_builds, kind, n):
+    a, b = small_builds[(kind, n)]
+    assert b["method"] == 1
+    assert a["failures"] == 0 and b["failures"] == 0
+    assert a["placed_once"] == b["placed_once"] == _finite_triangles(_small_scene(kind, n))
+    if a["method"] == 2:  # (declined: a host tree, checked above; a one-leaf root is the host's business)
+        assert (a["nodes"], a["leaves"], a["depth"]) == (b["nodes"], b["leaves"], b["depth"])
+        assert (a["nodes_hash"], a["tris_hash"]) == (b["nodes_hash"], b["tris_hash"])
+
+
+def test_small_device_builds_reach_the_device(small_builds):
+    """Enough of the small cases must have been built on the device for them to say anything about it."""
+    methods = {c: small_builds[c][0]["method"] for c in SMALL}
+    assert sum(m == 2 for m in methods.values()) >= 3, methods
+    assert all(methods[("soup", n)] == 2 for n in (1024, 1025, 1531)), methods
 
 
 def test_small_scenes_use_the_host_build(rt_api, monkeypatch):
