@@ -33,6 +33,8 @@ PREPARE_SHADOW_GRIDS = 1
 PREPARE_QUALITY_TREE = 2
 QUERY_COUNTERS = 1  # RT_QUERY_COUNTERS of rt_intersect / rt_occluded
 QUERY_CHUNK = 4194304  # RT_QUERY_CHUNK: host batches are staged in chunks of at most this many rays
+QUERY_COUNT_ALL = 2  # RT_QUERY_COUNT_ALL of rt_intersect_all: counts are all candidates in the range, not the records written
+MULTI_HIT_MAX = 16  # RT_MULTI_HIT_MAX: the most hits rt_intersect_all lists per ray
 UPDATE_REBUILD = 1  # RT_UPDATE_REBUILD of rt_update_geometry
 AOV_SAMPLES_PER_LAUNCH = T.AOV_SAMPLES_PER_LAUNCH  # RT_AOV_SAMPLES_PER_LAUNCH: rt_aovs traces at most this many samples per kernel
 DENOISE_DEMODULATE = T.DENOISE_DEMODULATE  # RT_DENOISE_DEMODULATE of rt_denoise_params.flags
@@ -49,7 +51,7 @@ ABI_SYMBOLS = [
     "rt_create", "rt_upload_scene", "rt_upload_scene_packed", "rt_upload_textures", "rt_prepare", "rt_render", "rt_dispatch_tile",
     "rt_read_rgb32f", "rt_read_rgba8_channels", "rt_read_rgba8_combined", "rt_read_hits",
     "rt_get_stats", "rt_last_error", "rt_destroy", "rt_version",
-    "rt_intersect", "rt_occluded", "rt_camera_rays",
+    "rt_intersect", "rt_occluded", "rt_camera_rays", "rt_intersect_all",
     "rt_update_geometry",
     "rt_accumulated_samples",
     "rt_aovs", "rt_sample_rays", "rt_denoise",
@@ -93,7 +95,7 @@ def _p(a):
     return C.c_void_p(a.ctypes.data) if a is not None and a.size else C.c_void_p(0)
 
 
-# -- ray batches (rt_intersect / rt_occluded / rt_camera_rays) ---------------------------------------------------------
+# -- ray batches (rt_intersect / rt_occluded / rt_intersect_all / rt_camera_rays) ---------------------------------------------------------
 # A batch is a C-contiguous float32 array of shape (N, 8), one rt_ray per row: ox oy oz tmin dx dy dz tmax; numpy, or a torch
 # tensor on the CPU or on a device of the context.  torch is imported only when a tensor is handed in.
 
@@ -120,6 +122,43 @@ def _check_batch(a, name, cols, dtype_name):
     if not contiguous:
         raise ValueError(f"{name}: not C-contiguous")
     return shape[0]
+
+
+def _contiguous(a):
+    return a.is_contiguous() if _is_torch(a) else a.flags.c_contiguous
+
+
+def _check_kind_dtype(a, name, dtype_name):
+    if _is_torch(a):
+        import torch
+        if a.dtype != getattr(torch, dtype_name):
+            raise TypeError(f"{name}: dtype {a.dtype}, expected torch.{dtype_name}")
+    elif not isinstance(a, np.ndarray):
+        raise TypeError(f"{name}: a numpy array or a torch tensor, not {type(a).__name__}")
+    elif a.dtype != np.dtype(dtype_name):
+        raise TypeError(f"{name}: dtype {a.dtype}, expected {dtype_name}")
+
+
+def _check_hit_lists(a, n, max_hits):
+    """Raises unless `a` is a C-contiguous float32 (n, max_hits, 4) array: rt_intersect_all's records, ray-major."""
+    _check_kind_dtype(a, "out", "float32")
+    if len(a.shape) != 3 or tuple(a.shape[1:]) != (max_hits, 4):
+        raise ValueError(f"out: shape {tuple(a.shape)}, expected (N, {max_hits}, 4)")
+    if not _contiguous(a):
+        raise ValueError("out: not C-contiguous")
+    if a.shape[0] != n:
+        raise ValueError(f"out: {a.shape[0]} rows for {n} rays")
+
+
+def _check_counts(a, n):
+    """Raises unless `a` is a C-contiguous (n,) array of rt_intersect_all's counts: uint32 for numpy, int32 for torch."""
+    _check_kind_dtype(a, "counts", "int32" if _is_torch(a) else "uint32")
+    if len(a.shape) != 1:
+        raise ValueError(f"counts: shape {tuple(a.shape)}, expected (N,)")
+    if not _contiguous(a):
+        raise ValueError("counts: not C-contiguous")
+    if a.shape[0] != n:
+        raise ValueError(f"counts: {a.shape[0]} rows for {n} rays")
 
 
 def _addr(a):
@@ -445,6 +484,41 @@ class Context:
     def occluded(self, rays, out=None, counters=False):
         """rt_occluded: any hit in each ray's range -> (N,) bool, same kind and device as `rays`."""
         return self._query("rt_occluded", rays, out, 0, "bool", counters)
+
+    def intersect_all(self, rays, max_hits, out=None, counts=None, count_all=False, counters=False):
+        """rt_intersect_all: the first max_hits (0 .. MULTI_HIT_MAX) hits along each ray of an (N, 8) batch, ordered as rt_intersect
+        would pick them -> (hits, counts), same kind and device as `rays`.  hits: (N, max_hits, 4) float32, unused slots miss
+        records (split_hits takes hits.reshape(-1, 4)), None for max_hits=0; counts: (N,) uint32 (numpy) / int32 (torch), the
+        records listed per ray, or with count_all every candidate in the ray's range.  max_hits=0 needs count_all: a crossing count."""
+        n = _check_batch(rays, "rays", 8, "float32")
+        if isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)) or not 0 <= max_hits <= MULTI_HIT_MAX:
+            raise ValueError(f"max_hits: {max_hits!r}, expected an integer in 0 .. {MULTI_HIT_MAX}")
+        max_hits = int(max_hits)
+        if max_hits == 0 and not count_all:
+            raise ValueError("max_hits: 0 lists nothing, which needs count_all=True (a pure crossing count)")
+        torch_kind = _is_torch(rays)
+        for name, a in (("out", out), ("counts", counts)):
+            if a is not None and _is_torch(a) != torch_kind:
+                raise TypeError(f"{name}: must be the same kind (numpy / torch) as rays")
+        if max_hits == 0:
+            out = None
+        elif out is None:
+            out = _empty_like_batch(rays, (n, max_hits, 4), "float32")
+        else:
+            _check_hit_lists(out, n, max_hits)
+        if counts is None:
+            if torch_kind:
+                import torch
+                counts = torch.empty((n,), dtype=torch.int32, device=rays.device)
+            else:
+                counts = np.empty((n,), np.uint32)
+        else:
+            _check_counts(counts, n)
+        _sync_torch(rays, out, counts)
+        flags = (QUERY_COUNTERS if counters else 0) | (QUERY_COUNT_ALL if count_all else 0)
+        self._check(self.lib.rt_intersect_all(self._h, _addr(rays), C.c_size_t(n), C.c_uint32(max_hits),
+                                              _addr(out) if out is not None else C.c_void_p(0), _addr(counts), C.c_uint32(flags)))
+        return out, counts
 
     def camera_rays(self, width, height, camera, mode=MODE_LEGACY, out=None):
         """rt_camera_rays: the width x height pixel-centre rays of mode 0/1 as a (width * height, 8) batch, row-major, y down.

@@ -133,8 +133,8 @@ struct DeviceState {
     } pipe;
     bool used_two_lanes = false; // the last pipeline frame ran on two lanes (its allocation is reused by a frame of the same shape)
     uint32_t wf_spp = 0;         // spp the current wavefront allocation was sized for
-    struct Query { // ray queries: staging of host batches (rays in, hit records / bytes out), grown on demand
-        DevMem in, out;
+    struct Query { // ray queries: staging of host batches (rays in, hit records / bytes out, rt_intersect_all's counts), grown on demand
+        DevMem in, out, counts;
     } rq;
     // RT_FLAG_ACCUMULATE: the running sum of the context's accumulation over this device's pixels (DevTargets::run_sum), frame-pixel
     // layout, w x h x 16 bytes.  Outlives the pipeline's WfBuffers (re-sized with the batch); made by the first accumulating call.

@@ -1,5 +1,5 @@
 // rt_query.cpp — calls that trace or filter outside a frame: ray queries (rt_hip.h "Ray queries": rt_intersect, rt_occluded,
-// rt_camera_rays) and the image passes ("Feature buffers (AOVs) and denoising": rt_aovs, rt_sample_rays, rt_denoise; kernels in
+// rt_intersect_all, rt_camera_rays) and the image passes ("Feature buffers (AOVs) and denoising": rt_aovs, rt_sample_rays, rt_denoise; kernels in
 // denoise.hip).  None of them touches the frame targets, the tile shares rt_read_* gather, or the running image of an accumulation.
 #include "rt_internal.h"
 
@@ -42,23 +42,52 @@ void drain_streams(rt_ctx* ctx) { // after a failure: nothing of the call is lef
     }
 }
 
-// Both query kinds: out_elem = 16 (rt_hit) or 1 (occluded byte).
-int run_query(rt_ctx* ctx, const char* fn, const rt_ray* rays, size_t n, void* out, size_t out_elem, uint32_t flags) {
+// rt_intersect_all's part of a query: max_hits records per ray, and a second output array.
+struct MultiHit {
+    uint32_t max_hits;
+    uint32_t* counts; // may be null
+};
+
+// Every query kind: out_elem = the bytes per ray at `out`: 16 (rt_hit), 1 (occluded byte), or with `mh` max_hits * 16 (`out` is then
+// ignored when that is 0).  Host batches go in chunks of RT_QUERY_CHUNK rays, with `mh` RT_QUERY_CHUNK / max(max_hits, 1): the hit
+// records of a chunk never need more staging than an rt_intersect chunk's.
+int run_query(rt_ctx* ctx, const char* fn, const rt_ray* rays, size_t n, void* out, size_t out_elem, uint32_t flags, const MultiHit* mh = nullptr) {
     const double w0 = now_ms();
     if (!ctx) return RT_ERR_BAD_ARG;
     if (n == 0) return RT_OK;
     const char* out_name = out_elem == 1 ? "occluded" : "hits";
-    if (!rays || !out) return ctx->fail(RT_ERR_BAD_ARG, "%s: %s is NULL with n = %zu", fn, !rays ? "rays" : out_name, n);
-    if (flags & ~RT_QUERY_COUNTERS) return ctx->fail(RT_ERR_BAD_ARG, "%s: unknown flag bits 0x%x", fn, flags & ~RT_QUERY_COUNTERS);
+    uint32_t known = RT_QUERY_COUNTERS;
+    if (mh) {
+        known |= RT_QUERY_COUNT_ALL;
+        if (!rays || (!out && mh->max_hits > 0)) return ctx->fail(RT_ERR_BAD_ARG, "%s: %s is NULL with n = %zu", fn, !rays ? "rays" : out_name, n);
+        if (mh->max_hits > RT_MULTI_HIT_MAX) return ctx->fail(RT_ERR_BAD_ARG, "%s: max_hits %u (0 .. %u)", fn, mh->max_hits, RT_MULTI_HIT_MAX);
+        if (mh->max_hits == 0 && (!(flags & RT_QUERY_COUNT_ALL) || !mh->counts))
+            return ctx->fail(RT_ERR_BAD_ARG, "%s: max_hits 0 needs RT_QUERY_COUNT_ALL and counts", fn);
+        if (mh->max_hits == 0) out = nullptr; // ignored
+    } else if (!rays || !out) {
+        return ctx->fail(RT_ERR_BAD_ARG, "%s: %s is NULL with n = %zu", fn, !rays ? "rays" : out_name, n);
+    }
+    if (flags & ~known) return ctx->fail(RT_ERR_BAD_ARG, "%s: unknown flag bits 0x%x", fn, flags & ~known);
     if (!ctx->uploaded) return ctx->fail(RT_ERR_NOT_UPLOADED, "%s: no scene uploaded", fn);
     if (int rcp = sync_pending(ctx)) return rcp;
-    QueryPtr pin, pout;
+    uint32_t* counts = mh ? mh->counts : nullptr;
+    QueryPtr pin, pout, pcnt;
     if (int rc = classify_ptr(ctx, fn, "rays", rays, pin)) return rc;
-    if (int rc = classify_ptr(ctx, fn, out_name, out, pout)) return rc;
+    if (out) {
+        if (int rc = classify_ptr(ctx, fn, out_name, out, pout)) return rc;
+    }
+    if (counts) {
+        if (int rc = classify_ptr(ctx, fn, "counts", counts, pcnt, 4)) return rc;
+    }
+    if (!out) pout = pcnt, out_name = "counts"; // a pure count: max_hits == 0
+    if (!counts) pcnt = pout;
     if (pin.device != pout.device || pin.dev != pout.dev)
         return ctx->fail(RT_ERR_BAD_ARG, "%s: rays (%s %zu) and %s (%s %zu) must both be host memory or both device memory of the same device", fn,
                          pin.device ? "device memory of context device" : "host memory", pin.device ? pin.dev : (size_t)0, out_name,
                          pout.device ? "device memory of context device" : "host memory", pout.device ? pout.dev : (size_t)0);
+    if (pcnt.device != pout.device || pcnt.dev != pout.dev)
+        return ctx->fail(RT_ERR_BAD_ARG, "%s: rays, hits and counts must all be host memory or all device memory of the same device", fn);
+    const size_t chunk = mh ? RT_QUERY_CHUNK / std::max(mh->max_hits, 1u) : RT_QUERY_CHUNK;
     const bool counters = (flags & RT_QUERY_COUNTERS) != 0;
     const size_t nd = ctx->devs.size();
     std::vector<size_t> first(nd, 0), count(nd, 0);
@@ -67,32 +96,39 @@ int run_query(rt_ctx* ctx, const char* fn, const rt_ray* rays, size_t n, void* o
         for (size_t j = 0; j < nd; j++) first[j] = n * j / nd, count[j] = n * (j + 1) / nd - first[j]; // contiguous ranges, one per device
     const uint8_t* src = reinterpret_cast<const uint8_t*>(rays);
     uint8_t* dst = reinterpret_cast<uint8_t*>(out);
+    const bool all = (flags & RT_QUERY_COUNT_ALL) != 0;
     // every device's range is enqueued before any is waited for
     auto enqueue = [&](size_t j) -> int {
         DeviceState& d = ctx->devs[j];
         HIPCHK(ctx, hipSetDevice(d.device));
         const DevScene sc = scene_for(ctx, d);
-        const size_t chunks = (count[j] + RT_QUERY_CHUNK - 1) / RT_QUERY_CHUNK;
+        const size_t chunks = (count[j] + chunk - 1) / chunk;
         if (int rc = ensure_query_events(ctx, d, 2 * chunks)) return rc;
         if (!pin.device) {
-            const size_t m = std::min<size_t>(count[j], RT_QUERY_CHUNK);
+            const size_t m = std::min<size_t>(count[j], chunk);
             HIPCHK(ctx, d.rq.in.reserve(m * sizeof(rt_ray)));
             HIPCHK(ctx, d.rq.out.reserve(m * out_elem));
+            if (counts) HIPCHK(ctx, d.rq.counts.reserve(m * sizeof(uint32_t)));
         }
         if (counters) HIPCHK(ctx, hipMemsetAsync(d.counters.get(), 0, (RT_CNT_TRI_TESTS + 1) * sizeof(unsigned long long), d.stream));
         for (size_t c = 0; c < chunks; c++) {
-            const size_t off = first[j] + c * RT_QUERY_CHUNK, m = std::min<size_t>(RT_QUERY_CHUNK, first[j] + count[j] - off);
+            const size_t off = first[j] + c * chunk, m = std::min<size_t>(chunk, first[j] + count[j] - off);
             const void* in = src + off * sizeof(rt_ray);
-            void* res = dst + off * out_elem;
+            void* res = out ? dst + off * out_elem : nullptr;
+            uint32_t* res_counts = counts ? counts + off : nullptr;
             if (!pin.device) {
                 HIPCHK(ctx, hipMemcpyAsync(d.rq.in.get(), in, m * sizeof(rt_ray), hipMemcpyHostToDevice, d.stream));
                 in = d.rq.in.get();
                 res = d.rq.out.get();
+                if (counts) res_counts = static_cast<uint32_t*>(d.rq.counts.get());
             }
+            unsigned long long* cnt = counters ? d.counters.get() : nullptr;
             HIPCHK(ctx, hipEventRecord(d.rq_events[2 * c], d.stream));
-            HIPCHK(ctx, rt::launch_ray_query(sc, in, res, (uint32_t)m, out_elem == 1, counters ? d.counters.get() : nullptr, d.stream));
+            if (mh) HIPCHK(ctx, rt::launch_ray_query_all(sc, in, res, res_counts, (uint32_t)m, mh->max_hits, all, cnt, d.stream));
+            else HIPCHK(ctx, rt::launch_ray_query(sc, in, res, (uint32_t)m, out_elem == 1, cnt, d.stream));
             HIPCHK(ctx, hipEventRecord(d.rq_events[2 * c + 1], d.stream));
-            if (!pin.device) HIPCHK(ctx, hipMemcpyAsync(dst + off * out_elem, d.rq.out.get(), m * out_elem, hipMemcpyDeviceToHost, d.stream));
+            if (!pin.device && out) HIPCHK(ctx, hipMemcpyAsync(dst + off * out_elem, res, m * out_elem, hipMemcpyDeviceToHost, d.stream));
+            if (!pin.device && counts) HIPCHK(ctx, hipMemcpyAsync(counts + off, res_counts, m * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
         }
         return RT_OK;
     };
@@ -114,7 +150,7 @@ int run_query(rt_ctx* ctx, const char* fn, const rt_ray* rays, size_t n, void* o
             return ctx->fail(RT_ERR_HIP, "%s: device %d: %s", fn, d.device, hipGetErrorString(e));
         }
         double ms = 0.0;
-        for (size_t c = 0; 2 * c + 1 < d.rq_events.size() && c * RT_QUERY_CHUNK < count[j]; c++) {
+        for (size_t c = 0; 2 * c + 1 < d.rq_events.size() && c * chunk < count[j]; c++) {
             float cm = 0.0f;
             HIPCHK(ctx, hipEventElapsedTime(&cm, d.rq_events[2 * c], d.rq_events[2 * c + 1]));
             ms += cm;
@@ -321,6 +357,11 @@ int rt_intersect(rt_ctx* ctx, const rt_ray* rays, size_t n, rt_hit* hits, uint32
 
 int rt_occluded(rt_ctx* ctx, const rt_ray* rays, size_t n, uint8_t* occluded, uint32_t flags) {
     return run_query(ctx, "rt_occluded", rays, n, occluded, 1, flags);
+}
+
+int rt_intersect_all(rt_ctx* ctx, const rt_ray* rays, size_t n, uint32_t max_hits, rt_hit* hits, uint32_t* counts, uint32_t flags) {
+    const MultiHit mh{max_hits, counts};
+    return run_query(ctx, "rt_intersect_all", rays, n, hits, (size_t)max_hits * sizeof(rt_hit), flags, &mh);
 }
 
 int rt_camera_rays(rt_ctx* ctx, const rt_camera* camera, uint32_t width, uint32_t height, uint32_t mode, rt_ray* out) {

@@ -286,7 +286,7 @@ int rt_render_adaptive(rt_ctx* ctx, const rt_render_params* p, const rt_adaptive
 int rt_read_adaptive(rt_ctx* ctx, rt_adaptive_pixel* out, size_t n_pixels);
 
 /* ---------------------------------------------------------------------------------------------------------------
- * Ray queries: closest hit and occlusion for caller-supplied rays (no reference counterpart; Embree's rtcIntersect /
+ * Ray queries: closest hit, occlusion and the first K hits for caller-supplied rays (no reference counterpart; Embree's rtcIntersect /
  * rtcOccluded are the model).  They trace the uploaded scene with the frames' rules and leave the last frame alone.
  *
  * Range: a triangle or sphere is accepted at tmin < t < tmax, both strict; t is parametric along `direction`, which
@@ -342,6 +342,41 @@ int rt_intersect(rt_ctx* ctx, const rt_ray* rays, size_t n, rt_hit* hits, uint32
 
 /* Any hit of each of the n rays: occluded[i] = 0 or 1. */
 int rt_occluded(rt_ctx* ctx, const rt_ray* rays, size_t n, uint8_t* occluded, uint32_t flags);
+
+/* Multi-hit: the first max_hits hits along each of the n rays, in order (Embree's / OptiX's "all hits" idiom: transparency done by
+ * the caller, depth peeling, thickness, crossing parity), in one walk per ray.
+ * Candidates: a triangle is a candidate when the frames' Moller-Trumbore arithmetic accepts it at tmin < t < tmax, both strict,
+ * tmin raised to RT_MIN_RAY_DISTANCE as for rt_intersect.  A sphere is a candidate at the single t the frames' sphere test gives
+ * for the ray's own tmin (t1 if t1 > tmin, else t2), if that lies in the range: a sphere appears at most once per ray.  Every
+ * triangle has exactly one record in the tree (the builders never split a triangle), so a triangle appears at most once per ray.
+ * Order: ascending t; at equal t bits spheres before triangles, spheres by ascending sphere index, triangles by ascending
+ * original triangle index.  That is the order in which rt_intersect's rules would pick a winner: for max_hits >= 1 ray i's first
+ * record hits[i * max_hits] is bit for bit the rt_intersect record of ray i.
+ * Output: ray i's first min(total, max_hits) candidates in that order as rt_hit records at hits[i * max_hits ..] (ray-major),
+ * t, u, v and prim_id exactly as rt_intersect defines them (u, v from the arithmetic that accepted the triangle, 0 for spheres).
+ * Unused slots are miss records: t = the ray's tmax as given, u = v = 0, prim_id = 0xFFFFFFFF.  max_hits == 1 gives exactly
+ * rt_intersect's bytes, degenerate rays (all misses without a walk, the same degeneracy rules) and an empty scene included.
+ * counts[i] = the number of hit records written for ray i; with RT_QUERY_COUNT_ALL instead the total number of candidates in the
+ * range, which can exceed max_hits (the records written are the same; the walk can then not shrink its range, so it costs more).
+ * `counts` may be NULL unless max_hits == 0.  max_hits == 0 is allowed only with RT_QUERY_COUNT_ALL and a non-NULL counts; `hits`
+ * is then ignored: a pure crossing count.
+ * The result does not depend on the tree in use (device build, host build, RT_PREPARE_QUALITY_TREE, refitted).
+ * Buffers: each pointer is classified as for the other queries; all are host memory, or all device memory of one context device
+ * (rays and hits 16-byte aligned, counts 4-byte aligned), anything else is RT_ERR_BAD_ARG.  Host batches are staged in chunks of
+ * at most RT_QUERY_CHUNK / max(max_hits, 1) rays, so the staged hit records never exceed those of an rt_intersect chunk; a context
+ * over several devices splits the batch into one contiguous range per device.
+ * Errors: n == 0 is RT_OK; a NULL rays, or a NULL hits with max_hits > 0, max_hits > RT_MULTI_HIT_MAX, max_hits == 0 without
+ * RT_QUERY_COUNT_ALL and counts, and unknown flag bits are RT_ERR_BAD_ARG; a call before any upload is RT_ERR_NOT_UPLOADED.
+ * Statistics, synchronisation and side effects as for rt_intersect: synchronous, first waits for an rt_dispatch_tile in flight;
+ * rays = n, the other counts 0, kernel_ms the maximum over devices, node_visits / tri_tests only with RT_QUERY_COUNTERS; the last
+ * frame, the rt_read_* results and a running accumulation are left alone. */
+#define RT_QUERY_COUNT_ALL 2u   /* rt_intersect_all only */
+#define RT_MULTI_HIT_MAX 16u
+
+int rt_intersect_all(rt_ctx* ctx, const rt_ray* rays, size_t n, uint32_t max_hits,
+                     rt_hit* hits,      /* n * max_hits records, ray-major: ray i's hits at hits[i*max_hits ..] */
+                     uint32_t* counts,  /* n entries; may be NULL unless max_hits == 0 */
+                     uint32_t flags);   /* RT_QUERY_COUNTERS | RT_QUERY_COUNT_ALL */
 
 /* The width x height pixel-centre camera rays of mode 0 (RT_MODE_LEGACY: direction normalised twice, as Ray::new) or
  * mode 1 (RT_MODE_WAVEFRONT: once), computed by the frames' own ray generation; any other mode is RT_ERR_BAD_ARG.
