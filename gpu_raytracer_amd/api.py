@@ -35,6 +35,7 @@ QUERY_COUNTERS = 1  # RT_QUERY_COUNTERS of rt_intersect / rt_occluded
 QUERY_CHUNK = 4194304  # RT_QUERY_CHUNK: host batches are staged in chunks of at most this many rays
 QUERY_COUNT_ALL = 2  # RT_QUERY_COUNT_ALL of rt_intersect_all: counts are all candidates in the range, not the records written
 MULTI_HIT_MAX = 16  # RT_MULTI_HIT_MAX: the most hits rt_intersect_all lists per ray
+AO_MAX_SAMPLES = 4096  # RT_AO_MAX_SAMPLES: the most samples rt_ambient_occlusion takes per point
 UPDATE_REBUILD = 1  # RT_UPDATE_REBUILD of rt_update_geometry
 AOV_SAMPLES_PER_LAUNCH = T.AOV_SAMPLES_PER_LAUNCH  # RT_AOV_SAMPLES_PER_LAUNCH: rt_aovs traces at most this many samples per kernel
 DENOISE_DEMODULATE = T.DENOISE_DEMODULATE  # RT_DENOISE_DEMODULATE of rt_denoise_params.flags
@@ -52,6 +53,7 @@ ABI_SYMBOLS = [
     "rt_read_rgb32f", "rt_read_rgba8_channels", "rt_read_rgba8_combined", "rt_read_hits",
     "rt_get_stats", "rt_last_error", "rt_destroy", "rt_version",
     "rt_intersect", "rt_occluded", "rt_camera_rays", "rt_intersect_all",
+    "rt_surface", "rt_ambient_occlusion",
     "rt_update_geometry",
     "rt_accumulated_samples",
     "rt_aovs", "rt_sample_rays", "rt_denoise",
@@ -95,7 +97,7 @@ def _p(a):
     return C.c_void_p(a.ctypes.data) if a is not None and a.size else C.c_void_p(0)
 
 
-# -- ray batches (rt_intersect / rt_occluded / rt_intersect_all / rt_camera_rays) ---------------------------------------------------------
+# -- ray batches (rt_intersect / rt_occluded / rt_intersect_all / rt_surface / rt_camera_rays) ---------------------------------------------------------
 # A batch is a C-contiguous float32 array of shape (N, 8), one rt_ray per row: ox oy oz tmin dx dy dz tmax; numpy, or a torch
 # tensor on the CPU or on a device of the context.  torch is imported only when a tensor is handed in.
 
@@ -150,15 +152,15 @@ def _check_hit_lists(a, n, max_hits):
         raise ValueError(f"out: {a.shape[0]} rows for {n} rays")
 
 
-def _check_counts(a, n):
-    """Raises unless `a` is a C-contiguous (n,) array of rt_intersect_all's counts: uint32 for numpy, int32 for torch."""
+def _check_counts(a, n, what="rays"):
+    """Raises unless `a` is a C-contiguous (n,) array of counts (rt_intersect_all's, rt_ambient_occlusion's): uint32 for numpy, int32 for torch."""
     _check_kind_dtype(a, "counts", "int32" if _is_torch(a) else "uint32")
     if len(a.shape) != 1:
         raise ValueError(f"counts: shape {tuple(a.shape)}, expected (N,)")
     if not _contiguous(a):
         raise ValueError("counts: not C-contiguous")
     if a.shape[0] != n:
-        raise ValueError(f"counts: {a.shape[0]} rows for {n} rays")
+        raise ValueError(f"counts: {a.shape[0]} rows for {n} {what}")
 
 
 def _addr(a):
@@ -204,6 +206,17 @@ def split_hits(hits):
         prim = hits[:, 3].contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
         return hits[:, 0], hits[:, 1], hits[:, 2], prim
     return hits[:, 0], hits[:, 1], hits[:, 2], np.ascontiguousarray(hits[:, 3]).view(np.uint32)
+
+
+def split_surface(points):
+    """(N, 8) surface records (rt_surface_point) -> (position (N, 3), prim_id (N,), normal (N, 3), material_id (N,)).  The ids are the
+    records' uint32 words: uint32 for numpy, int64 for torch (a miss is 4294967295 = PRIM_MISS), as split_hits gives prim."""
+    if _is_torch(points):
+        import torch
+        ids = [points[:, c].contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF for c in (3, 7)]
+    else:
+        ids = [np.ascontiguousarray(points[:, c]).view(np.uint32) for c in (3, 7)]
+    return points[:, 0:3], ids[0], points[:, 4:7], ids[1]
 
 
 def split_aovs(aovs):
@@ -518,6 +531,52 @@ class Context:
         flags = (QUERY_COUNTERS if counters else 0) | (QUERY_COUNT_ALL if count_all else 0)
         self._check(self.lib.rt_intersect_all(self._h, _addr(rays), C.c_size_t(n), C.c_uint32(max_hits),
                                               _addr(out) if out is not None else C.c_void_p(0), _addr(counts), C.c_uint32(flags)))
+        return out, counts
+
+    def surface(self, rays, out=None, counters=False):
+        """rt_surface: the hit point, face-forwarded geometric normal, prim_id and material_id of each ray's closest hit -> (N, 8)
+        float32 rt_surface_point records (split_surface), same kind and device as `rays`; a miss is all zero but prim_id = PRIM_MISS."""
+        return self._query("rt_surface", rays, out, 8, "float32", counters)
+
+    def ambient_occlusion(self, points, samples, seed=0, max_distance=float("inf"), bias=1e-3, out=None, counts=None, counters=False):
+        """rt_ambient_occlusion: `samples` (1 .. AO_MAX_SAMPLES) cosine-distributed occlusion rays from each record of an (N, 8) batch
+        of surface points (surface()) -> (visibility, counts), same kind and device as `points`.  visibility: (N,) float32, the
+        fraction of a point's samples that reached max_distance; counts: (N,) uint32 (numpy) / int32 (torch), their number.  Sample s
+        of point i draws from rng_for(seed + i, s); its ray starts at position + normal * bias."""
+        n = _check_batch(points, "points", 8, "float32")
+        if isinstance(samples, bool) or not isinstance(samples, (int, np.integer)) or not 1 <= samples <= AO_MAX_SAMPLES:
+            raise ValueError(f"samples: {samples!r}, expected an integer in 1 .. {AO_MAX_SAMPLES}")
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed <= 0xFFFFFFFF:
+            raise ValueError(f"seed: {seed!r}, expected an integer in 0 .. 2^32 - 1")
+        try:
+            max_distance, bias = float(max_distance), float(bias)
+        except (TypeError, ValueError):
+            raise ValueError(f"max_distance / bias: {max_distance!r}, {bias!r}, expected numbers") from None
+        if not max_distance > 0:
+            raise ValueError(f"max_distance: {max_distance!r}, expected > 0 (inf allowed)")
+        if not (np.isfinite(bias) and bias >= 0):
+            raise ValueError(f"bias: {bias!r}, expected finite and >= 0")
+        torch_kind = _is_torch(points)
+        for name, a in (("out", out), ("counts", counts)):
+            if a is not None and _is_torch(a) != torch_kind:
+                raise TypeError(f"{name}: must be the same kind (numpy / torch) as points")
+        if out is None:
+            out = _empty_like_batch(points, (n,), "float32")
+        elif _check_batch(out, "out", 0, "float32") != n:
+            raise ValueError(f"out: {out.shape[0]} rows for {n} points")
+        if counts is None:
+            if torch_kind:
+                import torch
+                counts = torch.empty((n,), dtype=torch.int32, device=points.device)
+            else:
+                counts = np.empty((n,), np.uint32)
+        else:
+            _check_counts(counts, n, "points")
+        ap = np.zeros((), dtype=T.AO_PARAMS)
+        ap["samples"], ap["seed"], ap["max_distance"], ap["bias"] = int(samples), int(seed), max_distance, bias
+        ap["flags"] = QUERY_COUNTERS if counters else 0
+        _sync_torch(points, out, counts)
+        self._check(self.lib.rt_ambient_occlusion(self._h, _addr(points), C.c_size_t(n), _p(ap), _addr(out), _addr(counts)))
         return out, counts
 
     def camera_rays(self, width, height, camera, mode=MODE_LEGACY, out=None):

@@ -28,6 +28,7 @@
 #include "ray_query.h"
 #include "refit.h"
 #include "shadow_grid.h"
+#include "surface_query.h"
 #include "wavefront.h"
 
 #define HIPCHK(ctx, call)                                                                                       \
@@ -135,6 +136,7 @@ struct DeviceState {
     uint32_t wf_spp = 0;         // spp the current wavefront allocation was sized for
     struct Query { // ray queries: staging of host batches (rays in, hit records / bytes out, rt_intersect_all's counts), grown on demand
         DevMem in, out, counts;
+        DevBuf<uint32_t> ao; // rt_ambient_occlusion: the per-point counts its kernel adds to, for host and device batches alike
     } rq;
     // RT_FLAG_ACCUMULATE: the running sum of the context's accumulation over this device's pixels (DevTargets::run_sum), frame-pixel
     // layout, w x h x 16 bytes.  Outlives the pipeline's WfBuffers (re-sized with the batch); made by the first accumulating call.

@@ -1,5 +1,6 @@
 // rt_query.cpp — calls that trace or filter outside a frame: ray queries (rt_hip.h "Ray queries": rt_intersect, rt_occluded,
-// rt_intersect_all, rt_camera_rays) and the image passes ("Feature buffers (AOVs) and denoising": rt_aovs, rt_sample_rays, rt_denoise; kernels in
+// rt_intersect_all, rt_camera_rays), surface queries ("Surface queries": rt_surface, rt_ambient_occlusion; kernels in
+// surface_query.hip) and the image passes ("Feature buffers (AOVs) and denoising": rt_aovs, rt_sample_rays, rt_denoise; kernels in
 // denoise.hip).  None of them touches the frame targets, the tile shares rt_read_* gather, or the running image of an accumulation.
 #include "rt_internal.h"
 
@@ -48,14 +49,15 @@ struct MultiHit {
     uint32_t* counts; // may be null
 };
 
-// Every query kind: out_elem = the bytes per ray at `out`: 16 (rt_hit), 1 (occluded byte), or with `mh` max_hits * 16 (`out` is then
-// ignored when that is 0).  Host batches go in chunks of RT_QUERY_CHUNK rays, with `mh` RT_QUERY_CHUNK / max(max_hits, 1): the hit
+// Every query kind: out_elem = the bytes per ray at `out`: 16 (rt_hit), 1 (occluded byte), with `surface` 32 (rt_surface_point), or
+// with `mh` max_hits * 16 (`out` is then ignored when that is 0).  Host batches go in chunks of RT_QUERY_CHUNK rays, with `mh` RT_QUERY_CHUNK / max(max_hits, 1): the hit
 // records of a chunk never need more staging than an rt_intersect chunk's.
-int run_query(rt_ctx* ctx, const char* fn, const rt_ray* rays, size_t n, void* out, size_t out_elem, uint32_t flags, const MultiHit* mh = nullptr) {
+int run_query(rt_ctx* ctx, const char* fn, const rt_ray* rays, size_t n, void* out, size_t out_elem, uint32_t flags, const MultiHit* mh = nullptr,
+              bool surface = false) {
     const double w0 = now_ms();
     if (!ctx) return RT_ERR_BAD_ARG;
     if (n == 0) return RT_OK;
-    const char* out_name = out_elem == 1 ? "occluded" : "hits";
+    const char* out_name = out_elem == 1 ? "occluded" : surface ? "out" : "hits";
     uint32_t known = RT_QUERY_COUNTERS;
     if (mh) {
         known |= RT_QUERY_COUNT_ALL;
@@ -125,6 +127,7 @@ int run_query(rt_ctx* ctx, const char* fn, const rt_ray* rays, size_t n, void* o
             unsigned long long* cnt = counters ? d.counters.get() : nullptr;
             HIPCHK(ctx, hipEventRecord(d.rq_events[2 * c], d.stream));
             if (mh) HIPCHK(ctx, rt::launch_ray_query_all(sc, in, res, res_counts, (uint32_t)m, mh->max_hits, all, cnt, d.stream));
+            else if (surface) HIPCHK(ctx, rt::launch_surface_query(sc, in, res, (uint32_t)m, cnt, d.stream));
             else HIPCHK(ctx, rt::launch_ray_query(sc, in, res, (uint32_t)m, out_elem == 1, cnt, d.stream));
             HIPCHK(ctx, hipEventRecord(d.rq_events[2 * c + 1], d.stream));
             if (!pin.device && out) HIPCHK(ctx, hipMemcpyAsync(dst + off * out_elem, res, m * out_elem, hipMemcpyDeviceToHost, d.stream));
@@ -165,6 +168,121 @@ int run_query(rt_ctx* ctx, const char* fn, const rt_ray* rays, size_t n, void* o
     }
     rt_stats& st = ctx->stats;
     st.rays = n;
+    st.primary_rays = st.continuation_rays = st.shadow_rays = st.pixels = 0;
+    st.node_visits = counters ? nodes : 0;
+    st.tri_tests = counters ? tris : 0;
+    st.kernel_ms = kernel_ms;
+    st.wall_ms = now_ms() - w0;
+    return RT_OK;
+}
+
+// rt_ambient_occlusion: run_query's shape with points for rays, samples lanes per point and two optional outputs.  Every chunk (host
+// batches: max(1, RT_QUERY_CHUNK / samples) points; a device batch: RT_AO_DEVICE_CHUNK) zeroes the device's per-point counts, lets the
+// kernel add to them and finishes them into visibility and counts; the chunk's first index goes to the kernel, so a point's seed is
+// that of its place in the caller's array.
+constexpr size_t RT_AO_DEVICE_CHUNK = (size_t)1 << 24; // points of a device batch per chunk: bounds the counts beside them (64 MiB)
+
+int run_ao(rt_ctx* ctx, const rt_surface_point* points, size_t n, const rt_ao_params* p, float* visibility, uint32_t* unoccluded) {
+    const char* fn = "rt_ambient_occlusion";
+    const double w0 = now_ms();
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (n == 0) return RT_OK;
+    if (!points || !p) return ctx->fail(RT_ERR_BAD_ARG, "%s: %s is NULL with n = %zu", fn, !points ? "points" : "params", n);
+    if (!visibility && !unoccluded) return ctx->fail(RT_ERR_BAD_ARG, "%s: visibility and unoccluded are both NULL with n = %zu", fn, n);
+    if (p->samples < 1 || p->samples > RT_AO_MAX_SAMPLES) return ctx->fail(RT_ERR_BAD_ARG, "%s: samples %u (1 .. %u)", fn, p->samples, RT_AO_MAX_SAMPLES);
+    if (!(p->max_distance > 0.0f)) return ctx->fail(RT_ERR_BAD_ARG, "%s: max_distance %g (> 0, +inf allowed)", fn, (double)p->max_distance);
+    if (!std::isfinite(p->bias) || p->bias < 0.0f) return ctx->fail(RT_ERR_BAD_ARG, "%s: bias %g (finite and >= 0)", fn, (double)p->bias);
+    if (p->flags & ~RT_QUERY_COUNTERS) return ctx->fail(RT_ERR_BAD_ARG, "%s: unknown flag bits 0x%x", fn, p->flags & ~RT_QUERY_COUNTERS);
+    if (!ctx->uploaded) return ctx->fail(RT_ERR_NOT_UPLOADED, "%s: no scene uploaded", fn);
+    if (int rcp = sync_pending(ctx)) return rcp;
+    QueryPtr pin, pvis, pcnt;
+    if (int rc = classify_ptr(ctx, fn, "points", points, pin)) return rc;
+    if (visibility) {
+        if (int rc = classify_ptr(ctx, fn, "visibility", visibility, pvis, 4)) return rc;
+    }
+    if (unoccluded) {
+        if (int rc = classify_ptr(ctx, fn, "unoccluded", unoccluded, pcnt, 4)) return rc;
+    }
+    if (!visibility) pvis = pcnt;
+    if (!unoccluded) pcnt = pvis;
+    if (pin.device != pvis.device || pin.dev != pvis.dev || pin.device != pcnt.device || pin.dev != pcnt.dev)
+        return ctx->fail(RT_ERR_BAD_ARG, "%s: points, visibility and unoccluded must all be host memory or all device memory of the same device", fn);
+    const rt::AoParams ap{p->samples, p->seed, p->max_distance, p->bias};
+    const size_t chunk = pin.device ? RT_AO_DEVICE_CHUNK : std::max<size_t>(1, RT_QUERY_CHUNK / p->samples);
+    const bool counters = (p->flags & RT_QUERY_COUNTERS) != 0;
+    const size_t nd = ctx->devs.size();
+    std::vector<size_t> first(nd, 0), count(nd, 0);
+    if (pin.device) count[pin.dev] = n; // a device batch runs where it lives
+    else
+        for (size_t j = 0; j < nd; j++) first[j] = n * j / nd, count[j] = n * (j + 1) / nd - first[j]; // contiguous ranges, one per device
+    // every device's range is enqueued before any is waited for
+    auto enqueue = [&](size_t j) -> int {
+        DeviceState& d = ctx->devs[j];
+        HIPCHK(ctx, hipSetDevice(d.device));
+        const DevScene sc = scene_for(ctx, d);
+        const size_t chunks = (count[j] + chunk - 1) / chunk;
+        if (int rc = ensure_query_events(ctx, d, 2 * chunks)) return rc;
+        const size_t most = std::min<size_t>(count[j], chunk);
+        HIPCHK(ctx, d.rq.ao.reserve(most * sizeof(uint32_t)));
+        if (!pin.device) {
+            HIPCHK(ctx, d.rq.in.reserve(most * sizeof(rt_surface_point)));
+            if (visibility) HIPCHK(ctx, d.rq.out.reserve(most * sizeof(float)));
+        }
+        if (counters) HIPCHK(ctx, hipMemsetAsync(d.counters.get(), 0, (RT_CNT_TRI_TESTS + 1) * sizeof(unsigned long long), d.stream));
+        for (size_t c = 0; c < chunks; c++) {
+            const size_t off = first[j] + c * chunk, m = std::min<size_t>(chunk, first[j] + count[j] - off);
+            const void* in = points + off;
+            float* vis = visibility ? visibility + off : nullptr;
+            uint32_t* cnt_out = unoccluded ? unoccluded + off : nullptr;
+            if (!pin.device) {
+                HIPCHK(ctx, hipMemcpyAsync(d.rq.in.get(), in, m * sizeof(rt_surface_point), hipMemcpyHostToDevice, d.stream));
+                in = d.rq.in.get();
+                vis = visibility ? static_cast<float*>(d.rq.out.get()) : nullptr;
+                cnt_out = nullptr; // the counts go to the host from where the kernel left them
+            }
+            HIPCHK(ctx, hipEventRecord(d.rq_events[2 * c], d.stream));
+            HIPCHK(ctx, hipMemsetAsync(d.rq.ao.get(), 0, m * sizeof(uint32_t), d.stream));
+            HIPCHK(ctx, rt::launch_ao(sc, in, off, (uint32_t)m, ap, d.rq.ao.get(), counters ? d.counters.get() : nullptr, d.stream));
+            if (vis || cnt_out) HIPCHK(ctx, rt::launch_ao_finish(d.rq.ao.get(), (uint32_t)m, ap.samples, vis, cnt_out, d.stream));
+            HIPCHK(ctx, hipEventRecord(d.rq_events[2 * c + 1], d.stream));
+            if (!pin.device && visibility) HIPCHK(ctx, hipMemcpyAsync(visibility + off, vis, m * sizeof(float), hipMemcpyDeviceToHost, d.stream));
+            if (!pin.device && unoccluded) HIPCHK(ctx, hipMemcpyAsync(unoccluded + off, d.rq.ao.get(), m * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
+        }
+        return RT_OK;
+    };
+    for (size_t j = 0; j < nd; j++)
+        if (count[j] > 0)
+            if (int rc = enqueue(j)) {
+                drain_streams(ctx);
+                return rc;
+            }
+    double kernel_ms = 0.0;
+    unsigned long long nodes = 0, tris = 0;
+    for (size_t j = 0; j < nd; j++) {
+        if (count[j] == 0) continue;
+        DeviceState& d = ctx->devs[j];
+        hipError_t e = hipSetDevice(d.device);
+        if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
+        if (e != hipSuccess) {
+            drain_streams(ctx);
+            return ctx->fail(RT_ERR_HIP, "%s: device %d: %s", fn, d.device, hipGetErrorString(e));
+        }
+        double ms = 0.0;
+        for (size_t c = 0; c * chunk < count[j]; c++) {
+            float cm = 0.0f;
+            HIPCHK(ctx, hipEventElapsedTime(&cm, d.rq_events[2 * c], d.rq_events[2 * c + 1]));
+            ms += cm;
+        }
+        kernel_ms = std::max(kernel_ms, ms);
+        if (counters) {
+            unsigned long long cn[RT_CNT_TRI_TESTS + 1];
+            HIPCHK(ctx, hipMemcpy(cn, d.counters.get(), sizeof cn, hipMemcpyDeviceToHost));
+            nodes += cn[RT_CNT_NODE_VISITS];
+            tris += cn[RT_CNT_TRI_TESTS];
+        }
+    }
+    rt_stats& st = ctx->stats;
+    st.rays = (uint64_t)n * p->samples;
     st.primary_rays = st.continuation_rays = st.shadow_rays = st.pixels = 0;
     st.node_visits = counters ? nodes : 0;
     st.tri_tests = counters ? tris : 0;
@@ -362,6 +480,14 @@ int rt_occluded(rt_ctx* ctx, const rt_ray* rays, size_t n, uint8_t* occluded, ui
 int rt_intersect_all(rt_ctx* ctx, const rt_ray* rays, size_t n, uint32_t max_hits, rt_hit* hits, uint32_t* counts, uint32_t flags) {
     const MultiHit mh{max_hits, counts};
     return run_query(ctx, "rt_intersect_all", rays, n, hits, (size_t)max_hits * sizeof(rt_hit), flags, &mh);
+}
+
+int rt_surface(rt_ctx* ctx, const rt_ray* rays, size_t n, rt_surface_point* out, uint32_t flags) {
+    return run_query(ctx, "rt_surface", rays, n, out, sizeof(rt_surface_point), flags, nullptr, true);
+}
+
+int rt_ambient_occlusion(rt_ctx* ctx, const rt_surface_point* points, size_t n, const rt_ao_params* params, float* visibility, uint32_t* unoccluded) {
+    return run_ao(ctx, points, n, params, visibility, unoccluded);
 }
 
 int rt_camera_rays(rt_ctx* ctx, const rt_camera* camera, uint32_t width, uint32_t height, uint32_t mode, rt_ray* out) {

@@ -224,7 +224,7 @@ int rt_get_stats(rt_ctx* ctx, rt_stats* out);
  * a new one at sample 0 by itself, as RT_FLAG_ACCUMULATE_RESTART does.  The other RT_FLAG_* bits change no bits and may differ.
  * The running image ends (the next accumulating call starts at 0) with rt_upload_scene*, rt_update_geometry, rt_dispatch_tile, any
  * rt_render without RT_FLAG_ACCUMULATE and an accumulating call that fails once it has passed its argument checks.  It survives rt_prepare,
- * rt_upload_textures, the ray queries, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
+ * rt_upload_textures, the ray queries, the surface queries, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
  * Limit: RT_ACCUMULATE_MAX_SAMPLES samples (where the float sample count stops being exact); a call that would pass it is RT_ERR_BAD_ARG
  * and leaves the running image as it was.  rt_stats describes the call alone (its segments, pixels, kernel_ms).
  * A context over several devices, and a tile_rank / tile_world share, accumulates its own share of the pixels.
@@ -383,6 +383,74 @@ int rt_intersect_all(rt_ctx* ctx, const rt_ray* rays, size_t n, uint32_t max_hit
  * Row-major, y down, tmin = RT_MIN_RAY_DISTANCE, tmax = FLT_MAX.  `out` (width * height records) may be host or
  * device memory, classified as for the queries.  Needs no scene.  Synchronous. */
 int rt_camera_rays(rt_ctx* ctx, const rt_camera* camera, uint32_t width, uint32_t height, uint32_t mode, rt_ray* out);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Surface queries: what a caller needs AT the hit - the point, the geometric normal and the material - and the ambient occlusion
+ * of such points (no reference counterpart; Embree's rtcInterpolate after rtcIntersect and the ambient-occlusion pass of every
+ * baker are the model).  Both are defined by composing calls above, so their results follow the device's records (after
+ * rt_update_geometry too) and the device's arithmetic.
+ *
+ * rt_surface: ray i's closest hit is exactly rt_intersect's (range, tmin floor, degenerate rays, tie rule, spheres first).  On a hit:
+ *   position = origin + direction * t (one multiply, one add per component, as Ray::at); normal = the geometric normal of the
+ *   primitive (triangle: normalize(cross(e1, e2)); sphere: normalize(position - centre)) face-forwarded against the ray:
+ *   dot(normal, direction) < 0 ? normal : -normal, the normal rt_aovs reports; prim_id as rt_hit.prim_id; material_id = the
+ *   record's material id, not checked against the material table.  On a miss, a degenerate ray included: position = normal = 0,
+ *   prim_id = 0xFFFFFFFF, material_id = 0.
+ * rt_ambient_occlusion: for point i (its index in the caller's array) with position P and normal N, and sample s < samples:
+ *   rng = rng_for(seed + i (mod 2^32), s) (the frames' generator), u1 = next_f32(), u2 = next_f32(),
+ *   direction = normalize(N + unit_vector(u1, u2)) (the cosine lobe of the extended mode's diffuse bounce), origin = P + N * bias,
+ *   tmin = RT_MIN_RAY_DISTANCE, tmax = max_distance, and this ray is traced by rt_occluded's rules, its degenerate-ray rule
+ *   included (a zero-length N + unit_vector is not occluded).  unoccluded[i] = the samples that were not occluded,
+ *   visibility[i] = (float)unoccluded[i] / (float)samples.  So unoccluded[i] = samples - the sum of rt_occluded over those rays,
+ *   whatever the tree, the device count, the kind of memory and the chunking.  A point with a non-finite position or normal
+ *   component or a zero normal traces nothing: unoccluded = samples, visibility = 1.  N is used as given (rt_surface gives unit
+ *   normals); prim_id and material_id are ignored.
+ *   params: samples 1 .. RT_AO_MAX_SAMPLES; max_distance > 0, +inf allowed (NaN or <= 0: RT_ERR_BAD_ARG); bias finite and >= 0
+ *   (the frames offset their secondary segments by 1e-3); flags RT_QUERY_COUNTERS; _pad ignored.
+ * Buffers: each pointer is classified as for the ray queries; all are host memory, or all device memory of one context device
+ * (records 16-byte aligned, visibility and unoccluded 4-byte aligned), anything else is RT_ERR_BAD_ARG.  Host batches are staged in
+ * chunks of at most RT_QUERY_CHUNK rays (rt_surface) or max(1, RT_QUERY_CHUNK / samples) points (rt_ambient_occlusion); a context
+ * over several devices splits the batch into one contiguous range per device.  Either of visibility and unoccluded may be NULL.
+ * Errors: n == 0 is RT_OK; a NULL rays / out / points / params, visibility and unoccluded both NULL, bad parameters and unknown flag
+ * bits are RT_ERR_BAD_ARG and change nothing; a call before any upload is RT_ERR_NOT_UPLOADED.
+ * Statistics, synchronisation and side effects as for rt_intersect: synchronous, first waits for an rt_dispatch_tile in flight;
+ * rays = n (rt_surface) or n * samples (rt_ambient_occlusion), the other counts 0, kernel_ms the maximum over devices,
+ * node_visits / tri_tests only with RT_QUERY_COUNTERS; the last frame, the rt_read_* results and a running accumulation are left alone.
+ * --------------------------------------------------------------------------------------------------------------- */
+typedef struct rt_surface_point {
+    float position[3];
+    uint32_t prim_id;     /* as rt_hit.prim_id; 0xFFFFFFFF = miss */
+    float normal[3];
+    uint32_t material_id; /* the record's material id, unchecked; 0 on a miss */
+} rt_surface_point; /* 32 bytes */
+
+RT_STATIC_ASSERT(sizeof(rt_surface_point) == 32, "rt_surface_point is 32 B");
+RT_STATIC_ASSERT(offsetof(rt_surface_point, prim_id) == 12 && offsetof(rt_surface_point, normal) == 16 && offsetof(rt_surface_point, material_id) == 28,
+                 "rt_surface_point offsets");
+
+#define RT_AO_MAX_SAMPLES 4096u
+
+typedef struct rt_ao_params {
+    uint32_t samples;   /* 1 .. RT_AO_MAX_SAMPLES */
+    uint32_t seed;
+    float max_distance; /* > 0, +inf allowed */
+    float bias;         /* finite, >= 0: the origin's offset along the normal */
+    uint32_t flags;     /* RT_QUERY_COUNTERS */
+    uint32_t _pad[3];
+} rt_ao_params; /* 32 bytes */
+
+RT_STATIC_ASSERT(sizeof(rt_ao_params) == 32, "rt_ao_params is 32 B");
+RT_STATIC_ASSERT(offsetof(rt_ao_params, seed) == 4 && offsetof(rt_ao_params, max_distance) == 8 && offsetof(rt_ao_params, bias) == 12 &&
+                     offsetof(rt_ao_params, flags) == 16,
+                 "rt_ao_params offsets");
+
+/* Point, face-forwarded geometric normal and material of the closest hit of each of the n rays. */
+int rt_surface(rt_ctx* ctx, const rt_ray* rays, size_t n, rt_surface_point* out, uint32_t flags);
+
+/* Ambient occlusion of the n points: params->samples cosine-distributed occlusion rays each. */
+int rt_ambient_occlusion(rt_ctx* ctx, const rt_surface_point* points, size_t n, const rt_ao_params* params,
+                         float* visibility,     /* n entries; may be NULL */
+                         uint32_t* unoccluded); /* n entries; may be NULL, not both */
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Geometry updates: new positions for the uploaded scene, in place (no reference counterpart; Embree's refit build,
