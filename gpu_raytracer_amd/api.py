@@ -36,6 +36,8 @@ QUERY_CHUNK = 4194304  # RT_QUERY_CHUNK: host batches are staged in chunks of at
 QUERY_COUNT_ALL = 2  # RT_QUERY_COUNT_ALL of rt_intersect_all: counts are all candidates in the range, not the records written
 MULTI_HIT_MAX = 16  # RT_MULTI_HIT_MAX: the most hits rt_intersect_all lists per ray
 AO_MAX_SAMPLES = 4096  # RT_AO_MAX_SAMPLES: the most samples rt_ambient_occlusion takes per point
+DIRECT_AMBIENT, DIRECT_NO_SHADOWS, DIRECT_NO_SHADOW_GRID = 4, 8, 16  # RT_DIRECT_* of rt_direct_light_params.flags
+DIRECT_MAX_LIGHTS = 32  # RT_DIRECT_MAX_LIGHTS: rt_direct_light's lit_mask has one bit per light
 UPDATE_REBUILD = 1  # RT_UPDATE_REBUILD of rt_update_geometry
 AOV_SAMPLES_PER_LAUNCH = T.AOV_SAMPLES_PER_LAUNCH  # RT_AOV_SAMPLES_PER_LAUNCH: rt_aovs traces at most this many samples per kernel
 DENOISE_DEMODULATE = T.DENOISE_DEMODULATE  # RT_DENOISE_DEMODULATE of rt_denoise_params.flags
@@ -53,7 +55,7 @@ ABI_SYMBOLS = [
     "rt_read_rgb32f", "rt_read_rgba8_channels", "rt_read_rgba8_combined", "rt_read_hits",
     "rt_get_stats", "rt_last_error", "rt_destroy", "rt_version",
     "rt_intersect", "rt_occluded", "rt_camera_rays", "rt_intersect_all",
-    "rt_surface", "rt_ambient_occlusion",
+    "rt_surface", "rt_ambient_occlusion", "rt_direct_light",
     "rt_update_geometry",
     "rt_accumulated_samples",
     "rt_aovs", "rt_sample_rays", "rt_denoise",
@@ -217,6 +219,17 @@ def split_surface(points):
     else:
         ids = [np.ascontiguousarray(points[:, c]).view(np.uint32) for c in (3, 7)]
     return points[:, 0:3], ids[0], points[:, 4:7], ids[1]
+
+
+def split_lighting(lighting):
+    """(N, 4) lighting records (rt_lighting) -> (radiance (N, 3), lit_mask (N,)).  lit_mask is the records' uint32 word: uint32 for
+    numpy, int64 for torch; bit li set: light li entered the sum."""
+    if _is_torch(lighting):
+        import torch
+        mask = lighting[:, 3].contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    else:
+        mask = np.ascontiguousarray(lighting[:, 3]).view(np.uint32)
+    return lighting[:, 0:3], mask
 
 
 def split_aovs(aovs):
@@ -578,6 +591,33 @@ class Context:
         _sync_torch(points, out, counts)
         self._check(self.lib.rt_ambient_occlusion(self._h, _addr(points), C.c_size_t(n), _p(ap), _addr(out), _addr(counts)))
         return out, counts
+
+    def direct_light(self, points, bias=1e-3, ambient=False, shadows=True, use_grids=True, out=None, counters=False):
+        """rt_direct_light: the scene's lights at each record of an (N, 8) batch of surface points (surface()), with shadows -> (N, 4)
+        float32 rt_lighting records (split_lighting: radiance, lit_mask), same kind and device as `points`.  The normal is used as
+        given: surface()'s face-forwarded one lights the side the ray arrived on.  ambient: add 0.1 * albedo first (the frames'
+        terminal vertex); shadows=False: no shadow segments; use_grids=False: every segment walks the tree (same results)."""
+        n = _check_batch(points, "points", 8, "float32")
+        try:
+            bias = float(bias)
+        except (TypeError, ValueError):
+            raise ValueError(f"bias: {bias!r}, expected a number") from None
+        if not (np.isfinite(bias) and bias >= 0):
+            raise ValueError(f"bias: {bias!r}, expected finite and >= 0")
+        if out is None:
+            out = _empty_like_batch(points, (n, 4), "float32")
+        else:
+            if _is_torch(out) != _is_torch(points):
+                raise TypeError("out: must be the same kind (numpy / torch) as points")
+            if _check_batch(out, "out", 4, "float32") != n:
+                raise ValueError(f"out: {out.shape[0]} rows for {n} points")
+        dp = np.zeros((), dtype=T.DIRECT_LIGHT_PARAMS)
+        dp["bias"] = bias
+        dp["flags"] = ((DIRECT_AMBIENT if ambient else 0) | (0 if shadows else DIRECT_NO_SHADOWS) | (0 if use_grids else DIRECT_NO_SHADOW_GRID)
+                       | (QUERY_COUNTERS if counters else 0))
+        _sync_torch(points, out)
+        self._check(self.lib.rt_direct_light(self._h, _addr(points), C.c_size_t(n), _p(dp), _addr(out)))
+        return out
 
     def camera_rays(self, width, height, camera, mode=MODE_LEGACY, out=None):
         """rt_camera_rays: the width x height pixel-centre rays of mode 0/1 as a (width * height, 8) batch, row-major, y down.

@@ -182,7 +182,8 @@ int rt_debug_counters(rt_ctx* ctx, unsigned long long out[8]) {
 
 // Development aid: what the light grids (shadow_grid.h) of the first device look like.  light < n_lights: out = {kind (0: refused), cells per
 // side, entries, near-list length, longest list, cells left to the BVH, cells with a list, 0}; light == 0xFFFFFFFF: out = {lights with a grid, all
-// entries, bytes, shadow segments the grids answered in the last frame rendered with RT_FLAG_COUNTERS, list entries read, 0, 0, 0}.
+// entries, bytes, shadow segments the grids answered in the last frame rendered with RT_FLAG_COUNTERS or the last rt_direct_light with
+// RT_QUERY_COUNTERS, list entries read, 0, 0, 0}.
 int rt_debug_shadow_grid(rt_ctx* ctx, uint32_t light, unsigned long long out[8]) {
     if (!ctx || !out) return RT_ERR_BAD_ARG;
     for (int k = 0; k < 8; k++) out[k] = 0;

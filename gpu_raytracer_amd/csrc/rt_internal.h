@@ -23,6 +23,7 @@
 #include "denoise.h"
 #include "device_build.h"
 #include "device_layout.h"
+#include "direct_light.h"
 #include "half.h"
 #include "kernels.h"
 #include "ray_query.h"
@@ -134,7 +135,7 @@ struct DeviceState {
     } pipe;
     bool used_two_lanes = false; // the last pipeline frame ran on two lanes (its allocation is reused by a frame of the same shape)
     uint32_t wf_spp = 0;         // spp the current wavefront allocation was sized for
-    struct Query { // ray queries: staging of host batches (rays in, hit records / bytes out, rt_intersect_all's counts), grown on demand
+    struct Query { // ray, surface and direct-light queries: staging of host batches (rays or points in, records / bytes out, rt_intersect_all's counts), grown on demand
         DevMem in, out, counts;
         DevBuf<uint32_t> ao; // rt_ambient_occlusion: the per-point counts its kernel adds to, for host and device batches alike
     } rq;
@@ -182,7 +183,7 @@ struct rt_ctx {
     uint32_t frame_w = 0, frame_h = 0, frame_tile = RT_TILE_SIZE, frame_tiles_x = 0, frame_tiles_y = 0;
     bool frame_valid = false;
     unsigned long long diag[RT_CNT_N_DIAG] = {0}; // diagnostics of the counting kernel variant (rt_debug_counters)
-    unsigned long long grid_diag[2] = {0}; // ... of the light grids: shadow segments they answered, list entries read
+    unsigned long long grid_diag[2] = {0}; // ... of the light grids: shadow segments they answered, list entries read (the last counting frame or rt_direct_light)
     double stage_ms[2] = {0.0, 0.0};       // RT_FLAG_STAGE_TIMES: [0] sum of the k_wf_shadow_grid launch durations of the last frame (device 0), [1] launches
     int fail_upload_at = -1;          // test hook: the next scene upload fails before its k-th device array (rt_debug_fail_upload)
     uint32_t n_input_tris = 0;        // triangles handed to the last scene upload (prim ids are < this)

@@ -1,6 +1,6 @@
 // rt_query.cpp — calls that trace or filter outside a frame: ray queries (rt_hip.h "Ray queries": rt_intersect, rt_occluded,
 // rt_intersect_all, rt_camera_rays), surface queries ("Surface queries": rt_surface, rt_ambient_occlusion; kernels in
-// surface_query.hip) and the image passes ("Feature buffers (AOVs) and denoising": rt_aovs, rt_sample_rays, rt_denoise; kernels in
+// surface_query.hip), the direct-light query ("Direct-light queries": rt_direct_light; kernel in direct_light.hip) and the image passes ("Feature buffers (AOVs) and denoising": rt_aovs, rt_sample_rays, rt_denoise; kernels in
 // denoise.hip).  None of them touches the frame targets, the tile shares rt_read_* gather, or the running image of an accumulation.
 #include "rt_internal.h"
 
@@ -291,6 +291,117 @@ int run_ao(rt_ctx* ctx, const rt_surface_point* points, size_t n, const rt_ao_pa
     return RT_OK;
 }
 
+// rt_direct_light: run_ao's shape with one 16-byte record out per point.  The segments are counted on the device (rt_stats.rays), so
+// every call zeroes and reads the device's counters.  A device hands over the light grids it already holds - from rt_prepare or an
+// extended-mode frame - when the call's bias is the one they were derived for; this call never builds any (ensure_grids).
+static_assert(RT_DIRECT_MAX_LIGHTS == RT_WF_MAX_LIGHTS, "the grid table and lit_mask hold one entry / bit per light, as the pipeline's visibility word");
+int run_direct_light(rt_ctx* ctx, const rt_surface_point* points, size_t n, const rt_direct_light_params* p, rt_lighting* out) {
+    const char* fn = "rt_direct_light";
+    const double w0 = now_ms();
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (n == 0) return RT_OK;
+    if (!points || !p || !out) return ctx->fail(RT_ERR_BAD_ARG, "%s: %s is NULL with n = %zu", fn, !points ? "points" : !p ? "params" : "out", n);
+    const uint32_t known = RT_QUERY_COUNTERS | RT_DIRECT_AMBIENT | RT_DIRECT_NO_SHADOWS | RT_DIRECT_NO_SHADOW_GRID;
+    if (p->flags & ~known) return ctx->fail(RT_ERR_BAD_ARG, "%s: unknown flag bits 0x%x", fn, p->flags & ~known);
+    if (!std::isfinite(p->bias) || p->bias < 0.0f) return ctx->fail(RT_ERR_BAD_ARG, "%s: bias %g (finite and >= 0)", fn, (double)p->bias);
+    if (!ctx->uploaded) return ctx->fail(RT_ERR_NOT_UPLOADED, "%s: no scene uploaded", fn);
+    if (ctx->scene_counts.n_lights > RT_DIRECT_MAX_LIGHTS)
+        return ctx->fail(RT_ERR_BAD_ARG, "%s: the scene has %u lights (at most %u: one bit of lit_mask each)", fn, ctx->scene_counts.n_lights, RT_DIRECT_MAX_LIGHTS);
+    if (int rcp = sync_pending(ctx)) return rcp;
+    QueryPtr pin, pout;
+    if (int rc = classify_ptr(ctx, fn, "points", points, pin)) return rc;
+    if (int rc = classify_ptr(ctx, fn, "out", out, pout)) return rc;
+    if (pin.device != pout.device || pin.dev != pout.dev)
+        return ctx->fail(RT_ERR_BAD_ARG, "%s: points and out must both be host memory or both device memory of the same device", fn);
+    rt::DirectLightArgs args{};
+    args.bias = p->bias;
+    args.ambient = (p->flags & RT_DIRECT_AMBIENT) ? 1u : 0u;
+    args.shadows = (p->flags & RT_DIRECT_NO_SHADOWS) ? 0u : 1u;
+    // the lists are supersets of what the triangle test accepts for segments that start EXT_EPS off their point: any other bias walks the tree
+    const float grid_bias = RT_SG_EXT_EPS;
+    const bool grids_allowed = args.shadows && !(p->flags & RT_DIRECT_NO_SHADOW_GRID) && std::memcmp(&p->bias, &grid_bias, sizeof(float)) == 0;
+    rt::direct_light_box(ctx->box_lo, ctx->box_hi, args.lo, args.hi); // (current whenever a device holds grids: ensure_grids)
+    const size_t chunk = RT_QUERY_CHUNK;
+    const bool counters = (p->flags & RT_QUERY_COUNTERS) != 0;
+    const size_t nd = ctx->devs.size();
+    std::vector<size_t> first(nd, 0), count(nd, 0);
+    if (pin.device) count[pin.dev] = n; // a device batch runs where it lives
+    else
+        for (size_t j = 0; j < nd; j++) first[j] = n * j / nd, count[j] = n * (j + 1) / nd - first[j]; // contiguous ranges, one per device
+    // every device's range is enqueued before any is waited for
+    auto enqueue = [&](size_t j) -> int {
+        DeviceState& d = ctx->devs[j];
+        HIPCHK(ctx, hipSetDevice(d.device));
+        const DevScene sc = scene_for(ctx, d);
+        rt::DirectLightArgs a = args;
+        a.grids = grids_allowed ? d.grids.table.get() : nullptr;
+        const size_t chunks = (count[j] + chunk - 1) / chunk;
+        if (int rc = ensure_query_events(ctx, d, 2 * chunks)) return rc;
+        if (!pin.device) {
+            const size_t most = std::min<size_t>(count[j], chunk);
+            HIPCHK(ctx, d.rq.in.reserve(most * sizeof(rt_surface_point)));
+            HIPCHK(ctx, d.rq.out.reserve(most * sizeof(rt_lighting)));
+        }
+        HIPCHK(ctx, hipMemsetAsync(d.counters.get(), 0, RT_CNT_DIAG * sizeof(unsigned long long), d.stream));
+        for (size_t c = 0; c < chunks; c++) {
+            const size_t off = first[j] + c * chunk, m = std::min<size_t>(chunk, first[j] + count[j] - off);
+            const void* in = points + off;
+            void* res = out + off;
+            if (!pin.device) {
+                HIPCHK(ctx, hipMemcpyAsync(d.rq.in.get(), in, m * sizeof(rt_surface_point), hipMemcpyHostToDevice, d.stream));
+                in = d.rq.in.get();
+                res = d.rq.out.get();
+            }
+            HIPCHK(ctx, hipEventRecord(d.rq_events[2 * c], d.stream));
+            HIPCHK(ctx, rt::launch_direct_light(sc, a, in, res, (uint32_t)m, counters, d.counters.get(), d.stream));
+            HIPCHK(ctx, hipEventRecord(d.rq_events[2 * c + 1], d.stream));
+            if (!pin.device) HIPCHK(ctx, hipMemcpyAsync(out + off, res, m * sizeof(rt_lighting), hipMemcpyDeviceToHost, d.stream));
+        }
+        return RT_OK;
+    };
+    for (size_t j = 0; j < nd; j++)
+        if (count[j] > 0)
+            if (int rc = enqueue(j)) {
+                drain_streams(ctx);
+                return rc;
+            }
+    double kernel_ms = 0.0;
+    unsigned long long segments = 0, nodes = 0, tris = 0, answered = 0, entries = 0;
+    for (size_t j = 0; j < nd; j++) {
+        if (count[j] == 0) continue;
+        DeviceState& d = ctx->devs[j];
+        hipError_t e = hipSetDevice(d.device);
+        if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
+        if (e != hipSuccess) {
+            drain_streams(ctx);
+            return ctx->fail(RT_ERR_HIP, "%s: device %d: %s", fn, d.device, hipGetErrorString(e));
+        }
+        double ms = 0.0;
+        for (size_t c = 0; c * chunk < count[j]; c++) {
+            float cm = 0.0f;
+            HIPCHK(ctx, hipEventElapsedTime(&cm, d.rq_events[2 * c], d.rq_events[2 * c + 1]));
+            ms += cm;
+        }
+        kernel_ms = std::max(kernel_ms, ms);
+        unsigned long long cn[RT_CNT_DIAG];
+        HIPCHK(ctx, hipMemcpy(cn, d.counters.get(), sizeof cn, hipMemcpyDeviceToHost));
+        segments += cn[RT_CNT_SHADOW];
+        nodes += cn[RT_CNT_NODE_VISITS];
+        tris += cn[RT_CNT_TRI_TESTS];
+        answered += cn[RT_CNT_DL_GRID_ANSWERED];
+        entries += cn[RT_CNT_DL_GRID_ENTRIES];
+    }
+    if (counters) ctx->grid_diag[0] = answered, ctx->grid_diag[1] = entries; // (rt_debug_shadow_grid: the lists' share of the segments)
+    rt_stats& st = ctx->stats;
+    st.rays = st.shadow_rays = segments;
+    st.primary_rays = st.continuation_rays = st.pixels = 0;
+    st.node_visits = counters ? nodes : 0;
+    st.tri_tests = counters ? tris : 0;
+    st.kernel_ms = kernel_ms;
+    st.wall_ms = now_ms() - w0;
+    return RT_OK;
+}
+
 // The jitter rule of the frames: a closed frame jitters when it has several samples (frame_of_params), an accumulation always.
 void sample_jitter(DevFrame& fr, uint32_t flags) {
     if (flags & RT_FLAG_ACCUMULATE) fr.jitter = 1u;
@@ -488,6 +599,10 @@ int rt_surface(rt_ctx* ctx, const rt_ray* rays, size_t n, rt_surface_point* out,
 
 int rt_ambient_occlusion(rt_ctx* ctx, const rt_surface_point* points, size_t n, const rt_ao_params* params, float* visibility, uint32_t* unoccluded) {
     return run_ao(ctx, points, n, params, visibility, unoccluded);
+}
+
+int rt_direct_light(rt_ctx* ctx, const rt_surface_point* points, size_t n, const rt_direct_light_params* params, rt_lighting* out) {
+    return run_direct_light(ctx, points, n, params, out);
 }
 
 int rt_camera_rays(rt_ctx* ctx, const rt_camera* camera, uint32_t width, uint32_t height, uint32_t mode, rt_ray* out) {

@@ -224,7 +224,7 @@ int rt_get_stats(rt_ctx* ctx, rt_stats* out);
  * a new one at sample 0 by itself, as RT_FLAG_ACCUMULATE_RESTART does.  The other RT_FLAG_* bits change no bits and may differ.
  * The running image ends (the next accumulating call starts at 0) with rt_upload_scene*, rt_update_geometry, rt_dispatch_tile, any
  * rt_render without RT_FLAG_ACCUMULATE and an accumulating call that fails once it has passed its argument checks.  It survives rt_prepare,
- * rt_upload_textures, the ray queries, the surface queries, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
+ * rt_upload_textures, the ray queries, the surface queries, rt_direct_light, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
  * Limit: RT_ACCUMULATE_MAX_SAMPLES samples (where the float sample count stops being exact); a call that would pass it is RT_ERR_BAD_ARG
  * and leaves the running image as it was.  rt_stats describes the call alone (its segments, pixels, kernel_ms).
  * A context over several devices, and a tile_rank / tile_world share, accumulates its own share of the pixels.
@@ -451,6 +451,70 @@ int rt_surface(rt_ctx* ctx, const rt_ray* rays, size_t n, rt_surface_point* out,
 int rt_ambient_occlusion(rt_ctx* ctx, const rt_surface_point* points, size_t n, const rt_ao_params* params,
                          float* visibility,     /* n entries; may be NULL */
                          uint32_t* unoccluded); /* n entries; may be NULL, not both */
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Direct-light queries: the light that the scene's own lights deliver to points the caller supplies, with shadows (no reference
+ * counterpart; the direct-lighting pass of a baker or a probe is the model).  It is the first vertex of the extended mode's path and
+ * nothing more: one light sum per point, no bounces, no random numbers.  Every bit is fixed by calls above and by the frames.
+ *
+ * rt_direct_light: for point i with position P, normal N and material_id as given (prim_id is ignored):
+ *   - a record with a non-finite P or N component or with N == 0 (what rt_surface writes for a miss) is no point: nothing is
+ *     traced, radiance = 0, lit_mask = 0;
+ *   - material_id >= the uploaded material count: radiance = (1, 0, 1), the frames' magenta, lit_mask = 0, nothing is traced;
+ *   - otherwise radiance is the extended mode's ordered light sum at a vertex with materials[material_id]:
+ *     0.1 * albedo first when RT_DIRECT_AMBIENT is set (as the frames' terminal vertex adds it), then the contribution of every light
+ *     in index order (the reference's calculate_light_contribution: f16-rounded attenuation, 0/1 type masks, spot factor), a light
+ *     whose shadow segment is occluded skipped, then the emission.  The transmission mix the frames apply when they leave a terminal
+ *     vertex of a transmissive material is NOT applied: radiance equals a closed frame's pixel (mode 2, max_bounces 0, 1 spp) only
+ *     for materials with transmission <= 0.
+ *   A light has a shadow segment when its contribution is non-zero and RT_DIRECT_NO_SHADOWS is clear: origin = P + N * bias (one
+ *   multiply, one add per component), direction and tmax = the direction toward the light and its distance as the contribution
+ *   computes them (normalize(L - P) and |L - P|; a directional light: -normalize(direction) and FLT_MAX), tmin =
+ *   RT_MIN_RAY_DISTANCE, traced by rt_occluded's rules, its degenerate-ray rule included.  So "occluded" is exactly rt_occluded of
+ *   that ray, whatever the tree, the device count, the kind of memory, the chunking, and whether light grids exist.
+ *   lit_mask: bit li is set when light li's contribution is non-zero and (unless RT_DIRECT_NO_SHADOWS) its segment is not occluded:
+ *   the lights that entered the sum.
+ *   N is used as given, neither flipped nor normalised.  The frames shade with the UNFLIPPED geometric normal of the primitive;
+ *   rt_surface reports the normal face-forwarded against its ray.  Pass rt_surface's normal to light the side the ray arrived on
+ *   (bakers, probes); negate it on back faces (dot(geometric normal, ray direction) > 0) to reproduce a frame's pixel.
+ *   params: bias finite and >= 0 (the frames use 1e-3); flags RT_DIRECT_AMBIENT, RT_DIRECT_NO_SHADOWS, RT_DIRECT_NO_SHADOW_GRID,
+ *   RT_QUERY_COUNTERS; _pad ignored.
+ * Light grids: the call never builds them.  A device that holds them (rt_prepare(RT_PREPARE_SHADOW_GRIDS), or an extended-mode frame
+ *   before) answers segments from the per-light triangle lists where that is proven to give rt_occluded's answer: bias bit-equal to
+ *   1e-3f, |N.N - 1| <= 1e-5 and P within one largest extent of the triangles' bounding box; every other segment, and every
+ *   segment with RT_DIRECT_NO_SHADOW_GRID, walks the tree.  The results are the same bits either way.
+ * Buffers, synchronisation and side effects as for rt_surface: both pointers host memory, or both device memory of one context
+ * device (16-byte aligned), anything else is RT_ERR_BAD_ARG; host batches are staged in chunks of at most RT_QUERY_CHUNK points; a
+ * context over several devices splits the batch into one contiguous range per device; synchronous, first waits for an
+ * rt_dispatch_tile in flight; the last frame, the rt_read_* results and a running accumulation are left alone.
+ * Errors: n == 0 is RT_OK; NULL points / params / out, unknown flag bits, a bad bias and a scene with more than
+ * RT_DIRECT_MAX_LIGHTS lights are RT_ERR_BAD_ARG and change nothing; a call before any upload is RT_ERR_NOT_UPLOADED.  A scene
+ * without lights gives radiance = emission (+ the ambient term with RT_DIRECT_AMBIENT) and lit_mask = 0.
+ * Statistics: rays = shadow_rays = the shadow segments of the call (counted on the device), the other counts 0, kernel_ms the
+ * maximum over devices, node_visits / tri_tests only with RT_QUERY_COUNTERS (list entries tested count as triangle tests).
+ * --------------------------------------------------------------------------------------------------------------- */
+typedef struct rt_lighting {
+    float radiance[3];
+    uint32_t lit_mask; /* bit li: light li entered the sum */
+} rt_lighting; /* 16 bytes */
+
+typedef struct rt_direct_light_params {
+    float bias;     /* finite, >= 0: the segments' origin offset along the normal */
+    uint32_t flags; /* RT_DIRECT_* | RT_QUERY_COUNTERS */
+    uint32_t _pad[2];
+} rt_direct_light_params; /* 16 bytes */
+
+RT_STATIC_ASSERT(sizeof(rt_lighting) == 16 && offsetof(rt_lighting, lit_mask) == 12, "rt_lighting is 16 B, lit_mask at 12");
+RT_STATIC_ASSERT(sizeof(rt_direct_light_params) == 16 && offsetof(rt_direct_light_params, flags) == 4 && offsetof(rt_direct_light_params, _pad) == 8,
+                 "rt_direct_light_params is 16 B, flags at 4");
+
+#define RT_DIRECT_AMBIENT 4u         /* add the 0.1 * albedo ambient term first, as the frames' terminal vertex does */
+#define RT_DIRECT_NO_SHADOWS 8u      /* no shadow segments: every non-zero contribution counts (RT_FLAG_NO_SHADOWS) */
+#define RT_DIRECT_NO_SHADOW_GRID 16u /* every segment walks the tree (A/B and tests; same results) */
+#define RT_DIRECT_MAX_LIGHTS 32u     /* one bit per light; the light count the extended mode's pipeline takes */
+
+/* Shadowed direct lighting of the n points. */
+int rt_direct_light(rt_ctx* ctx, const rt_surface_point* points, size_t n, const rt_direct_light_params* params, rt_lighting* out);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Geometry updates: new positions for the uploaded scene, in place (no reference counterpart; Embree's refit build,
