@@ -38,6 +38,9 @@ MULTI_HIT_MAX = 16  # RT_MULTI_HIT_MAX: the most hits rt_intersect_all lists per
 AO_MAX_SAMPLES = 4096  # RT_AO_MAX_SAMPLES: the most samples rt_ambient_occlusion takes per point
 DIRECT_AMBIENT, DIRECT_NO_SHADOWS, DIRECT_NO_SHADOW_GRID = 4, 8, 16  # RT_DIRECT_* of rt_direct_light_params.flags
 DIRECT_MAX_LIGHTS = 32  # RT_DIRECT_MAX_LIGHTS: rt_direct_light's lit_mask has one bit per light
+PATH_NO_SHADOWS, PATH_CAMERA_DRAWS = 32, 64  # RT_PATH_* of rt_path_params.flags
+PATH_MAX_SAMPLES = 4096  # RT_PATH_MAX_SAMPLES: the most paths rt_radiance traces per ray
+MAX_BOUNCES = T.MAX_BOUNCES  # RT_MAX_BOUNCES
 UPDATE_REBUILD = 1  # RT_UPDATE_REBUILD of rt_update_geometry
 AOV_SAMPLES_PER_LAUNCH = T.AOV_SAMPLES_PER_LAUNCH  # RT_AOV_SAMPLES_PER_LAUNCH: rt_aovs traces at most this many samples per kernel
 DENOISE_DEMODULATE = T.DENOISE_DEMODULATE  # RT_DENOISE_DEMODULATE of rt_denoise_params.flags
@@ -55,7 +58,7 @@ ABI_SYMBOLS = [
     "rt_read_rgb32f", "rt_read_rgba8_channels", "rt_read_rgba8_combined", "rt_read_hits",
     "rt_get_stats", "rt_last_error", "rt_destroy", "rt_version",
     "rt_intersect", "rt_occluded", "rt_camera_rays", "rt_intersect_all",
-    "rt_surface", "rt_ambient_occlusion", "rt_direct_light",
+    "rt_surface", "rt_ambient_occlusion", "rt_direct_light", "rt_radiance",
     "rt_update_geometry",
     "rt_accumulated_samples",
     "rt_aovs", "rt_sample_rays", "rt_denoise",
@@ -99,7 +102,7 @@ def _p(a):
     return C.c_void_p(a.ctypes.data) if a is not None and a.size else C.c_void_p(0)
 
 
-# -- ray batches (rt_intersect / rt_occluded / rt_intersect_all / rt_surface / rt_camera_rays) ---------------------------------------------------------
+# -- ray batches (rt_intersect / rt_occluded / rt_intersect_all / rt_surface / rt_radiance / rt_camera_rays) ---------------------------------------------------------
 # A batch is a C-contiguous float32 array of shape (N, 8), one rt_ray per row: ox oy oz tmin dx dy dz tmax; numpy, or a torch
 # tensor on the CPU or on a device of the context.  torch is imported only when a tensor is handed in.
 
@@ -230,6 +233,17 @@ def split_lighting(lighting):
     else:
         mask = np.ascontiguousarray(lighting[:, 3]).view(np.uint32)
     return lighting[:, 0:3], mask
+
+
+def split_radiance(results):
+    """(N, 4) path results (rt_path_result) -> (radiance (N, 3), segments (N,)).  segments is the records' uint32 word: uint32 for
+    numpy, int64 for torch; the segments traced for the ray over all its samples."""
+    if _is_torch(results):
+        import torch
+        segments = results[:, 3].contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    else:
+        segments = np.ascontiguousarray(results[:, 3]).view(np.uint32)
+    return results[:, 0:3], segments
 
 
 def split_aovs(aovs):
@@ -617,6 +631,33 @@ class Context:
                        | (QUERY_COUNTERS if counters else 0))
         _sync_torch(points, out)
         self._check(self.lib.rt_direct_light(self._h, _addr(points), C.c_size_t(n), _p(dp), _addr(out)))
+        return out
+
+    def radiance(self, rays, samples=1, max_bounces=4, seed=0, first_sample=0, shadows=True, camera_draws=False, out=None, counters=False):
+        """rt_radiance: the extended mode's path radiance along each ray of an (N, 8) batch, `samples` (1 .. PATH_MAX_SAMPLES) paths
+        per ray averaged as the frames average a pixel's samples -> (N, 4) float32 rt_path_result records (split_radiance: radiance,
+        segments), same kind and device as `rays`.  Sample k of ray i draws from rng_for(seed + i, first_sample + k); max_bounces as
+        in an extended-mode frame; shadows=False: no shadow segments; camera_draws=True: two draws are dropped first, the ones a
+        jittered camera sample (sample_rays) spent on its jitter."""
+        n = _check_batch(rays, "rays", 8, "float32")
+        for name, v, lo, hi in (("samples", samples, 1, PATH_MAX_SAMPLES), ("max_bounces", max_bounces, 0, MAX_BOUNCES), ("seed", seed, 0, 0xFFFFFFFF),
+                                ("first_sample", first_sample, 0, 0xFFFFFFFF)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+                raise ValueError(f"{name}: {v!r}, expected an integer in {lo} .. {hi}")
+        if int(first_sample) + int(samples) > 1 << 32:
+            raise ValueError(f"first_sample: {first_sample!r} + samples {samples!r} passes 2^32")
+        if out is None:
+            out = _empty_like_batch(rays, (n, 4), "float32")
+        else:
+            if _is_torch(out) != _is_torch(rays):
+                raise TypeError("out: must be the same kind (numpy / torch) as rays")
+            if _check_batch(out, "out", 4, "float32") != n:
+                raise ValueError(f"out: {out.shape[0]} rows for {n} rays")
+        pp = np.zeros((), dtype=T.PATH_PARAMS)
+        pp["samples"], pp["max_bounces"], pp["seed"], pp["first_sample"] = int(samples), int(max_bounces), int(seed), int(first_sample)
+        pp["flags"] = (0 if shadows else PATH_NO_SHADOWS) | (PATH_CAMERA_DRAWS if camera_draws else 0) | (QUERY_COUNTERS if counters else 0)
+        _sync_torch(rays, out)
+        self._check(self.lib.rt_radiance(self._h, _addr(rays), C.c_size_t(n), _p(pp), _addr(out)))
         return out
 
     def camera_rays(self, width, height, camera, mode=MODE_LEGACY, out=None):

@@ -337,6 +337,7 @@ __device__ __forceinline__ void traverse(const DevScene& sc, V3 o, V3 d, uint2* 
 
 // find_closest_intersection (shader/src/lib.rs:174-249): spheres first, then triangles with
 // max_t = sphere t; a triangle is only accepted strictly closer, so it wins when both hit.
+// (k_pq_trace, path_query.hip, writes these statements out with the segment's own (tmin, tmax): a change here is a change there.)
 template <bool COUNT>
 __device__ __forceinline__ Hit find_closest(const DevScene& sc, V3 o, V3 d, uint2* stack, Counts& cnt) {
     Hit hit;

@@ -26,6 +26,7 @@
 #include "direct_light.h"
 #include "half.h"
 #include "kernels.h"
+#include "path_query.h"
 #include "ray_query.h"
 #include "refit.h"
 #include "shadow_grid.h"
@@ -135,9 +136,10 @@ struct DeviceState {
     } pipe;
     bool used_two_lanes = false; // the last pipeline frame ran on two lanes (its allocation is reused by a frame of the same shape)
     uint32_t wf_spp = 0;         // spp the current wavefront allocation was sized for
-    struct Query { // ray, surface and direct-light queries: staging of host batches (rays or points in, records / bytes out, rt_intersect_all's counts), grown on demand
+    struct Query { // ray, surface, direct-light and path queries: staging of host batches (rays or points in, records / bytes out, rt_intersect_all's counts), grown on demand
         DevMem in, out, counts;
         DevBuf<uint32_t> ao; // rt_ambient_occlusion: the per-point counts its kernel adds to, for host and device batches alike
+        DevBuf<uint4> paths; // rt_radiance with several samples: one record per path of a chunk (at most RT_QUERY_CHUNK), which its reduction adds up
     } rq;
     // RT_FLAG_ACCUMULATE: the running sum of the context's accumulation over this device's pixels (DevTargets::run_sum), frame-pixel
     // layout, w x h x 16 bytes.  Outlives the pipeline's WfBuffers (re-sized with the batch); made by the first accumulating call.

@@ -224,7 +224,7 @@ int rt_get_stats(rt_ctx* ctx, rt_stats* out);
  * a new one at sample 0 by itself, as RT_FLAG_ACCUMULATE_RESTART does.  The other RT_FLAG_* bits change no bits and may differ.
  * The running image ends (the next accumulating call starts at 0) with rt_upload_scene*, rt_update_geometry, rt_dispatch_tile, any
  * rt_render without RT_FLAG_ACCUMULATE and an accumulating call that fails once it has passed its argument checks.  It survives rt_prepare,
- * rt_upload_textures, the ray queries, the surface queries, rt_direct_light, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
+ * rt_upload_textures, the ray queries, the surface queries, rt_direct_light, rt_radiance, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
  * Limit: RT_ACCUMULATE_MAX_SAMPLES samples (where the float sample count stops being exact); a call that would pass it is RT_ERR_BAD_ARG
  * and leaves the running image as it was.  rt_stats describes the call alone (its segments, pixels, kernel_ms).
  * A context over several devices, and a tile_rank / tile_world share, accumulates its own share of the pixels.
@@ -515,6 +515,77 @@ RT_STATIC_ASSERT(sizeof(rt_direct_light_params) == 16 && offsetof(rt_direct_ligh
 
 /* Shadowed direct lighting of the n points. */
 int rt_direct_light(rt_ctx* ctx, const rt_surface_point* points, size_t n, const rt_direct_light_params* params, rt_lighting* out);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Path queries: the radiance the extended mode carries back along rays the caller supplies (no reference counterpart; the probe,
+ * lightmap-texel and irradiance-cache passes of a baker are the model).  It is the extended mode's whole path - the nested-loop
+ * statement of DESIGN.md section 5 - started from a ray that need not be a camera ray.  Every bit is fixed by calls above and by the
+ * frames.
+ *
+ * rt_radiance: for ray i (its index in the caller's array):
+ *   - a degenerate ray (rt_intersect's rules: a non-finite origin or direction component, a zero direction, a NaN bound, or
+ *     !(tmin < tmax) after tmin is raised to RT_MIN_RAY_DISTANCE) is no path: nothing is traced, radiance = 0, segments = 0;
+ *   - otherwise sample k < samples draws from rng = rng_for(seed + i (mod 2^32), first_sample + k), the frames' generator; with
+ *     RT_PATH_CAMERA_DRAWS two next_f32() are drawn and dropped first.  Then radiance = 0, throughput = 1, no hero channel, and for
+ *     depth = 0, 1, ..: the closest hit of the segment - the first segment in the ray's own (tmin, tmax) exactly as rt_intersect, every
+ *     later one as the frames trace a continuation; a miss adds sky * throughput and ends the path; a material id past the table adds
+ *     (1, 0, 1) * throughput and ends it; else the vertex is terminal when depth >= max_bounces, its light sum is rt_direct_light's
+ *     (the scene's lights in index order, the ambient term at the terminal vertex only, each shadow segment from point + normal * 1e-3
+ *     by rt_occluded's rules, none with RT_PATH_NO_SHADOWS) with the UNFLIPPED geometric normal, as in the frames; the path leaves the
+ *     vertex as the frames do (the transmission mix at the terminal vertex) and scatters as they do (transmission with the hero
+ *     channel and Snell's refraction, the metallic lobe, the cosine lobe, the roulette from the third vertex on, the same draws in the
+ *     same order).  x_k is the path's radiance.
+ *   out[i].radiance = (0 + x_0 + x_1 + ...) / (float)samples: an f32 sum from zero in sample order and one division, the frames'
+ *   pixel reduction.  out[i].segments = the segments traced for ray i over all its samples (first + continuation + shadow), mod 2^32.
+ *   Any number of lights: the 32-light limit of the extended mode's pipeline and of rt_direct_light does not apply.
+ * What follows:
+ *   - rays = rt_camera_rays(mode 1) of a W x H frame, seed = frame_seed, first_sample = 0, samples = 1, no RT_PATH_CAMERA_DRAWS:
+ *     out[x + y * W].radiance is bit for bit that pixel of the closed mode-2 frame with 1 spp, for any max_bounces, with or without
+ *     shadows, and the sum of the segments is that frame's rt_stats.rays;
+ *   - rays = rt_sample_rays(p, s), first_sample = s, samples = 1, RT_PATH_CAMERA_DRAWS: the result is sample x_s of that pixel of a
+ *     frame of S >= 2 spp; summing s = 0 .. S-1 from zero in f32 and dividing by (float)S gives that frame's pixel bit for bit;
+ *   - the result does not depend on the tree in use (device build, host build, RT_PREPARE_QUALITY_TREE, refitted), the device count,
+ *     the kind of memory or the chunking.  Light grids are never looked at: every shadow segment walks the tree.
+ * params: samples 1 .. RT_PATH_MAX_SAMPLES; max_bounces 0 .. RT_MAX_BOUNCES; first_sample + samples <= 2^32; flags RT_PATH_NO_SHADOWS,
+ *   RT_PATH_CAMERA_DRAWS, RT_QUERY_COUNTERS; _pad ignored.
+ * Buffers, synchronisation and side effects as for rt_direct_light: both pointers host memory, or both device memory of one context
+ * device (16-byte aligned), anything else is RT_ERR_BAD_ARG; batches are traced in chunks of at most max(1, RT_QUERY_CHUNK / samples)
+ * rays, host batches staged chunk by chunk; a context over several devices splits a host batch into one contiguous range per device
+ * (the seed's i stays the index in the caller's array); synchronous, first waits for an rt_dispatch_tile in flight; the last frame,
+ * the rt_read_* results and a running accumulation are left alone.
+ * Errors: n == 0 is RT_OK; NULL rays / params / out, samples out of range, max_bounces > RT_MAX_BOUNCES, first_sample + samples > 2^32
+ * and unknown flag bits are RT_ERR_BAD_ARG and change nothing; a call before any upload is RT_ERR_NOT_UPLOADED.  An empty scene gives
+ * the sky and segments = samples.
+ * Statistics: rays = all segments, primary_rays = first segments (valid rays x samples), continuation_rays and shadow_rays as the
+ * frames count them (on the device), pixels = 0, kernel_ms the maximum over devices, node_visits / tri_tests only with
+ * RT_QUERY_COUNTERS.
+ * --------------------------------------------------------------------------------------------------------------- */
+typedef struct rt_path_params {
+    uint32_t samples;      /* paths per ray, 1 .. RT_PATH_MAX_SAMPLES */
+    uint32_t max_bounces;  /* as rt_render_params.max_bounces in mode 2: 0 .. RT_MAX_BOUNCES */
+    uint32_t seed;         /* the frames' frame_seed */
+    uint32_t first_sample; /* global index of the ray's first sample; first_sample + samples must not pass 2^32 */
+    uint32_t flags;        /* RT_PATH_* | RT_QUERY_COUNTERS */
+    uint32_t _pad[3];
+} rt_path_params; /* 32 bytes */
+
+typedef struct rt_path_result {
+    float radiance[3];
+    uint32_t segments; /* segments traced for this ray over all its samples (first + continuation + shadow), mod 2^32 */
+} rt_path_result; /* 16 bytes */
+
+RT_STATIC_ASSERT(sizeof(rt_path_params) == 32, "rt_path_params is 32 B");
+RT_STATIC_ASSERT(offsetof(rt_path_params, max_bounces) == 4 && offsetof(rt_path_params, seed) == 8 && offsetof(rt_path_params, first_sample) == 12 &&
+                     offsetof(rt_path_params, flags) == 16 && offsetof(rt_path_params, _pad) == 20,
+                 "rt_path_params offsets");
+RT_STATIC_ASSERT(sizeof(rt_path_result) == 16 && offsetof(rt_path_result, segments) == 12, "rt_path_result is 16 B, segments at 12");
+
+#define RT_PATH_NO_SHADOWS 32u   /* lights are not gated by shadow segments (RT_FLAG_NO_SHADOWS) */
+#define RT_PATH_CAMERA_DRAWS 64u /* two next_f32 are drawn and dropped before the path: the draws a jittered camera sample spent on its jitter */
+#define RT_PATH_MAX_SAMPLES 4096u
+
+/* Extended-mode path radiance along each of the n rays: params->samples paths each. */
+int rt_radiance(rt_ctx* ctx, const rt_ray* rays, size_t n, const rt_path_params* params, rt_path_result* out);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Geometry updates: new positions for the uploaded scene, in place (no reference counterpart; Embree's refit build,
