@@ -58,7 +58,7 @@ ABI_SYMBOLS = [
     "rt_read_rgb32f", "rt_read_rgba8_channels", "rt_read_rgba8_combined", "rt_read_hits",
     "rt_get_stats", "rt_last_error", "rt_destroy", "rt_version",
     "rt_intersect", "rt_occluded", "rt_camera_rays", "rt_intersect_all",
-    "rt_surface", "rt_ambient_occlusion", "rt_direct_light", "rt_radiance",
+    "rt_surface", "rt_ambient_occlusion", "rt_direct_light", "rt_radiance", "rt_closest_point",
     "rt_update_geometry",
     "rt_accumulated_samples",
     "rt_aovs", "rt_sample_rays", "rt_denoise",
@@ -222,6 +222,32 @@ def split_surface(points):
     else:
         ids = [np.ascontiguousarray(points[:, c]).view(np.uint32) for c in (3, 7)]
     return points[:, 0:3], ids[0], points[:, 4:7], ids[1]
+
+
+def make_points(positions, radius=float("inf")):
+    """(N, 3) positions (numpy or torch, the result has the same kind and device) -> an (N, 4) float32 batch of rt_point_query
+    records: px py pz radius.  radius: a scalar or an (N,) array; only surface strictly nearer than it is reported."""
+    if _is_torch(positions):
+        import torch
+        p = positions.reshape(-1, 3)
+        out = torch.empty((p.shape[0], 4), dtype=torch.float32, device=p.device)
+    else:
+        p = np.asarray(positions, np.float32).reshape(-1, 3)
+        out = np.empty((p.shape[0], 4), np.float32)
+    out[:, 0:3] = p
+    out[:, 3] = radius
+    return out
+
+
+def split_nearest(nearest):
+    """(N, 8) closest-point records (rt_nearest) -> (position (N, 3), distance (N,), u (N,), v (N,), prim_id (N,), material_id (N,)).
+    The ids are the records' uint32 words: uint32 for numpy, int64 for torch (a miss is 4294967295 = PRIM_MISS), as split_hits gives prim."""
+    if _is_torch(nearest):
+        import torch
+        ids = [nearest[:, c].contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF for c in (6, 7)]
+    else:
+        ids = [np.ascontiguousarray(nearest[:, c]).view(np.uint32) for c in (6, 7)]
+    return nearest[:, 0:3], nearest[:, 3], nearest[:, 4], nearest[:, 5], ids[0], ids[1]
 
 
 def split_lighting(lighting):
@@ -502,16 +528,16 @@ class Context:
         return d
 
     # -- ray queries ---------------------------------------------------------------------
-    def _query(self, fn, rays, out, cols, dtype_name, counters):
-        n = _check_batch(rays, "rays", 8, "float32")
+    def _query(self, fn, rays, out, cols, dtype_name, counters, in_cols=8, in_name="rays"):
+        n = _check_batch(rays, in_name, in_cols, "float32")
         shape = (n, cols) if cols else (n,)
         if out is None:
             out = _empty_like_batch(rays, shape, dtype_name)
         else:
             if _is_torch(out) != _is_torch(rays):
-                raise TypeError("out: must be the same kind (numpy / torch) as rays")
+                raise TypeError(f"out: must be the same kind (numpy / torch) as {in_name}")
             if _check_batch(out, "out", cols, dtype_name) != n:
-                raise ValueError(f"out: {len(out)} rows for {n} rays")
+                raise ValueError(f"out: {len(out)} rows for {n} {in_name}")
         _sync_torch(rays, out)
         self._check(getattr(self.lib, fn)(self._h, _addr(rays), C.c_size_t(n), _addr(out), C.c_uint32(QUERY_COUNTERS if counters else 0)))
         return out
@@ -659,6 +685,13 @@ class Context:
         _sync_torch(rays, out)
         self._check(self.lib.rt_radiance(self._h, _addr(rays), C.c_size_t(n), _p(pp), _addr(out)))
         return out
+
+    def closest_point(self, points, out=None, counters=False):
+        """rt_closest_point: the nearest point of the scene's surface to each record of an (N, 4) batch of points (make_points:
+        position, radius) -> (N, 8) float32 rt_nearest records (split_nearest: position, distance, u, v, prim_id, material_id), same
+        kind and device as `points`.  Only surface strictly nearer than the radius is reported; a miss is position 0, the radius as
+        distance and prim_id = PRIM_MISS."""
+        return self._query("rt_closest_point", points, out, 8, "float32", counters, in_cols=4, in_name="points")
 
     def camera_rays(self, width, height, camera, mode=MODE_LEGACY, out=None):
         """rt_camera_rays: the width x height pixel-centre rays of mode 0/1 as a (width * height, 8) batch, row-major, y down.

@@ -1,0 +1,110 @@
+// closest_point.hip — the kernel of the closest-point query of include/rt_hip.h (rt_closest_point): for each point the caller
+// supplies, the nearest point of the scene's surface within the query's radius.
+//
+// Every statement that decides a bit of the answer, and the walk itself, is in closest_point_rules.h, which the host check
+// (tests/check_closest_point.cpp) runs against a brute force; this file supplies how a lane reads a node and a record, its stack and
+// the output record.  One lane per point, one wave per block, the per-lane stack in LDS: the launch shape of k_rq_trace.
+#include "closest_point.h"
+
+#include "closest_point_rules.h"
+#include "device_common.h"
+
+using namespace rtdev;
+
+namespace {
+
+// What cp_walk (closest_point_rules.h, rule 5) asks of its caller, for one lane.
+template <bool COUNT>
+struct LaneAccess {
+    const uint4* __restrict__ nodes;
+    const DevTri* __restrict__ tris;
+    uint2* stack; // lane-interleaved: entry k of this lane at stack[k * WAVE]; at most depth - 1 of the depth + 2 entries are in use (rule 5)
+    Counts cnt;
+
+    __device__ __forceinline__ void node(uint32_t idx, uint32_t w[20]) {
+        const uint4* n = nodes + (size_t)idx * 5;
+        const uint4 w0 = n[0], w1 = n[1], w2 = n[2], w3 = n[3], w4 = n[4]; // one visit = 5 x dwordx4, as visit_node8
+        if (COUNT) cnt.nodes++;
+        w[0] = w0.x, w[1] = w0.y, w[2] = w0.z, w[3] = w0.w;
+        w[4] = w1.x, w[5] = w1.y, w[6] = w1.z, w[7] = w1.w;
+        w[8] = w2.x, w[9] = w2.y, w[10] = w2.z, w[11] = w2.w;
+        w[12] = w3.x, w[13] = w3.y, w[14] = w3.z, w[15] = w3.w;
+        w[16] = w4.x, w[17] = w4.y, w[18] = w4.z, w[19] = w4.w;
+    }
+    __device__ __forceinline__ void record(uint32_t slot, float q[9], uint32_t ids[3]) {
+        if (COUNT) cnt.tris++;
+        const float4* p = reinterpret_cast<const float4*>(tris + slot);
+        float4 q0 = p[0], q1 = p[1], q2 = p[2]; // the record in three loads issued together, as traverse_all
+        asm volatile("" : "+v"(q0.x), "+v"(q0.y), "+v"(q0.z), "+v"(q0.w), "+v"(q1.x), "+v"(q1.y), "+v"(q1.z), "+v"(q1.w), "+v"(q2.x), "+v"(q2.y), "+v"(q2.z), "+v"(q2.w));
+        q[0] = q0.x, q[1] = q0.y, q[2] = q0.z, q[3] = q0.w, q[4] = q1.x, q[5] = q1.y, q[6] = q1.z, q[7] = q1.w, q[8] = q2.x;
+        ids[0] = __float_as_uint(q2.y), ids[1] = __float_as_uint(q2.z), ids[2] = __float_as_uint(q2.w);
+    }
+    __device__ __forceinline__ void push(int sp, uint32_t base, uint32_t bits) { stack[sp * WAVE] = make_uint2(base, bits); }
+    __device__ __forceinline__ void pop(int sp, uint32_t& base, uint32_t& bits) {
+        const uint2 e = stack[sp * WAVE];
+        base = e.x, bits = e.y;
+    }
+};
+
+// One rt_point_query (px py pz radius) per lane -> one rt_nearest (position | distance | u v | prim_id material_id).
+template <bool COUNT>
+__global__ __launch_bounds__(WAVE) void k_cp_nearest(DevScene sc, const float4* __restrict__ points, uint4* __restrict__ out, uint32_t n,
+                                                      unsigned long long* __restrict__ counters) {
+    extern __shared__ uint2 s_stack[]; // (DevScene::stack_entries / 2 + 1) * 64 64-bit entries
+    const uint32_t i = blockIdx.x * WAVE + threadIdx.x;
+    if (i >= n) return;
+    const float4 pq = points[i];
+    const float p[3] = {pq.x, pq.y, pq.z};
+    LaneAccess<COUNT> acc;
+    acc.nodes = reinterpret_cast<const uint4*>(sc.nodes);
+    acc.tris = sc.tris;
+    acc.stack = s_stack + threadIdx.x;
+    acc.cnt = {0u, 0u};
+    uint32_t r[8];
+    rt::cp_answer_miss(pq.w, r);
+    if (rt::cp_query_valid(p, pq.w)) { // degenerate queries are misses without a walk
+        rt::CpBest best;
+        best.order = rt::cp_start(pq.w);
+        best.slot = 0xFFFFFFFFu;
+        float pos[3];
+        for (uint32_t s = 0; s < sc.n_spheres; s++) { // the spheres by brute force, in index order
+            const uint64_t c = rt::cp_order(rt::cp_sphere(sc.spheres[s].center, sc.spheres[s].radius, p, pos), s);
+            if (c < best.order) best.order = c, best.slot = s;
+        }
+        rt::cp_walk(acc, sc.n_nodes, p, best);
+        if (best.slot != 0xFFFFFFFFu) {
+            if ((uint32_t)best.order & RT_PRIM_SPHERE_FLAG) { // a triangle's key
+                float q[9];
+                uint32_t ids[3];
+                LaneAccess<false>{nullptr, sc.tris, nullptr, {0u, 0u}}.record(best.slot, q, ids);
+                rt::cp_answer_triangle(q, ids[0], best.order, p, r);
+            } else {
+                const DevSphere& s = sc.spheres[best.slot];
+                rt::cp_answer_sphere(s.center, s.radius, s.material_id, best.order, p, r);
+            }
+        }
+    }
+    out[2 * (size_t)i] = make_uint4(r[0], r[1], r[2], r[3]);
+    out[2 * (size_t)i + 1] = make_uint4(r[4], r[5], r[6], r[7]);
+    if (COUNT) {
+        atomicAdd(&counters[RT_CNT_NODE_VISITS], (unsigned long long)acc.cnt.nodes);
+        atomicAdd(&counters[RT_CNT_TRI_TESTS], (unsigned long long)acc.cnt.tris);
+    }
+}
+
+} // namespace
+
+namespace rt {
+
+hipError_t launch_closest_point(const DevScene& sc, const void* points, void* out, uint32_t n, unsigned long long* counters, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const dim3 grid((n + WAVE - 1) / WAVE), block(WAVE);
+    const size_t lds = (size_t)(sc.stack_entries / 2u + 1u) * WAVE * sizeof(uint2); // as launch_ray_query
+    const float4* p = reinterpret_cast<const float4*>(points);
+    uint4* o = reinterpret_cast<uint4*>(out);
+    if (counters) hipLaunchKernelGGL((k_cp_nearest<true>), grid, block, lds, stream, sc, p, o, n, counters);
+    else hipLaunchKernelGGL((k_cp_nearest<false>), grid, block, lds, stream, sc, p, o, n, counters);
+    return hipGetLastError();
+}
+
+} // namespace rt

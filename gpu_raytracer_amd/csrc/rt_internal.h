@@ -20,6 +20,7 @@
 #include "../../include/rt_hip.h"
 #include "adaptive.h"
 #include "bvh_builder.h"
+#include "closest_point.h"
 #include "denoise.h"
 #include "device_build.h"
 #include "device_layout.h"

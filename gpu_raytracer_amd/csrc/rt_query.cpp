@@ -1,7 +1,7 @@
 // rt_query.cpp — calls that trace or filter outside a frame: ray queries (rt_hip.h "Ray queries": rt_intersect, rt_occluded,
 // rt_intersect_all, rt_camera_rays), surface queries ("Surface queries": rt_surface, rt_ambient_occlusion; kernels in
 // surface_query.hip), the direct-light query ("Direct-light queries": rt_direct_light; kernel in direct_light.hip), the path query ("Path queries":
-// rt_radiance; kernels in path_query.hip) and the image passes ("Feature buffers (AOVs) and denoising": rt_aovs, rt_sample_rays, rt_denoise; kernels in
+// rt_radiance; kernels in path_query.hip), the closest-point query ("Closest-point queries": rt_closest_point; kernel in closest_point.hip) and the image passes ("Feature buffers (AOVs) and denoising": rt_aovs, rt_sample_rays, rt_denoise; kernels in
 // denoise.hip).  None of them touches the frame targets, the tile shares rt_read_* gather, or the running image of an accumulation.
 #include "rt_internal.h"
 
@@ -511,6 +511,98 @@ int run_radiance(rt_ctx* ctx, const rt_ray* rays, size_t n, const rt_path_params
     return RT_OK;
 }
 
+// rt_closest_point: run_query's shape with points for rays: 16 bytes in, 32 bytes out per point.
+int run_closest_point(rt_ctx* ctx, const rt_point_query* points, size_t n, rt_nearest* out, uint32_t flags) {
+    const char* fn = "rt_closest_point";
+    const double w0 = now_ms();
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (n == 0) return RT_OK;
+    if (!points || !out) return ctx->fail(RT_ERR_BAD_ARG, "%s: %s is NULL with n = %zu", fn, !points ? "points" : "out", n);
+    if (flags & ~RT_QUERY_COUNTERS) return ctx->fail(RT_ERR_BAD_ARG, "%s: unknown flag bits 0x%x", fn, flags & ~RT_QUERY_COUNTERS);
+    if (!ctx->uploaded) return ctx->fail(RT_ERR_NOT_UPLOADED, "%s: no scene uploaded", fn);
+    if (int rcp = sync_pending(ctx)) return rcp;
+    QueryPtr pin, pout;
+    if (int rc = classify_ptr(ctx, fn, "points", points, pin)) return rc;
+    if (int rc = classify_ptr(ctx, fn, "out", out, pout)) return rc;
+    if (pin.device != pout.device || pin.dev != pout.dev)
+        return ctx->fail(RT_ERR_BAD_ARG, "%s: points and out must both be host memory or both device memory of the same device", fn);
+    const size_t chunk = RT_QUERY_CHUNK;
+    const bool counters = (flags & RT_QUERY_COUNTERS) != 0;
+    const size_t nd = ctx->devs.size();
+    std::vector<size_t> first(nd, 0), count(nd, 0);
+    if (pin.device) count[pin.dev] = n; // a device batch runs where it lives
+    else
+        for (size_t j = 0; j < nd; j++) first[j] = n * j / nd, count[j] = n * (j + 1) / nd - first[j]; // contiguous ranges, one per device
+    // every device's range is enqueued before any is waited for
+    auto enqueue = [&](size_t j) -> int {
+        DeviceState& d = ctx->devs[j];
+        HIPCHK(ctx, hipSetDevice(d.device));
+        const DevScene sc = scene_for(ctx, d);
+        const size_t chunks = (count[j] + chunk - 1) / chunk;
+        if (int rc = ensure_query_events(ctx, d, 2 * chunks)) return rc;
+        if (!pin.device) {
+            const size_t most = std::min<size_t>(count[j], chunk);
+            HIPCHK(ctx, d.rq.in.reserve(most * sizeof(rt_point_query)));
+            HIPCHK(ctx, d.rq.out.reserve(most * sizeof(rt_nearest)));
+        }
+        if (counters) HIPCHK(ctx, hipMemsetAsync(d.counters.get(), 0, (RT_CNT_TRI_TESTS + 1) * sizeof(unsigned long long), d.stream));
+        for (size_t c = 0; c < chunks; c++) {
+            const size_t off = first[j] + c * chunk, m = std::min<size_t>(chunk, first[j] + count[j] - off);
+            const void* in = points + off;
+            void* res = out + off;
+            if (!pin.device) {
+                HIPCHK(ctx, hipMemcpyAsync(d.rq.in.get(), in, m * sizeof(rt_point_query), hipMemcpyHostToDevice, d.stream));
+                in = d.rq.in.get();
+                res = d.rq.out.get();
+            }
+            HIPCHK(ctx, hipEventRecord(d.rq_events[2 * c], d.stream));
+            HIPCHK(ctx, rt::launch_closest_point(sc, in, res, (uint32_t)m, counters ? d.counters.get() : nullptr, d.stream));
+            HIPCHK(ctx, hipEventRecord(d.rq_events[2 * c + 1], d.stream));
+            if (!pin.device) HIPCHK(ctx, hipMemcpyAsync(out + off, res, m * sizeof(rt_nearest), hipMemcpyDeviceToHost, d.stream));
+        }
+        return RT_OK;
+    };
+    for (size_t j = 0; j < nd; j++)
+        if (count[j] > 0)
+            if (int rc = enqueue(j)) {
+                drain_streams(ctx);
+                return rc;
+            }
+    double kernel_ms = 0.0;
+    unsigned long long nodes = 0, tris = 0;
+    for (size_t j = 0; j < nd; j++) {
+        if (count[j] == 0) continue;
+        DeviceState& d = ctx->devs[j];
+        hipError_t e = hipSetDevice(d.device);
+        if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
+        if (e != hipSuccess) {
+            drain_streams(ctx);
+            return ctx->fail(RT_ERR_HIP, "%s: device %d: %s", fn, d.device, hipGetErrorString(e));
+        }
+        double ms = 0.0;
+        for (size_t c = 0; c * chunk < count[j]; c++) {
+            float cm = 0.0f;
+            HIPCHK(ctx, hipEventElapsedTime(&cm, d.rq_events[2 * c], d.rq_events[2 * c + 1]));
+            ms += cm;
+        }
+        kernel_ms = std::max(kernel_ms, ms);
+        if (counters) {
+            unsigned long long cn[RT_CNT_TRI_TESTS + 1];
+            HIPCHK(ctx, hipMemcpy(cn, d.counters.get(), sizeof cn, hipMemcpyDeviceToHost));
+            nodes += cn[RT_CNT_NODE_VISITS];
+            tris += cn[RT_CNT_TRI_TESTS];
+        }
+    }
+    rt_stats& st = ctx->stats;
+    st.rays = n;
+    st.primary_rays = st.continuation_rays = st.shadow_rays = st.pixels = 0;
+    st.node_visits = counters ? nodes : 0;
+    st.tri_tests = counters ? tris : 0;
+    st.kernel_ms = kernel_ms;
+    st.wall_ms = now_ms() - w0;
+    return RT_OK;
+}
+
 // The jitter rule of the frames: a closed frame jitters when it has several samples (frame_of_params), an accumulation always.
 void sample_jitter(DevFrame& fr, uint32_t flags) {
     if (flags & RT_FLAG_ACCUMULATE) fr.jitter = 1u;
@@ -716,6 +808,10 @@ int rt_direct_light(rt_ctx* ctx, const rt_surface_point* points, size_t n, const
 
 int rt_radiance(rt_ctx* ctx, const rt_ray* rays, size_t n, const rt_path_params* params, rt_path_result* out) {
     return run_radiance(ctx, rays, n, params, out);
+}
+
+int rt_closest_point(rt_ctx* ctx, const rt_point_query* points, size_t n, rt_nearest* out, uint32_t flags) {
+    return run_closest_point(ctx, points, n, out, flags);
 }
 
 int rt_camera_rays(rt_ctx* ctx, const rt_camera* camera, uint32_t width, uint32_t height, uint32_t mode, rt_ray* out) {

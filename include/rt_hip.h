@@ -224,7 +224,7 @@ int rt_get_stats(rt_ctx* ctx, rt_stats* out);
  * a new one at sample 0 by itself, as RT_FLAG_ACCUMULATE_RESTART does.  The other RT_FLAG_* bits change no bits and may differ.
  * The running image ends (the next accumulating call starts at 0) with rt_upload_scene*, rt_update_geometry, rt_dispatch_tile, any
  * rt_render without RT_FLAG_ACCUMULATE and an accumulating call that fails once it has passed its argument checks.  It survives rt_prepare,
- * rt_upload_textures, the ray queries, the surface queries, rt_direct_light, rt_radiance, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
+ * rt_upload_textures, the ray queries, the surface queries, rt_direct_light, rt_radiance, rt_closest_point, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
  * Limit: RT_ACCUMULATE_MAX_SAMPLES samples (where the float sample count stops being exact); a call that would pass it is RT_ERR_BAD_ARG
  * and leaves the running image as it was.  rt_stats describes the call alone (its segments, pixels, kernel_ms).
  * A context over several devices, and a tile_rank / tile_world share, accumulates its own share of the pixels.
@@ -586,6 +586,72 @@ RT_STATIC_ASSERT(sizeof(rt_path_result) == 16 && offsetof(rt_path_result, segmen
 
 /* Extended-mode path radiance along each of the n rays: params->samples paths each. */
 int rt_radiance(rt_ctx* ctx, const rt_ray* rays, size_t n, const rt_path_params* params, rt_path_result* out);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Closest-point queries: the nearest point of the scene's surface to points the caller supplies (no reference counterpart; Embree's
+ * rtcPointQuery is the model): snapping probes and lightmap texels onto geometry, clearance tests, distance fields.  No ray call can
+ * answer it.  The answer is one f32 statement (csrc/closest_point_rules.h; every operation one f32 rounding, nothing fused):
+ *
+ * Triangle, from its record's v0, e1 = v1 - v0, e2 = v2 - v0 (the f32 differences the ray queries use) and the point p, with
+ * dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z:
+ *     ap = p - v0;        d1 = dot(e1, ap); d2 = dot(e2, ap)
+ *     bp = ap - e1;       d3 = dot(e1, bp); d4 = dot(e2, bp)
+ *     cp = ap - e2;       d5 = dot(e1, cp); d6 = dot(e2, cp)
+ *     vc = d1*d4 - d3*d2; vb = d5*d2 - d1*d6; va = d3*d6 - d5*d4
+ *     the first rule that holds, in this order:
+ *       d1 <= 0 && d2 <= 0                         -> (v, w) = (0, 0)
+ *       d3 >= 0 && d4 <= d3                        -> (1, 0)
+ *       vc <= 0 && d1 >= 0 && d3 <= 0              -> (d1 / (d1 - d3), 0)
+ *       d6 >= 0 && d5 <= d6                        -> (0, 1)
+ *       vb <= 0 && d2 >= 0 && d6 <= 0              -> (0, d2 / (d2 - d6))
+ *       va <= 0 && d4-d3 >= 0 && d5-d6 >= 0        -> w = (d4-d3) / ((d4-d3) + (d5-d6)), v = 1 - w
+ *       otherwise                                  -> den = 1 / ((va + vb) + vc), v = vb*den, w = vc*den
+ *     r = (e1*v + e2*w) - ap;  dist2 = dot(r, r);  position = v0 + (e1*v + e2*w);  u = v, v = w (the weights of v1 and v2, as rt_hit)
+ *   (Ericson, Real-Time Collision Detection 5.1.5.)
+ * Sphere i: oc = p - centre; len = sqrtf(dot(oc, oc)); d = fabsf(len - radius); dist2 = d*d;
+ *     position = len > 0 ? centre + oc * (radius / len) : centre + (radius, 0, 0); u = v = 0.  The surface, from inside or outside.
+ * Order: a candidate is (the bits of dist2, key) as one 64-bit unsigned number, key = prim_id ^ 0x80000000 (rt_intersect_all's key: at
+ *   equal dist2 spheres before triangles, each kind by ascending index).  The best starts at (the bits of radius * radius, 0) and a
+ *   candidate replaces it iff it is below it.  So only dist2 < radius * radius is ever accepted, strictly; a NaN or infinite dist2
+ *   never is (degenerate triangles, triangles with a non-finite vertex, bad spheres).  radius = +inf is allowed.
+ * Result: position, distance = sqrtf(dist2), u, v of the winner; prim_id as rt_hit.prim_id; material_id = the record's, not checked
+ *   against the material table.  Nothing accepted: position = 0, distance = the radius as given, u = v = 0, prim_id = 0xFFFFFFFF,
+ *   material_id = 0.  A query with a non-finite position component, a NaN radius or radius <= 0 is such a miss without a walk.  The
+ *   kernel checks this itself.
+ * The result follows from these rules alone: it does not depend on the tree in use (device build, host build,
+ *   RT_PREPARE_QUALITY_TREE, refitted), the device count, the kind of memory or the chunking, and after rt_update_geometry it is
+ *   that of a fresh upload of the moved scene.  The tree only culls, by a lower bound of each box widened past the statement's own
+ *   rounding.
+ * Buffers, synchronisation and side effects as for rt_intersect: both pointers host memory, or both device memory of one context
+ * device (16-byte aligned), anything else is RT_ERR_BAD_ARG; host batches are staged in chunks of at most RT_QUERY_CHUNK points; a
+ * context over several devices splits a host batch into one contiguous range per device; synchronous, first waits for an
+ * rt_dispatch_tile in flight; the last frame, the rt_read_* results and a running accumulation are left alone.
+ * flags: RT_QUERY_COUNTERS.  Statistics: rays = n, the other counts 0, kernel_ms the maximum over devices, node_visits / tri_tests
+ * only with RT_QUERY_COUNTERS.
+ * Errors: n == 0 is RT_OK; a NULL pointer with n > 0 or unknown flag bits are RT_ERR_BAD_ARG; a call before any upload is
+ * RT_ERR_NOT_UPLOADED.  An empty scene gives all misses.
+ * --------------------------------------------------------------------------------------------------------------- */
+typedef struct rt_point_query {
+    float position[3];
+    float radius; /* only surface strictly nearer than this is reported; > 0, +inf allowed */
+} rt_point_query; /* 16 bytes */
+
+typedef struct rt_nearest {
+    float position[3];    /* the nearest point of the surface */
+    float distance;       /* from the query's position; the radius as given on a miss */
+    float u, v;           /* triangle: the weights of v1 and v2 at the point; sphere: 0 */
+    uint32_t prim_id;     /* as rt_hit.prim_id; 0xFFFFFFFF = miss */
+    uint32_t material_id; /* the record's material id, unchecked; 0 on a miss */
+} rt_nearest; /* 32 bytes */
+
+RT_STATIC_ASSERT(sizeof(rt_point_query) == 16 && offsetof(rt_point_query, radius) == 12, "rt_point_query is 16 B, radius at 12");
+RT_STATIC_ASSERT(sizeof(rt_nearest) == 32, "rt_nearest is 32 B");
+RT_STATIC_ASSERT(offsetof(rt_nearest, distance) == 12 && offsetof(rt_nearest, u) == 16 && offsetof(rt_nearest, v) == 20 &&
+                     offsetof(rt_nearest, prim_id) == 24 && offsetof(rt_nearest, material_id) == 28,
+                 "rt_nearest offsets");
+
+/* Nearest surface point to each of the n points. */
+int rt_closest_point(rt_ctx* ctx, const rt_point_query* points, size_t n, rt_nearest* out, uint32_t flags);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Geometry updates: new positions for the uploaded scene, in place (no reference counterpart; Embree's refit build,

@@ -1,0 +1,193 @@
+// Host check of the closest-point query (gpu_raytracer_amd/csrc/closest_point_rules.h), built by tests/test_closest_point_abi.py with
+// AddressSanitizer + UBSan.  It builds trees with bvh_builder.cpp on check_bvh's inputs, runs the walk the kernel runs - cp_walk with
+// the same per-node bound, order, stack discipline and leaf test - with a host-side stack whose index is checked against what the
+// kernel's launch provides, and compares every answer's bytes with a brute force over all records and spheres by the same rules.
+// A bound that culls a box holding the winner, a visiting order that loses a tie, or a stack that outgrows its entries shows here,
+// before any kernel runs.
+// usage: check_closest_point <n_triangles> <seed> <kind> [method]   as check_bvh: method 0 binned SAH (default), 1 PLOC; kind 0 soup,
+//                            1 coplanar grid, 2 coincident points, 3 collinear chain, 4 huge + tiny mixed, 5 with NaN / inf vertices
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <limits>
+#include <random>
+#include <vector>
+
+#include "bvh_builder.h"
+#include "closest_point_rules.h"
+
+using namespace rt;
+
+namespace {
+
+int g_fail = 0;
+
+struct HostAccess {
+    const BvhBuild* b;
+    std::vector<uint64_t> stack; // the entries a lane of the kernel owns: DevScene::stack_entries / 2 + 1
+    int max_sp = 0;
+    unsigned long long nodes = 0, tris = 0;
+
+    void node(uint32_t idx, uint32_t w[20]) {
+        if (idx >= b->nodes.size()) {
+            std::printf("FAIL: node %u out of %zu\n", idx, b->nodes.size());
+            std::exit(1);
+        }
+        static_assert(sizeof(DevNode8) == 80, "DevNode8 is 20 words");
+        std::memcpy(w, &b->nodes[idx], sizeof(DevNode8));
+        nodes++;
+    }
+    void record(uint32_t slot, float q[9], uint32_t ids[3]) {
+        if (slot >= b->tris.size()) {
+            std::printf("FAIL: record %u out of %zu\n", slot, b->tris.size());
+            std::exit(1);
+        }
+        const DevTri& t = b->tris[slot];
+        for (int a = 0; a < 3; a++) q[a] = t.v0[a], q[3 + a] = t.e1[a], q[6 + a] = t.e2[a];
+        ids[0] = t.material_id, ids[1] = t.prim_id, ids[2] = t.leaf_count;
+        tris++;
+    }
+    void push(int sp, uint32_t base, uint32_t bits) {
+        if (sp < 0 || (size_t)sp >= stack.size()) {
+            std::printf("FAIL: stack entry %d of %zu\n", sp, stack.size());
+            std::exit(1);
+        }
+        stack[(size_t)sp] = ((uint64_t)base << 32) | bits;
+        if (sp + 1 > max_sp) max_sp = sp + 1;
+    }
+    void pop(int sp, uint32_t& base, uint32_t& bits) {
+        if (sp < 0 || (size_t)sp >= stack.size()) {
+            std::printf("FAIL: stack entry %d of %zu\n", sp, stack.size());
+            std::exit(1);
+        }
+        base = (uint32_t)(stack[(size_t)sp] >> 32), bits = (uint32_t)stack[(size_t)sp];
+    }
+};
+
+struct Sphere {
+    float centre[3], radius;
+    uint32_t material;
+};
+
+void answer(const BvhBuild& b, const std::vector<Sphere>& spheres, const CpBest& best, const float p[3], float radius, uint32_t out[8]) {
+    cp_answer_miss(radius, out);
+    if (best.slot == 0xFFFFFFFFu) return;
+    if ((uint32_t)best.order & RT_PRIM_SPHERE_FLAG) {
+        const DevTri& t = b.tris[best.slot];
+        float q[9];
+        for (int a = 0; a < 3; a++) q[a] = t.v0[a], q[3 + a] = t.e1[a], q[6 + a] = t.e2[a];
+        cp_answer_triangle(q, t.material_id, best.order, p, out);
+    } else {
+        const Sphere& s = spheres[best.slot];
+        cp_answer_sphere(s.centre, s.radius, s.material, best.order, p, out);
+    }
+}
+
+} // namespace
+
+int main(int argc, char** argv) {
+    const size_t n = argc > 1 ? (size_t)std::atoll(argv[1]) : 1000;
+    const uint32_t seed = argc > 2 ? (uint32_t)std::atoi(argv[2]) : 1;
+    const int kind = argc > 3 ? std::atoi(argv[3]) : 0;
+    std::mt19937 rng(seed);
+    std::uniform_real_distribution<float> u(-1.0f, 1.0f);
+    std::vector<BuildTri> tris(n);
+    for (size_t i = 0; i < n; i++) { // check_bvh's inputs
+        BuildTri& t = tris[i];
+        t.material_id = (uint32_t)(i % 5);
+        t.prim_id = (uint32_t)i;
+        float c[3] = {u(rng) * 10, u(rng) * 10, u(rng) * 10}, s = 0.3f;
+        if (kind == 1) c[2] = -3.0f;
+        if (kind == 2) c[0] = c[1] = c[2] = 1.25f, s = 0.0f;
+        if (kind == 3) c[0] = std::pow(1.001f, (float)i), c[1] = 0.0f, c[2] = 0.0f, s = 1e-3f;
+        if (kind == 4) s = (i % 97 == 0) ? 1e5f : 1e-4f;
+        for (int a = 0; a < 3; a++) {
+            t.v0[a] = c[a] + u(rng) * s;
+            t.v1[a] = c[a] + u(rng) * s;
+            t.v2[a] = c[a] + u(rng) * s;
+            if (kind == 1 && a == 2) t.v0[a] = t.v1[a] = t.v2[a] = -3.0f;
+        }
+        if (kind == 5 && i % 7 == 0) t.v1[i % 3] = (i % 14 == 0) ? std::numeric_limits<float>::quiet_NaN() : std::numeric_limits<float>::infinity();
+    }
+    BvhBuild b;
+    BvhBuildOptions opt;
+    opt.method = argc > 4 ? std::atoi(argv[4]) : 0;
+    build_bvh(tris.data(), tris.size(), opt, b);
+    const std::vector<Sphere> spheres = {{{2.0f, 1.0f, -1.0f}, 0.75f, 1u}, {{-4.0f, 0.5f, 3.0f}, 1.5f, 2u}, {{2.0f, 1.0f, -1.0f}, 0.75f, 3u}};
+
+    // the leaves' records: padding records are not triangles
+    std::vector<uint32_t> recs;
+    for (size_t first = 0; first + RT_DEV_LEAF_STRIDE <= b.tris.size(); first += RT_DEV_LEAF_STRIDE)
+        for (uint32_t x = 0; x < b.tris[first].leaf_count && x < RT_DEV_LEAF_STRIDE; x++) recs.push_back((uint32_t)(first + x));
+
+    // points: near surfaces, on vertices and on surfaces, far outside, with coordinates around 1e4, inside and at the centre of a sphere
+    struct Query {
+        float p[3], radius;
+    };
+    std::vector<Query> qs;
+    const float inf = std::numeric_limits<float>::infinity();
+    const size_t n_each = 96;
+    for (size_t k = 0; k < n_each && !recs.empty(); k++) {
+        const DevTri& t = b.tris[recs[rng() % recs.size()]];
+        const float bu = 0.5f * (u(rng) + 1.0f) * 0.5f, bv = 0.5f * (u(rng) + 1.0f) * 0.5f;
+        Query near, vert, surf;
+        for (int a = 0; a < 3; a++) {
+            surf.p[a] = t.v0[a] + (t.e1[a] * bu + t.e2[a] * bv);
+            near.p[a] = surf.p[a] + u(rng) * 0.05f;
+            vert.p[a] = k % 3 == 0 ? t.v0[a] : k % 3 == 1 ? t.v0[a] + t.e1[a] : t.v0[a] + t.e2[a];
+        }
+        near.radius = vert.radius = surf.radius = inf;
+        if (k % 4 == 3) near.radius = 0.04f; // some within a finite radius, some not
+        qs.push_back(near), qs.push_back(vert), qs.push_back(surf);
+    }
+    for (size_t k = 0; k < n_each; k++) {
+        Query scat, far, big;
+        for (int a = 0; a < 3; a++) scat.p[a] = u(rng) * 30.0f, far.p[a] = u(rng) * 3000.0f, big.p[a] = 1e4f + u(rng) * 50.0f;
+        scat.radius = k % 2 ? inf : 6.0f;
+        far.radius = inf;
+        big.radius = k % 2 ? inf : 2.0e4f;
+        qs.push_back(scat), qs.push_back(far), qs.push_back(big);
+    }
+    qs.push_back({{2.0f, 1.0f, -1.0f}, inf});   // a sphere's centre (two coincident spheres: the lower index wins)
+    qs.push_back({{2.1f, 1.2f, -0.9f}, inf});   // inside it
+    qs.push_back({{2.1f, 1.2f, -0.9f}, 1e-3f}); // ... and too far for this radius
+    qs.push_back({{0.0f, 0.0f, 0.0f}, 3.0e38f}); // radius * radius overflows to +inf: every finite distance is accepted
+
+    HostAccess acc;
+    acc.b = &b;
+    acc.stack.resize((2u * b.depth + 2u) / 2u + 1u); // DevScene::stack_entries / 2 + 1, the kernel's LDS per lane
+    size_t found = 0;
+    for (size_t k = 0; k < qs.size(); k++) {
+        const Query& q = qs[k];
+        uint32_t got[8], want[8];
+        CpBest walk{cp_start(q.radius), 0xFFFFFFFFu}, brute = walk;
+        for (uint32_t s = 0; s < spheres.size(); s++) {
+            float pos[3];
+            const uint64_t c = cp_order(cp_sphere(spheres[s].centre, spheres[s].radius, q.p, pos), s);
+            if (c < walk.order) walk.order = c, walk.slot = s;
+        }
+        brute = walk;
+        cp_walk(acc, (uint32_t)b.nodes.size(), q.p, walk);
+        for (uint32_t r : recs) {
+            const DevTri& t = b.tris[r];
+            float v, w;
+            const uint64_t c = cp_order(cp_triangle(t.v0, t.e1, t.e2, q.p, v, w), t.prim_id ^ RT_PRIM_SPHERE_FLAG);
+            if (c < brute.order) brute.order = c, brute.slot = r;
+        }
+        answer(b, spheres, walk, q.p, q.radius, got);
+        answer(b, spheres, brute, q.p, q.radius, want);
+        found += want[6] != RT_PRIM_MISS;
+        if (std::memcmp(got, want, sizeof got) != 0) {
+            if (g_fail < 20)
+                std::printf("FAIL: query %zu (%.9g %.9g %.9g r %.9g): walk prim %08x dist %.9g, brute force prim %08x dist %.9g\n", k, q.p[0], q.p[1], q.p[2],
+                            q.radius, got[6], cp_float(got[3]), want[6], cp_float(want[3]));
+            g_fail++;
+        }
+    }
+    std::printf("kind %d n %zu method %d: %zu nodes depth %u, %zu queries (%zu answered), %.1f node visits and %.1f triangle tests per query (brute force %zu), "
+                "stack %d of %zu, %d failures\n",
+                kind, n, opt.method, b.nodes.size(), b.depth, qs.size(), found, (double)acc.nodes / (double)qs.size(), (double)acc.tris / (double)qs.size(),
+                recs.size(), acc.max_sp, acc.stack.size(), g_fail);
+    return g_fail ? 1 : 0;
+}
