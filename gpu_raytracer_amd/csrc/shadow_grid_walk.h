@@ -39,6 +39,13 @@ struct GridPending {
     uint32_t i, count; // ... which is entry i of `count`
 };
 static_assert(RT_SG_BLOCK_ENTRIES == 2u, "grid_segment_head tests the block's two entries by name");
+// The grids' arrays are reached through pointers that come from the table staged in LDS, so the compiler cannot tell their address space
+// and would read them with flat loads (each waited for with the LDS counter as well); they are device allocations: global loads.
+typedef uint32_t sg_u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ uint4 sg_ldg4(const uint4* p) {
+    const sg_u32x4 v = *reinterpret_cast<const __attribute__((address_space(1))) sg_u32x4*>(reinterpret_cast<uintptr_t>(p));
+    return make_uint4(v.x, v.y, v.z, v.w);
+}
 template <bool COUNT>
 __device__ __forceinline__ uint32_t grid_segment_head(const DevScene& sc, const DevLight& light, const DevShadowGrid& g, V3 point, V3 normal, GridPending& pend,
                                                       uint32_t& n_tests, uint32_t& n_entries) {
@@ -80,8 +87,8 @@ __device__ __forceinline__ uint32_t grid_segment_head(const DevScene& sc, const 
     uint4 hd = make_uint4(0u, 0u, 0x7F800000u, 0u), q0 = hd, q1 = hd, q2 = hd;
     const uint4* __restrict__ blk = g.blocks + (size_t)(cell == 0xFFFFFFFFu ? 0u : cell) * RT_SG_BLOCK_QUADS;
     if (cell != 0xFFFFFFFFu) {
-        hd = blk[0];
-        q0 = blk[1], q1 = blk[2], q2 = blk[3];
+        hd = sg_ldg4(blk);
+        q0 = sg_ldg4(blk + 1), q1 = sg_ldg4(blk + 2), q2 = sg_ldg4(blk + 3);
         RT_KEEP4(hd);
         RT_KEEP4(q0);
         RT_KEEP4(q1);
@@ -92,7 +99,7 @@ __device__ __forceinline__ uint32_t grid_segment_head(const DevScene& sc, const 
     const uint4* __restrict__ ovf = g.overflow; // 48-byte entries: {key, v0} {e1, e2.x} {e2.yz, record, 0}
     // triangles too close to the light for a bounded dilation: tested by every segment of the light (normally none)
     for (uint32_t k = g.near_begin; k < g.near_end; k++) {
-        const uint4 n0 = ovf[3 * (size_t)k], n1 = ovf[3 * (size_t)k + 1], n2 = ovf[3 * (size_t)k + 2];
+        const uint4 n0 = sg_ldg4(ovf + 3 * (size_t)k), n1 = sg_ldg4(ovf + 3 * (size_t)k + 1), n2 = sg_ldg4(ovf + 3 * (size_t)k + 2);
         if (COUNT) n_tests++;
         float t;
         if (moller_trumbore(v3(__uint_as_float(n0.y), __uint_as_float(n0.z), __uint_as_float(n0.w)), v3(__uint_as_float(n1.x), __uint_as_float(n1.y), __uint_as_float(n1.z)),
@@ -110,7 +117,7 @@ __device__ __forceinline__ uint32_t grid_segment_head(const DevScene& sc, const 
         t > RT_MIN_RAY_DISTANCE && t < dist)
         return GRID_OCCLUDED;
     if (count == 1u) return GRID_VISIBLE;
-    q0 = blk[4], q1 = blk[5], q2 = blk[6];
+    q0 = sg_ldg4(blk + 4), q1 = sg_ldg4(blk + 5), q2 = sg_ldg4(blk + 6);
     if (!(__uint_as_float(q0.x) < limit)) return GRID_VISIBLE;
     if (COUNT) n_entries++, n_tests++;
     if (moller_trumbore(v3(__uint_as_float(q0.y), __uint_as_float(q0.z), __uint_as_float(q0.w)), v3(__uint_as_float(q1.x), __uint_as_float(q1.y), __uint_as_float(q1.z)),
@@ -129,7 +136,7 @@ __device__ __forceinline__ uint32_t grid_walk_on(const DevShadowGrid& g, GridPen
     const uint4* __restrict__ ovf = g.overflow;
     for (uint32_t k = 0; k < trips; k++) {
         const size_t at = 3 * (size_t)pend.at;
-        uint4 q0 = ovf[at], q1 = ovf[at + 1], q2 = ovf[at + 2];
+        uint4 q0 = sg_ldg4(ovf + at), q1 = sg_ldg4(ovf + at + 1), q2 = sg_ldg4(ovf + at + 2);
         RT_KEEP4(q0);
         RT_KEEP4(q1);
         RT_KEEP4(q2);
