@@ -18,6 +18,8 @@
 // a walk can look at.  A grid only pays when its lists are not too long: the build measures them and refuses the grid otherwise
 // (shadow_grid.hip), and a scene keeps its grids only when every light that casts shadows has one (rt_api.cpp).  tests/test_gpu_shadow_grid.py renders every kind of scene and
 // light placement with the lists and with RT_FLAG_NO_SHADOW_GRID and asks for equal bits; the oracle parity tests run on the lists.
+// tests/test_gpu_shadow_grid_edges.py tests the superset property itself: segments aimed within an ulp of silhouettes, seams, cell borders,
+// the near-list threshold, a key's own limit and every boundary of the list bookkeeping must get the tree's answer, byte for byte.
 #ifndef RT_SHADOW_GRID_H
 #define RT_SHADOW_GRID_H
 
