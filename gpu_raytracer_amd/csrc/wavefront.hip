@@ -466,8 +466,9 @@ __global__ __launch_bounds__(WAVE, RT_WF8_MIN_WAVES) void k_wf_trace(DevScene sc
 // (14 node visits x ~200 instructions at 74 % of the lanes) for a third of the closest-hit segments.  Same results: which triangle is
 // hit is decided by the same Moeller-Trumbore statement with the same tie rule (lowest triangle index among equal t), and the list is a
 // superset of the triangles that statement can accept for any segment of the block - the pyramid is widened by an eighth of a pixel
-// (600 x the rounding of a direction) and the leaf boxes by 2e-6 of their magnitude.  Blocks whose list would exceed RT_BEAM_CAP leaves
-// (views along a colonnade) or whose pyramid is degenerate (NaN cameras) keep the per-lane tree walk.
+// (600 x the rounding of a direction at 60 degrees and 1080 rows) and the leaf boxes by 2e-6 of their magnitude.  Blocks whose list would
+// exceed RT_BEAM_CAP leaves (views along a colonnade) or whose pyramid is degenerate (NaN cameras, or a field of view so narrow that the
+// widening drowns in the rounding of a corner direction: under a degree at 1080 rows) keep the per-lane tree walk.
 // Replaces, for depth-0 segments, BvhTraverser::traverse_and_intersect (shader/src/bvh.rs:18-88).
 // ---------------------------------------------------------------------------------------------------------
 #ifndef RT_BEAM_STACK
@@ -527,6 +528,8 @@ __global__ __launch_bounds__(WAVE) void k_wf_beams(DevScene sc, DevFrame fr, rt:
     };
     const V3 cs[4] = {dir(x0, y0), dir(x1, y0), dir(x1, y1), dir(x0, y1)};
     const V3 cc = dir(0.5f * (x0 + x1), 0.5f * (y0 + y1));
+    const float ux0 = (float)p0.x, ux1 = (float)p0.x + 8.0f, uy0 = (float)p0.y, uy1 = (float)p0.y + 8.0f;
+    const V3 cu[4] = {dir(ux0, uy0), dir(ux1, uy0), dir(ux1, uy1), dir(ux0, uy1)}; // the block's own corners: every sample's direction lies between them
     BeamPlanes bp;
     bp.o = ld3(cam.origin);
     bool bad = false;
@@ -538,6 +541,12 @@ __global__ __launch_bounds__(WAVE) void k_wf_beams(DevScene sc, DevFrame fr, rt:
         for (int j = 0; j < 4; j++)
             bad = bad || !(dot(bp.n[k], cs[j]) >= -1e-6f * (fabsf(bp.n[k].x) + fabsf(bp.n[k].y) + fabsf(bp.n[k].z)) * (fabsf(cs[j].x) + fabsf(cs[j].y) + fabsf(cs[j].z)));
         bad = bad || !(fabsf(s) > 0.0f) || !(fabsf(s) < RT_F32_MAX);
+        // the widening must be more than rounding: a sample's direction is a convex combination of the un-widened corners cu up to the 6
+        // roundings of camera_ray's sums, beam_outside's dot product adds 4 and the one below 3 - 13 x 2^-24 of |n|_1 |d|_1 in all - so the
+        // planes tell a sample's ray from the outside only while they keep cu that far inside (2^-20: 16 x 2^-24).  Under about
+        // tan(fov / 2) / height = 4e-6 (1e-5 for a view along no axis: |.|_1 against |.|_2) only blocks whose planes rounding pushed outward pass
+        for (int j = 0; j < 4; j++)
+            bad = bad || !(dot(bp.n[k], cu[j]) >= 0x1p-20f * (fabsf(bp.n[k].x) + fabsf(bp.n[k].y) + fabsf(bp.n[k].z)) * (fabsf(cu[j].x) + fabsf(cu[j].y) + fabsf(cu[j].z)));
     }
     uint32_t n_stack = 0, n_leaf = 0;
     bool overflow = bad;
