@@ -39,7 +39,7 @@ AO_MAX_SAMPLES = 4096  # RT_AO_MAX_SAMPLES: the most samples rt_ambient_occlusio
 DIRECT_AMBIENT, DIRECT_NO_SHADOWS, DIRECT_NO_SHADOW_GRID = 4, 8, 16  # RT_DIRECT_* of rt_direct_light_params.flags
 DIRECT_MAX_LIGHTS = 32  # RT_DIRECT_MAX_LIGHTS: rt_direct_light's lit_mask has one bit per light
 PATH_NO_SHADOWS, PATH_CAMERA_DRAWS = 32, 64  # RT_PATH_* of rt_path_params.flags
-PATH_MAX_SAMPLES = 4096  # RT_PATH_MAX_SAMPLES: the most paths rt_radiance traces per ray
+PATH_MAX_SAMPLES = 4096  # RT_PATH_MAX_SAMPLES: the most paths rt_radiance traces per ray, rt_radiance_sh per probe
 MAX_BOUNCES = T.MAX_BOUNCES  # RT_MAX_BOUNCES
 UPDATE_REBUILD = 1  # RT_UPDATE_REBUILD of rt_update_geometry
 AOV_SAMPLES_PER_LAUNCH = T.AOV_SAMPLES_PER_LAUNCH  # RT_AOV_SAMPLES_PER_LAUNCH: rt_aovs traces at most this many samples per kernel
@@ -58,7 +58,7 @@ ABI_SYMBOLS = [
     "rt_read_rgb32f", "rt_read_rgba8_channels", "rt_read_rgba8_combined", "rt_read_hits",
     "rt_get_stats", "rt_last_error", "rt_destroy", "rt_version",
     "rt_intersect", "rt_occluded", "rt_camera_rays", "rt_intersect_all",
-    "rt_surface", "rt_ambient_occlusion", "rt_direct_light", "rt_radiance", "rt_closest_point",
+    "rt_surface", "rt_ambient_occlusion", "rt_direct_light", "rt_radiance", "rt_radiance_sh", "rt_closest_point",
     "rt_update_geometry",
     "rt_accumulated_samples",
     "rt_aovs", "rt_sample_rays", "rt_denoise",
@@ -270,6 +270,51 @@ def split_radiance(results):
     else:
         segments = np.ascontiguousarray(results[:, 3]).view(np.uint32)
     return results[:, 0:3], segments
+
+
+def make_probes(positions):
+    """(N, 3) positions (numpy or torch, the result has the same kind and device) -> an (N, 4) float32 batch of rt_probe records:
+    px py pz and the ignored pad word, zero."""
+    return make_points(positions, 0.0)
+
+
+def split_sh(results):
+    """(N, 28) probe results (rt_sh9) -> (sh (N, 9, 3), segments (N,)).  sh[:, j, c] is coefficient j of colour channel c; segments is
+    the records' uint32 word: uint32 for numpy, int64 for torch; the segments traced for the probe over all its samples."""
+    if _is_torch(results):
+        import torch
+        segments = results[:, 27].contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    else:
+        segments = np.ascontiguousarray(results[:, 27]).view(np.uint32)
+    return results[:, 0:27].reshape(-1, 9, 3), segments
+
+
+_SH9_COSINE = (np.pi, 2.0 * np.pi / 3.0, 2.0 * np.pi / 3.0, 2.0 * np.pi / 3.0, np.pi / 4.0, np.pi / 4.0, np.pi / 4.0, np.pi / 4.0, np.pi / 4.0)
+
+
+def _sh9_basis(directions):
+    """The 9 real SH basis functions of rt_radiance_sh at (N, 3) unit directions (numpy or torch) -> (N, 9), in the input's dtype."""
+    x, y, z = directions[:, 0], directions[:, 1], directions[:, 2]
+    cols = [0.2820948 + 0.0 * x, 0.4886025 * y, 0.4886025 * z, 0.4886025 * x, 1.0925484 * (x * y), 1.0925484 * (y * z),
+            0.31539157 * (3.0 * (z * z) - 1.0), 1.0925484 * (x * z), 0.5462742 * (x * x - y * y)]
+    if _is_torch(directions):
+        import torch
+        return torch.stack(cols, dim=1)
+    return np.stack(cols, axis=1)
+
+
+def sh9_irradiance(sh, normals):
+    """The cosine-convolved irradiance of (N, 9, 3) coefficients (split_sh) at (N, 3) unit normals -> (N, 3): sum_j A_j sh_j Y_j(n) with
+    A = pi (j = 0), 2 pi / 3 (j = 1..3), pi / 4 (j = 4..8) (Ramamoorthi and Hanrahan 2001).  numpy or torch, both of one kind."""
+    if _is_torch(sh) != _is_torch(normals):
+        raise TypeError("normals: must be the same kind (numpy / torch) as sh")
+    weights = _sh9_basis(normals)
+    if _is_torch(sh):
+        import torch
+        weights = weights * torch.tensor(_SH9_COSINE, dtype=weights.dtype, device=weights.device)
+    else:
+        weights = weights * np.asarray(_SH9_COSINE, weights.dtype)
+    return (sh * weights[:, :, None]).sum(1)
 
 
 def split_aovs(aovs):
@@ -684,6 +729,33 @@ class Context:
         pp["flags"] = (0 if shadows else PATH_NO_SHADOWS) | (PATH_CAMERA_DRAWS if camera_draws else 0) | (QUERY_COUNTERS if counters else 0)
         _sync_torch(rays, out)
         self._check(self.lib.rt_radiance(self._h, _addr(rays), C.c_size_t(n), _p(pp), _addr(out)))
+        return out
+
+    def radiance_sh(self, probes, samples, max_bounces=4, seed=0, first_sample=0, shadows=True, out=None, counters=False):
+        """rt_radiance_sh: the radiance field at each probe of an (N, 4) batch (make_probes: position and an ignored word) as 9 L2
+        spherical-harmonic coefficients per colour channel, from `samples` (1 .. PATH_MAX_SAMPLES) paths along uniformly drawn
+        directions -> (N, 28) float32 rt_sh9 records (split_sh: sh (N, 9, 3), segments), same kind and device as `probes`.  Sample k of
+        probe i draws its direction and its path from rng_for(seed + i, first_sample + k): it is radiance() along that direction with
+        camera_draws=True, projected in sample order.  max_bounces and shadows as radiance()."""
+        n = _check_batch(probes, "probes", 4, "float32")
+        for name, v, lo, hi in (("samples", samples, 1, PATH_MAX_SAMPLES), ("max_bounces", max_bounces, 0, MAX_BOUNCES), ("seed", seed, 0, 0xFFFFFFFF),
+                                ("first_sample", first_sample, 0, 0xFFFFFFFF)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+                raise ValueError(f"{name}: {v!r}, expected an integer in {lo} .. {hi}")
+        if int(first_sample) + int(samples) > 1 << 32:
+            raise ValueError(f"first_sample: {first_sample!r} + samples {samples!r} passes 2^32")
+        if out is None:
+            out = _empty_like_batch(probes, (n, 28), "float32")
+        else:
+            if _is_torch(out) != _is_torch(probes):
+                raise TypeError("out: must be the same kind (numpy / torch) as probes")
+            if _check_batch(out, "out", 28, "float32") != n:
+                raise ValueError(f"out: {out.shape[0]} rows for {n} probes")
+        pp = np.zeros((), dtype=T.PATH_PARAMS)
+        pp["samples"], pp["max_bounces"], pp["seed"], pp["first_sample"] = int(samples), int(max_bounces), int(seed), int(first_sample)
+        pp["flags"] = (0 if shadows else PATH_NO_SHADOWS) | (QUERY_COUNTERS if counters else 0)
+        _sync_torch(probes, out)
+        self._check(self.lib.rt_radiance_sh(self._h, _addr(probes), C.c_size_t(n), _p(pp), _addr(out)))
         return out
 
     def closest_point(self, points, out=None, counters=False):

@@ -1,7 +1,7 @@
 // rt_query.cpp — calls that trace or filter outside a frame: ray queries (rt_hip.h "Ray queries": rt_intersect, rt_occluded,
 // rt_intersect_all, rt_camera_rays), surface queries ("Surface queries": rt_surface, rt_ambient_occlusion; kernels in
 // surface_query.hip), the direct-light query ("Direct-light queries": rt_direct_light; kernel in direct_light.hip), the path query ("Path queries":
-// rt_radiance; kernels in path_query.hip), the closest-point query ("Closest-point queries": rt_closest_point; kernel in closest_point.hip) and the image passes ("Feature buffers (AOVs) and denoising": rt_aovs, rt_sample_rays, rt_denoise; kernels in
+// rt_radiance; kernels in path_query.hip), the probe query ("Probe queries": rt_radiance_sh; kernels in probe_query.hip), the closest-point query ("Closest-point queries": rt_closest_point; kernel in closest_point.hip) and the image passes ("Feature buffers (AOVs) and denoising": rt_aovs, rt_sample_rays, rt_denoise; kernels in
 // denoise.hip).  None of them touches the frame targets, the tile shares rt_read_* gather, or the running image of an accumulation.
 #include "rt_internal.h"
 
@@ -511,6 +511,112 @@ int run_radiance(rt_ctx* ctx, const rt_ray* rays, size_t n, const rt_path_params
     return RT_OK;
 }
 
+// rt_radiance_sh: run_radiance's shape with probes for rays (16 bytes in, 112 bytes out per probe).  The scratch of one record per path
+// is used with any number of samples: the record is not the result, a projection always runs.
+int run_radiance_sh(rt_ctx* ctx, const rt_probe* probes, size_t n, const rt_path_params* p, rt_sh9* out) {
+    const char* fn = "rt_radiance_sh";
+    const double w0 = now_ms();
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (n == 0) return RT_OK;
+    if (!probes || !p || !out) return ctx->fail(RT_ERR_BAD_ARG, "%s: %s is NULL with n = %zu", fn, !probes ? "probes" : !p ? "params" : "out", n);
+    if (p->samples < 1 || p->samples > RT_PATH_MAX_SAMPLES) return ctx->fail(RT_ERR_BAD_ARG, "%s: samples %u (1 .. %u)", fn, p->samples, RT_PATH_MAX_SAMPLES);
+    if (p->max_bounces > RT_MAX_BOUNCES) return ctx->fail(RT_ERR_BAD_ARG, "%s: max_bounces %u (0 .. %u)", fn, p->max_bounces, RT_MAX_BOUNCES);
+    if ((uint64_t)p->first_sample + p->samples > (1ull << 32))
+        return ctx->fail(RT_ERR_BAD_ARG, "%s: first_sample %u + samples %u passes 2^32", fn, p->first_sample, p->samples);
+    if (p->flags & RT_PATH_CAMERA_DRAWS) return ctx->fail(RT_ERR_BAD_ARG, "%s: flags: RT_PATH_CAMERA_DRAWS (the call spends those two draws itself)", fn);
+    const uint32_t known = RT_QUERY_COUNTERS | RT_PATH_NO_SHADOWS;
+    if (p->flags & ~known) return ctx->fail(RT_ERR_BAD_ARG, "%s: unknown flag bits 0x%x", fn, p->flags & ~known);
+    if (!ctx->uploaded) return ctx->fail(RT_ERR_NOT_UPLOADED, "%s: no scene uploaded", fn);
+    if (int rcp = sync_pending(ctx)) return rcp;
+    QueryPtr pin, pout;
+    if (int rc = classify_ptr(ctx, fn, "probes", probes, pin)) return rc;
+    if (int rc = classify_ptr(ctx, fn, "out", out, pout)) return rc;
+    if (pin.device != pout.device || pin.dev != pout.dev)
+        return ctx->fail(RT_ERR_BAD_ARG, "%s: probes and out must both be host memory or both device memory of the same device", fn);
+    const rt::PathArgs args{p->samples, p->max_bounces, p->seed, p->first_sample, (p->flags & RT_PATH_NO_SHADOWS) ? 0u : 1u, 1u};
+    const size_t chunk = std::max<size_t>(1, RT_QUERY_CHUNK / p->samples);
+    const bool counters = (p->flags & RT_QUERY_COUNTERS) != 0;
+    const size_t nd = ctx->devs.size();
+    std::vector<size_t> first(nd, 0), count(nd, 0);
+    if (pin.device) count[pin.dev] = n; // a device batch runs where it lives
+    else
+        for (size_t j = 0; j < nd; j++) first[j] = n * j / nd, count[j] = n * (j + 1) / nd - first[j]; // contiguous ranges, one per device
+    // every device's range is enqueued before any is waited for
+    auto enqueue = [&](size_t j) -> int {
+        DeviceState& d = ctx->devs[j];
+        HIPCHK(ctx, hipSetDevice(d.device));
+        const DevScene sc = scene_for(ctx, d);
+        const size_t chunks = (count[j] + chunk - 1) / chunk;
+        // a host batch times each chunk's launches apart from its copies; a device batch has no copies between its launches: one pair
+        if (int rc = ensure_query_events(ctx, d, pin.device ? 2 : 2 * chunks)) return rc;
+        const size_t most = std::min<size_t>(count[j], chunk);
+        HIPCHK(ctx, d.rq.paths.reserve(most * args.samples * sizeof(uint4)));
+        if (!pin.device) {
+            HIPCHK(ctx, d.rq.in.reserve(most * sizeof(rt_probe)));
+            HIPCHK(ctx, d.rq.out.reserve(most * sizeof(rt_sh9)));
+        }
+        HIPCHK(ctx, hipMemsetAsync(d.counters.get(), 0, RT_CNT_DIAG * sizeof(unsigned long long), d.stream));
+        for (size_t c = 0; c < chunks; c++) {
+            const size_t off = first[j] + c * chunk, m = std::min<size_t>(chunk, first[j] + count[j] - off);
+            const void* in = probes + off;
+            void* res = out + off;
+            if (!pin.device) {
+                HIPCHK(ctx, hipMemcpyAsync(d.rq.in.get(), in, m * sizeof(rt_probe), hipMemcpyHostToDevice, d.stream));
+                in = d.rq.in.get();
+                res = d.rq.out.get();
+            }
+            if (!pin.device || c == 0) HIPCHK(ctx, hipEventRecord(d.rq_events[pin.device ? 0 : 2 * c], d.stream));
+            HIPCHK(ctx, rt::launch_probe_query(sc, args, in, off, (uint32_t)m, d.rq.paths.get(), res, counters, d.counters.get(), d.stream));
+            if (!pin.device || c + 1 == chunks) HIPCHK(ctx, hipEventRecord(d.rq_events[pin.device ? 1 : 2 * c + 1], d.stream));
+            if (!pin.device) HIPCHK(ctx, hipMemcpyAsync(out + off, res, m * sizeof(rt_sh9), hipMemcpyDeviceToHost, d.stream));
+        }
+        return RT_OK;
+    };
+    for (size_t j = 0; j < nd; j++)
+        if (count[j] > 0)
+            if (int rc = enqueue(j)) {
+                drain_streams(ctx);
+                return rc;
+            }
+    double kernel_ms = 0.0;
+    unsigned long long camera = 0, continuation = 0, shadow = 0, nodes = 0, tris = 0;
+    for (size_t j = 0; j < nd; j++) {
+        if (count[j] == 0) continue;
+        DeviceState& d = ctx->devs[j];
+        hipError_t e = hipSetDevice(d.device);
+        if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
+        if (e != hipSuccess) {
+            drain_streams(ctx);
+            return ctx->fail(RT_ERR_HIP, "%s: device %d: %s", fn, d.device, hipGetErrorString(e));
+        }
+        double ms = 0.0;
+        for (size_t c = 0; c * chunk < count[j] && (c == 0 || !pin.device); c++) {
+            float cm = 0.0f;
+            HIPCHK(ctx, hipEventElapsedTime(&cm, d.rq_events[2 * c], d.rq_events[2 * c + 1]));
+            ms += cm;
+        }
+        kernel_ms = std::max(kernel_ms, ms);
+        unsigned long long cn[RT_CNT_DIAG];
+        HIPCHK(ctx, hipMemcpy(cn, d.counters.get(), sizeof cn, hipMemcpyDeviceToHost));
+        camera += cn[RT_CNT_CAMERA];
+        continuation += cn[RT_CNT_CONTINUATION];
+        shadow += cn[RT_CNT_SHADOW];
+        nodes += cn[RT_CNT_NODE_VISITS];
+        tris += cn[RT_CNT_TRI_TESTS];
+    }
+    rt_stats& st = ctx->stats;
+    st.rays = camera + continuation + shadow;
+    st.primary_rays = camera;
+    st.continuation_rays = continuation;
+    st.shadow_rays = shadow;
+    st.pixels = 0;
+    st.node_visits = counters ? nodes : 0;
+    st.tri_tests = counters ? tris : 0;
+    st.kernel_ms = kernel_ms;
+    st.wall_ms = now_ms() - w0;
+    return RT_OK;
+}
+
 // rt_closest_point: run_query's shape with points for rays: 16 bytes in, 32 bytes out per point.
 int run_closest_point(rt_ctx* ctx, const rt_point_query* points, size_t n, rt_nearest* out, uint32_t flags) {
     const char* fn = "rt_closest_point";
@@ -808,6 +914,10 @@ int rt_direct_light(rt_ctx* ctx, const rt_surface_point* points, size_t n, const
 
 int rt_radiance(rt_ctx* ctx, const rt_ray* rays, size_t n, const rt_path_params* params, rt_path_result* out) {
     return run_radiance(ctx, rays, n, params, out);
+}
+
+int rt_radiance_sh(rt_ctx* ctx, const rt_probe* probes, size_t n, const rt_path_params* params, rt_sh9* out) {
+    return run_radiance_sh(ctx, probes, n, params, out);
 }
 
 int rt_closest_point(rt_ctx* ctx, const rt_point_query* points, size_t n, rt_nearest* out, uint32_t flags) {

@@ -224,7 +224,7 @@ int rt_get_stats(rt_ctx* ctx, rt_stats* out);
  * a new one at sample 0 by itself, as RT_FLAG_ACCUMULATE_RESTART does.  The other RT_FLAG_* bits change no bits and may differ.
  * The running image ends (the next accumulating call starts at 0) with rt_upload_scene*, rt_update_geometry, rt_dispatch_tile, any
  * rt_render without RT_FLAG_ACCUMULATE and an accumulating call that fails once it has passed its argument checks.  It survives rt_prepare,
- * rt_upload_textures, the ray queries, the surface queries, rt_direct_light, rt_radiance, rt_closest_point, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
+ * rt_upload_textures, the ray queries, the surface queries, rt_direct_light, rt_radiance, rt_radiance_sh, rt_closest_point, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
  * Limit: RT_ACCUMULATE_MAX_SAMPLES samples (where the float sample count stops being exact); a call that would pass it is RT_ERR_BAD_ARG
  * and leaves the running image as it was.  rt_stats describes the call alone (its segments, pixels, kernel_ms).
  * A context over several devices, and a tile_rank / tile_world share, accumulates its own share of the pixels.
@@ -586,6 +586,62 @@ RT_STATIC_ASSERT(sizeof(rt_path_result) == 16 && offsetof(rt_path_result, segmen
 
 /* Extended-mode path radiance along each of the n rays: params->samples paths each. */
 int rt_radiance(rt_ctx* ctx, const rt_ray* rays, size_t n, const rt_path_params* params, rt_path_result* out);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Probe queries: the radiance field at points the caller supplies, as 9 real spherical-harmonic coefficients per colour channel (L2;
+ * Ramamoorthi and Hanrahan 2001) - the form DDGI-style probe grids and lightmap bakers store (no reference counterpart).  It is
+ * rt_radiance over directions the device draws itself, projected in sample order.  Every bit is fixed by rt_radiance and one f32
+ * statement.
+ *
+ * rt_radiance_sh: for probe i (its index in the caller's array) and sample k < samples:
+ *   1. rng = rng_for(seed + i (mod 2^32), first_sample + k), the frames' generator; u1 = next_f32(), u2 = next_f32();
+ *      d_k = unit_vector(u1, u2), the frames' uniformly distributed unit direction, used as it comes: not renormalised.
+ *   2. x_k = the radiance rt_radiance gives for the ray {origin = position, tmin = RT_MIN_RAY_DISTANCE, direction = d_k, tmax = FLT_MAX}
+ *      with samples = 1, first_sample = first_sample + k, the same seed and ray index i, the same max_bounces and RT_PATH_NO_SHADOWS,
+ *      and RT_PATH_CAMERA_DRAWS: the path goes on from the generator's third draw.  g_k = that ray's segments.
+ *   3. the basis at d = (x, y, z), every operation one f32 rounding, as written, nothing fused:
+ *        Y0 = 0.2820948f                   Y1 = 0.4886025f*y                        Y2 = 0.4886025f*z
+ *        Y3 = 0.4886025f*x                 Y4 = 1.0925484f*(x*y)                    Y5 = 1.0925484f*(y*z)
+ *        Y6 = 0.31539157f*(3.0f*(z*z) - 1.0f)   Y7 = 1.0925484f*(x*z)               Y8 = 0.5462742f*(x*x - y*y)
+ *   4. out[i].sh[j][c] = (0 + x_0[c]*Y_j(d_0) + x_1[c]*Y_j(d_1) + ...) * (12.566371f / (float)samples): an f32 sum from zero in
+ *      sample order, each term one product, then one division and one multiply in that grouping (the Monte-Carlo estimate of the
+ *      projection integral over the sphere, 4 pi / samples per sample).  out[i].segments = g_0 + g_1 + ... mod 2^32.
+ *   5. a probe with a non-finite position component is no probe: nothing is traced, all 27 coefficients are 0 and segments = 0.  A
+ *      sample whose d_k is zero contributes x_k = 0, g_k = 0 by rt_radiance's own degeneracy rule.
+ * What follows:
+ *   - the result does not depend on the tree in use (device build, host build, RT_PREPARE_QUALITY_TREE, refitted), the device count,
+ *     the kind of memory or the chunking.  Light grids are never looked at.  Any number of lights, as rt_radiance.
+ *   - an empty scene gives the sky's projection: sh[0][c] = sky[c] * 4 pi * 0.2820948 within (samples + 4) * 2^-24 of it, the other
+ *     coefficients the Monte-Carlo noise around 0 (standard deviation sky[c] * sqrt(4 pi / samples)), segments = samples.
+ * params: rt_path_params as rt_radiance reads it - samples (directions per probe) 1 .. RT_PATH_MAX_SAMPLES; max_bounces 0 ..
+ *   RT_MAX_BOUNCES; first_sample + samples <= 2^32; flags RT_PATH_NO_SHADOWS, RT_QUERY_COUNTERS - except RT_PATH_CAMERA_DRAWS, which
+ *   is RT_ERR_BAD_ARG: the call spends those two draws itself.  _pad ignored; rt_probe._pad ignored.
+ * Buffers, synchronisation and side effects as for rt_radiance: both pointers host memory, or both device memory of one context
+ * device (16-byte aligned), anything else is RT_ERR_BAD_ARG; batches are traced in chunks of at most max(1, RT_QUERY_CHUNK / samples)
+ * probes, host batches staged chunk by chunk; a context over several devices splits a host batch into one contiguous range per device
+ * (the seed's i stays the index in the caller's array); synchronous, first waits for an rt_dispatch_tile in flight; the last frame,
+ * the rt_read_* results and a running accumulation are left alone.
+ * Errors: n == 0 is RT_OK; NULL probes / params / out, samples out of range, max_bounces > RT_MAX_BOUNCES, first_sample + samples > 2^32,
+ * RT_PATH_CAMERA_DRAWS and unknown flag bits are RT_ERR_BAD_ARG and change nothing; a call before any upload is RT_ERR_NOT_UPLOADED.
+ * Statistics: as rt_radiance - rays = all segments, primary_rays = first segments (valid probes x samples), continuation_rays and
+ * shadow_rays as the frames count them, pixels = 0, kernel_ms the maximum over devices, node_visits / tri_tests only with
+ * RT_QUERY_COUNTERS.
+ * --------------------------------------------------------------------------------------------------------------- */
+typedef struct rt_probe {
+    float position[3];
+    uint32_t _pad; /* ignored */
+} rt_probe; /* 16 bytes */
+
+typedef struct rt_sh9 {
+    float sh[9][3];    /* coefficient j, channel c at sh[j][c] */
+    uint32_t segments; /* segments traced for this probe over all its samples (first + continuation + shadow), mod 2^32 */
+} rt_sh9; /* 112 bytes */
+
+RT_STATIC_ASSERT(sizeof(rt_probe) == 16 && offsetof(rt_probe, _pad) == 12, "rt_probe is 16 B, _pad at 12");
+RT_STATIC_ASSERT(sizeof(rt_sh9) == 112 && offsetof(rt_sh9, sh) == 0 && offsetof(rt_sh9, segments) == 108, "rt_sh9 is 112 B, segments at 108");
+
+/* L2 spherical-harmonic radiance probes at each of the n points: params->samples paths each. */
+int rt_radiance_sh(rt_ctx* ctx, const rt_probe* probes, size_t n, const rt_path_params* params, rt_sh9* out);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Closest-point queries: the nearest point of the scene's surface to points the caller supplies (no reference counterpart; Embree's
