@@ -58,7 +58,7 @@ ABI_SYMBOLS = [
     "rt_read_rgb32f", "rt_read_rgba8_channels", "rt_read_rgba8_combined", "rt_read_hits",
     "rt_get_stats", "rt_last_error", "rt_destroy", "rt_version",
     "rt_intersect", "rt_occluded", "rt_camera_rays", "rt_intersect_all",
-    "rt_surface", "rt_ambient_occlusion", "rt_direct_light", "rt_radiance", "rt_radiance_sh", "rt_closest_point",
+    "rt_surface", "rt_ambient_occlusion", "rt_direct_light", "rt_radiance", "rt_radiance_sh", "rt_closest_point", "rt_sweep_sphere",
     "rt_update_geometry",
     "rt_accumulated_samples",
     "rt_aovs", "rt_sample_rays", "rt_denoise",
@@ -248,6 +248,20 @@ def split_nearest(nearest):
     else:
         ids = [np.ascontiguousarray(nearest[:, c]).view(np.uint32) for c in (6, 7)]
     return nearest[:, 0:3], nearest[:, 3], nearest[:, 4], nearest[:, 5], ids[0], ids[1]
+
+
+def make_sweeps(origins, directions, radius, tmax=float("inf")):
+    """(N, 3) origins and directions (numpy or torch, the result has the same kind and device) -> an (N, 8) float32 batch of rt_sweep
+    records: ox oy oz radius dx dy dz tmax.  radius / tmax: scalars or (N,) arrays; contacts at 0 <= t < tmax are reported."""
+    out = make_rays(origins, directions, tmin=0.0, tmax=tmax)
+    out[:, 3] = radius
+    return out
+
+
+def split_sweep_hits(records):
+    """(N, 8) sweep records (rt_sweep_hit) -> (position (N, 3), t (N,), u (N,), v (N,), prim_id (N,), material_id (N,)): rt_nearest's
+    layout with t where the distance is, so the ids come as split_nearest gives them."""
+    return split_nearest(records)
 
 
 def split_lighting(lighting):
@@ -764,6 +778,13 @@ class Context:
         kind and device as `points`.  Only surface strictly nearer than the radius is reported; a miss is position 0, the radius as
         distance and prim_id = PRIM_MISS."""
         return self._query("rt_closest_point", points, out, 8, "float32", counters, in_cols=4, in_name="points")
+
+    def sweep_sphere(self, sweeps, out=None, counters=False):
+        """rt_sweep_sphere: the first contact of each moving sphere of an (N, 8) batch (make_sweeps: origin, radius, direction, tmax)
+        with the scene's surface -> (N, 8) float32 rt_sweep_hit records (split_sweep_hits: position, t, u, v, prim_id, material_id),
+        same kind and device as `sweeps`.  Only contacts at 0 <= t < tmax are reported; a miss is position 0, tmax as t and
+        prim_id = PRIM_MISS.  The contact normal is origin + direction * t - position."""
+        return self._query("rt_sweep_sphere", sweeps, out, 8, "float32", counters, in_name="sweeps")
 
     def camera_rays(self, width, height, camera, mode=MODE_LEGACY, out=None):
         """rt_camera_rays: the width x height pixel-centre rays of mode 0/1 as a (width * height, 8) batch, row-major, y down.

@@ -33,6 +33,7 @@
 #include "refit.h"
 #include "shadow_grid.h"
 #include "surface_query.h"
+#include "sweep.h"
 #include "wavefront.h"
 
 #define HIPCHK(ctx, call)                                                                                       \

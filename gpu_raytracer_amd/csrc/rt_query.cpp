@@ -1,7 +1,7 @@
 // rt_query.cpp — calls that trace or filter outside a frame: ray queries (rt_hip.h "Ray queries": rt_intersect, rt_occluded,
 // rt_intersect_all, rt_camera_rays), surface queries ("Surface queries": rt_surface, rt_ambient_occlusion; kernels in
 // surface_query.hip), the direct-light query ("Direct-light queries": rt_direct_light; kernel in direct_light.hip), the path query ("Path queries":
-// rt_radiance; kernels in path_query.hip), the probe query ("Probe queries": rt_radiance_sh; kernels in probe_query.hip), the closest-point query ("Closest-point queries": rt_closest_point; kernel in closest_point.hip) and the image passes ("Feature buffers (AOVs) and denoising": rt_aovs, rt_sample_rays, rt_denoise; kernels in
+// rt_radiance; kernels in path_query.hip), the probe query ("Probe queries": rt_radiance_sh; kernels in probe_query.hip), the closest-point query ("Closest-point queries": rt_closest_point; kernel in closest_point.hip), the sphere sweep ("Sphere sweeps": rt_sweep_sphere; kernel in sweep.hip) and the image passes ("Feature buffers (AOVs) and denoising": rt_aovs, rt_sample_rays, rt_denoise; kernels in
 // denoise.hip).  None of them touches the frame targets, the tile shares rt_read_* gather, or the running image of an accumulation.
 #include "rt_internal.h"
 
@@ -617,21 +617,25 @@ int run_radiance_sh(rt_ctx* ctx, const rt_probe* probes, size_t n, const rt_path
     return RT_OK;
 }
 
-// rt_closest_point: run_query's shape with points for rays: 16 bytes in, 32 bytes out per point.
-int run_closest_point(rt_ctx* ctx, const rt_point_query* points, size_t n, rt_nearest* out, uint32_t flags) {
-    const char* fn = "rt_closest_point";
+// rt_closest_point and rt_sweep_sphere: run_query's shape with records of in_size bytes for rays and records of out_size bytes out,
+// one lane of `launch` per record.  in_name: what the records are called in messages.
+using RecordLaunch = hipError_t (*)(const DevScene&, const void*, void*, uint32_t, unsigned long long*, hipStream_t);
+int run_record_query(rt_ctx* ctx, const char* fn, const char* in_name, const void* records, size_t in_size, size_t n, void* results, size_t out_size,
+                     uint32_t flags, RecordLaunch launch) {
+    const char* points = static_cast<const char*>(records);
+    char* out = static_cast<char*>(results);
     const double w0 = now_ms();
     if (!ctx) return RT_ERR_BAD_ARG;
     if (n == 0) return RT_OK;
-    if (!points || !out) return ctx->fail(RT_ERR_BAD_ARG, "%s: %s is NULL with n = %zu", fn, !points ? "points" : "out", n);
+    if (!points || !out) return ctx->fail(RT_ERR_BAD_ARG, "%s: %s is NULL with n = %zu", fn, !points ? in_name : "out", n);
     if (flags & ~RT_QUERY_COUNTERS) return ctx->fail(RT_ERR_BAD_ARG, "%s: unknown flag bits 0x%x", fn, flags & ~RT_QUERY_COUNTERS);
     if (!ctx->uploaded) return ctx->fail(RT_ERR_NOT_UPLOADED, "%s: no scene uploaded", fn);
     if (int rcp = sync_pending(ctx)) return rcp;
     QueryPtr pin, pout;
-    if (int rc = classify_ptr(ctx, fn, "points", points, pin)) return rc;
+    if (int rc = classify_ptr(ctx, fn, in_name, points, pin)) return rc;
     if (int rc = classify_ptr(ctx, fn, "out", out, pout)) return rc;
     if (pin.device != pout.device || pin.dev != pout.dev)
-        return ctx->fail(RT_ERR_BAD_ARG, "%s: points and out must both be host memory or both device memory of the same device", fn);
+        return ctx->fail(RT_ERR_BAD_ARG, "%s: %s and out must both be host memory or both device memory of the same device", fn, in_name);
     const size_t chunk = RT_QUERY_CHUNK;
     const bool counters = (flags & RT_QUERY_COUNTERS) != 0;
     const size_t nd = ctx->devs.size();
@@ -648,23 +652,23 @@ int run_closest_point(rt_ctx* ctx, const rt_point_query* points, size_t n, rt_ne
         if (int rc = ensure_query_events(ctx, d, 2 * chunks)) return rc;
         if (!pin.device) {
             const size_t most = std::min<size_t>(count[j], chunk);
-            HIPCHK(ctx, d.rq.in.reserve(most * sizeof(rt_point_query)));
-            HIPCHK(ctx, d.rq.out.reserve(most * sizeof(rt_nearest)));
+            HIPCHK(ctx, d.rq.in.reserve(most * in_size));
+            HIPCHK(ctx, d.rq.out.reserve(most * out_size));
         }
         if (counters) HIPCHK(ctx, hipMemsetAsync(d.counters.get(), 0, (RT_CNT_TRI_TESTS + 1) * sizeof(unsigned long long), d.stream));
         for (size_t c = 0; c < chunks; c++) {
             const size_t off = first[j] + c * chunk, m = std::min<size_t>(chunk, first[j] + count[j] - off);
-            const void* in = points + off;
-            void* res = out + off;
+            const void* in = points + off * in_size;
+            void* res = out + off * out_size;
             if (!pin.device) {
-                HIPCHK(ctx, hipMemcpyAsync(d.rq.in.get(), in, m * sizeof(rt_point_query), hipMemcpyHostToDevice, d.stream));
+                HIPCHK(ctx, hipMemcpyAsync(d.rq.in.get(), in, m * in_size, hipMemcpyHostToDevice, d.stream));
                 in = d.rq.in.get();
                 res = d.rq.out.get();
             }
             HIPCHK(ctx, hipEventRecord(d.rq_events[2 * c], d.stream));
-            HIPCHK(ctx, rt::launch_closest_point(sc, in, res, (uint32_t)m, counters ? d.counters.get() : nullptr, d.stream));
+            HIPCHK(ctx, launch(sc, in, res, (uint32_t)m, counters ? d.counters.get() : nullptr, d.stream));
             HIPCHK(ctx, hipEventRecord(d.rq_events[2 * c + 1], d.stream));
-            if (!pin.device) HIPCHK(ctx, hipMemcpyAsync(out + off, res, m * sizeof(rt_nearest), hipMemcpyDeviceToHost, d.stream));
+            if (!pin.device) HIPCHK(ctx, hipMemcpyAsync(out + off * out_size, res, m * out_size, hipMemcpyDeviceToHost, d.stream));
         }
         return RT_OK;
     };
@@ -921,7 +925,10 @@ int rt_radiance_sh(rt_ctx* ctx, const rt_probe* probes, size_t n, const rt_path_
 }
 
 int rt_closest_point(rt_ctx* ctx, const rt_point_query* points, size_t n, rt_nearest* out, uint32_t flags) {
-    return run_closest_point(ctx, points, n, out, flags);
+    return run_record_query(ctx, "rt_closest_point", "points", points, sizeof(rt_point_query), n, out, sizeof(rt_nearest), flags, rt::launch_closest_point);
+}
+int rt_sweep_sphere(rt_ctx* ctx, const rt_sweep* sweeps, size_t n, rt_sweep_hit* out, uint32_t flags) {
+    return run_record_query(ctx, "rt_sweep_sphere", "sweeps", sweeps, sizeof(rt_sweep), n, out, sizeof(rt_sweep_hit), flags, rt::launch_sweep_sphere);
 }
 
 int rt_camera_rays(rt_ctx* ctx, const rt_camera* camera, uint32_t width, uint32_t height, uint32_t mode, rt_ray* out) {

@@ -86,6 +86,8 @@ PROBE = np.dtype([("position", f32, 3), ("_pad", u32)])  # rt_probe
 SH9 = np.dtype([("sh", f32, (9, 3)), ("segments", u32)])  # rt_sh9
 POINT_QUERY = np.dtype([("position", f32, 3), ("radius", f32)])  # rt_point_query
 NEAREST = np.dtype([("position", f32, 3), ("distance", f32), ("u", f32), ("v", f32), ("prim_id", u32), ("material_id", u32)])  # rt_nearest
+SWEEP = np.dtype([("origin", f32, 3), ("radius", f32), ("direction", f32, 3), ("tmax", f32)])  # rt_sweep
+SWEEP_HIT = np.dtype([("position", f32, 3), ("t", f32), ("u", f32), ("v", f32), ("prim_id", u32), ("material_id", u32)])  # rt_sweep_hit
 AOV_SAMPLES_PER_LAUNCH = 64  # RT_AOV_SAMPLES_PER_LAUNCH
 DENOISE_DEMODULATE = 1  # RT_DENOISE_DEMODULATE
 DENOISE_MAX_ITERATIONS = 10
@@ -106,6 +108,7 @@ EXPECTED_SIZES = {
     "SCENE_METADATA_OFFSETS": 40, "PUSH_CONSTANTS": 128, "AOV": 32, "DENOISE_PARAMS": 32,
     "ADAPTIVE_PARAMS": 16, "ADAPTIVE_PIXEL": 32, "SURFACE_POINT": 32, "AO_PARAMS": 32, "LIGHTING": 16, "DIRECT_LIGHT_PARAMS": 16,
     "PATH_PARAMS": 32, "PATH_RESULT": 16, "PROBE": 16, "SH9": 112, "POINT_QUERY": 16, "NEAREST": 32,
+    "SWEEP": 32, "SWEEP_HIT": 32,
 }
 for _name, _size in EXPECTED_SIZES.items():
     assert globals()[_name].itemsize == _size, (_name, globals()[_name].itemsize, _size)

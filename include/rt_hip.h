@@ -224,7 +224,7 @@ int rt_get_stats(rt_ctx* ctx, rt_stats* out);
  * a new one at sample 0 by itself, as RT_FLAG_ACCUMULATE_RESTART does.  The other RT_FLAG_* bits change no bits and may differ.
  * The running image ends (the next accumulating call starts at 0) with rt_upload_scene*, rt_update_geometry, rt_dispatch_tile, any
  * rt_render without RT_FLAG_ACCUMULATE and an accumulating call that fails once it has passed its argument checks.  It survives rt_prepare,
- * rt_upload_textures, the ray queries, the surface queries, rt_direct_light, rt_radiance, rt_radiance_sh, rt_closest_point, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
+ * rt_upload_textures, the ray queries, the surface queries, rt_direct_light, rt_radiance, rt_radiance_sh, rt_closest_point, rt_sweep_sphere, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
  * Limit: RT_ACCUMULATE_MAX_SAMPLES samples (where the float sample count stops being exact); a call that would pass it is RT_ERR_BAD_ARG
  * and leaves the running image as it was.  rt_stats describes the call alone (its segments, pixels, kernel_ms).
  * A context over several devices, and a tile_rank / tile_world share, accumulates its own share of the pixels.
@@ -708,6 +708,86 @@ RT_STATIC_ASSERT(offsetof(rt_nearest, distance) == 12 && offsetof(rt_nearest, u)
 
 /* Nearest surface point to each of the n points. */
 int rt_closest_point(rt_ctx* ctx, const rt_point_query* points, size_t n, rt_nearest* out, uint32_t flags);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Sphere sweeps: the first contact of a moving sphere with the scene's surface (no reference counterpart; the "sphere cast" of the
+ * collision libraries is the model): camera and character collision, pushing a probe along a direction until it has clearance,
+ * clearance along a path, thick-ray visibility.  A ray is not conservative for a body with extent, and stepping rt_closest_point
+ * along the segment misses thin contacts between steps.  The sphere's centre moves as centre(t) = origin + direction * t; the answer
+ * is the smallest t in [0, tmax) at which it lies within `radius` of the surface, and the point of the surface it touches there.
+ * The surface is two-sided and a sphere primitive is its surface, as for rt_closest_point.  The answer is one f32 statement
+ * (csrc/sweep_rules.h; every operation one f32 rounding, nothing fused), with dot as in "Closest-point queries",
+ * cross(a, b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x), c = origin, d = direction, r = radius, rr = r*r,
+ * dd = dot(d, d).  The candidate time of a primitive is the minimum, by value, of the pieces below that accept (a -0 counts as +0);
+ * a NaN never accepts.  The pieces are the first entry into the primitive's Minkowski sum with the ball.
+ *
+ * Triangle, from its record's v0, e1, e2; ap = c - v0:
+ *   Overlap at the start: the closest-point statement's dist2 of the triangle from c is <= rr               -> t = 0
+ *   Face: n = cross(e1, e2); nn = dot(n, n); ln = sqrtf(nn); h = dot(n, ap); nd = dot(n, d); s = h < 0 ? -1 : 1
+ *       num = fabsf(h) - r*ln; den = -(s*nd); t = num / den; k = s*r / ln; q = (ap + d*t) - n*k  (per component)
+ *       fv = dot(cross(q, e2), n) / nn; fw = dot(cross(e1, q), n) / nn
+ *       accepts iff num >= 0 && den > 0 && fv >= 0 && fw >= 0 && fv + fw <= 1
+ *   Vertices a in (0, e1, e2): m = ap - a; b = dot(m, d); x = cross(m, d); disc = dd*rr - dot(x, x); t = (-b - sqrtf(disc)) / dd
+ *       accepts iff disc >= 0 && t >= 0
+ *   Edges (a, e) in ((0, e1), (0, e2), (e1, e2 - e1)): m = ap - a; g = cross(e, d); p = cross(g, e)
+ *       A = dot(g, g); B = dot(m, p); h = dot(m, g); ee = dot(e, e); disc = rr*A - h*h; t = (-B - sqrtf(ee*disc)) / A
+ *       sp = (dot(m, e) + t*dot(d, e)) / ee
+ *       accepts iff A > 0 && disc >= 0 && t >= 0 && 0 <= sp && sp <= 1
+ *     The cylinder's caps and the prism's sides lie inside the vertex balls and the cylinders, so these pieces give the exact first
+ *     contact.  disc is b*b - dd*(dot(m, m) - rr) and (B*B - A*C) / ee of the usual quadratics, in the form that does not cancel two
+ *     terms of the size |m|^2 to get at r^2.
+ * Sphere i (centre o, radius R): m = c - o; len = sqrtf(dot(m, m)); b = dot(m, d); x = cross(m, d); xx = dot(x, x)
+ *   fabsf(len - R) <= r                                                                                        -> t = 0
+ *   otherwise len > R (from outside):  rs = R + r; disc = dd*(rs*rs) - xx; t = (-b - sqrtf(disc)) / dd  (the entering root)
+ *   otherwise (from inside):           rs = R - r; disc = dd*(rs*rs) - xx; t = (-b + sqrtf(disc)) / dd  (the leaving root)
+ *   both accept iff disc >= 0 && t >= 0
+ * Order: a candidate is (the bits of t, key) as one 64-bit unsigned number, key = prim_id ^ 0x80000000 as for rt_closest_point.  The
+ *   best starts at (the bits of tmax, 0) and a candidate replaces it iff it is below it.  So only t < tmax is ever accepted,
+ *   strictly; at equal t spheres come before triangles, each kind by ascending index.  Among several primitives in contact at the
+ *   start (all of them t = 0) the LOWEST KEY wins, not the nearest.
+ * Result: t of the winner; position, u, v are the closest-point statement of the winner alone, evaluated at
+ *   centre = c + d*t (per component c_a + d_a*t).  So a contact at t = 0 carries exactly the point rt_closest_point computes for
+ *   that primitive from `origin`.  The contact normal is centre - position; the caller computes it.  prim_id as rt_hit.prim_id;
+ *   material_id = the record's, unchecked.  A miss: position = 0, t = tmax as given, u = v = 0, prim_id = 0xFFFFFFFF, material_id = 0.
+ *   A query with a non-finite origin or direction component, a zero direction, a radius that is NaN, <= 0 or infinite, or a tmax that
+ *   is NaN or <= 0 is such a miss without a walk.  The kernel checks this itself.
+ * The result follows from these rules alone: it does not depend on the tree in use, the device count, the kind of memory or the
+ *   chunking, and after rt_update_geometry it is that of a fresh upload of the moved scene.  The tree only culls, by the ray's entry
+ *   time into each box widened by the radius and a margin past the statement's own rounding.
+ * Buffers, synchronisation and side effects as for rt_closest_point: both pointers host memory, or both device memory of one context
+ * device (16-byte aligned), anything else is RT_ERR_BAD_ARG; host batches are staged in chunks of at most RT_QUERY_CHUNK sweeps; a
+ * context over several devices splits a host batch into one contiguous range per device; synchronous, first waits for an
+ * rt_dispatch_tile in flight; the last frame, the rt_read_* results and a running accumulation are left alone.
+ * flags: RT_QUERY_COUNTERS.  Statistics: rays = n, the other counts 0, kernel_ms the maximum over devices, node_visits / tri_tests
+ * only with RT_QUERY_COUNTERS.
+ * Errors: n == 0 is RT_OK; a NULL pointer with n > 0 or unknown flag bits are RT_ERR_BAD_ARG; a call before any upload is
+ * RT_ERR_NOT_UPLOADED.  An empty scene gives all misses.
+ * --------------------------------------------------------------------------------------------------------------- */
+typedef struct rt_sweep {  /* rt_ray's layout with the radius where tmin is */
+    float origin[3];       /* the sphere's centre at t = 0 */
+    float radius;          /* > 0, finite */
+    float direction[3];    /* need not be normalised; centre(t) = origin + direction * t */
+    float tmax;            /* contacts at 0 <= t < tmax are reported; > 0, +inf allowed */
+} rt_sweep; /* 32 bytes */
+
+typedef struct rt_sweep_hit { /* rt_nearest's layout with t where distance is */
+    float position[3];    /* the point of the surface the sphere touches */
+    float t;              /* time of first contact; tmax as given on a miss */
+    float u, v;           /* triangle: the weights of v1 and v2 at `position`; sphere: 0 */
+    uint32_t prim_id;     /* as rt_hit.prim_id; 0xFFFFFFFF = miss */
+    uint32_t material_id; /* the record's material id, unchecked; 0 on a miss */
+} rt_sweep_hit; /* 32 bytes */
+
+RT_STATIC_ASSERT(sizeof(rt_sweep) == 32 && offsetof(rt_sweep, origin) == 0 && offsetof(rt_sweep, radius) == 12 &&
+                     offsetof(rt_sweep, direction) == 16 && offsetof(rt_sweep, tmax) == 28,
+                 "rt_sweep is 32 B: origin, radius at 12, direction at 16, tmax at 28");
+RT_STATIC_ASSERT(sizeof(rt_sweep_hit) == 32 && offsetof(rt_sweep_hit, position) == 0 && offsetof(rt_sweep_hit, t) == 12 &&
+                     offsetof(rt_sweep_hit, u) == 16 && offsetof(rt_sweep_hit, v) == 20 && offsetof(rt_sweep_hit, prim_id) == 24 &&
+                     offsetof(rt_sweep_hit, material_id) == 28,
+                 "rt_sweep_hit is 32 B: position, t at 12, u, v, prim_id at 24, material_id at 28");
+
+/* First contact of each of the n moving spheres. */
+int rt_sweep_sphere(rt_ctx* ctx, const rt_sweep* sweeps, size_t n, rt_sweep_hit* out, uint32_t flags);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Geometry updates: new positions for the uploaded scene, in place (no reference counterpart; Embree's refit build,

@@ -1,0 +1,226 @@
+// Host check of the sphere sweep (gpu_raytracer_amd/csrc/sweep_rules.h), built by tests/test_sweep_abi.py with AddressSanitizer +
+// UBSan.  It builds trees with bvh_builder.cpp on check_bvh's inputs, runs the walk the kernel runs - sw_walk with the same per-node
+// bound, order, stack discipline and leaf test - with a host-side stack whose index is checked against what the kernel's launch
+// provides, and compares every answer's bytes with a brute force over all records and spheres by the same rules.  A bound that culls
+// a box holding the winner, a visiting order that loses a tie, or a stack that outgrows its entries shows here, before any kernel runs.
+// usage: check_sweep <n_triangles> <seed> <kind> [method]   as check_bvh: method 0 binned SAH (default), 1 PLOC; kind 0 soup,
+//                    1 coplanar grid, 2 coincident points, 3 collinear chain, 4 huge + tiny mixed, 5 with NaN / inf vertices
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <limits>
+#include <random>
+#include <vector>
+
+#include "bvh_builder.h"
+#include "sweep_rules.h"
+
+using namespace rt;
+
+namespace {
+
+int g_fail = 0;
+
+struct HostAccess {
+    const BvhBuild* b;
+    std::vector<uint64_t> stack; // the entries a lane of the kernel owns: DevScene::stack_entries / 2 + 1
+    int max_sp = 0;
+    unsigned long long nodes = 0, tris = 0;
+
+    void node(uint32_t idx, uint32_t w[20]) {
+        if (idx >= b->nodes.size()) {
+            std::printf("FAIL: node %u out of %zu\n", idx, b->nodes.size());
+            std::exit(1);
+        }
+        static_assert(sizeof(DevNode8) == 80, "DevNode8 is 20 words");
+        std::memcpy(w, &b->nodes[idx], sizeof(DevNode8));
+        nodes++;
+    }
+    void record(uint32_t slot, float q[9], uint32_t ids[3]) {
+        if (slot >= b->tris.size()) {
+            std::printf("FAIL: record %u out of %zu\n", slot, b->tris.size());
+            std::exit(1);
+        }
+        const DevTri& t = b->tris[slot];
+        for (int a = 0; a < 3; a++) q[a] = t.v0[a], q[3 + a] = t.e1[a], q[6 + a] = t.e2[a];
+        ids[0] = t.material_id, ids[1] = t.prim_id, ids[2] = t.leaf_count;
+        tris++;
+    }
+    void push(int sp, uint32_t base, uint32_t bits) {
+        if (sp < 0 || (size_t)sp >= stack.size()) {
+            std::printf("FAIL: stack entry %d of %zu\n", sp, stack.size());
+            std::exit(1);
+        }
+        stack[(size_t)sp] = ((uint64_t)base << 32) | bits;
+        if (sp + 1 > max_sp) max_sp = sp + 1;
+    }
+    void pop(int sp, uint32_t& base, uint32_t& bits) {
+        if (sp < 0 || (size_t)sp >= stack.size()) {
+            std::printf("FAIL: stack entry %d of %zu\n", sp, stack.size());
+            std::exit(1);
+        }
+        base = (uint32_t)(stack[(size_t)sp] >> 32), bits = (uint32_t)stack[(size_t)sp];
+    }
+};
+
+struct Sphere {
+    float centre[3], radius;
+    uint32_t material;
+};
+
+void answer(const BvhBuild& b, const std::vector<Sphere>& spheres, const CpBest& best, const SwQuery& q, uint32_t out[8]) {
+    sw_answer_miss(q.tmax, out);
+    if (best.slot == 0xFFFFFFFFu) return;
+    if ((uint32_t)best.order & RT_PRIM_SPHERE_FLAG) {
+        const DevTri& t = b.tris[best.slot];
+        float rec[9];
+        for (int a = 0; a < 3; a++) rec[a] = t.v0[a], rec[3 + a] = t.e1[a], rec[6 + a] = t.e2[a];
+        sw_answer_triangle(rec, t.material_id, best.order, q, out);
+    } else {
+        const Sphere& s = spheres[best.slot];
+        sw_answer_sphere(s.centre, s.radius, s.material, best.order, q, out);
+    }
+}
+
+} // namespace
+
+int main(int argc, char** argv) {
+    const size_t n = argc > 1 ? (size_t)std::atoll(argv[1]) : 1000;
+    const uint32_t seed = argc > 2 ? (uint32_t)std::atoi(argv[2]) : 1;
+    const int kind = argc > 3 ? std::atoi(argv[3]) : 0;
+    std::mt19937 rng(seed);
+    std::uniform_real_distribution<float> u(-1.0f, 1.0f);
+    std::vector<BuildTri> tris(n);
+    for (size_t i = 0; i < n; i++) { // check_bvh's inputs
+        BuildTri& t = tris[i];
+        t.material_id = (uint32_t)(i % 5);
+        t.prim_id = (uint32_t)i;
+        float c[3] = {u(rng) * 10, u(rng) * 10, u(rng) * 10}, s = 0.3f;
+        if (kind == 1) c[2] = -3.0f;
+        if (kind == 2) c[0] = c[1] = c[2] = 1.25f, s = 0.0f;
+        if (kind == 3) c[0] = std::pow(1.001f, (float)i), c[1] = 0.0f, c[2] = 0.0f, s = 1e-3f;
+        if (kind == 4) s = (i % 97 == 0) ? 1e5f : 1e-4f;
+        for (int a = 0; a < 3; a++) {
+            t.v0[a] = c[a] + u(rng) * s;
+            t.v1[a] = c[a] + u(rng) * s;
+            t.v2[a] = c[a] + u(rng) * s;
+            if (kind == 1 && a == 2) t.v0[a] = t.v1[a] = t.v2[a] = -3.0f;
+        }
+        if (kind == 5 && i % 7 == 0) t.v1[i % 3] = (i % 14 == 0) ? std::numeric_limits<float>::quiet_NaN() : std::numeric_limits<float>::infinity();
+    }
+    BvhBuild b;
+    BvhBuildOptions opt;
+    opt.method = argc > 4 ? std::atoi(argv[4]) : 0;
+    build_bvh(tris.data(), tris.size(), opt, b);
+    const std::vector<Sphere> spheres = {{{2.0f, 1.0f, -1.0f}, 0.75f, 1u}, {{-4.0f, 0.5f, 3.0f}, 1.5f, 2u}, {{2.0f, 1.0f, -1.0f}, 0.75f, 3u}};
+
+    // the leaves' records: padding records are not triangles
+    std::vector<uint32_t> recs;
+    for (size_t first = 0; first + RT_DEV_LEAF_STRIDE <= b.tris.size(); first += RT_DEV_LEAF_STRIDE)
+        for (uint32_t x = 0; x < b.tris[first].leaf_count && x < RT_DEV_LEAF_STRIDE; x++) recs.push_back((uint32_t)(first + x));
+
+    // sweeps: toward a point of a surface, grazing past a surface at r -+ a little, starting in contact, from far outside, with
+    // coordinates around 1e4, along an axis (zero direction components), inside and toward the spheres
+    struct Sweep {
+        float o[3], radius, d[3], tmax;
+    };
+    std::vector<Sweep> qs;
+    const float inf = std::numeric_limits<float>::infinity();
+    const size_t n_each = 96;
+    auto aim = [&](Sweep& s, const float from[3], const float to[3], float speed) {
+        for (int a = 0; a < 3; a++) s.o[a] = from[a], s.d[a] = (to[a] - from[a]) * speed;
+    };
+    for (size_t k = 0; k < n_each && !recs.empty(); k++) {
+        const DevTri& t = b.tris[recs[rng() % recs.size()]];
+        const float bu = 0.5f * (u(rng) + 1.0f) * 0.5f, bv = 0.5f * (u(rng) + 1.0f) * 0.5f;
+        float surf[3], from[3], off[3], side[3];
+        for (int a = 0; a < 3; a++) {
+            surf[a] = k % 4 == 0 ? t.v0[a] : k % 4 == 1 ? t.v0[a] + t.e1[a] * bu : t.v0[a] + (t.e1[a] * bu + t.e2[a] * bv); // vertex, edge, face
+            off[a] = u(rng);
+            from[a] = surf[a] + off[a] * (k % 2 ? 1.5f : 8.0f);
+        }
+        Sweep toward, graze, touch;
+        toward.radius = 0.01f + 0.29f * 0.5f * (u(rng) + 1.0f);
+        toward.tmax = k % 5 == 4 ? 0.5f : inf; // some end before the contact
+        aim(toward, from, surf, 0.2f + 2.4f * (u(rng) + 1.0f));
+        // past the point at a distance of radius * (1 -+ 1e-3): a direction perpendicular to the offset
+        graze.radius = 0.05f + 0.1f * (u(rng) + 1.0f);
+        const float g[3] = {u(rng), u(rng), u(rng)};
+        sw_cross(off, g, side);
+        const float sl = std::sqrt(cp_dot(side, side)), ol = std::sqrt(cp_dot(off, off));
+        float pass[3];
+        for (int a = 0; a < 3; a++) {
+            pass[a] = surf[a] + off[a] / ol * graze.radius * (k % 2 ? 1.001f : 0.999f);
+            from[a] = pass[a] - side[a] / sl * 3.0f;
+        }
+        graze.tmax = inf;
+        aim(graze, from, pass, 0.7f);
+        // in contact at the start: the centre within the radius of the point
+        touch.radius = 0.2f;
+        for (int a = 0; a < 3; a++) from[a] = surf[a] + off[a] * 0.1f;
+        touch.tmax = k % 3 == 0 ? 1e-30f : inf;
+        aim(touch, from, surf, 1.0f);
+        touch.d[k % 3] = 0.0f; // and a zero direction component
+        qs.push_back(toward), qs.push_back(graze), qs.push_back(touch);
+    }
+    for (size_t k = 0; k < n_each; k++) {
+        Sweep scat, far, big;
+        float to[3], from[3];
+        for (int a = 0; a < 3; a++) to[a] = u(rng) * 10.0f, from[a] = u(rng) * 30.0f;
+        scat.radius = k % 2 ? 0.3f : 1e-3f;
+        scat.tmax = k % 4 == 3 ? 0.9f : inf;
+        aim(scat, from, to, 1.0f);
+        if (k % 8 == 0) scat.d[0] = 0.0f, scat.d[1] = -0.0f; // along z
+        for (int a = 0; a < 3; a++) from[a] = u(rng) * 3000.0f;
+        far.radius = 0.5f, far.tmax = inf;
+        aim(far, from, to, 1e-3f);
+        for (int a = 0; a < 3; a++) from[a] = 1e4f + u(rng) * 50.0f;
+        big.radius = k % 2 ? 2.0f : 0.05f, big.tmax = k % 2 ? inf : 2.0f;
+        aim(big, from, to, 1.0f);
+        qs.push_back(scat), qs.push_back(far), qs.push_back(big);
+    }
+    qs.push_back({{2.0f, 1.0f, -1.0f}, 0.1f, {0.3f, 0.2f, -0.1f}, inf});  // from a sphere's centre outward (two coincident spheres: the lower index)
+    qs.push_back({{2.1f, 1.2f, -0.9f}, 0.1f, {0.0f, 1.0f, 0.0f}, inf});   // inside it
+    qs.push_back({{2.1f, 1.2f, -0.9f}, 0.1f, {0.0f, 1.0f, 0.0f}, 1e-3f}); // ... and too far for this tmax
+    qs.push_back({{2.0f, 1.7f, -1.0f}, 0.1f, {1.0f, 0.0f, 0.0f}, inf});   // in contact with it from inside
+    qs.push_back({{9.0f, 0.5f, 3.0f}, 0.25f, {-2.0f, 0.0f, 0.0f}, inf});  // toward the other from outside
+
+    HostAccess acc;
+    acc.b = &b;
+    acc.stack.resize((2u * b.depth + 2u) / 2u + 1u); // DevScene::stack_entries / 2 + 1, the kernel's LDS per lane
+    size_t found = 0, at_start = 0;
+    for (size_t k = 0; k < qs.size(); k++) {
+        const SwQuery q = sw_query(qs[k].o, qs[k].radius, qs[k].d, qs[k].tmax);
+        uint32_t got[8], want[8];
+        CpBest walk{sw_start(q.tmax), 0xFFFFFFFFu}, brute = walk;
+        if (sw_query_valid(q)) {
+            for (uint32_t s = 0; s < spheres.size(); s++) {
+                const uint64_t c = cp_order(sw_sphere(spheres[s].centre, spheres[s].radius, q), s);
+                if (c < walk.order) walk.order = c, walk.slot = s;
+            }
+            brute = walk;
+            sw_walk(acc, (uint32_t)b.nodes.size(), q, walk);
+            for (uint32_t r : recs) {
+                const DevTri& t = b.tris[r];
+                const uint64_t c = cp_order(sw_triangle(t.v0, t.e1, t.e2, q), t.prim_id ^ RT_PRIM_SPHERE_FLAG);
+                if (c < brute.order) brute.order = c, brute.slot = r;
+            }
+        }
+        answer(b, spheres, walk, q, got);
+        answer(b, spheres, brute, q, want);
+        found += want[6] != RT_PRIM_MISS;
+        at_start += want[6] != RT_PRIM_MISS && want[3] == 0u;
+        if (std::memcmp(got, want, sizeof got) != 0) {
+            if (g_fail < 20)
+                std::printf("FAIL: sweep %zu (%.9g %.9g %.9g r %.9g, d %.9g %.9g %.9g, tmax %.9g): walk prim %08x t %.9g, brute force prim %08x t %.9g\n", k,
+                            q.c[0], q.c[1], q.c[2], q.r, q.d[0], q.d[1], q.d[2], q.tmax, got[6], cp_float(got[3]), want[6], cp_float(want[3]));
+            g_fail++;
+        }
+    }
+    std::printf("kind %d n %zu method %d: %zu nodes depth %u, %zu sweeps (%zu hit, %zu of them at the start), %.1f node visits and %.1f triangle tests per "
+                "sweep (brute force %zu), stack %d of %zu, %d failures\n",
+                kind, n, opt.method, b.nodes.size(), b.depth, qs.size(), found, at_start, (double)acc.nodes / (double)qs.size(),
+                (double)acc.tris / (double)qs.size(), recs.size(), acc.max_sp, acc.stack.size(), g_fail);
+    return g_fail ? 1 : 0;
+}
