@@ -218,7 +218,6 @@ int ensure_wavefront(rt_ctx* ctx, DeviceState& d, uint32_t n_blocks, uint32_t ba
     HIPCHK(ctx, alloc((void**)&w.next_d, S * 16));
     HIPCHK(ctx, alloc((void**)&w.next_thr, S * 16));
     HIPCHK(ctx, alloc((void**)&w.next_rad, S * 16));
-    HIPCHK(ctx, alloc((void**)&w.hit, S * 16));
     HIPCHK(ctx, alloc((void**)&w.vtx, S * 32));
     HIPCHK(ctx, alloc((void**)&w.sample_rad, P * 16));
     HIPCHK(ctx, alloc((void**)&w.pxy, P * 4));
@@ -287,10 +286,10 @@ uint32_t wavefront_batch(uint32_t n_blocks, uint32_t spp, uint32_t n_lights, siz
     uint64_t target_paths = 64ull << 20;
     if (const char* e = std::getenv("RT_WF_TARGET_PATHS")) target_paths = std::max<uint64_t>(1, std::strtoull(e, nullptr, 10));
     const uint64_t lights = std::max(1u, n_lights);
-    // path state indexed by id (two sets of ray_o / ray_d / thr / rad, hit, vtx: 176 bytes per record, wf_state_slots records = under 2 per path
+    // path state indexed by id (two sets of ray_o / ray_d / thr / rad, vtx: 160 bytes per record, wf_state_slots records = under 2 per path
     // slot for batches large enough that memory bounds them), sample_rad, pxy, two extension queues, shadow queue (4 slots per entry), the
     // handed-on shadow queue (dense)
-    const uint64_t bytes_per_path = 2 * 11 * 16 + 16 + 4 + 2 * 16 + 16 * lights + 4 * lights;
+    const uint64_t bytes_per_path = 2 * 10 * 16 + 16 + 4 + 2 * 16 + 16 * lights + 4 * lights;
     target_paths = std::min<uint64_t>(target_paths, free_bytes / 2 / bytes_per_path);
     target_paths = std::min<uint64_t>(target_paths, wavefront_max_paths(n_lights));
     uint32_t max_batch = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(spp, target_paths / per_sample));

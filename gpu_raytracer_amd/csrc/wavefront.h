@@ -40,7 +40,7 @@ enum WfCounter : uint32_t {
 enum WfTotal : uint32_t {
     WF_TOTAL_CAMERA = 0,       // camera segments (k_wf_generate)
     WF_TOTAL_CONTINUATION = 1, // continuation segments (k_wf_finish)
-    WF_TOTAL_SHADOW = 2,       // shadow segments (k_wf_shade)
+    WF_TOTAL_SHADOW = 2,       // shadow segments (k_wf_shadow_grid with light grids, k_wf_shade without)
     WF_TOTAL_NODE_VISITS = 3,  // counting variants only (k_wf_trace, k_wf_trace_camera)
     WF_TOTAL_TRI_TESTS = 4,    // counting variants only (k_wf_trace, k_wf_trace_camera, k_wf_shadow_grid)
     // 5-12: diagnostics of the counting variant of k_wf_trace (rt_debug_counters, in this order)
@@ -65,16 +65,19 @@ struct WfBuffers {
     // state_cap (wf_state_slots) records, those indexed by origin P.
     float4* ray_o;       // [id] xyz origin (the current bounce's state; wf_bounce selects one of the two sets by bounce parity)
     float4* ray_d;       // [id] xyz direction (also the incoming direction of the current vertex), w = bits: origin slot of the path
-    uint4* hit;          // [id] xyz = hit point bits, w = RT_PRIM_MISS | RT_PRIM_SPHERE_FLAG + sphere index | triangle slot
     float4* thr;         // [id] xyz throughput, w = bits: hero channel | depth << 8
     float4* rad;         // [id] xyz radiance of the sample so far, w = bits: rng state
     float4* next_o;      // [queue position] the same four records of the paths that continue, written by k_wf_finish
     float4* next_d;
     float4* next_thr;
     float4* next_rad;
-    float4* vtx;         // [id] two per path, always used together, so one 32-byte record = one cache line per gather:
-                         //   [2 id]     xyz vertex position, w = bits: material id
-                         //   [2 id + 1] xyz geometric normal, w = bits: the lights with a shadow segment from the current vertex (k_wf_shade), less those the shadow stage found occluded
+    float4* vtx;         // [id] two per path, always used together, so one 32-byte record = one cache line per gather; written by the kernel
+                         // that finds the closest hit (k_wf_trace<closest>, k_wf_trace_camera):
+                         //   [2 id]     xyz vertex position, w = bits: material id.  w = 0xFFFFFFFF: no vertex, the path ends at this hit and
+                         //              x = bits: how (0: a miss, the sky; 1: a material index outside the table, magenta); k_wf_finish ends it
+                         //   [2 id + 1] xyz geometric normal, w = bits: one per light, all set at first; the shadow stage clears a light's bit when
+                         //              its segment is occluded.  Only the bits of lights that need a segment from this vertex are ever read
+                         //              (without light grids k_wf_shade replaces the word with exactly those bits, one per shadow queue entry)
     float4* sample_rad;  // [origin] xyz final radiance of the sample (written when the path ends)
     uint32_t* pxy;       // [origin] x | y << 16, 0xFFFFFFFF = no pixel (tile edge)
     // queues

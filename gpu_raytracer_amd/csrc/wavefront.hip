@@ -1,14 +1,15 @@
 // wavefront.hip — queue-based pipeline of the extended mode (see wavefront.h).
 //
 // Stages per bounce iteration (each a kernel, one code path per wave):
-//   k_wf_trace<closest>  persistent; lanes pull path ids from the extension queue, walk the BVH, store the hit
-//   k_wf_shade           consume the hit: miss / invalid material end the path; otherwise store the vertex and
-//                        enqueue one shadow segment per light with a non-zero contribution
-//   k_wf_shadow_grid     shadow segments of lights that have a triangle-list grid (shadow_grid.h): look up the segment's cell as seen
-//                        from the light, test the cell's few triangles; sets a visibility bit per (path, light); what it cannot
-//                        decide cheaply goes on to
-//   k_wf_trace<any hit>  persistent; shadow segments walk the BVH and set the same visibility bits
-//   k_wf_finish          sum the visible contributions IN LIGHT ORDER, add emission, then terminal shading or
+//   k_wf_trace<closest>  persistent; lanes pull path ids from the extension queue, walk the BVH and store the path's vertex (point,
+//                        material, geometric normal, every light visible), or the marker of a path that ends at the hit (miss /
+//                        invalid material); depth 0 with beam lists: k_wf_trace_camera, same record
+//   k_wf_shadow_grid     frames with light grids (shadow_grid.h): by vertex, which lights have a non-zero contribution and so need a shadow
+//                        segment; for each, look up the segment's cell as seen from the light, test the cell's few triangles; clears the
+//                        light's visibility bit when occluded; what it cannot decide cheaply goes on to
+//   k_wf_shade           frames without light grids instead: the same lights become entries of the shadow queue for
+//   k_wf_trace<any hit>  persistent; shadow segments walk the BVH and clear the same visibility bits
+//   k_wf_finish          end the marked paths (sky / magenta); sum the visible contributions IN LIGHT ORDER, add emission, then terminal shading or
 //                        continuation sampling + russian roulette; survivors go to the next extension queue, and their
 //                        state to the slot they reserve there (the other of two state sets): ids are queue positions
 //                        from depth 1 on, so the stages of the next bounce read live paths densely
@@ -52,6 +53,9 @@ using namespace rtdev;
 #endif
 #ifndef RT_WF_SHADOW_LIGHT_MAJOR
 #define RT_WF_SHADOW_LIGHT_MAJOR 1
+#endif
+#ifndef RT_WF_GRID_MASK
+#define RT_WF_GRID_MASK 1 /* k_wf_shadow_grid works out which lights need a shadow segment itself; 0: k_wf_shade runs before it (profiles/ab_r06.json) */
 #endif
 
 namespace {
@@ -212,6 +216,24 @@ __global__ __launch_bounds__(256) void k_wf_generate(DevFrame fr, rt::WfBuffers 
 #define WF8_KIND_T 0x80000000u
 #define WF8_NONE 0xFFFFFFFFu
 
+// The vertex record of a closest hit (wavefront.h, WfBuffers::vtx), written by the kernel that found the hit.  A path that ends at the hit -
+// a miss, or a material index outside the scene's table - gets the "no vertex" marker with the kind of its end; k_wf_finish, which reads
+// the path's radiance and throughput anyway, ends it.  The visibility word starts with every light's bit set: the shadow stage only clears
+// bits, and ext_light_sum asks only about the lights that need a segment, so the bits of the others are never read.
+#define WF_NO_VERTEX 0xFFFFFFFFu
+#define WF_END_SKY 0u
+#define WF_END_MAGENTA 1u
+__device__ __forceinline__ uint32_t wf_all_lights(uint32_t n_lights) { return n_lights >= RT_WF_MAX_LIGHTS ? 0xFFFFFFFFu : (1u << n_lights) - 1u; }
+__device__ __forceinline__ void wf_store_vertex(const DevScene& sc, const rt::WfBuffers& wb, uint32_t id, bool found, V3 point, V3 normal, uint32_t material_id) {
+    float4* __restrict__ rec = wb.vtx + 2 * (size_t)id;
+    if (found && material_id < sc.n_materials) {
+        rec[0] = make_float4(point.x, point.y, point.z, __uint_as_float(material_id));
+        rec[1] = make_float4(normal.x, normal.y, normal.z, __uint_as_float(wf_all_lights(sc.n_lights)));
+    } else {
+        rec[0] = make_float4(__uint_as_float(found ? WF_END_MAGENTA : WF_END_SKY), 0.0f, 0.0f, __uint_as_float(WF_NO_VERTEX));
+    }
+}
+
 template <bool COUNT, bool ANY>
 __global__ __launch_bounds__(WAVE, RT_WF8_MIN_WAVES) void k_wf_trace(DevScene sc, rt::WfBuffers wb, const uint32_t* __restrict__ queue, uint32_t count_slot,
                                                     uint32_t cursor_slot, uint32_t window_slot) {
@@ -265,6 +287,23 @@ __global__ __launch_bounds__(WAVE, RT_WF8_MIN_WAVES) void k_wf_trace(DevScene sc
     uint32_t t_base = 0, t_bits = 0;  // the postponed leaf group: tri_base, hit mask | lmask << 8
     uint32_t oct = 0;                 // table row of this segment: (dx < 0) | (dy < 0) << 1 | (dz < 0) << 2, times 256
     int sp = 0;
+    // Closest hits: a lane whose segment is finished keeps its result (o, d, hit, id: the lane is idle, nothing touches them) until the
+    // wave refills or leaves, and writes the path's vertex record then - the triangle's record is gathered beside the refill's own
+    // loads, once per refill, not as a dependent load in every iteration of the traversal loop
+    bool pending = false;
+    auto write_pending = [&]() {
+        if (ANY || !pending) return;
+        const bool found = hit.prim != RT_PRIM_MISS;
+        V3 hp = v3(0.0f, 0.0f, 0.0f), normal = hp;
+        uint32_t material_id = 0;
+        if (found) {
+            hp = o + d * hit.t;
+            const uint32_t code = (hit.prim & RT_PRIM_SPHERE_FLAG) ? hit.prim : hit.slot;
+            surface_at(sc, (code & RT_PRIM_SPHERE_FLAG) != 0, code & ~RT_PRIM_SPHERE_FLAG, hp, normal, material_id);
+        }
+        wf_store_vertex(sc, wb, id, found, hp, normal, material_id);
+        pending = false;
+    };
 
     for (;;) {
         const unsigned long long idle = __ballot(!active);
@@ -285,6 +324,7 @@ __global__ __launch_bounds__(WAVE, RT_WF8_MIN_WAVES) void k_wf_trace(DevScene sc
                 chunk_next += n_fetch;
                 uint32_t e = WF_SENTINEL;
                 if (!active && idx < chunk_end) e = queue[idx];
+                write_pending(); // (behind the queue load: its gather is in flight together with it)
                 if (__ballot(!active && idx == last && e == WF_SENTINEL) != 0ull) chunk_next = max(chunk_next, (last + window_mask + 1u) & ~window_mask);
                 if (e != WF_SENTINEL) {
                     if (ANY) {
@@ -422,11 +462,9 @@ __global__ __launch_bounds__(WAVE, RT_WF8_MIN_WAVES) void k_wf_trace(DevScene sc
             if (active && busy == 0u) { // segment finished
                 second = false;
                 if (ANY) {
-                    if (hit.prim != RT_PRIM_MISS) atomicAnd(reinterpret_cast<uint32_t*>(&wb.vtx[2 * (size_t)id + 1]) + 3, ~(1u << li)); // occluded: the light leaves the visibility word (k_wf_shade set it)
+                    if (hit.prim != RT_PRIM_MISS) atomicAnd(reinterpret_cast<uint32_t*>(&wb.vtx[2 * (size_t)id + 1]) + 3, ~(1u << li)); // occluded: the light leaves the visibility word
                 } else {
-                    const V3 hp = o + d * hit.t;
-                    const uint32_t code = hit.prim == RT_PRIM_MISS ? RT_PRIM_MISS : ((hit.prim & RT_PRIM_SPHERE_FLAG) ? hit.prim : hit.slot);
-                    wb.hit[id] = make_uint4(__float_as_uint(hp.x), __float_as_uint(hp.y), __float_as_uint(hp.z), code);
+                    pending = true; // (write_pending, at the wave's next refill or at its exit)
                 }
                 active = false;
             }
@@ -435,6 +473,7 @@ __global__ __launch_bounds__(WAVE, RT_WF8_MIN_WAVES) void k_wf_trace(DevScene sc
             if (!exhausted && __popcll(~still) >= RT_WF_REFILL) break;
         }
     }
+    write_pending(); // what finished after the wave's last refill
     if (COUNT) {
         unsigned long long n0 = wave_sum(cnt.nodes), n1 = wave_sum(cnt.tris);
         for (int off = 32; off > 0; off >>= 1) sp_max = max(sp_max, __shfl_down(sp_max, off, WAVE));
@@ -705,6 +744,7 @@ __global__ __launch_bounds__(WAVE) void k_wf_trace_camera(DevScene sc, rt::WfBuf
             hit.t = valid ? RT_F32_MAX : -1.0f; // (lanes without a path never ask for another triangle)
             hit.prim = RT_PRIM_MISS;
             hit.slot = 0;
+            uint32_t hit_i = 0; // the accepted triangle's place in the list: its record is still in LDS when the vertex is written
             if (valid) test_spheres(sc, o, d, hit, RT_MIN_RAY_DISTANCE);
             {
                 for (uint32_t i = 0; i < n_list; i++) {
@@ -722,6 +762,7 @@ __global__ __launch_bounds__(WAVE) void k_wf_trace_camera(DevScene sc, rt::WfBuf
                     hit.t = accept ? t : hit.t;
                     hit.prim = accept ? prim : hit.prim;
                     hit.slot = accept ? q2.w : hit.slot;
+                    hit_i = accept ? i : hit_i;
                 }
             }
             if (COUNT && wb.probe == 2u && valid) { // development probe: the same segment by the tree walk (the launch provides the extra LDS)
@@ -742,10 +783,23 @@ __global__ __launch_bounds__(WAVE) void k_wf_trace_camera(DevScene sc, rt::WfBuf
                     }
                 }
             }
-            if (valid) {
-                const V3 hp = o + d * hit.t;
-                const uint32_t code = hit.prim == RT_PRIM_MISS ? RT_PRIM_MISS : ((hit.prim & RT_PRIM_SPHERE_FLAG) ? hit.prim : hit.slot);
-                wb.hit[p] = make_uint4(__float_as_uint(hp.x), __float_as_uint(hp.y), __float_as_uint(hp.z), code);
+            if (valid) { // the vertex record, as k_wf_trace<closest> writes it; a triangle's edges and material come from the staged list
+                const bool found = hit.prim != RT_PRIM_MISS;
+                V3 hp = v3(0.0f, 0.0f, 0.0f), normal = hp;
+                uint32_t material_id = 0;
+                if (found) {
+                    hp = o + d * hit.t;
+                    if (hit.prim & RT_PRIM_SPHERE_FLAG) {
+                        surface_at(sc, true, hit.prim & ~RT_PRIM_SPHERE_FLAG, hp, normal, material_id);
+                    } else { // surface_at's triangle branch on the LDS copy of the record
+                        const uint4 q0 = s_cam[3u * hit_i], q1 = s_cam[3u * hit_i + 1u], q2 = s_cam[3u * hit_i + 2u];
+                        const V3 e1 = v3(__uint_as_float(q0.w), __uint_as_float(q1.x), __uint_as_float(q1.y));
+                        const V3 e2 = v3(__uint_as_float(q1.z), __uint_as_float(q1.w), __uint_as_float(q2.x));
+                        normal = normalize(cross(e1, e2));
+                        material_id = q2.y;
+                    }
+                }
+                wf_store_vertex(sc, wb, p, found, hp, normal, material_id);
             }
         }
     }
@@ -794,9 +848,11 @@ __device__ __forceinline__ DevMaterial load_material(const DevScene& sc, uint32_
                                 5, 6 and 7 waves had measured the same before (profiles/ab_r03.json) */
 #endif
 
-// One thread per vertex of the bounce (the entries of the extension queue, as k_wf_shade and k_wf_finish read it); k_wf_shade has left the
-// lights that need a segment as the vertex record's visibility word, and what this stage (and k_wf_trace<any hit> after it) does is CLEAR
-// the bits of occluded segments - every update of the word is an atomic and-not, so their order does not matter.  The wave goes through the
+// One thread per vertex of the bounce (the entries of the extension queue, as k_wf_finish reads it).  The closest-hit kernel has left the
+// vertex record with every light's bit set in its visibility word; which lights need a segment this stage works out itself, from the
+// point and normal it holds anyway and the material's albedo (RT_WF_GRID_MASK; 0: k_wf_shade runs before it and leaves them as the word),
+// and what it (and k_wf_trace<any hit> after it) does to the word is CLEAR the bits of occluded segments - every update is an atomic
+// and-not, so their order does not matter, and k_wf_finish never looks at the bit of a light that needs no segment.  The wave goes through the
 // lights together - neighbouring vertices toward one light fall into neighbouring cells - and a lane skips the lights it has no segment for.
 // Against one thread per (vertex, light) entry of a shadow queue (rounds 1-2): the 32-byte vertex record is read once instead of once per
 // light, and the queue (4 bytes written and read per segment) is gone.
@@ -830,6 +886,9 @@ __global__ __launch_bounds__(256, RT_WF_GRID_MIN_WAVES) void k_wf_shadow_grid(De
         __syncthreads();
     }
     uint32_t n_tests = 0, n_entries = 0, n_answered = 0;
+#if RT_WF_GRID_MASK
+    uint32_t n_want = 0;
+#endif
     uint32_t(*park)[RT_WF_GRID_PARK] = s_park[wave];
     // hand on: collected per wave in LDS and appended 64 or more at a time (one atomic on the queue's counter per append: an atomic per
     // wave and iteration, 1.5 M of them on one address, cost more than the whole list walk)
@@ -896,7 +955,24 @@ __global__ __launch_bounds__(256, RT_WF_GRID_MIN_WAVES) void k_wf_shadow_grid(De
             RT_KEEP4(vp);
             RT_KEEP4(vn);
             point = f4v(vp), normal = f4v(vn);
-            if (__float_as_uint(vp.w) != 0xFFFFFFFFu) want = __float_as_uint(vn.w); // ("no vertex": the path ended in k_wf_shade)
+            if (__float_as_uint(vp.w) != WF_NO_VERTEX) { // ("no vertex": the path ends at this hit, k_wf_finish sees to it)
+#if RT_WF_GRID_MASK
+                // the lights that need a segment: the statement of the vertex (device_common.h) on the material's first four words - the
+                // albedo and the metallic switch are all light_contribution reads of it
+                float4 a = *reinterpret_cast<const float4*>(sc.materials + __float_as_uint(vp.w));
+                RT_KEEP4(a);
+                DevMaterial m = {};
+                m.albedo[0] = a.x, m.albedo[1] = a.y, m.albedo[2] = a.z, m.metallic = a.w;
+                for (uint32_t li = 0; li < sc.n_lights; li++) {
+                    V3 sdir;
+                    float sdist;
+                    if (needs_shadow_segment(light_contribution(s_lights[li], m, point, normal, sdir, sdist))) want |= 1u << li;
+                }
+                n_want += (uint32_t)__popc(want);
+#else
+                want = __float_as_uint(vn.w); // k_wf_shade's mask
+#endif
+            }
         }
         uint32_t occluded = 0;
         for (uint32_t li = 0; li < sc.n_lights; li++) {
@@ -918,6 +994,12 @@ __global__ __launch_bounds__(256, RT_WF_GRID_MIN_WAVES) void k_wf_shadow_grid(De
     }
     while (n_park != 0u) walk_parked();
     hand_on(false, 0u, true);
+#if RT_WF_GRID_MASK
+    { // the frame's shadow segments (rt_stats): counted where they are decided, in both variants
+        const unsigned long long ns = wave_sum(n_want);
+        if (lane == 0 && ns) atomicAdd(&wb.totals[rt::WF_TOTAL_SHADOW], ns);
+    }
+#endif
     if (COUNT) {
         const unsigned long long t = wave_sum(n_tests), a = wave_sum(n_answered), en = wave_sum(n_entries);
         if ((threadIdx.x & 63u) == 0) {
@@ -929,22 +1011,22 @@ __global__ __launch_bounds__(256, RT_WF_GRID_MIN_WAVES) void k_wf_shadow_grid(De
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// shading stage 1: consume the closest hit, store the vertex, enqueue shadow segments
+// mask stage, for frames whose shadow stage does not go by vertex over light grids (RT_FLAG_NO_SHADOW_GRID, scenes without grids; with
+// RT_WF_GRID_MASK 0 every frame that traces shadow segments): which lights need a shadow segment from the vertex the closest-hit kernel
+// stored?  Their bits replace the visibility word, and without grids each becomes an entry of the shadow queue
 // ---------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void wf_end_path(const rt::WfBuffers& wb, uint32_t origin, V3 radiance) {
     wb.sample_rad[origin] = make_float4(radiance.x, radiance.y, radiance.z, 0.0f);
 }
-__device__ __forceinline__ uint32_t wf_origin(const rt::WfBuffers& wb, uint32_t id) { return __float_as_uint(wb.ray_d[id].w); }
 
-__global__ __launch_bounds__(256, RT_WF_SHADE_WAVES) void k_wf_shade(DevScene sc, DevFrame fr, rt::WfBuffers wb, const uint32_t* __restrict__ queue) {
+__global__ __launch_bounds__(256, RT_WF_SHADE_WAVES) void k_wf_shade(DevScene sc, rt::WfBuffers wb, const uint32_t* __restrict__ queue) {
     __shared__ DevLight s_lights[RT_WF_MAX_LIGHTS];
     if (wb.totals[rt::WF_TOTAL_ERROR] != 0ull) return;
     stage_lights(s_lights, sc);
     const uint32_t count = wb.counters[rt::WF_EXT_COUNT];
-    const bool shadows = (fr.flags & RT_FLAG_NO_SHADOWS) == 0;
-    // with light grids the shadow stage works per vertex (k_wf_shadow_grid): the lights that need a segment go into the vertex record's
-    // visibility word as a mask, not into the shadow queue as entries
-    const bool to_grids = shadows && wb.grids != nullptr;
+    // with light grids the shadow stage works per vertex (k_wf_shadow_grid): the lights that need a segment stay in the vertex record's
+    // visibility word as a mask and do not go into the shadow queue as entries
+    const bool to_grids = wb.grids != nullptr;
     const uint32_t stride = gridDim.x * blockDim.x;
     OutWindow win = {0u, 0u};
     uint32_t n_shadow = 0;
@@ -956,47 +1038,29 @@ __global__ __launch_bounds__(256, RT_WF_SHADE_WAVES) void k_wf_shade(DevScene sc
         const uint32_t id = id_next;
         const uint32_t i_next = base + stride + threadIdx.x; // the next entry is fetched a whole iteration ahead
         id_next = i_next < count ? queue[i_next] : WF_SENTINEL;
-        const bool have = id != WF_SENTINEL;
-        bool vertex = false;
-        V3 point = v3(0, 0, 0), normal = point;
-        uint32_t material_id = 0;
-        DevMaterial m = {};
-        if (have) {
-            uint4 h = wb.hit[id];
-            asm volatile("" : "+v"(h.x), "+v"(h.y), "+v"(h.z), "+v"(h.w));
-            // throughput / radiance / origin are only read where a path ends here (a quarter of this stage's read traffic otherwise)
-            if (h.w == RT_PRIM_MISS) { // process_wavefront_ray, wavefront.rs:146-151
-                const V3 radiance = f4v(wb.rad[id]) + RT_SKY() * f4v(wb.thr[id]);
-                wf_end_path(wb, wf_origin(wb, id), radiance);
-            } else {
-                point = v3(__uint_as_float(h.x), __uint_as_float(h.y), __uint_as_float(h.z));
-                surface_at(sc, (h.w & RT_PRIM_SPHERE_FLAG) != 0, h.w & ~RT_PRIM_SPHERE_FLAG, point, normal, material_id);
-                if (material_id >= sc.n_materials) {
-                    const V3 radiance = f4v(wb.rad[id]) + RT_MAGENTA() * f4v(wb.thr[id]);
-                    wf_end_path(wb, wf_origin(wb, id), radiance);
-                } else {
-                    vertex = true;
-                    m = load_material(sc, material_id);
-                    wb.vtx[2 * (size_t)id] = make_float4(point.x, point.y, point.z, __uint_as_float(material_id));
-                    if (!shadows) wb.vtx[2 * (size_t)id + 1] = make_float4(normal.x, normal.y, normal.z, 0.0f);
-                }
-            }
-        }
-        if (have && !vertex) wb.vtx[2 * (size_t)id] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu)); // "no vertex": k_wf_finish skips it
-        if (shadows) {
+        {
             // which lights need a shadow segment (non-zero contribution)?  One bit per light, then ONE
             // aggregated append per wave: exclusive scan of the per-lane counts + a single atomicAdd.
             uint32_t mask = 0;
-            if (vertex) {
-                for (uint32_t li = 0; li < sc.n_lights; li++) {
-                    V3 sdir;
-                    float sdist;
-                    const V3 contrib = light_contribution(s_lights[li], m, point, normal, sdir, sdist);
-                    if (needs_shadow_segment(contrib)) mask |= 1u << li;
+            if (id != WF_SENTINEL) {
+                float4 vp = wb.vtx[2 * (size_t)id], vn = wb.vtx[2 * (size_t)id + 1];
+                RT_KEEP4(vp);
+                RT_KEEP4(vn);
+                if (__float_as_uint(vp.w) != WF_NO_VERTEX) {
+                    float4 a = *reinterpret_cast<const float4*>(sc.materials + __float_as_uint(vp.w)); // albedo, metallic: all light_contribution reads
+                    RT_KEEP4(a);
+                    DevMaterial m = {};
+                    m.albedo[0] = a.x, m.albedo[1] = a.y, m.albedo[2] = a.z, m.metallic = a.w;
+                    for (uint32_t li = 0; li < sc.n_lights; li++) {
+                        V3 sdir;
+                        float sdist;
+                        const V3 contrib = light_contribution(s_lights[li], m, f4v(vp), f4v(vn), sdir, sdist);
+                        if (needs_shadow_segment(contrib)) mask |= 1u << li;
+                    }
+                    // the visibility word of the vertex record becomes this mask; the shadow stage clears the bits of occluded segments
+                    reinterpret_cast<uint32_t*>(&wb.vtx[2 * (size_t)id + 1])[3] = mask;
                 }
             }
-            // the visibility word of the vertex record starts as this mask; the shadow stage clears the bits of occluded segments
-            if (vertex) wb.vtx[2 * (size_t)id + 1] = make_float4(normal.x, normal.y, normal.z, __uint_as_float(mask));
             if (to_grids) { // (k_wf_shadow_grid goes by vertex, not by queue entry)
                 n_shadow += (uint32_t)__popc(mask);
                 continue;
@@ -1091,8 +1155,12 @@ __global__ __launch_bounds__(256, RT_WF_SHADE_WAVES) void k_wf_finish(DevScene s
             RT_KEEP4(ra);
             RT_KEEP4(rdin);
         }
-        const uint32_t vis = __float_as_uint(vn.w); // one bit per light: k_wf_shade's mask of lights with a segment, less those the shadow stage found occluded
-        if (__float_as_uint(vp.w) != 0xFFFFFFFFu) { // paths that ended in k_wf_shade carry the "no vertex" marker
+        const uint32_t vis = __float_as_uint(vn.w); // one bit per light, cleared where the shadow stage found the light's segment occluded (bits of lights without a segment: unspecified)
+        if (id != WF_SENTINEL && __float_as_uint(vp.w) == WF_NO_VERTEX) {
+            // the path ends at its hit: a miss (process_wavefront_ray, wavefront.rs:146-151) or a material index outside the table
+            const V3 end = __float_as_uint(vp.x) == WF_END_SKY ? RT_SKY() : RT_MAGENTA();
+            wf_end_path(wb, __float_as_uint(rdin.w), f4v(ra) + end * f4v(th));
+        } else if (__float_as_uint(vp.w) != WF_NO_VERTEX) {
             const V3 point = f4v(vp), normal = f4v(vn);
             const uint32_t material_id = __float_as_uint(vp.w);
             const uint32_t origin = __float_as_uint(rdin.w);
@@ -1312,7 +1380,8 @@ hipError_t wf_bounce(const DevScene& sc, const DevFrame& fr, const WfBuffers& wb
         }
     } else if (counters) launch_trace<true, false>(sc, wb, cur_q, WF_EXT_COUNT, WF_EXT_CURSOR, WF_EXT_WINDOW, s);
     else launch_trace<false, false>(sc, wb, cur_q, WF_EXT_COUNT, WF_EXT_CURSOR, WF_EXT_WINDOW, s);
-    hipLaunchKernelGGL(k_wf_shade, sgrid, sblock, 0, s, sc, fr, wb, (const uint32_t*)cur_q);
+    // the closest-hit kernels have stored the vertices.  The mask stage runs only where the shadow stage does not work the lights out itself
+    if ((fr.flags & RT_FLAG_NO_SHADOWS) == 0 && !(RT_WF_GRID_MASK && wf_runs_shadow_grid(fr, wb))) hipLaunchKernelGGL(k_wf_shade, sgrid, sblock, 0, s, sc, wb, (const uint32_t*)cur_q);
     if (wf_runs_shadow_grid(fr, wb)) { // the light grids answer what they can and hand the rest on to the traversal
         const dim3 ggrid((uint32_t)(cu_count() * RT_WF_GRID_BLOCKS_PER_CU));
         if (grid_events) (void)hipEventRecord(grid_events[0], s);
