@@ -179,6 +179,44 @@ def _empty_like_batch(rays, shape, dtype_name):
     return np.empty(shape, np.dtype(dtype_name))
 
 
+def _out_like(out, batch, batch_name, n, cols, dtype_name="float32"):
+    """The output array of a query over `batch` (n records): made like it (kind, device) when `out` is None, else `out` once it is of
+    the same kind and a C-contiguous (n, cols) array - (n,) with cols = 0 - of dtype_name."""
+    if out is None:
+        return _empty_like_batch(batch, (n, cols) if cols else (n,), dtype_name)
+    if _is_torch(out) != _is_torch(batch):
+        raise TypeError(f"out: must be the same kind (numpy / torch) as {batch_name}")
+    if _check_batch(out, "out", cols, dtype_name) != n:
+        raise ValueError(f"out: {out.shape[0]} rows for {n} {batch_name}")
+    return out
+
+
+def _counts_like(counts, batch, batch_name, n):
+    """The (n,) counts array beside a query's output (_check_counts): made like `batch` when None, else checked."""
+    if counts is None:
+        if _is_torch(batch):
+            import torch
+            return torch.empty((n,), dtype=torch.int32, device=batch.device)
+        return np.empty((n,), np.uint32)
+    if _is_torch(counts) != _is_torch(batch):
+        raise TypeError(f"counts: must be the same kind (numpy / torch) as {batch_name}")
+    _check_counts(counts, n, batch_name)
+    return counts
+
+
+def _path_params(samples, max_bounces, seed, first_sample, flags):
+    """The rt_path_params record (types.PATH_PARAMS) of radiance / radiance_sh from their four integers, checked."""
+    for name, v, lo, hi in (("samples", samples, 1, PATH_MAX_SAMPLES), ("max_bounces", max_bounces, 0, MAX_BOUNCES), ("seed", seed, 0, 0xFFFFFFFF),
+                            ("first_sample", first_sample, 0, 0xFFFFFFFF)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise ValueError(f"{name}: {v!r}, expected an integer in {lo} .. {hi}")
+    if int(first_sample) + int(samples) > 1 << 32:
+        raise ValueError(f"first_sample: {first_sample!r} + samples {samples!r} passes 2^32")
+    pp = np.zeros((), dtype=T.PATH_PARAMS)
+    pp["samples"], pp["max_bounces"], pp["seed"], pp["first_sample"], pp["flags"] = int(samples), int(max_bounces), int(seed), int(first_sample), flags
+    return pp
+
+
 def _sync_torch(*tensors):
     """The library reads device tensors on its own stream: finish what torch has queued for them first."""
     for a in tensors:
@@ -589,14 +627,7 @@ class Context:
     # -- ray queries ---------------------------------------------------------------------
     def _query(self, fn, rays, out, cols, dtype_name, counters, in_cols=8, in_name="rays"):
         n = _check_batch(rays, in_name, in_cols, "float32")
-        shape = (n, cols) if cols else (n,)
-        if out is None:
-            out = _empty_like_batch(rays, shape, dtype_name)
-        else:
-            if _is_torch(out) != _is_torch(rays):
-                raise TypeError(f"out: must be the same kind (numpy / torch) as {in_name}")
-            if _check_batch(out, "out", cols, dtype_name) != n:
-                raise ValueError(f"out: {len(out)} rows for {n} {in_name}")
+        out = _out_like(out, rays, in_name, n, cols, dtype_name)
         _sync_torch(rays, out)
         self._check(getattr(self.lib, fn)(self._h, _addr(rays), C.c_size_t(n), _addr(out), C.c_uint32(QUERY_COUNTERS if counters else 0)))
         return out
@@ -621,24 +652,15 @@ class Context:
         max_hits = int(max_hits)
         if max_hits == 0 and not count_all:
             raise ValueError("max_hits: 0 lists nothing, which needs count_all=True (a pure crossing count)")
-        torch_kind = _is_torch(rays)
-        for name, a in (("out", out), ("counts", counts)):
-            if a is not None and _is_torch(a) != torch_kind:
-                raise TypeError(f"{name}: must be the same kind (numpy / torch) as rays")
+        if out is not None and _is_torch(out) != _is_torch(rays):
+            raise TypeError("out: must be the same kind (numpy / torch) as rays")
         if max_hits == 0:
             out = None
         elif out is None:
             out = _empty_like_batch(rays, (n, max_hits, 4), "float32")
         else:
             _check_hit_lists(out, n, max_hits)
-        if counts is None:
-            if torch_kind:
-                import torch
-                counts = torch.empty((n,), dtype=torch.int32, device=rays.device)
-            else:
-                counts = np.empty((n,), np.uint32)
-        else:
-            _check_counts(counts, n)
+        counts = _counts_like(counts, rays, "rays", n)
         _sync_torch(rays, out, counts)
         flags = (QUERY_COUNTERS if counters else 0) | (QUERY_COUNT_ALL if count_all else 0)
         self._check(self.lib.rt_intersect_all(self._h, _addr(rays), C.c_size_t(n), C.c_uint32(max_hits),
@@ -668,22 +690,8 @@ class Context:
             raise ValueError(f"max_distance: {max_distance!r}, expected > 0 (inf allowed)")
         if not (np.isfinite(bias) and bias >= 0):
             raise ValueError(f"bias: {bias!r}, expected finite and >= 0")
-        torch_kind = _is_torch(points)
-        for name, a in (("out", out), ("counts", counts)):
-            if a is not None and _is_torch(a) != torch_kind:
-                raise TypeError(f"{name}: must be the same kind (numpy / torch) as points")
-        if out is None:
-            out = _empty_like_batch(points, (n,), "float32")
-        elif _check_batch(out, "out", 0, "float32") != n:
-            raise ValueError(f"out: {out.shape[0]} rows for {n} points")
-        if counts is None:
-            if torch_kind:
-                import torch
-                counts = torch.empty((n,), dtype=torch.int32, device=points.device)
-            else:
-                counts = np.empty((n,), np.uint32)
-        else:
-            _check_counts(counts, n, "points")
+        out = _out_like(out, points, "points", n, 0)
+        counts = _counts_like(counts, points, "points", n)
         ap = np.zeros((), dtype=T.AO_PARAMS)
         ap["samples"], ap["seed"], ap["max_distance"], ap["bias"] = int(samples), int(seed), max_distance, bias
         ap["flags"] = QUERY_COUNTERS if counters else 0
@@ -703,13 +711,7 @@ class Context:
             raise ValueError(f"bias: {bias!r}, expected a number") from None
         if not (np.isfinite(bias) and bias >= 0):
             raise ValueError(f"bias: {bias!r}, expected finite and >= 0")
-        if out is None:
-            out = _empty_like_batch(points, (n, 4), "float32")
-        else:
-            if _is_torch(out) != _is_torch(points):
-                raise TypeError("out: must be the same kind (numpy / torch) as points")
-            if _check_batch(out, "out", 4, "float32") != n:
-                raise ValueError(f"out: {out.shape[0]} rows for {n} points")
+        out = _out_like(out, points, "points", n, 4)
         dp = np.zeros((), dtype=T.DIRECT_LIGHT_PARAMS)
         dp["bias"] = bias
         dp["flags"] = ((DIRECT_AMBIENT if ambient else 0) | (0 if shadows else DIRECT_NO_SHADOWS) | (0 if use_grids else DIRECT_NO_SHADOW_GRID)
@@ -725,22 +727,9 @@ class Context:
         in an extended-mode frame; shadows=False: no shadow segments; camera_draws=True: two draws are dropped first, the ones a
         jittered camera sample (sample_rays) spent on its jitter."""
         n = _check_batch(rays, "rays", 8, "float32")
-        for name, v, lo, hi in (("samples", samples, 1, PATH_MAX_SAMPLES), ("max_bounces", max_bounces, 0, MAX_BOUNCES), ("seed", seed, 0, 0xFFFFFFFF),
-                                ("first_sample", first_sample, 0, 0xFFFFFFFF)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
-                raise ValueError(f"{name}: {v!r}, expected an integer in {lo} .. {hi}")
-        if int(first_sample) + int(samples) > 1 << 32:
-            raise ValueError(f"first_sample: {first_sample!r} + samples {samples!r} passes 2^32")
-        if out is None:
-            out = _empty_like_batch(rays, (n, 4), "float32")
-        else:
-            if _is_torch(out) != _is_torch(rays):
-                raise TypeError("out: must be the same kind (numpy / torch) as rays")
-            if _check_batch(out, "out", 4, "float32") != n:
-                raise ValueError(f"out: {out.shape[0]} rows for {n} rays")
-        pp = np.zeros((), dtype=T.PATH_PARAMS)
-        pp["samples"], pp["max_bounces"], pp["seed"], pp["first_sample"] = int(samples), int(max_bounces), int(seed), int(first_sample)
-        pp["flags"] = (0 if shadows else PATH_NO_SHADOWS) | (PATH_CAMERA_DRAWS if camera_draws else 0) | (QUERY_COUNTERS if counters else 0)
+        pp = _path_params(samples, max_bounces, seed, first_sample,
+                          (0 if shadows else PATH_NO_SHADOWS) | (PATH_CAMERA_DRAWS if camera_draws else 0) | (QUERY_COUNTERS if counters else 0))
+        out = _out_like(out, rays, "rays", n, 4)
         _sync_torch(rays, out)
         self._check(self.lib.rt_radiance(self._h, _addr(rays), C.c_size_t(n), _p(pp), _addr(out)))
         return out
@@ -752,22 +741,8 @@ class Context:
         probe i draws its direction and its path from rng_for(seed + i, first_sample + k): it is radiance() along that direction with
         camera_draws=True, projected in sample order.  max_bounces and shadows as radiance()."""
         n = _check_batch(probes, "probes", 4, "float32")
-        for name, v, lo, hi in (("samples", samples, 1, PATH_MAX_SAMPLES), ("max_bounces", max_bounces, 0, MAX_BOUNCES), ("seed", seed, 0, 0xFFFFFFFF),
-                                ("first_sample", first_sample, 0, 0xFFFFFFFF)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
-                raise ValueError(f"{name}: {v!r}, expected an integer in {lo} .. {hi}")
-        if int(first_sample) + int(samples) > 1 << 32:
-            raise ValueError(f"first_sample: {first_sample!r} + samples {samples!r} passes 2^32")
-        if out is None:
-            out = _empty_like_batch(probes, (n, 28), "float32")
-        else:
-            if _is_torch(out) != _is_torch(probes):
-                raise TypeError("out: must be the same kind (numpy / torch) as probes")
-            if _check_batch(out, "out", 28, "float32") != n:
-                raise ValueError(f"out: {out.shape[0]} rows for {n} probes")
-        pp = np.zeros((), dtype=T.PATH_PARAMS)
-        pp["samples"], pp["max_bounces"], pp["seed"], pp["first_sample"] = int(samples), int(max_bounces), int(seed), int(first_sample)
-        pp["flags"] = (0 if shadows else PATH_NO_SHADOWS) | (QUERY_COUNTERS if counters else 0)
+        pp = _path_params(samples, max_bounces, seed, first_sample, (0 if shadows else PATH_NO_SHADOWS) | (QUERY_COUNTERS if counters else 0))
+        out = _out_like(out, probes, "probes", n, 28)
         _sync_torch(probes, out)
         self._check(self.lib.rt_radiance_sh(self._h, _addr(probes), C.c_size_t(n), _p(pp), _addr(out)))
         return out

@@ -156,7 +156,7 @@ struct DevTargets {
 };
 
 // Slots of DevTargets::counters (zeroed per frame and device; rt_intersect / rt_occluded zero the first three).  Written by k_render_reference,
-// k_render_extended, k_render_extended_sm and k_rq_trace; read by run_frame, run_query and (the diagnostic slots) rt_debug_counters.
+// k_render_extended, k_render_extended_sm and k_rq_trace; read by run_frame, run_batch and (the diagnostic slots) rt_debug_counters.
 enum DevCounterSlot : uint32_t {
     RT_CNT_SEGMENTS = 0,     // segments traced: camera + continuation + shadow (modes 0/1: pixels traced; queries: not written)
     RT_CNT_NODE_VISITS = 1,  // counting variants only

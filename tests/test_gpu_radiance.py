@@ -279,6 +279,27 @@ def test_host_batch_across_a_chunk_boundary(gpu_ctx, scene_of):
         assert two.radiance(rays, seed=SEED, **kw).tobytes() == whole.tobytes()
 
 
+def test_device_batch_across_a_chunk_boundary(gpu_ctx, scene_of):
+    """A device batch of two chunks (1024 rays and 5) is timed by one event pair around both launches, where the host batch has a pair
+    per chunk: the bytes are the host batch's, and the pair has measured something."""
+    if torch is None:
+        pytest.skip("torch is not installed")
+    scene = scene_of("cornell12")
+    gpu_ctx.upload_scene(scene)
+    samples = api.PATH_MAX_SAMPLES
+    n = api.QUERY_CHUNK // samples + 5
+    assert n == 1029
+    rays = np.ascontiguousarray(gpu_ctx.camera_rays(W, H, scene.camera, mode=1)[1000:1000 + n])
+    kw = dict(samples=samples, max_bounces=1, seed=SEED, first_sample=2)
+    whole = gpu_ctx.radiance(rays, **kw)
+    host = gpu_ctx.stats()
+    dev = gpu_ctx.radiance(torch.from_numpy(rays).to("cuda:0"), **kw)
+    st = gpu_ctx.stats()
+    assert dev.cpu().numpy().tobytes() == whole.tobytes()
+    assert st["kernel_ms"] > 0
+    assert st["primary_rays"] == n * samples and all(st[k] == host[k] for k in ("rays", "continuation_rays", "shadow_rays"))
+
+
 # 6. edges -----------------------------------------------------------------------------------------------------------------------
 def test_edges(gpu_ctx, scene_of):
     scene = scene_of("cornell12")
