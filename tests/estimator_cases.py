@@ -179,6 +179,10 @@ class Case:
         jx, jy = jitter(self.frame_seed, self.w, self.h, samples)
         return camera_rays(self.scene.camera, self.w, self.h, jx, jy)
 
+    def centre_rays(self):
+        """Float64 camera rays through the pixel centres, which a closed frame with spp = 1 uses: origin, directions (h, w, 3)."""
+        return camera_rays(self.scene.camera, self.w, self.h, 0.5, 0.5)
+
 
 # ------------------------------------------------------------------------------------------------------------------------
 # 1. Furnace
@@ -461,19 +465,45 @@ def direct_light(kind, w=64, h=64):
     Step 2, restated in float64 in `direct_light_expected`: l = direction to the light; point: d = |L - P|,
     att = f16(1 / (1 + 0.01 d^2)); intensity = max(N . l, 0) * I * att (directional: no att, l = -normalize(direction));
     BRDF of a dielectric = albedo / pi * intensity; times the light's colour; visible unless the segment from P + N 1e-3 along l
-    meets something before the light (directional: at all).  The vertex is terminal: + 0.1 rho."""
+    meets something before the light (directional: at all).  The vertex is terminal: + 0.1 rho.
+
+    The kinds with two lights put that scene under a spot light at the point light's place, aimed along SPOT_DIR, and a second point
+    light at POINT2_LIGHT_POS with a colour and an intensity of its own; the occluder's two shadows (around (-0.15, 0.1) and
+    (1.0, -0.67), each about 1.5 wide) overlap in a corner only, so most shadowed pixels keep one of the two lights.  A spot light
+    is the point light times max(dot(-normalize(direction), l), 0); its range and cone angles are never read (the scene gives them
+    values that would darken the floor if they were).  The lights are summed in their order, each gated on its own.
+    "spot_and_point": the diffuse floor.  "metallic_two_lights": a metallic floor, whose BRDF is albedo * intensity * 0.5.
+    "backface": the diffuse floor with the geometric normal -y: N . l < 0 for both lights, step 2 uses the unflipped normal, so every
+    floor pixel is the ambient term alone and no light has a contribution to gate."""
     mesh = _Mesh()
-    _quad(mesh, (-6, 0, -6), (6, 0, -6), (6, 0, 30), (-6, 0, 30), 0, (0, 1, 0))
+    _quad(mesh, (-6, 0, -6), (6, 0, -6), (6, 0, 30), (-6, 0, 30), 0, (0, -1, 0) if kind == "backface" else (0, 1, 0))
     y, hf = OCCLUDER["y"], OCCLUDER["half"]
     _quad(mesh, (-hf, y, -hf), (hf, y, -hf), (hf, y, hf), (-hf, y, hf), 1, (0, 1, 0))
-    if kind == "point":
+    if kind != "directional":
         _quad(mesh, (-6, 5, -6), (6, 5, -6), (6, 5, 6), (-6, 5, 6), 1, (0, -1, 0))
-        light = H.light_point(tuple(POINT_LIGHT_POS), tuple(LIGHT_COLOR), LIGHT_INTENSITY)
+    if kind == "point":
+        lights = [H.light_point(tuple(POINT_LIGHT_POS), tuple(LIGHT_COLOR), LIGHT_INTENSITY)]
+    elif kind == "directional":
+        lights = [H.light_directional(tuple(DIRECTIONAL_DIR), tuple(LIGHT_COLOR), LIGHT_INTENSITY)]
     else:
-        light = H.light_directional(tuple(DIRECTIONAL_DIR), tuple(LIGHT_COLOR), LIGHT_INTENSITY)
-    mats = [H.material_diffuse(tuple(LIT_RHO)), H.material_diffuse((0.0, 0.0, 0.0))]
+        assert kind in TWO_LIGHT_KINDS, kind
+        lights = [H.light_spot(tuple(POINT_LIGHT_POS), tuple(SPOT_DIR), tuple(LIGHT_COLOR), LIGHT_INTENSITY, 0.5, 0.01, 0.02),
+                  H.light_point(tuple(POINT2_LIGHT_POS), tuple(LIGHT2_COLOR), LIGHT2_INTENSITY, rng=0.5)]
+    floor = H.material_metallic(tuple(LIT_RHO), 1.0) if kind == "metallic_two_lights" else H.material_diffuse(tuple(LIT_RHO))
+    mats = [floor, H.material_diffuse((0.0, 0.0, 0.0))]
     cam = H.camera((0.1, 4.5, 0.05), (0.0, -1.0, 0.0), (0.0, 0.0, -1.0), 50.0)
-    return Case(f"direct_{kind}", _scene("direct_light", mesh, mats, cam, [light]), w, h, 0, info={"kind": kind})
+    return Case(f"direct_{kind}", _scene("direct_light", mesh, mats, cam, lights), w, h, 0, info={"kind": kind})
+
+
+TWO_LIGHT_KINDS = ("spot_and_point", "metallic_two_lights", "backface")
+SPOT_DIR = np.array([0.2, -1.0, 0.1])          # the way the spot light points
+POINT2_LIGHT_POS = np.array([-1.5, 2.5, 1.0])
+LIGHT2_COLOR = np.array([0.6, 1.0, 0.7])
+LIGHT2_INTENSITY = 3.0
+DIRECT_VARIANTS = {"point": ("shadow_below",), "directional": ("shadow_below", "not_negated"),
+                   "spot_and_point": ("shadow_below", "spot_plus_direction", "one_occluded_removes_both"),
+                   "metallic_two_lights": ("dielectric_on_metal", "spot_plus_direction", "one_occluded_removes_both"),
+                   "backface": ("flipped_normal",)}
 
 
 def _in_square(q, half):
@@ -481,37 +511,82 @@ def _in_square(q, half):
     return d > 0, np.abs(d) < SHADOW_MARGIN
 
 
-def direct_light_expected(case, samples, variant="right"):
-    """-> (per-sample radiance (n, h, w, 3), unsure (n, h, w)).  variant "shadow_below": the shadow segment starts at P - N 1e-3
-    (the floor itself occludes everything); "not_negated": the directional light's direction used as it is (N . l < 0: no light)."""
+def _direct_lights(kind):
+    """(type, position, direction, colour, intensity) of the case's lights, in the scene's order."""
+    if kind == "point":
+        return [("point", POINT_LIGHT_POS, None, LIGHT_COLOR, LIGHT_INTENSITY)]
+    if kind == "directional":
+        return [("directional", None, DIRECTIONAL_DIR, LIGHT_COLOR, LIGHT_INTENSITY)]
+    return [("spot", POINT_LIGHT_POS, SPOT_DIR, LIGHT_COLOR, LIGHT_INTENSITY), ("point", POINT2_LIGHT_POS, None, LIGHT2_COLOR, LIGHT2_INTENSITY)]
+
+
+def direct_light_eval(case, samples, variant="right", lights=None):
+    """-> (per-sample radiance (n, h, w, 3), unsure (n, h, w), shadow segments): step 2 at the floor point of every sample, and the
+    number of (sample, light) pairs whose contribution is not zero - the pairs a shadow segment is traced for.  `lights`: the indices
+    of the lights that are summed (all of them by default).  Variants:
+    "shadow_below": the shadow segment starts at P - N 1e-3 (the floor itself occludes everything); "not_negated": the directional
+    light's direction used as it is (N . l < 0: no light); "spot_plus_direction": the spot factor max(dot(+normalize(direction), l), 0)
+    (the spot light goes dark); "dielectric_on_metal": albedo / pi on the metallic floor; "one_occluded_removes_both": a sample
+    loses all its lights where any one of them is occluded; "flipped_normal": step 2 with the face-forwarded normal (the back face
+    is lit like a front face)."""
+    kind = case.info["kind"]
     o, d = case.rays(samples)
-    n = np.array([0.0, 1.0, 0.0])
+    n = np.array([0.0, -1.0, 0.0]) if kind == "backface" else np.array([0.0, 1.0, 0.0])
+    if variant == "flipped_normal":
+        n = -n
     # what the camera ray meets first: the occluder's top (black: 0) or the floor
     tq = (OCCLUDER["y"] - o[1]) / d[..., 1]
     on_occluder, unsure = _in_square(o + d * tq[..., None], OCCLUDER["half"])
     p = o + d * (-o[1] / d[..., 1])[..., None]
-    if case.info["kind"] == "point":
-        to_light = POINT_LIGHT_POS - p
-        dist = np.linalg.norm(to_light, axis=-1)
-        l = to_light / dist[..., None]
-        with np.errstate(over="ignore"):
-            att = (1.0 / (1.0 + dist * dist * 0.01)).astype(np.float16).astype(np.float64)
-    else:
-        l = np.broadcast_to(-_unit(DIRECTIONAL_DIR), p.shape)
-        att = 1.0
-        if variant == "not_negated":
-            l = -l
-    intensity = np.maximum(l @ n, 0.0) * LIGHT_INTENSITY * att
-    lit = LIT_RHO / math.pi * intensity[..., None] * LIGHT_COLOR
-    # shadow segment from P + N eps along l: where it crosses the occluder's plane (always before the light, which is at y = 3)
-    org = p + n * ORIGIN_EPS
-    s = (OCCLUDER["y"] - org[..., 1]) / l[..., 1]
-    shadowed, edge = _in_square(org + l * s[..., None], OCCLUDER["half"])
-    if variant == "shadow_below":
-        shadowed = np.ones_like(shadowed)
-    rad = 0.1 * LIT_RHO + np.where(shadowed[..., None], 0.0, lit)
+    metallic = kind == "metallic_two_lights" and variant != "dielectric_on_metal"
+    total = np.zeros(p.shape)
+    any_shadowed = np.zeros(p.shape[:-1], bool)
+    edge_any = np.zeros(p.shape[:-1], bool)
+    segments = 0
+    terms = []
+    for index, (ltype, pos, direction, colour, power) in enumerate(_direct_lights(kind)):
+        if lights is not None and index not in lights:
+            continue
+        if ltype == "directional":
+            l = np.broadcast_to(-_unit(direction), p.shape)
+            att = 1.0
+            if variant == "not_negated":
+                l = -l
+        else:
+            to_light = pos - p
+            dist = np.linalg.norm(to_light, axis=-1)
+            l = to_light / dist[..., None]
+            with np.errstate(over="ignore"):
+                att = (1.0 / (1.0 + dist * dist * 0.01)).astype(np.float16).astype(np.float64)
+        intensity = np.maximum(l @ n, 0.0) * power * att
+        if ltype == "spot":
+            axis = _unit(direction) if variant == "spot_plus_direction" else -_unit(direction)
+            intensity = intensity * np.maximum(l @ axis, 0.0)
+        brdf = LIT_RHO * 0.5 if metallic else LIT_RHO / math.pi
+        lit = brdf * intensity[..., None] * colour
+        # shadow segment from P + N eps along l: where it crosses the occluder's plane (always before the light: both are above y = 1)
+        org = p + n * ORIGIN_EPS
+        with np.errstate(divide="ignore", invalid="ignore"):
+            s = (OCCLUDER["y"] - org[..., 1]) / l[..., 1]
+            shadowed, edge = _in_square(org + l * s[..., None], OCCLUDER["half"])
+        shadowed = shadowed & (s > 0)
+        if variant == "shadow_below":
+            shadowed = np.ones_like(shadowed)
+        gated = (intensity > 0) & ~on_occluder
+        segments += int(gated.sum())
+        any_shadowed |= shadowed & gated
+        edge_any |= edge & gated
+        terms.append(np.where(shadowed[..., None], 0.0, lit))
+    for term in terms:   # in the lights' order
+        total = total + (np.where(any_shadowed[..., None], 0.0, term) if variant == "one_occluded_removes_both" else term)
+    rad = 0.1 * LIT_RHO + total
     rad = np.where(on_occluder[..., None], 0.0, rad)
-    return rad, unsure | (edge & ~on_occluder)
+    return rad, unsure | edge_any, segments
+
+
+def direct_light_expected(case, samples, variant="right"):
+    """-> (per-sample radiance (n, h, w, 3), unsure (n, h, w)) of direct_light_eval."""
+    return direct_light_eval(case, samples, variant)[:2]
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -535,6 +610,199 @@ def seed_collisions_brute_force(w, h, spp, mult=GOLDEN, frame_seed=0):
     _, counts = np.unique(seeds, return_counts=True)
     counts = counts.astype(np.int64)
     return int((counts * (counts - 1) // 2).sum())
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# 7. Refraction through the front face, total reflection at the back face
+# ------------------------------------------------------------------------------------------------------------------------
+GLASS_IOR = 1.5                                   # f16 holds it exactly
+DISPERSION = (-0.018, 0.0, 0.035)                 # step 4: ior_c = ior + {-0.018, 0, +0.035}[c]
+# ior_c as f32 forms it: f32(1.5) + f32(offset), rounded to f32
+IOR_C = np.array([float(np.float32(GLASS_IOR) + np.float32(o)) for o in DISPERSION])
+GLASS_Y = 1.0
+REFRACT_X0 = 0.65625                              # where the floor's emissive half ends (exact in f32)
+REFRACT_MARGIN = 1e-4                             # a segment that lands this close to X0 is not classified (f32 error ~1e-6)
+TIR_MARGIN = 1e-5                                 # |ior_c^2 sin^2 - 1| below which the branch is not classified (tir_back)
+# the terminal shading of a T = 1 vertex (step 3, the reference's per-channel transmission mix): (0.2, 0.2, 0.3) * (ior_c - 1) / (ior - 1)
+GLASS_TERMINAL_MIX = np.array([0.2, 0.2, 0.3]) * (IOR_C - 1.0) / (GLASS_IOR - 1.0)
+HERO_F32_REL_BOUND = 6 * U32
+"""A path of one transmission that ends on an emitter or the sky is 3 a_c V_c in its hero channel: the throughput 1 * 3 and
+(3) * a_c are two roundings, V * throughput one, the sum 0 + x and the division by spp = 1 are exact, and a_c and V_c are each
+within 2^-24 of their float64 values as f32: five; six leaves one over."""
+
+
+def _big_glass_quad(mesh, mat=0):
+    # the diagonal a-c passes x = -10 at z = 0, far from both cameras' footprints near the origin: see SHARED EDGES
+    _quad(mesh, (-20, GLASS_Y, -20), (20, GLASS_Y, -20), (20, GLASS_Y, 60), (-20, GLASS_Y, 60), mat, (0, 1, 0))
+
+
+def _glass_t1():
+    return H.material_new(tuple(GLASS_A), 0.0, 0.0, (0, 0, 0), GLASS_IOR, 1.0)
+
+
+def _tilted_camera(position, theta_deg, roll_deg, fov, upward=False):
+    """A camera at `position` looking along (sin theta, -+cos theta, 0) - theta from the vertical, down unless `upward` - with an
+    up vector perpendicular to that direction, turned by `roll_deg` about it."""
+    th, ro = math.radians(theta_deg), math.radians(roll_deg)
+    sign = 1.0 if upward else -1.0
+    fwd = np.array([math.sin(th), sign * math.cos(th), 0.0])
+    up0 = np.array([-sign * math.cos(th), math.sin(th), 0.0])          # perpendicular to fwd, in the plane of incidence
+    up = math.cos(ro) * up0 + math.sin(ro) * np.cross(fwd, up0)
+    return H.camera(tuple(position), tuple(fwd), tuple(up), fov)
+
+
+def snell(d, nf, eta):
+    """Step 4's transmission direction for an incoming direction d (..., 3) (used as it is, unit or not, as the step does),
+    the face-forwarded normal nf and eta (..., ) or scalar: cos i = -nf . d, sin^2 t = eta^2 (1 - cos^2 i);
+    sin^2 t > 1: the mirror direction d - 2 (d . nf) nf; else normalize(eta d + (eta cos i - cos t) nf).
+    -> (direction (..., 3), total reflection (...,), sin^2 t (...,))."""
+    d = np.asarray(d, np.float64)
+    eta = np.asarray(eta, np.float64)
+    cos_i = -(d @ nf)
+    sin2_t = eta * eta * (1.0 - cos_i * cos_i)
+    tir = sin2_t > 1.0
+    cos_t = np.sqrt(np.where(tir, 0.0, 1.0 - sin2_t))
+    refr = d * eta[..., None] + nf * (eta * cos_i - cos_t)[..., None]
+    refl = d - 2.0 * (d @ nf)[..., None] * nf
+    out = np.where(tir[..., None], refl, refr)
+    return out / np.linalg.norm(out, axis=-1, keepdims=True), tir, sin2_t
+
+
+def refract_front(w=96, h=96):
+    """The T = 1 glass quad (albedo a, ior 1.5, no emission) at y = 1 over a floor at y = 0 whose half x < X0 is emissive (albedo 0,
+    emission Ef) and whose other half is black; no lights, B = 1; a 2-degree camera looks down at 55 degrees from the vertical,
+    toward +x, rolled by 12 degrees about its axis so that the boundary crosses the pixel rows.
+
+    A closed 1-spp frame sends one path through each pixel centre.  The quad adds nothing (no emission, no light).  Step 4 transmits
+    (T = 1), picks the hero channel c and leaves throughput 3 a_c e_c; it enters through the front face, so eta = 1 / ior_c, and the
+    segment runs from P - N 1e-3 along normalize(eta d + (eta cos i - cos t) N).  The floor is the terminal vertex: Ef + 0.1 * 0 on
+    the emissive half, 0 on the black one.  So the pixel is 3 a_c Ef_c in channel c alone if channel c's segment lands at x < X0,
+    and 0 otherwise.  At 55 degrees and depth 1 the three channels land 0.0107 (red to green) and 0.0201 (green to blue) apart, the
+    frame spans about 0.24 in x on the quad, and the camera is aimed so that the straddling band lies inside the frame.
+
+    Rejects (refract_front_values' variants): no dispersion, eta inverted (ior_c from the front: total reflection, the sky),
+    no bending, an origin at P + N 1e-3 (the segment meets the quad again, whose terminal shading is the transmission mix)."""
+    mesh = _Mesh()
+    _big_glass_quad(mesh)
+    z0, z1 = -30.0, 70.0   # the halves' diagonals pass x = -34.5 and x = 15.5 at z = 0
+    _quad(mesh, (-50, 0, z0), (REFRACT_X0, 0, z0), (REFRACT_X0, 0, z1), (-50, 0, z1), 1, (0, 1, 0))
+    _quad(mesh, (REFRACT_X0, 0, z0), (50, 0, z0), (50, 0, z1), (REFRACT_X0, 0, z1), 2, (0, 1, 0))
+    mats = [_glass_t1(), H.material_emissive((0.0, 0.0, 0.0), tuple(FLOOR_E)), H.material_diffuse((0.0, 0.0, 0.0))]
+    th = math.radians(55.0)
+    aim = np.array([0.01, GLASS_Y, 0.0])   # green lands 0.651 further: the frame's centre is on the straddling band
+    pos = aim - 4.0 * np.array([math.sin(th), -math.cos(th), 0.0])
+    return Case("refract_front", _scene("refract_front", mesh, mats, _tilted_camera(pos, 55.0, 12.0, 2.0)), w, h, 1)
+
+
+def refract_front_values(o, d, variant="right"):
+    """For rays (origin o (3,) or (..., 3), directions d (..., 3)) that meet the quad of refract_front from above:
+    -> (V (..., 3), unsure (..., 3), landing x (..., 3)), V_c the radiance the terminal vertex of a path with hero channel c
+    returns (the path's value is 3 a_c V_c in channel c), unsure_c whether channel c's segment lands within REFRACT_MARGIN of X0."""
+    o, d = np.asarray(o, np.float64), np.asarray(d, np.float64)
+    n = np.array([0.0, 1.0, 0.0])
+    p = o + d * ((GLASS_Y - o[..., 1]) / d[..., 1])[..., None]
+    ior = np.full(3, GLASS_IOR) if variant == "no_dispersion" else IOR_C
+    v, unsure, land = [], [], []
+    for c in range(3):
+        eta = ior[c] if variant == "eta_inverted" else 1.0 / ior[c]
+        t, tir, _ = snell(d, n, eta)
+        if variant == "straight":
+            t, tir = d / np.linalg.norm(d, axis=-1, keepdims=True), np.zeros(d.shape[:-1], bool)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            x = p[..., 0] + t[..., 0] * (GLASS_Y - ORIGIN_EPS) / -t[..., 1]
+        x = np.where(tir, np.inf, x)
+        val = np.where(tir, SKY[c], np.where(x < REFRACT_X0, FLOOR_E[c], 0.0))   # a reflected segment leaves for the sky
+        if variant == "origin_above":
+            val = np.full(x.shape, GLASS_TERMINAL_MIX[c])
+        v.append(val)
+        unsure.append(np.abs(x - REFRACT_X0) < REFRACT_MARGIN)
+        land.append(x)
+    return np.stack(v, -1), np.stack(unsure, -1), np.stack(land, -1)
+
+
+REFRACT_VARIANTS = ("no_dispersion", "eta_inverted", "straight", "origin_above")
+
+
+def tir_back(w=128, h=64):
+    """The same quad seen from below: a camera at y = 0.5 looks up at 41.6 degrees from the vertical with 4 degrees of (vertical)
+    field, the plane of incidence vertical in the image, rolled by 10 degrees; an emissive floor (albedo 0, emission Ef) at y = 0, the
+    sky above; B = 1.  The frame's incidence angles run from about 38.9 to 44.3 degrees, across the three critical angles
+    asin(1 / ior_c) = 42.436, 41.810, 40.652 degrees.
+
+    The quad is met from behind: Nf = -N, eta = ior_c.  With x_c = ior_c^2 sin^2(theta) the hero channel c refracts when x_c <= 1 -
+    from P - Nf 1e-3, above the quad, to the sky: 3 a_c sky_c - and is totally reflected when x_c > 1 - from P + Nf 1e-3, below the
+    quad, down to the floor, the terminal vertex: 3 a_c Ef_c.  Ef and the sky differ in every channel, so a pixel's value names its
+    hero channel and its branch.
+
+    TIR_MARGIN.  f32 forms x_c as eta * eta * (1 - cos_i * cos_i) from the camera direction's y component.  That component is within
+    32 * 2^-24 of float64's (CAMERA_DIR_F32_BOUND); cos_i <= 0.78, so cos_i^2 is within 2 * 0.78 * 32 + 1 = 51 units of 2^-24, the
+    difference 1 - cos_i^2 (about 0.44) within 52, eta^2 <= 2.36 (ior_c one rounding, the square another: 3 relative, on a product
+    of about 1: 3 absolute) and the last product one more: 2.36 * 52 + 4 = 127 units = 7.6e-6 < 1e-5.  With caller-supplied rays
+    (rt_radiance) the direction is taken as it is and only the 4 + 2.36 * 2 units of the arithmetic remain.  The margin is a
+    condition on what is classified, not a measurement of the code under test.
+
+    Rejects (tir_back_values' variants): no total-reflection branch (the sky everywhere), one critical angle for all channels, a
+    reflection that starts on the far side (P - Nf 1e-3: it meets the quad again, whose terminal shading is the transmission mix)."""
+    mesh = _Mesh()
+    _big_glass_quad(mesh)
+    _quad(mesh, (-50, 0, -30), (50, 0, -30), (50, 0, 70), (-50, 0, 70), 1, (0, 1, 0))   # diagonal: x = -20 at z = 0
+    mats = [_glass_t1(), H.material_emissive((0.0, 0.0, 0.0), tuple(FLOOR_E))]
+    return Case("tir_back", _scene("tir_back", mesh, mats, _tilted_camera((0.0, 0.5, 0.0), 41.6, 10.0, 4.0, upward=True)), w, h, 1)
+
+
+def tir_back_values(d, variant="right"):
+    """For directions d (..., 3) that meet the quad of tir_back from below: -> (V (..., 3), unsure (..., 3), x (..., 3)) as
+    refract_front_values, x_c = ior_c^2 (1 - d_y^2)."""
+    d = np.asarray(d, np.float64)
+    ior = np.full(3, GLASS_IOR) if variant == "one_critical_angle" else IOR_C
+    x = ior ** 2 * (1.0 - d[..., 1:2] ** 2)
+    reflects = x > 1.0
+    if variant == "no_tir_branch":
+        reflects = np.zeros_like(reflects)
+    below = GLASS_TERMINAL_MIX if variant == "reflect_from_far_side" else FLOOR_E
+    return np.where(reflects, below, SKY), np.abs(x - 1.0) < TIR_MARGIN, x
+
+
+TIR_VARIANTS = ("no_tir_branch", "one_critical_angle", "reflect_from_far_side")
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# 8. The rough metallic lobe's absorbed cap
+# ------------------------------------------------------------------------------------------------------------------------
+ROUGH_LAYOUTS = {"front": (0, 1, 0), "backface": (0, -1, 0)}   # the floor's geometric normal; the camera is above it in both
+ROUGH_EMPTY_CAP_MARGIN = 1e-5   # the cap counts as empty for c > roughness + this (the f32 lobe's c and |unit vector| are within 1e-6)
+
+
+def rough_metal(roughness, layout="front", w=64, h=64):
+    """A metallic floor (albedo a = MIRROR_A, roughness rho) in the plane y = 0 under the sky, nothing else, B = 1; the camera looks
+    down at 65 degrees from the vertical with 40 degrees of field, so c = r . Nf = -d . Nf runs from 0.08 to 0.71 over the frame.
+    The floor is ONE triangle, so that no shared edge lies in the footprint (SHARED EDGES).  layout "backface": its geometric normal
+    is -y and the camera sees it from behind, so Nf = -N.
+
+    Step 4, metallic: ndir = normalize(r + rho * u), u uniform on the sphere, absorbed if ndir . Nf <= 0.  ndir . Nf has the sign of
+    c + rho z with z = u . Nf uniform on [-1, 1] (Archimedes), so the path is absorbed with probability max(0, (1 - c / rho) / 2) -
+    the cap - and then traces no continuation segment and returns 0; otherwise its segment leaves upward from P + Nf 1e-3, meets
+    nothing and returns a sky.  Every pixel is a sky k / spp with k the number of its samples that continue, the sum of k is the
+    frame's continuation-segment count, and k = spp where c > rho for all the pixel's samples (rho = 0.5: the nearer part of the
+    frame).
+
+    Rejects: nothing absorbed, the roughness ignored (the cap of rho = 1 at rho = 0.5), a normal that is not face-forwarded (on the
+    back face ndir . N > 0 exactly where the lobe should be absorbed)."""
+    normal = np.array(ROUGH_LAYOUTS[layout], np.float64)
+    a, b, c = np.array([-100.0, 0, -1000.0]), np.array([-100.0, 0, 1000.0]), np.array([2000.0, 0, 0.0])
+    if np.dot(np.cross(b - a, c - a), normal) < 0:
+        b, c = c, b
+    mesh = _Mesh()
+    mesh.add([a, b, c], [(0, 1, 2)], 0)
+    mats = [H.material_metallic(tuple(MIRROR_A), roughness)]
+    cam = _tilted_camera((0.0, 2.0, 0.0), 65.0, 0.0, 40.0)
+    return Case(f"rough_metal_{roughness}_{layout}", _scene("rough_metal", mesh, mats, cam), w, h, 1,
+                info={"roughness": roughness, "layout": layout})
+
+
+def rough_cap(c, roughness):
+    """The absorbed share of the lobe at c = r . Nf: max(0, (1 - c / roughness) / 2)."""
+    return np.maximum(0.0, 0.5 * (1.0 - np.asarray(c, np.float64) / roughness))
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -652,24 +920,204 @@ def check_mirror(rgb, case, spp):
     assert ((k > 0) & (k < spp) & ~unsure).sum() >= 16 and (err[~unsure] <= tol).all()
 
 
-def check_direct_light(rgb, case, spp):
-    """Every classified pixel within 2^-10 relative of the float64 restatement (f16 attenuation: 2^-11, the f32 chain a few 2^-24);
-    pixels with a sample within SHADOW_MARGIN of the occluder's outline or its shadow's are left out, at most 2 % of the frame."""
-    rad, unsure = direct_light_expected(case, np.arange(spp))
+def check_direct_light(rgb, case, spp, segments=None):
+    """Every classified pixel within 2^-10 relative of the float64 restatement (f16 attenuation: 2^-11 on each light's term, so on
+    their sum; the f32 chain a few 2^-24); pixels with a sample within SHADOW_MARGIN of the occluder's outline or of one of its
+    shadows' are left out, at most 2 % of the frame.  `segments` (the frame's segment counts): the shadow segments are the
+    (sample, light) pairs whose contribution is not zero in float64 - one per light and floor sample, none on the black occluder,
+    none on a floor that faces away.
+
+    Each named alternative differs from the restatement by more than twice the tolerance on a share of the frame that follows from
+    the scene: most of it where the alternative changes every lit pixel, the shadows' area where it changes only those."""
+    kind = case.info["kind"]
+    rad, unsure, shadow_segments = direct_light_eval(case, np.arange(spp))
     want, unsure = rad.mean(0), unsure.any(0)
     got = np.asarray(rgb, np.float64)
     tol = 2.0 ** -10 * want
     err = np.abs(got - want)
     lit = want[..., 0] > 0.1 * LIT_RHO[0] * (1 + 1e-9)
+    floor = want[..., 0] > 0
     print(f"{case.name}: left out {unsure.mean():.4f} (cap {EDGE_SHARE_CAP}), lit pixels {(lit & ~unsure).sum()}, shadowed "
-          f"{((want[..., 0] > 0) & ~lit & ~unsure).sum()}, occluder {(want[..., 0] == 0).sum()}, "
-          f"largest relative error on lit pixels {(err[lit & ~unsure] / want[lit & ~unsure]).max():.3e}, tolerance {2.0 ** -10:.3e}")
+          f"{(floor & ~lit & ~unsure).sum()}, occluder {(~floor).sum()}, "
+          f"largest relative error on floor pixels {(err[floor & ~unsure] / want[floor & ~unsure]).max():.3e}, tolerance {2.0 ** -10:.3e}")
     assert unsure.mean() <= EDGE_SHARE_CAP
-    assert (lit & ~unsure).mean() > 0.5 and ((want[..., 0] > 0) & ~lit & ~unsure).sum() > 50
+    if kind == "backface":
+        # the ambient term alone: f32(rho) * f32(0.1) summed spp times and divided, (spp + 2) roundings - far below 2^-10
+        ambient = 0.1 * LIT_RHO
+        exact = (spp + 2) * U32 * ambient
+        pure = (np.abs(want - ambient) <= 1e-12).all(-1)   # every sample of the pixel is on the floor
+        print(f"  backface: largest |pixel - 0.1 rho| on the {pure.sum()} pixels that are all floor {np.abs(got[pure] - ambient).max(0)}, bound {exact}; "
+              f"shadow segments expected {shadow_segments}")
+        assert shadow_segments == 0 and pure.mean() > 0.85 and not lit.any()
+        assert (np.abs(got[pure] - ambient) <= exact).all() and not got[~floor & ~unsure].any()
+    elif len(_direct_lights(kind)) == 1:
+        assert (lit & ~unsure).mean() > 0.5 and (floor & ~lit & ~unsure).sum() > 50
+    else:   # (the two shadows hardly overlap: what is asserted below is that each light has pixels it lights alone)
+        assert (lit & ~unsure).mean() > 0.5
     assert (err[~unsure] <= tol[~unsure]).all()
-    # the wrong alternatives this rejects, each further from `want` than the tolerance on most of the frame
-    for variant in ("shadow_below",) + (("not_negated",) if case.info["kind"] == "directional" else ()):
-        alt = direct_light_expected(case, np.arange(spp), variant)[0].mean(0)
+    if segments is not None:
+        print(f"  shadow segments {segments['shadow']}, (sample, light) pairs with a contribution in float64 {shadow_segments}")
+        assert segments["shadow"] == shadow_segments
+    if len(_direct_lights(kind)) == 2 and kind != "backface":
+        # the ordered sum: pixels that keep exactly one of their two lights are in the frame, for either light
+        one = [direct_light_eval(case, np.arange(spp), lights=(k,))[0].mean(0) for k in (0, 1)]
+        dark = [(np.abs(one[k] - 0.1 * LIT_RHO) <= 1e-12).all(-1) for k in (0, 1)]   # every sample of the pixel lost light k
+        only = [dark[1 - k] & ~dark[k] & ~unsure & floor for k in (0, 1)]
+        print(f"  pixels lit by the spot light alone {only[0].sum()}, by the second point light alone {only[1].sum()}")
+        assert only[0].sum() > 50 and only[1].sum() > 50
+    # the wrong alternatives this rejects, each further from `want` than the tolerance on the stated share of the frame
+    for variant in DIRECT_VARIANTS[kind]:
+        alt = direct_light_eval(case, np.arange(spp), variant)[0].mean(0)
         share = (np.abs(alt - want) > 2 * tol)[~unsure].all(-1).mean()
-        print(f"  alternative {variant}: differs by more than twice the tolerance on {share:.3f} of the frame")
-        assert share > 0.5
+        least = 0.02 if variant == "one_occluded_removes_both" else 0.5
+        print(f"  alternative {variant}: differs by more than twice the tolerance on {share:.3f} of the frame (at least {least})")
+        assert share > least
+
+
+def check_hero_candidates(label, rgb, values, unsure, alternatives, min_differs=200):
+    """The shared pixel rule of refract_front and tir_back, for an image or a batch of rays (..., 3): `values[..., c]` is what the
+    terminal vertex returns to a path whose hero channel is c, so the path is 3 a_c values_c in channel c alone - one of three
+    candidates, the hero pick deciding which.  Asserts, over the pixels none of whose channels is unsure: at most one channel is
+    non-zero, and the pixel is one of its candidates within HERO_F32_REL_BOUND (a non-zero channel c needs values_c > 0 and names
+    its value; a pixel whose candidates are all non-zero is non-zero; one whose candidates are all 0 is 0).  The share left out is
+    at most EDGE_SHARE_CAP.
+
+    `alternatives` (name -> values of a wrong rule): `differs` counts the classified pixels at which the alternative changes at least
+    one candidate - it follows from the scene alone and must be at least `min_differs` - and `violations` the pixels of THIS image
+    that are none of the alternative's candidates: every pixel of `differs` whose hero channel is a changed one, so about a third
+    of `differs` at the least; asserted above a sixth.  -> dict(left_out, violations per alternative)."""
+    got = np.asarray(rgb, np.float64)
+    sure = ~unsure.any(-1)
+    left_out = 1.0 - sure.mean()
+
+    def matches(vals):
+        cand = 3.0 * GLASS_A * vals
+        ok = np.zeros(got.shape[:-1], bool)
+        for c in range(3):
+            others = [k for k in range(3) if k != c]
+            ok |= (np.abs(got[..., c] - cand[..., c]) <= HERO_F32_REL_BOUND * cand[..., c]) & ~got[..., others].any(-1)
+        return ok
+
+    nonzero = (got != 0).sum(-1)
+    ok = matches(values)
+    lit = (values > 0).sum(-1)
+    print(f"{label}: {sure.sum()} of {sure.size} classified, left out {left_out:.4f} (cap {EDGE_SHARE_CAP}); candidates non-zero in "
+          f"3 / some / 0 channels: {(sure & (lit == 3)).sum()} / {(sure & (lit > 0) & (lit < 3)).sum()} / {(sure & (lit == 0)).sum()}; "
+          f"pixels with more than one channel {(nonzero > 1).sum()}, violations {(sure & ~ok).sum()}")
+    assert left_out <= EDGE_SHARE_CAP
+    assert (nonzero <= 1).all()
+    assert not (sure & ~ok).any()
+    score = {}
+    for name, alt in alternatives.items():
+        differs = int((sure & (np.abs(alt - values) > 1e-3 * np.maximum(values, alt)).any(-1)).sum())
+        wrong = int((sure & ~matches(alt)).sum())
+        print(f"  alternative {name}: changes a candidate at {differs} classified pixels, {wrong} pixels of this image are none of its candidates")
+        assert differs >= min_differs and wrong * 6 >= differs
+        score[name] = wrong
+    return {"left_out": left_out, "violations": score}
+
+
+def check_refract_front(rgb, case, spp, segments=None):
+    """refract_front's closed form on a closed 1-spp frame (pixel centres); all three classes of pixel are in the frame."""
+    assert spp == 1
+    o, d = case.centre_rays()
+    values, unsure, land = refract_front_values(o, d)
+    lit = (values > 0).sum(-1)
+    sure = ~unsure.any(-1)
+    print(f"{case.name}: landing x red {land[..., 0].min():.4f} .. {land[..., 0].max():.4f}, blue {land[..., 2].min():.4f} .. {land[..., 2].max():.4f}, "
+          f"X0 {REFRACT_X0}; mean separation red-green {np.mean(land[..., 0] - land[..., 1]):.5f}, green-blue {np.mean(land[..., 1] - land[..., 2]):.5f}")
+    assert min((sure & (lit == 3)).sum(), (sure & (lit == 0)).sum(), (sure & (lit > 0) & (lit < 3)).sum()) >= 500
+    if segments is not None:
+        assert segments["continuation"] == segments["camera"] == case.w * case.h and segments["shadow"] == 0
+    return check_hero_candidates(case.name, rgb, values, unsure, {v: refract_front_values(o, d, v)[0] for v in REFRACT_VARIANTS})
+
+
+def check_hero_uniform(images, case):
+    """Frames of refract_front whose seeds are at least w * h apart (disjoint streams): over the pixels whose three channels all
+    land on the emitter, the hero counts are uniform - chi-square with 2 degrees of freedom below chi2_critical(2) (p = 1e-6)."""
+    o, d = case.centre_rays()
+    values, unsure, _ = refract_front_values(o, d)
+    full = (values > 0).all(-1) & ~unsure.any(-1)
+    counts = np.zeros(3)
+    for rgb in images:
+        nz = np.asarray(rgb)[full] != 0
+        assert (nz.sum(-1) == 1).all()
+        counts += nz.sum(0)
+    e = counts.sum() / 3.0
+    chi2 = float(((counts - e) ** 2 / e).sum())
+    print(f"{case.name}: hero counts {counts.astype(int)} over {len(images)} frames x {full.sum()} fully lit pixels, chi2 {chi2:.2f} "
+          f"(critical {chi2_critical(2):.2f})")
+    assert counts.sum() >= 10000 and chi2 < chi2_critical(2)
+
+
+def check_tir_back(rgb, case, spp, segments=None):
+    """tir_back's closed form on a closed 1-spp frame; every channel has both branches in the frame."""
+    assert spp == 1
+    _, d = case.centre_rays()
+    values, unsure, x = tir_back_values(d)
+    share = (x > 1.0).reshape(-1, 3).mean(0)
+    theta = np.degrees(np.arccos(d[..., 1]))
+    print(f"{case.name}: incidence {theta.min():.2f} .. {theta.max():.2f} degrees, critical angles {np.degrees(np.arcsin(1.0 / IOR_C))}, "
+          f"total-reflection share per channel {share}, pixels inside the margin {unsure.any(-1).sum()}")
+    assert (share > 0.1).all() and (share < 0.9).all()
+    assert ((np.asarray(rgb) != 0).sum(-1) == 1).all()   # the sky and Ef are positive in every channel: exactly one, the hero
+    if segments is not None:
+        assert segments["continuation"] == segments["camera"] == case.w * case.h and segments["shadow"] == 0
+    return check_hero_candidates(case.name, rgb, values, unsure, {v: tir_back_values(d, v)[0] for v in TIR_VARIANTS})
+
+
+_ROUGH_CACHE = {}
+
+
+def rough_metal_moments(case, spp, chunk=64):
+    """-> (mean continuing share of the frame's samples, the same with the cap of roughness 1, per-pixel smallest c) for samples
+    0 .. spp - 1, c = -d . Nf from each sample's own jittered ray."""
+    key = (case.name, case.w, case.h, spp, case.frame_seed)
+    if key not in _ROUGH_CACHE:
+        rho = case.info["roughness"]
+        keep = keep1 = 0.0
+        c_min = np.full((case.h, case.w), np.inf)
+        for s0 in range(0, spp, chunk):
+            _, d = case.rays(np.arange(s0, min(s0 + chunk, spp)))
+            c = -d[..., 1]      # the camera is above the floor in both layouts: Nf = +y
+            keep += (1.0 - rough_cap(c, rho)).sum()
+            keep1 += (1.0 - rough_cap(c, 1.0)).sum()
+            c_min = np.minimum(c_min, c.min(0))
+        n = case.w * case.h * spp
+        _ROUGH_CACHE[key] = (keep / n, keep1 / n, c_min)
+    return _ROUGH_CACHE[key]
+
+
+def check_rough_metal(rgb, case, spp, segments=None):
+    """The image mean a sky (1 - cap) within Hoeffding's band (samples in [0, a sky]) plus the f32 slack, the named alternatives at
+    least two bands away; and, where the f32 sum still tells k from k + 1 (spp <= 1024): every pixel a sky k / spp for one integer k,
+    k = spp where the cap is empty for all the pixel's samples, and sum k = the frame's continuation segments."""
+    rho, n = case.info["roughness"], case.w * case.h * spp
+    full = MIRROR_A * SKY
+    keep, keep_rho1, c_min = rough_metal_moments(case, spp)
+    eps = hoeffding_eps(full, n) + f32_mean_slack(full, spp)
+    alternatives = {"nothing absorbed": full}
+    if rho < 1.0:
+        alternatives["roughness ignored (the cap of roughness 1)"] = full * keep_rho1
+    if case.info["layout"] == "backface":
+        alternatives["normal not face-forwarded"] = full * (1.0 - keep)
+    print(f"{case.name}: expected continuing share {keep:.4f}" + (f", measured {segments['continuation'] / n:.4f}" if segments else "")
+          + f"; c from {c_min.min():.3f}; pixels with an empty cap {(c_min > rho + ROUGH_EMPTY_CAP_MARGIN).sum()}")
+    _assert_mean(case.name, rgb, full * keep, eps, alternatives)
+    if spp > 1024:
+        return
+    got = np.asarray(rgb, np.float64)
+    k = np.rint(got[..., 0] * spp / full[0])
+    err = np.abs(got - (k / spp)[..., None] * full)
+    tol = mirror_f32_rel_bound(spp) * full
+    empty = c_min > rho + ROUGH_EMPTY_CAP_MARGIN
+    print(f"  largest |pixel - a sky k / spp| {err.max((0, 1))}, tolerance {tol}; sum k {int(k.sum())}; k from {int(k.min())} to {int(k.max())}")
+    assert (err <= tol).all()
+    assert (k[empty] == spp).all()
+    if rho >= 1.0:
+        assert not empty.any()
+    else:
+        assert empty.mean() > 0.2 and (~empty).mean() > 0.2
+    if segments is not None:
+        assert segments["camera"] == n and segments["shadow"] == 0
+        assert int(k.sum()) == segments["continuation"]

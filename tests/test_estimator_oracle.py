@@ -94,13 +94,54 @@ def test_rough_mirror_absorbs_nothing_at_roughness_below_one(oracle_mod):
 
 
 DIRECT_SPP = 4
+DIRECT_KINDS = ("point", "directional") + ec.TWO_LIGHT_KINDS
 
 
-@pytest.mark.parametrize("kind", ["point", "directional"])
+@pytest.mark.parametrize("kind", DIRECT_KINDS)
 def test_direct_light_and_hard_shadow(oracle_mod, kind):
-    """Step 2 restated in float64 (f16 attenuation included): 2^-10 relative on every classified pixel, at most 2 % left out."""
+    """Step 2 restated in float64 (f16 attenuation included): 2^-10 relative on every classified pixel, at most 2 % left out; one
+    shadow segment per (sample, light) pair with a contribution.  Two lights: the spot factor, the metallic BRDF, the ordered sum
+    where the occluder hides one light and not the other, and a floor that faces away from both (the ambient term, no segment)."""
     case = ec.direct_light(kind)
-    ec.check_direct_light(_render(oracle_mod, case, DIRECT_SPP)["rgb"], case, DIRECT_SPP)
+    out = _render(oracle_mod, case, DIRECT_SPP)
+    ec.check_direct_light(out["rgb"], case, DIRECT_SPP, out["segments"])
+
+
+HERO_FRAMES = 4
+
+
+def test_refraction_through_the_front_face(oracle_mod):
+    """Snell's direction with eta = 1 / ior_c and the three channels' own indices, from P - N 1e-3: each pixel of a closed 1-spp
+    frame is 3 a_c Ef_c or 0 by where ITS channel's segment lands; the hero pick is uniform over frames with disjoint streams."""
+    case = ec.refract_front()
+    out = _render(oracle_mod, case, 1)
+    ec.check_refract_front(out["rgb"], case, 1, out["segments"])
+    images = [out["rgb"]]
+    for k in range(1, HERO_FRAMES):
+        case.frame_seed = k * case.w * case.h
+        images.append(_render(oracle_mod, case, 1)["rgb"])
+        ec.check_refract_front(images[-1], case, 1)
+    ec.check_hero_uniform(images, case)
+
+
+def test_total_reflection_at_the_back_face(oracle_mod):
+    """eta = ior_c from behind: each channel refracts to the sky below its own critical angle and reflects to the floor above it."""
+    case = ec.tir_back()
+    out = _render(oracle_mod, case, 1)
+    ec.check_tir_back(out["rgb"], case, 1, out["segments"])
+
+
+ROUGH_SPP = 64
+ROUGH_CASES = [(1.0, "front"), (0.5, "front"), (1.0, "backface"), (0.5, "backface")]
+
+
+@pytest.mark.parametrize("roughness,layout", ROUGH_CASES)
+def test_rough_metal_absorbs_its_cap(oracle_mod, roughness, layout):
+    """a sky (1 - max(0, (1 - c / roughness) / 2)) as an image mean, a sky k / spp pixel by pixel with sum k = the continuation
+    segments, k = spp where the cap is empty."""
+    case = ec.rough_metal(roughness, layout)
+    out = _render(oracle_mod, case, ROUGH_SPP)
+    ec.check_rough_metal(out["rgb"], case, ROUGH_SPP, out["segments"])
 
 
 # ---- the sampler ---------------------------------------------------------------------------------------------------------

@@ -3,7 +3,8 @@
 Against the frames: over the pixel-centre camera rays of a frame, with the frame's seed, the radiance is that pixel of the closed
 extended-mode frame with one sample, bit for bit, for every bounce limit, with and without shadows, and the segments add up to the
 frame's; composed per sample over rt_sample_rays it is the frame of several samples.  Against the queries: with no bounce it is
-rt_direct_light at rt_surface's hit.  Against the closed form of the furnace (estimator_cases.py).  Against itself: the tree, the
+rt_direct_light at rt_surface's hit.  Against the closed forms of estimator_cases.py: the furnace, and rays aimed at the three
+channels' critical angles, at the landing points of their refracted segments and at fixed incidences on the rough metal.  Against itself: the tree, the
 device count, the kind of memory and the chunking change no byte."""
 import ctypes as C
 import dataclasses
@@ -213,6 +214,100 @@ def test_furnace_closed_form_from_interior_rays(gpu_ctx, bounces):
     print(f"furnace B={bounces}: largest relative error {np.sort(rel)[-1 - off]:.3e} outside {off} rays, bound {bound:.3e}, allowed off {allowed}")
     assert off <= allowed
     assert int((segments != bounces + 1).sum()) <= off, "no lights: a path that does not escape has exactly B + 1 segments"
+
+
+# 4b. step 4's geometry on aimed rays ----------------------------------------------------------------------------------------------
+def _cone_rays(origin, cos_theta, phi):
+    """f32 rays from `origin` whose y component is cos_theta (negative: downward) at azimuth phi about the y axis."""
+    cos_theta, phi = np.broadcast_arrays(np.asarray(cos_theta, np.float64), np.asarray(phi, np.float64))
+    s = np.sqrt(1.0 - cos_theta ** 2)
+    d = np.stack([s * np.cos(phi), cos_theta, s * np.sin(phi)], -1)
+    return api.make_rays(np.broadcast_to(np.asarray(origin, F32), d.shape), d.astype(F32))
+
+
+def test_total_reflection_at_aimed_incidences(gpu_ctx):
+    """The tir_back scene from below, samples = 1, max_bounces = 1: for each channel c, 4096 rays whose incidence puts
+    x_c = ior_c^2 sin^2(theta) evenly across 1 +- 2e-3 - which no frame's pixel grid can aim at.  x_c is taken in float64 from the
+    f32 direction that is passed; outside |x_c - 1| < 1e-5 (0.5 % of the rays aimed at that channel) the value names the hero channel
+    and the branch (estimator_cases.check_hero_candidates), and every path has its two segments."""
+    case = ec.tir_back()
+    gpu_ctx.upload_scene(case.scene)
+    n = 4096
+    rng = np.random.default_rng(17)
+    delta = (np.arange(n) + 0.5) / n * 4e-3 - 2e-3
+    rays = np.concatenate([_cone_rays((0.0, 0.5, 0.0), np.sqrt(1.0 - (1.0 + delta) / ec.IOR_C[c] ** 2), rng.uniform(0, 2 * np.pi, n)) for c in range(3)])
+    d = rays[:, 4:7].astype(np.float64)
+    values, unsure, x = ec.tir_back_values(d)
+    for c in range(3):
+        aimed = x[c * n:(c + 1) * n, c] - 1.0
+        assert abs(aimed.min() + 2e-3) < 1e-5 and abs(aimed.max() - 2e-3) < 1e-5 and 0.4 < (aimed > 0).mean() < 0.6
+    got, segments = api.split_radiance(gpu_ctx.radiance(np.ascontiguousarray(rays), samples=1, max_bounces=1, seed=SEED))
+    res = ec.check_hero_candidates("tir_back, aimed rays", got, values, unsure, {v: ec.tir_back_values(d, v)[0] for v in ec.TIR_VARIANTS})
+    assert res["left_out"] <= 0.006
+    assert np.all(segments == 2)
+    heroes = (got != 0).sum(0)
+    print(f"hero counts {heroes}")
+    assert heroes.min() > 3000   # every channel is some paths' hero: all three critical angles are exercised
+
+
+def test_refraction_at_aimed_landing_points(gpu_ctx):
+    """The refract_front scene from above at 20, 55 and 75 degrees of incidence: for each incidence and channel c, 1024 rays whose
+    channel-c segment lands evenly across X0 +- 2e-2; classified from the f32 rays that are passed, outside 1e-4 of X0."""
+    case = ec.refract_front()
+    gpu_ctx.upload_scene(case.scene)
+    n = 1024
+    rng = np.random.default_rng(18)
+    u = (np.arange(n) + 0.5) / n * 4e-2 - 2e-2
+    batches = []
+    for theta in (20.0, 55.0, 75.0):
+        th = np.radians(theta)
+        d = np.array([np.sin(th), -np.cos(th), 0.0])
+        for c in range(3):
+            t, _, _ = ec.snell(d, np.array([0.0, 1.0, 0.0]), 1.0 / ec.IOR_C[c])
+            glass_x = ec.REFRACT_X0 + u - (ec.GLASS_Y - ec.ORIGIN_EPS) * t[0] / -t[1]
+            o = np.stack([glass_x - np.tan(th), np.full(n, ec.GLASS_Y + 1.0), rng.uniform(-0.05, 0.05, n)], -1)
+            batches.append(api.make_rays(o.astype(F32), np.broadcast_to(d.astype(F32), o.shape)))
+    rays = np.ascontiguousarray(np.concatenate(batches))
+    o, d = rays[:, 0:3].astype(np.float64), rays[:, 4:7].astype(np.float64)
+    values, unsure, land = ec.refract_front_values(o, d)
+    for k in range(9):
+        aimed = land[k * n:(k + 1) * n, k % 3] - ec.REFRACT_X0
+        assert abs(aimed.min() + 2e-2) < 1e-4 and abs(aimed.max() - 2e-2) < 1e-4
+    got, segments = api.split_radiance(gpu_ctx.radiance(rays, samples=1, max_bounces=1, seed=SEED))
+    ec.check_hero_candidates("refract_front, aimed rays", got, values, unsure, {v: ec.refract_front_values(o, d, v)[0] for v in ec.REFRACT_VARIANTS})
+    assert np.all(segments == 2)
+
+
+@pytest.mark.parametrize("roughness,layout", [(1.0, "front"), (0.5, "backface")])
+def test_rough_lobe_cap_at_fixed_incidences(gpu_ctx, roughness, layout):
+    """The rough_metal scene: 256 rays at each of c = r . Nf = 0.1, 0.3, 0.5, 0.7, 0.9, 256 samples each.  Every ray is a sky k / 256
+    with k the samples that were not absorbed, it traced 256 + k segments, and the mean of k / 256 over an incidence's 65,536 samples
+    is 1 - max(0, (1 - c / roughness) / 2) within Hoeffding's band (0.0128 at p = 1e-9); where the cap is empty k = 256."""
+    case = ec.rough_metal(roughness, layout)
+    gpu_ctx.upload_scene(case.scene)
+    n, samples = 256, 256
+    rng = np.random.default_rng(19)
+    cs = (0.1, 0.3, 0.5, 0.7, 0.9)
+    rays = np.ascontiguousarray(np.concatenate([_cone_rays((0.5, 2.0, 0.0), np.full(n, -c), rng.uniform(-0.3, 0.3, n)) for c in cs]))
+    got, segments = api.split_radiance(gpu_ctx.radiance(rays, samples=samples, max_bounces=1, seed=SEED))
+    full = ec.MIRROR_A * ec.SKY
+    k = np.rint(got[:, 0].astype(np.float64) * samples / full[0])
+    err = np.abs(got.astype(np.float64) - (k / samples)[:, None] * full)
+    tol = ec.mirror_f32_rel_bound(samples) * full
+    print(f"largest |value - a sky k / {samples}| {err.max(0)}, tolerance {tol}")
+    assert (err <= tol).all()
+    np.testing.assert_array_equal(segments.astype(np.int64), samples + k.astype(np.int64))
+    band = float(ec.hoeffding_eps(1.0, n * samples))
+    for i, c in enumerate(cs):
+        c32 = -rays[i * n:(i + 1) * n, 5].astype(np.float64)
+        want = float((1.0 - ec.rough_cap(c32, roughness)).mean())
+        share = k[i * n:(i + 1) * n].mean() / samples
+        print(f"c = {c}: continuing share {share:.4f}, expected {want:.4f}, band {band:.4f}, nothing absorbed 1.0")
+        assert abs(share - want) <= band
+        if c < roughness - 0.05:
+            assert 1.0 - want >= 2 * band   # the band rejects 'nothing absorbed'
+        if c > roughness + 0.05:
+            assert np.all(k[i * n:(i + 1) * n] == samples)
 
 
 # 5. independence ----------------------------------------------------------------------------------------------------------------
