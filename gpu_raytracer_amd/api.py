@@ -58,7 +58,7 @@ ABI_SYMBOLS = [
     "rt_read_rgb32f", "rt_read_rgba8_channels", "rt_read_rgba8_combined", "rt_read_hits",
     "rt_get_stats", "rt_last_error", "rt_destroy", "rt_version",
     "rt_intersect", "rt_occluded", "rt_camera_rays", "rt_intersect_all",
-    "rt_surface", "rt_ambient_occlusion", "rt_direct_light", "rt_radiance", "rt_radiance_sh", "rt_closest_point", "rt_sweep_sphere",
+    "rt_surface", "rt_ambient_occlusion", "rt_direct_light", "rt_radiance", "rt_radiance_sh", "rt_irradiance", "rt_closest_point", "rt_sweep_sphere",
     "rt_update_geometry",
     "rt_accumulated_samples",
     "rt_aovs", "rt_sample_rays", "rt_denoise",
@@ -205,7 +205,7 @@ def _counts_like(counts, batch, batch_name, n):
 
 
 def _path_params(samples, max_bounces, seed, first_sample, flags):
-    """The rt_path_params record (types.PATH_PARAMS) of radiance / radiance_sh from their four integers, checked."""
+    """The rt_path_params record (types.PATH_PARAMS) of radiance / radiance_sh / irradiance from their four integers, checked."""
     for name, v, lo, hi in (("samples", samples, 1, PATH_MAX_SAMPLES), ("max_bounces", max_bounces, 0, MAX_BOUNCES), ("seed", seed, 0, 0xFFFFFFFF),
                             ("first_sample", first_sample, 0, 0xFFFFFFFF)):
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
@@ -339,6 +339,12 @@ def split_sh(results):
     else:
         segments = np.ascontiguousarray(results[:, 27]).view(np.uint32)
     return results[:, 0:27].reshape(-1, 9, 3), segments
+
+
+def split_irradiance(results):
+    """(N, 4) irradiance records (rt_irradiance_result) -> (irradiance (N, 3), segments (N,)).  segments is the records' uint32 word:
+    uint32 for numpy, int64 for torch; the segments traced for the point over all its samples."""
+    return split_radiance(results)
 
 
 _SH9_COSINE = (np.pi, 2.0 * np.pi / 3.0, 2.0 * np.pi / 3.0, 2.0 * np.pi / 3.0, np.pi / 4.0, np.pi / 4.0, np.pi / 4.0, np.pi / 4.0, np.pi / 4.0)
@@ -745,6 +751,21 @@ class Context:
         out = _out_like(out, probes, "probes", n, 28)
         _sync_torch(probes, out)
         self._check(self.lib.rt_radiance_sh(self._h, _addr(probes), C.c_size_t(n), _p(pp), _addr(out)))
+        return out
+
+    def irradiance(self, points, samples, max_bounces=4, seed=0, first_sample=0, shadows=True, out=None, counters=False):
+        """rt_irradiance: the cosine-weighted irradiance at each record of an (N, 8) batch of surface points (surface()), from `samples`
+        (1 .. PATH_MAX_SAMPLES) paths along directions of the cosine lobe around the record's normal -> (N, 4) float32
+        rt_irradiance_result records (split_irradiance: irradiance, segments), same kind and device as `points`.  The normal is used as
+        given: surface()'s face-forwarded one gathers on the side the ray arrived on; a miss record is no point and gives zeros.  Sample
+        k of point i draws its direction and its path from rng_for(seed + i, first_sample + k): it is radiance() along that direction
+        from position + normal * 1e-3 with camera_draws=True, summed in sample order and scaled by pi / samples.  max_bounces and
+        shadows as radiance()."""
+        n = _check_batch(points, "points", 8, "float32")
+        pp = _path_params(samples, max_bounces, seed, first_sample, (0 if shadows else PATH_NO_SHADOWS) | (QUERY_COUNTERS if counters else 0))
+        out = _out_like(out, points, "points", n, 4)
+        _sync_torch(points, out)
+        self._check(self.lib.rt_irradiance(self._h, _addr(points), C.c_size_t(n), _p(pp), _addr(out)))
         return out
 
     def closest_point(self, points, out=None, counters=False):

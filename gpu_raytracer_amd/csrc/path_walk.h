@@ -3,10 +3,10 @@
 // frames trace it.  Every vertex is ext_light_sum with its shadow segments traced on the spot by occluded<> (ext_direct's lambda), then
 // ext_leave_vertex and ext_scatter (device_common.h).  `rng` is the path's generator after whatever was drawn before the path; `stack`
 // the lane's own stack in LDS.
-// k_ps_trace (probe_query.hip, rt_radiance_sh) calls it.  k_pq_trace (path_query.hip, rt_radiance) holds the same statements in its own
-// body: called from there, the same optimised IR but for the order of its phis came out of the register allocator with 114 VGPRs
-// where the kernel has 101 ("Probe queries"), so it is left as it was.  rt_radiance_sh's tests hold the two to
-// the same bits.
+// k_ps_trace (probe_query.hip, rt_radiance_sh) and k_ir_trace (irradiance_query.hip, rt_irradiance) call it.  k_pq_trace
+// (path_query.hip, rt_radiance) holds the same statements in its own body: called from there, the same optimised IR but for the order
+// of its phis came out of the register allocator with 114 VGPRs where the kernel has 101 ("Probe queries"), so it
+// is left as it was.  rt_radiance_sh's and rt_irradiance's tests hold the two to the same bits.
 #ifndef RT_PATH_WALK_H
 #define RT_PATH_WALK_H
 

@@ -26,6 +26,7 @@
 #include "device_layout.h"
 #include "direct_light.h"
 #include "half.h"
+#include "irradiance_query.h"
 #include "kernels.h"
 #include "path_query.h"
 #include "probe_query.h"
@@ -142,7 +143,7 @@ struct DeviceState {
     struct Query { // ray, surface, direct-light and path queries: staging of host batches (rays or points in, records / bytes out, rt_intersect_all's counts), grown on demand
         DevMem in, out, counts;
         DevBuf<uint32_t> ao; // rt_ambient_occlusion: the per-point counts its kernel adds to, for host and device batches alike
-        DevBuf<uint4> paths; // rt_radiance with several samples, rt_radiance_sh: one record per path of a chunk (at most RT_QUERY_CHUNK), which its reduction / projection adds up
+        DevBuf<uint4> paths; // rt_radiance with several samples, rt_radiance_sh, rt_irradiance: one record per path of a chunk (at most RT_QUERY_CHUNK), which its reduction / projection adds up
     } rq;
     // RT_FLAG_ACCUMULATE: the running sum of the context's accumulation over this device's pixels (DevTargets::run_sum), frame-pixel
     // layout, w x h x 16 bytes.  Outlives the pipeline's WfBuffers (re-sized with the batch); made by the first accumulating call.

@@ -1,7 +1,7 @@
 // rt_query.cpp — calls that trace or filter outside a frame: ray queries (rt_hip.h "Ray queries": rt_intersect, rt_occluded,
 // rt_intersect_all, rt_camera_rays), surface queries ("Surface queries": rt_surface, rt_ambient_occlusion; kernels in
 // surface_query.hip), the direct-light query ("Direct-light queries": rt_direct_light; kernel in direct_light.hip), the path query ("Path queries":
-// rt_radiance; kernels in path_query.hip), the probe query ("Probe queries": rt_radiance_sh; kernels in probe_query.hip), the closest-point query ("Closest-point queries": rt_closest_point; kernel in closest_point.hip), the sphere sweep ("Sphere sweeps": rt_sweep_sphere; kernel in sweep.hip) and the image passes ("Feature buffers (AOVs) and denoising": rt_aovs, rt_sample_rays, rt_denoise; kernels in
+// rt_radiance; kernels in path_query.hip), the probe query ("Probe queries": rt_radiance_sh; kernels in probe_query.hip), the irradiance query ("Irradiance queries": rt_irradiance; kernels in irradiance_query.hip), the closest-point query ("Closest-point queries": rt_closest_point; kernel in closest_point.hip), the sphere sweep ("Sphere sweeps": rt_sweep_sphere; kernel in sweep.hip) and the image passes ("Feature buffers (AOVs) and denoising": rt_aovs, rt_sample_rays, rt_denoise; kernels in
 // denoise.hip).  None of them touches the frame targets, the tile shares rt_read_* gather, or the running image of an accumulation.
 #include "rt_internal.h"
 #include "query_plan.h"
@@ -46,7 +46,7 @@ void drain_streams(rt_ctx* ctx) { // after a failure: nothing of the call is lef
 }
 
 // ---- batch calls: an array of records in, one or two arrays of records out ------------------------------------------------------
-// run_batch is the procedure all ten share; an entry function states its own checks, describes its arrays in a Batch, supplies the
+// run_batch is the procedure all eleven share; an entry function states its own checks, describes its arrays in a Batch, supplies the
 // launches of one chunk and turns the Totals into rt_stats.
 
 enum Stage { ST_OUT, ST_COUNTS, ST_AO, ST_PATHS }; // a buffer of DeviceState::rq
@@ -229,13 +229,14 @@ hipError_t launch_any_hit(const DevScene& sc, const void* rays, void* out, uint3
     return rt::launch_ray_query(sc, rays, out, n, true, cnt, s);
 }
 
-// rt_radiance (rays) and rt_radiance_sh (probes: a direction is drawn per path and a projection always runs): samples paths per record
-// and a scratch of one record per path.  Host and device batches alike go in chunks of max(1, RT_QUERY_CHUNK / samples) records, so a
-// launch covers at most RT_QUERY_CHUNK paths and the scratch never grows past that; the chunk's first index goes to the kernel, so a
-// record's seed is that of its place in the caller's array.  The segments are counted on the device (rt_stats.rays), so every call
-// zeroes and reads the device's counters.
+// rt_radiance (rays), rt_radiance_sh (probes) and rt_irradiance (surface points): samples paths per record and a scratch of one record
+// per path.  `own_directions`: the call draws a direction per path itself - the two draws RT_PATH_CAMERA_DRAWS names, so the flag is
+// refused - and its reduction always runs, so the scratch is there with one sample too (rt_radiance_sh, rt_irradiance).  Host and
+// device batches alike go in chunks of max(1, RT_QUERY_CHUNK / samples) records, so a launch covers at most RT_QUERY_CHUNK paths and
+// the scratch never grows past that; the chunk's first index goes to the kernel, so a record's seed is that of its place in the
+// caller's array.  The segments are counted on the device (rt_stats.rays), so every call zeroes and reads the device's counters.
 using PathLaunch = hipError_t (*)(const DevScene&, const rt::PathArgs&, const void*, uint64_t, uint32_t, void*, void*, bool, unsigned long long*, hipStream_t);
-int path_query(rt_ctx* ctx, const char* fn, BatchIn in, size_t n, const rt_path_params* p, void* out, size_t out_size, bool probes, PathLaunch launch) {
+int path_query(rt_ctx* ctx, const char* fn, BatchIn in, size_t n, const rt_path_params* p, void* out, size_t out_size, bool own_directions, PathLaunch launch) {
     const double w0 = now_ms();
     if (!ctx) return RT_ERR_BAD_ARG;
     if (n == 0) return RT_OK;
@@ -244,18 +245,18 @@ int path_query(rt_ctx* ctx, const char* fn, BatchIn in, size_t n, const rt_path_
     if (p->max_bounces > RT_MAX_BOUNCES) return ctx->fail(RT_ERR_BAD_ARG, "%s: max_bounces %u (0 .. %u)", fn, p->max_bounces, RT_MAX_BOUNCES);
     if ((uint64_t)p->first_sample + p->samples > (1ull << 32))
         return ctx->fail(RT_ERR_BAD_ARG, "%s: first_sample %u + samples %u passes 2^32", fn, p->first_sample, p->samples);
-    if (probes && (p->flags & RT_PATH_CAMERA_DRAWS))
+    if (own_directions && (p->flags & RT_PATH_CAMERA_DRAWS))
         return ctx->fail(RT_ERR_BAD_ARG, "%s: flags: RT_PATH_CAMERA_DRAWS (the call spends those two draws itself)", fn);
     const uint32_t known = RT_QUERY_COUNTERS | RT_PATH_NO_SHADOWS | RT_PATH_CAMERA_DRAWS;
     if (p->flags & ~known) return ctx->fail(RT_ERR_BAD_ARG, "%s: unknown flag bits 0x%x", fn, p->flags & ~known);
     if (!ctx->uploaded) return ctx->fail(RT_ERR_NOT_UPLOADED, "%s: no scene uploaded", fn);
     const rt::PathArgs args{p->samples, p->max_bounces, p->seed, p->first_sample, (p->flags & RT_PATH_NO_SHADOWS) ? 0u : 1u,
-                            (probes || (p->flags & RT_PATH_CAMERA_DRAWS)) ? 1u : 0u};
+                            (own_directions || (p->flags & RT_PATH_CAMERA_DRAWS)) ? 1u : 0u};
     const bool counters = (p->flags & RT_QUERY_COUNTERS) != 0;
     const size_t chunk = std::max<size_t>(1, RT_QUERY_CHUNK / p->samples);
     Batch b{fn, n, in, {{"out", out, out_size}, {}}, chunk, chunk, RT_CNT_DIAG};
     b.device_one_pair = true;
-    if (probes || args.samples > 1) b.scratch_size = args.samples * sizeof(uint4); // with one sample the record is the ray's result
+    if (own_directions || args.samples > 1) b.scratch_size = args.samples * sizeof(uint4); // with one sample the record is the ray's result
     Totals t;
     if (int rc = run_batch(ctx, b, t, [&](DeviceState& d, const DevScene& sc, const Chunk& ck) {
             return launch(sc, args, ck.in, ck.off, ck.m, d.rq.paths.get(), ck.out[0], counters, d.counters.get(), d.stream);
@@ -598,6 +599,11 @@ int rt_radiance(rt_ctx* ctx, const rt_ray* rays, size_t n, const rt_path_params*
 
 int rt_radiance_sh(rt_ctx* ctx, const rt_probe* probes, size_t n, const rt_path_params* params, rt_sh9* out) {
     return path_query(ctx, "rt_radiance_sh", {"probes", probes, sizeof(rt_probe)}, n, params, out, sizeof(rt_sh9), true, rt::launch_probe_query);
+}
+
+int rt_irradiance(rt_ctx* ctx, const rt_surface_point* points, size_t n, const rt_path_params* params, rt_irradiance_result* out) {
+    return path_query(ctx, "rt_irradiance", {"points", points, sizeof(rt_surface_point)}, n, params, out, sizeof(rt_irradiance_result), true,
+                      rt::launch_irradiance_query);
 }
 
 int rt_camera_rays(rt_ctx* ctx, const rt_camera* camera, uint32_t width, uint32_t height, uint32_t mode, rt_ray* out) {

@@ -84,6 +84,7 @@ PATH_PARAMS = np.dtype([("samples", u32), ("max_bounces", u32), ("seed", u32), (
 PATH_RESULT = np.dtype([("radiance", f32, 3), ("segments", u32)])  # rt_path_result
 PROBE = np.dtype([("position", f32, 3), ("_pad", u32)])  # rt_probe
 SH9 = np.dtype([("sh", f32, (9, 3)), ("segments", u32)])  # rt_sh9
+IRRADIANCE = np.dtype([("irradiance", f32, 3), ("segments", u32)])  # rt_irradiance_result
 POINT_QUERY = np.dtype([("position", f32, 3), ("radius", f32)])  # rt_point_query
 NEAREST = np.dtype([("position", f32, 3), ("distance", f32), ("u", f32), ("v", f32), ("prim_id", u32), ("material_id", u32)])  # rt_nearest
 SWEEP = np.dtype([("origin", f32, 3), ("radius", f32), ("direction", f32, 3), ("tmax", f32)])  # rt_sweep
@@ -107,7 +108,7 @@ EXPECTED_SIZES = {
     "TRIANGLE": 16, "AABB": 32, "BVH_NODE": 48, "WAVEFRONT_RAY": 76, "WAVEFRONT_COUNTERS": 60,
     "SCENE_METADATA_OFFSETS": 40, "PUSH_CONSTANTS": 128, "AOV": 32, "DENOISE_PARAMS": 32,
     "ADAPTIVE_PARAMS": 16, "ADAPTIVE_PIXEL": 32, "SURFACE_POINT": 32, "AO_PARAMS": 32, "LIGHTING": 16, "DIRECT_LIGHT_PARAMS": 16,
-    "PATH_PARAMS": 32, "PATH_RESULT": 16, "PROBE": 16, "SH9": 112, "POINT_QUERY": 16, "NEAREST": 32,
+    "PATH_PARAMS": 32, "PATH_RESULT": 16, "PROBE": 16, "SH9": 112, "IRRADIANCE": 16, "POINT_QUERY": 16, "NEAREST": 32,
     "SWEEP": 32, "SWEEP_HIT": 32,
 }
 for _name, _size in EXPECTED_SIZES.items():

@@ -224,7 +224,7 @@ int rt_get_stats(rt_ctx* ctx, rt_stats* out);
  * a new one at sample 0 by itself, as RT_FLAG_ACCUMULATE_RESTART does.  The other RT_FLAG_* bits change no bits and may differ.
  * The running image ends (the next accumulating call starts at 0) with rt_upload_scene*, rt_update_geometry, rt_dispatch_tile, any
  * rt_render without RT_FLAG_ACCUMULATE and an accumulating call that fails once it has passed its argument checks.  It survives rt_prepare,
- * rt_upload_textures, the ray queries, the surface queries, rt_direct_light, rt_radiance, rt_radiance_sh, rt_closest_point, rt_sweep_sphere, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
+ * rt_upload_textures, the ray queries, the surface queries, rt_direct_light, rt_radiance, rt_radiance_sh, rt_irradiance, rt_closest_point, rt_sweep_sphere, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
  * Limit: RT_ACCUMULATE_MAX_SAMPLES samples (where the float sample count stops being exact); a call that would pass it is RT_ERR_BAD_ARG
  * and leaves the running image as it was.  rt_stats describes the call alone (its segments, pixels, kernel_ms).
  * A context over several devices, and a tile_rank / tile_world share, accumulates its own share of the pixels.
@@ -642,6 +642,58 @@ RT_STATIC_ASSERT(sizeof(rt_sh9) == 112 && offsetof(rt_sh9, sh) == 0 && offsetof(
 
 /* L2 spherical-harmonic radiance probes at each of the n points: params->samples paths each. */
 int rt_radiance_sh(rt_ctx* ctx, const rt_probe* probes, size_t n, const rt_path_params* params, rt_sh9* out);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Irradiance queries: the cosine-weighted hemispherical gather at surface points the caller supplies, E = integral of L(w) cos(theta)
+ * over the hemisphere of the point's normal - what a lightmap texel's or an irradiance-cache record's diffuse response multiplies (no
+ * reference counterpart).  It is rt_radiance over directions the device draws itself from the frames' cosine lobe, summed in sample
+ * order: the frames' diffuse continuation from that point.  Every bit is fixed by rt_radiance and one f32 statement.
+ *
+ * rt_irradiance: for point i (its index in the caller's array), position P and normal N as given - N is not renormalised and not
+ * flipped; prim_id and material_id are ignored - and sample k < samples:
+ *   1. rng = rng_for(seed + i (mod 2^32), first_sample + k), the frames' generator; u1 = next_f32(), u2 = next_f32().
+ *   2. the frames' cosine lobe as their diffuse continuation writes it, with dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z and every
+ *      operation one f32 rounding, nothing fused:
+ *        w = N + unit_vector(u1, u2);  if (dot(w, w) < 1e-12f) w = N;  d_k = w * (1.0f / sqrtf(dot(w, w)));
+ *        o = P + N * 0.001f  (per component: the continuation's origin offset).
+ *   3. x_k = the radiance rt_radiance gives for the ray {origin = o, tmin = RT_MIN_RAY_DISTANCE, direction = d_k, tmax = FLT_MAX}
+ *      with samples = 1, first_sample = first_sample + k, the same seed and ray index i, the same max_bounces and RT_PATH_NO_SHADOWS,
+ *      and RT_PATH_CAMERA_DRAWS: the path goes on from the generator's third draw.  g_k = that ray's segments.  A ray that is
+ *      degenerate by rt_radiance's own rule (a non-finite component of o or d_k, d_k = 0: only a very large N gives one) contributes
+ *      x_k = 0, g_k = 0.
+ *   4. out[i].irradiance[c] = (0 + x_0[c] + x_1[c] + ...) * (3.1415927f / (float)samples): an f32 sum from zero in sample order, then
+ *      one division and one multiply in that grouping, nothing fused (the estimator pi / samples * sum of L for directions of density
+ *      cos(theta) / pi).  out[i].segments = g_0 + g_1 + ... mod 2^32.
+ *   5. a point with a non-finite component of P or N, or with N = (0, 0, 0), is no point (rt_ambient_occlusion's rule): nothing is
+ *      traced, the irradiance is 0 and segments = 0.  A miss record of rt_surface has a zero normal, so it is no point.
+ * What follows:
+ *   - the result does not depend on the tree in use (device build, host build, RT_PREPARE_QUALITY_TREE, refitted), the device count,
+ *     the kind of memory or the chunking.  Light grids are never looked at.  Any number of lights, as rt_radiance.
+ *   - an empty scene gives pi * sky[c] within a relative (samples + 4) * 2^-24, and segments = samples.
+ *   - unlike rt_radiance_sh followed by a cosine convolution it is not band-limited, and no light from behind the surface enters it.
+ * params: rt_path_params as rt_radiance_sh reads it - samples (directions per point) 1 .. RT_PATH_MAX_SAMPLES; max_bounces 0 ..
+ *   RT_MAX_BOUNCES; first_sample + samples <= 2^32; flags RT_PATH_NO_SHADOWS, RT_QUERY_COUNTERS - except RT_PATH_CAMERA_DRAWS, which
+ *   is RT_ERR_BAD_ARG: the call spends those two draws itself.  _pad ignored.
+ * Buffers, synchronisation and side effects as for rt_radiance_sh: both pointers host memory, or both device memory of one context
+ * device (16-byte aligned), anything else is RT_ERR_BAD_ARG; batches are traced in chunks of at most max(1, RT_QUERY_CHUNK / samples)
+ * points, host batches staged chunk by chunk; a context over several devices splits a host batch into one contiguous range per device
+ * (the seed's i stays the index in the caller's array); synchronous, first waits for an rt_dispatch_tile in flight; the last frame,
+ * the rt_read_* results and a running accumulation are left alone.
+ * Errors: n == 0 is RT_OK; NULL points / params / out, samples out of range, max_bounces > RT_MAX_BOUNCES, first_sample + samples > 2^32,
+ * RT_PATH_CAMERA_DRAWS and unknown flag bits are RT_ERR_BAD_ARG and change nothing; a call before any upload is RT_ERR_NOT_UPLOADED.
+ * Statistics: as rt_radiance_sh - rays = all segments, primary_rays = first segments (valid first segments: valid points x samples
+ * but for degenerate rays), continuation_rays and shadow_rays as the frames count them, pixels = 0, kernel_ms the maximum over
+ * devices, node_visits / tri_tests only with RT_QUERY_COUNTERS.
+ * --------------------------------------------------------------------------------------------------------------- */
+typedef struct rt_irradiance_result {
+    float irradiance[3];
+    uint32_t segments; /* segments traced for this point over all its samples (first + continuation + shadow), mod 2^32 */
+} rt_irradiance_result; /* 16 bytes */
+
+RT_STATIC_ASSERT(sizeof(rt_irradiance_result) == 16 && offsetof(rt_irradiance_result, segments) == 12, "rt_irradiance_result is 16 B, segments at 12");
+
+/* Cosine-weighted path irradiance at each of the n surface points: params->samples paths each. */
+int rt_irradiance(rt_ctx* ctx, const rt_surface_point* points, size_t n, const rt_path_params* params, rt_irradiance_result* out);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Closest-point queries: the nearest point of the scene's surface to points the caller supplies (no reference counterpart; Embree's
