@@ -33,8 +33,9 @@ PREPARE_SHADOW_GRIDS = 1
 PREPARE_QUALITY_TREE = 2
 QUERY_COUNTERS = 1  # RT_QUERY_COUNTERS of rt_intersect / rt_occluded
 QUERY_CHUNK = 4194304  # RT_QUERY_CHUNK: host batches are staged in chunks of at most this many rays
-QUERY_COUNT_ALL = 2  # RT_QUERY_COUNT_ALL of rt_intersect_all: counts are all candidates in the range, not the records written
+QUERY_COUNT_ALL = 2  # RT_QUERY_COUNT_ALL of rt_intersect_all / rt_closest_point_all: counts are all candidates in the range, not the records written
 MULTI_HIT_MAX = 16  # RT_MULTI_HIT_MAX: the most hits rt_intersect_all lists per ray
+NEAREST_MAX = 16  # RT_NEAREST_MAX: the most primitives rt_closest_point_all lists per point
 AO_MAX_SAMPLES = 4096  # RT_AO_MAX_SAMPLES: the most samples rt_ambient_occlusion takes per point
 DIRECT_AMBIENT, DIRECT_NO_SHADOWS, DIRECT_NO_SHADOW_GRID = 4, 8, 16  # RT_DIRECT_* of rt_direct_light_params.flags
 DIRECT_MAX_LIGHTS = 32  # RT_DIRECT_MAX_LIGHTS: rt_direct_light's lit_mask has one bit per light
@@ -58,7 +59,7 @@ ABI_SYMBOLS = [
     "rt_read_rgb32f", "rt_read_rgba8_channels", "rt_read_rgba8_combined", "rt_read_hits",
     "rt_get_stats", "rt_last_error", "rt_destroy", "rt_version",
     "rt_intersect", "rt_occluded", "rt_camera_rays", "rt_intersect_all",
-    "rt_surface", "rt_ambient_occlusion", "rt_direct_light", "rt_radiance", "rt_radiance_sh", "rt_irradiance", "rt_closest_point", "rt_sweep_sphere",
+    "rt_surface", "rt_ambient_occlusion", "rt_direct_light", "rt_radiance", "rt_radiance_sh", "rt_irradiance", "rt_closest_point", "rt_closest_point_all", "rt_sweep_sphere",
     "rt_update_geometry",
     "rt_accumulated_samples",
     "rt_aovs", "rt_sample_rays", "rt_denoise",
@@ -155,6 +156,17 @@ def _check_hit_lists(a, n, max_hits):
         raise ValueError("out: not C-contiguous")
     if a.shape[0] != n:
         raise ValueError(f"out: {a.shape[0]} rows for {n} rays")
+
+
+def _check_nearest_lists(a, n, max_nearest):
+    """Raises unless `a` is a C-contiguous float32 (n, max_nearest, 8) array: rt_closest_point_all's records, query-major."""
+    _check_kind_dtype(a, "out", "float32")
+    if len(a.shape) != 3 or tuple(a.shape[1:]) != (max_nearest, 8):
+        raise ValueError(f"out: shape {tuple(a.shape)}, expected (N, {max_nearest}, 8)")
+    if not _contiguous(a):
+        raise ValueError("out: not C-contiguous")
+    if a.shape[0] != n:
+        raise ValueError(f"out: {a.shape[0]} rows for {n} points")
 
 
 def _check_counts(a, n, what="rays"):
@@ -774,6 +786,34 @@ class Context:
         kind and device as `points`.  Only surface strictly nearer than the radius is reported; a miss is position 0, the radius as
         distance and prim_id = PRIM_MISS."""
         return self._query("rt_closest_point", points, out, 8, "float32", counters, in_cols=4, in_name="points")
+
+    def closest_point_all(self, points, max_nearest, out=None, counts=None, count_all=False, counters=False):
+        """rt_closest_point_all: the max_nearest (0 .. NEAREST_MAX) nearest primitives within the radius of each record of an (N, 4)
+        batch of points (make_points), nearest first as rt_closest_point would pick them -> (out, counts), same kind and device as
+        `points`.  out: (N, max_nearest, 8) float32 rt_nearest records, unused slots miss records (split_nearest takes
+        out.reshape(-1, 8)), None for max_nearest=0; counts: (N,) uint32 (numpy) / int32 (torch), the records listed per point, or with
+        count_all every primitive within the radius (with an infinite radius that tests the whole scene for every point).
+        max_nearest=0 needs count_all: a pure count."""
+        n = _check_batch(points, "points", 4, "float32")
+        if isinstance(max_nearest, bool) or not isinstance(max_nearest, (int, np.integer)) or not 0 <= max_nearest <= NEAREST_MAX:
+            raise ValueError(f"max_nearest: {max_nearest!r}, expected an integer in 0 .. {NEAREST_MAX}")
+        max_nearest = int(max_nearest)
+        if max_nearest == 0 and not count_all:
+            raise ValueError("max_nearest: 0 lists nothing, which needs count_all=True (a pure count)")
+        if out is not None and _is_torch(out) != _is_torch(points):
+            raise TypeError("out: must be the same kind (numpy / torch) as points")
+        if max_nearest == 0:
+            out = None
+        elif out is None:
+            out = _empty_like_batch(points, (n, max_nearest, 8), "float32")
+        else:
+            _check_nearest_lists(out, n, max_nearest)
+        counts = _counts_like(counts, points, "points", n)
+        _sync_torch(points, out, counts)
+        flags = (QUERY_COUNTERS if counters else 0) | (QUERY_COUNT_ALL if count_all else 0)
+        self._check(self.lib.rt_closest_point_all(self._h, _addr(points), C.c_size_t(n), C.c_uint32(max_nearest),
+                                                  _addr(out) if out is not None else C.c_void_p(0), _addr(counts), C.c_uint32(flags)))
+        return out, counts
 
     def sweep_sphere(self, sweeps, out=None, counters=False):
         """rt_sweep_sphere: the first contact of each moving sphere of an (N, 8) batch (make_sweeps: origin, radius, direction, tmax)

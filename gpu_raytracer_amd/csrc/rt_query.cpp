@@ -1,7 +1,7 @@
 // rt_query.cpp — calls that trace or filter outside a frame: ray queries (rt_hip.h "Ray queries": rt_intersect, rt_occluded,
 // rt_intersect_all, rt_camera_rays), surface queries ("Surface queries": rt_surface, rt_ambient_occlusion; kernels in
 // surface_query.hip), the direct-light query ("Direct-light queries": rt_direct_light; kernel in direct_light.hip), the path query ("Path queries":
-// rt_radiance; kernels in path_query.hip), the probe query ("Probe queries": rt_radiance_sh; kernels in probe_query.hip), the irradiance query ("Irradiance queries": rt_irradiance; kernels in irradiance_query.hip), the closest-point query ("Closest-point queries": rt_closest_point; kernel in closest_point.hip), the sphere sweep ("Sphere sweeps": rt_sweep_sphere; kernel in sweep.hip) and the image passes ("Feature buffers (AOVs) and denoising": rt_aovs, rt_sample_rays, rt_denoise; kernels in
+// rt_radiance; kernels in path_query.hip), the probe query ("Probe queries": rt_radiance_sh; kernels in probe_query.hip), the irradiance query ("Irradiance queries": rt_irradiance; kernels in irradiance_query.hip), the closest-point queries ("Closest-point queries": rt_closest_point, rt_closest_point_all; kernels in closest_point.hip, closest_point_all.hip), the sphere sweep ("Sphere sweeps": rt_sweep_sphere; kernel in sweep.hip) and the image passes ("Feature buffers (AOVs) and denoising": rt_aovs, rt_sample_rays, rt_denoise; kernels in
 // denoise.hip).  None of them touches the frame targets, the tile shares rt_read_* gather, or the running image of an accumulation.
 #include "rt_internal.h"
 #include "query_plan.h"
@@ -46,7 +46,7 @@ void drain_streams(rt_ctx* ctx) { // after a failure: nothing of the call is lef
 }
 
 // ---- batch calls: an array of records in, one or two arrays of records out ------------------------------------------------------
-// run_batch is the procedure all eleven share; an entry function states its own checks, describes its arrays in a Batch, supplies the
+// run_batch is the procedure all twelve share; an entry function states its own checks, describes its arrays in a Batch, supplies the
 // launches of one chunk and turns the Totals into rt_stats.
 
 enum Stage { ST_OUT, ST_COUNTS, ST_AO, ST_PATHS }; // a buffer of DeviceState::rq
@@ -514,6 +514,36 @@ int rt_intersect_all(rt_ctx* ctx, const rt_ray* rays, size_t n, uint32_t max_hit
     Totals t;
     if (int rc = run_batch(ctx, b, t, [&](DeviceState& d, const DevScene& sc, const Chunk& ck) {
             return rt::launch_ray_query_all(sc, ck.in, ck.out[0], static_cast<uint32_t*>(ck.out[1]), ck.m, max_hits, all, counters ? d.counters.get() : nullptr, d.stream);
+        }))
+        return rc;
+    batch_stats(ctx, w0, t, counters, n);
+    return RT_OK;
+}
+
+// max_nearest records per point and a second output, the counts: rt_intersect_all's shape.  A chunk is RT_QUERY_CHUNK /
+// max(max_nearest, 1) points: its records never need more staging than an rt_closest_point chunk's.
+static_assert(RT_NEAREST_MAX == rt::CP_NEAREST_MAX, "the kernel's list holds RT_NEAREST_MAX entries");
+int rt_closest_point_all(rt_ctx* ctx, const rt_point_query* points, size_t n, uint32_t max_nearest, rt_nearest* out, uint32_t* counts, uint32_t flags) {
+    const char* fn = "rt_closest_point_all";
+    const double w0 = now_ms();
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (n == 0) return RT_OK;
+    if (!points || (!out && max_nearest > 0)) return ctx->fail(RT_ERR_BAD_ARG, "%s: %s is NULL with n = %zu", fn, !points ? "points" : "out", n);
+    if (max_nearest > RT_NEAREST_MAX) return ctx->fail(RT_ERR_BAD_ARG, "%s: max_nearest %u (0 .. %u)", fn, max_nearest, RT_NEAREST_MAX);
+    if (max_nearest == 0 && (!(flags & RT_QUERY_COUNT_ALL) || !counts))
+        return ctx->fail(RT_ERR_BAD_ARG, "%s: max_nearest 0 needs RT_QUERY_COUNT_ALL and counts", fn);
+    const uint32_t known = RT_QUERY_COUNTERS | RT_QUERY_COUNT_ALL;
+    if (flags & ~known) return ctx->fail(RT_ERR_BAD_ARG, "%s: unknown flag bits 0x%x", fn, flags & ~known);
+    if (!ctx->uploaded) return ctx->fail(RT_ERR_NOT_UPLOADED, "%s: no scene uploaded", fn);
+    if (max_nearest == 0) out = nullptr; // ignored: a pure count
+    const bool counters = (flags & RT_QUERY_COUNTERS) != 0, all = (flags & RT_QUERY_COUNT_ALL) != 0;
+    const size_t chunk = RT_QUERY_CHUNK / std::max(max_nearest, 1u);
+    const Batch b{fn, n, {"points", points, sizeof(rt_point_query)},
+                  {{"out", out, max_nearest * sizeof(rt_nearest)}, {"counts", counts, sizeof(uint32_t), 4, ST_COUNTS}},
+                  chunk, chunk, counters ? RT_CNT_TRI_TESTS + 1u : 0u};
+    Totals t;
+    if (int rc = run_batch(ctx, b, t, [&](DeviceState& d, const DevScene& sc, const Chunk& ck) {
+            return rt::launch_closest_point_all(sc, ck.in, ck.out[0], static_cast<uint32_t*>(ck.out[1]), ck.m, max_nearest, all, counters ? d.counters.get() : nullptr, d.stream);
         }))
         return rc;
     batch_stats(ctx, w0, t, counters, n);

@@ -224,7 +224,7 @@ int rt_get_stats(rt_ctx* ctx, rt_stats* out);
  * a new one at sample 0 by itself, as RT_FLAG_ACCUMULATE_RESTART does.  The other RT_FLAG_* bits change no bits and may differ.
  * The running image ends (the next accumulating call starts at 0) with rt_upload_scene*, rt_update_geometry, rt_dispatch_tile, any
  * rt_render without RT_FLAG_ACCUMULATE and an accumulating call that fails once it has passed its argument checks.  It survives rt_prepare,
- * rt_upload_textures, the ray queries, the surface queries, rt_direct_light, rt_radiance, rt_radiance_sh, rt_irradiance, rt_closest_point, rt_sweep_sphere, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
+ * rt_upload_textures, the ray queries, the surface queries, rt_direct_light, rt_radiance, rt_radiance_sh, rt_irradiance, rt_closest_point, rt_closest_point_all, rt_sweep_sphere, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
  * Limit: RT_ACCUMULATE_MAX_SAMPLES samples (where the float sample count stops being exact); a call that would pass it is RT_ERR_BAD_ARG
  * and leaves the running image as it was.  rt_stats describes the call alone (its segments, pixels, kernel_ms).
  * A context over several devices, and a tile_rank / tile_world share, accumulates its own share of the pixels.
@@ -370,7 +370,7 @@ int rt_occluded(rt_ctx* ctx, const rt_ray* rays, size_t n, uint8_t* occluded, ui
  * Statistics, synchronisation and side effects as for rt_intersect: synchronous, first waits for an rt_dispatch_tile in flight;
  * rays = n, the other counts 0, kernel_ms the maximum over devices, node_visits / tri_tests only with RT_QUERY_COUNTERS; the last
  * frame, the rt_read_* results and a running accumulation are left alone. */
-#define RT_QUERY_COUNT_ALL 2u   /* rt_intersect_all only */
+#define RT_QUERY_COUNT_ALL 2u   /* rt_intersect_all and rt_closest_point_all only */
 #define RT_MULTI_HIT_MAX 16u
 
 int rt_intersect_all(rt_ctx* ctx, const rt_ray* rays, size_t n, uint32_t max_hits,
@@ -760,6 +760,49 @@ RT_STATIC_ASSERT(offsetof(rt_nearest, distance) == 12 && offsetof(rt_nearest, u)
 
 /* Nearest surface point to each of the n points. */
 int rt_closest_point(rt_ctx* ctx, const rt_point_query* points, size_t n, rt_nearest* out, uint32_t flags);
+
+/* Nearest-K: the max_nearest nearest primitives of each of the n points within the query's radius, nearest first, in one walk per
+ * point (rtcPointQuery as the collecting query it is: contact manifolds, de-penetration, brushes and selection, cache lookups).
+ * rt_closest_point cannot be told to skip the primitive it returned, so no sequence of its calls gives this.
+ * Candidates: every sphere s, as (its dist2 above, key s), and every triangle record, as (its dist2 above on the record's v0, e1, e2,
+ * key 0x80000000 | prim_id).  A candidate is in range iff (the bits of dist2, key) is below (the bits of radius * radius, 0):
+ * dist2 < radius * radius, strictly; a NaN or infinite dist2 never is.  That is rt_closest_point's acceptance.  Every triangle has
+ * exactly one record in the tree (the builders never split a triangle), so no primitive is listed twice.
+ * Order: ascending (the bits of dist2, key) as one 64-bit unsigned number; at equal dist2 spheres before triangles, spheres by
+ * ascending sphere index, triangles by ascending original triangle index.  That is the order in which rt_closest_point's rules
+ * would pick a winner: for max_nearest >= 1 point i's first record out[i * max_nearest] is bit for bit the rt_closest_point record
+ * of point i.
+ * Output: point i's first min(total, max_nearest) candidates in that order as rt_nearest records at out[i * max_nearest ..]
+ * (query-major), each the record rt_closest_point would give were that primitive alone in the scene: position, distance =
+ * sqrtf(dist2), u, v, prim_id, the record's material_id.  Unused slots are miss records: position = 0, distance = the radius as
+ * given, u = v = 0, prim_id = 0xFFFFFFFF, material_id = 0.  max_nearest == 1 gives exactly rt_closest_point's bytes, misses,
+ * degenerate queries (all misses and a count of 0 without a walk, the same rules; the kernel checks this itself) and an empty scene
+ * included, and with RT_QUERY_COUNTERS its node visits and triangle tests: the walk is culled by the same values at every step.
+ * counts[i] = the number of records written for point i; with RT_QUERY_COUNT_ALL instead the number of candidates in range, which
+ * can exceed max_nearest (the records written are the same).  The walk can then not shrink its range: it is culled by
+ * radius * radius throughout, and RT_QUERY_COUNT_ALL with radius = +inf tests every primitive of the scene for every point.
+ * `counts` may be NULL unless max_nearest == 0.  max_nearest == 0 is allowed only with RT_QUERY_COUNT_ALL and a non-NULL counts;
+ * `out` is then ignored: a pure count of what lies within the radius.
+ * The result follows from these rules alone - it is the max_nearest smallest elements of a totally ordered set - so it does not
+ * depend on the tree in use (device build, host build, RT_PREPARE_QUALITY_TREE, refitted), the device count, the kind of memory or
+ * the chunking, and after rt_update_geometry it is that of a fresh upload of the moved scene.  The tree only culls, by the bound of
+ * rt_closest_point held against the list's last entry once the list is full (csrc/closest_point_all_rules.h).
+ * Buffers: each pointer is classified as for the other queries; all are host memory, or all device memory of one context device
+ * (points and out 16-byte aligned, counts 4-byte aligned), anything else is RT_ERR_BAD_ARG.  Batches go in chunks of at most
+ * RT_QUERY_CHUNK / max(max_nearest, 1) points, so the staged records never exceed those of an rt_closest_point chunk; a context
+ * over several devices splits a host batch into one contiguous range per device.
+ * Errors: n == 0 is RT_OK; a NULL points, or a NULL out with max_nearest > 0, max_nearest > RT_NEAREST_MAX, max_nearest == 0 without
+ * RT_QUERY_COUNT_ALL and counts, and unknown flag bits are RT_ERR_BAD_ARG and change nothing; a call before any upload is
+ * RT_ERR_NOT_UPLOADED.  An empty scene gives all misses and counts of 0.
+ * Statistics, synchronisation and side effects as for rt_intersect_all: synchronous, first waits for an rt_dispatch_tile in flight;
+ * rays = n, the other counts 0, kernel_ms the maximum over devices, node_visits / tri_tests only with RT_QUERY_COUNTERS; the last
+ * frame, the rt_read_* results and a running accumulation are left alone. */
+#define RT_NEAREST_MAX 16u
+
+int rt_closest_point_all(rt_ctx* ctx, const rt_point_query* points, size_t n, uint32_t max_nearest,
+                         rt_nearest* out,   /* n * max_nearest records, query-major: point i's at out[i*max_nearest ..] */
+                         uint32_t* counts,  /* n entries; may be NULL unless max_nearest == 0 */
+                         uint32_t flags);   /* RT_QUERY_COUNTERS | RT_QUERY_COUNT_ALL */
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Sphere sweeps: the first contact of a moving sphere with the scene's surface (no reference counterpart; the "sphere cast" of the
