@@ -36,6 +36,11 @@ QUERY_CHUNK = 4194304  # RT_QUERY_CHUNK: host batches are staged in chunks of at
 QUERY_COUNT_ALL = 2  # RT_QUERY_COUNT_ALL of rt_intersect_all / rt_closest_point_all: counts are all candidates in the range, not the records written
 MULTI_HIT_MAX = 16  # RT_MULTI_HIT_MAX: the most hits rt_intersect_all lists per ray
 NEAREST_MAX = 16  # RT_NEAREST_MAX: the most primitives rt_closest_point_all lists per point
+INSIDE_MAX_RAYS = 7  # RT_INSIDE_MAX_RAYS: the most parity rays rt_inside / rt_signed_distance trace per point
+INSIDE_DIRECTIONS = np.array([  # RT_INSIDE_DIRECTIONS: direction k of vote k, used as given
+    [0.5377, 0.7431, 0.3982], [-0.6241, 0.3517, 0.6977], [0.2893, -0.4719, 0.8328],
+    [-0.3361, -0.8154, -0.4703], [0.8467, -0.2249, -0.4821], [-0.1873, 0.5566, -0.8094],
+    [0.4129, 0.1683, -0.8951]], np.float32)
 AO_MAX_SAMPLES = 4096  # RT_AO_MAX_SAMPLES: the most samples rt_ambient_occlusion takes per point
 DIRECT_AMBIENT, DIRECT_NO_SHADOWS, DIRECT_NO_SHADOW_GRID = 4, 8, 16  # RT_DIRECT_* of rt_direct_light_params.flags
 DIRECT_MAX_LIGHTS = 32  # RT_DIRECT_MAX_LIGHTS: rt_direct_light's lit_mask has one bit per light
@@ -60,6 +65,7 @@ ABI_SYMBOLS = [
     "rt_get_stats", "rt_last_error", "rt_destroy", "rt_version",
     "rt_intersect", "rt_occluded", "rt_camera_rays", "rt_intersect_all",
     "rt_surface", "rt_ambient_occlusion", "rt_direct_light", "rt_radiance", "rt_radiance_sh", "rt_irradiance", "rt_closest_point", "rt_closest_point_all", "rt_sweep_sphere",
+    "rt_inside", "rt_signed_distance",
     "rt_update_geometry",
     "rt_accumulated_samples",
     "rt_aovs", "rt_sample_rays", "rt_denoise",
@@ -216,7 +222,38 @@ def _counts_like(counts, batch, batch_name, n):
     return counts
 
 
-def _path_params(samples, max_bounces, seed, first_sample, flags):
+def _votes_like(votes, batch, n):
+    """The (n,) uint8 votes array of inside / signed_distance: None when not asked for (False / None), made like `batch` for True,
+    else the caller's array, checked."""
+    if votes is None or votes is False:
+        return None
+    if votes is True:
+        if _is_torch(batch):
+            import torch
+            return torch.empty((n,), dtype=torch.uint8, device=batch.device)
+        return np.empty((n,), np.uint8)
+    _check_kind_dtype(votes, "votes", "uint8")
+    if _is_torch(votes) != _is_torch(batch):
+        raise TypeError("votes: must be the same kind (numpy / torch) as points")
+    if len(votes.shape) != 1:
+        raise ValueError(f"votes: shape {tuple(votes.shape)}, expected (N,)")
+    if not _contiguous(votes):
+        raise ValueError("votes: not C-contiguous")
+    if votes.shape[0] != n:
+        raise ValueError(f"votes: {votes.shape[0]} rows for {n} points")
+    return votes
+
+
+def _inside_params(rays, counters):
+    """The rt_inside_params record (types.INSIDE_PARAMS) of inside / signed_distance, `rays` checked before the library sees it."""
+    if isinstance(rays, bool) or not isinstance(rays, (int, np.integer)) or rays not in (1, 3, 5, 7):
+        raise ValueError(f"rays: {rays!r}, expected one of the integers 1, 3, 5, 7")
+    ip = np.zeros((), dtype=T.INSIDE_PARAMS)
+    ip["rays"], ip["flags"] = int(rays), QUERY_COUNTERS if counters else 0
+    return ip
+
+
+def _path_params(samples,max_bounces, seed, first_sample, flags):
     """The rt_path_params record (types.PATH_PARAMS) of radiance / radiance_sh / irradiance from their four integers, checked."""
     for name, v, lo, hi in (("samples", samples, 1, PATH_MAX_SAMPLES), ("max_bounces", max_bounces, 0, MAX_BOUNCES), ("seed", seed, 0, 0xFFFFFFFF),
                             ("first_sample", first_sample, 0, 0xFFFFFFFF)):
@@ -814,6 +851,29 @@ class Context:
         self._check(self.lib.rt_closest_point_all(self._h, _addr(points), C.c_size_t(n), C.c_uint32(max_nearest),
                                                   _addr(out) if out is not None else C.c_void_p(0), _addr(counts), C.c_uint32(flags)))
         return out, counts
+
+    def _inside_query(self, fn, points, rays, out, cols, dtype_name, votes, counters):
+        n = _check_batch(points, "points", 4, "float32")
+        ip = _inside_params(rays, counters)
+        out = _out_like(out, points, "points", n, cols, dtype_name)
+        v = _votes_like(votes, points, n)
+        _sync_torch(points, out, v)
+        self._check(getattr(self.lib, fn)(self._h, _addr(points), C.c_size_t(n), _p(ip), _addr(out), _addr(v) if v is not None else C.c_void_p(0)))
+        return out if v is None else (out, v)
+
+    def inside(self, points, rays=3, out=None, votes=False, counters=False):
+        """rt_inside: whether each record of an (N, 4) batch of points (make_points; the radius is ignored) lies inside the scene's
+        solids -> (N,) bool, same kind and device as `points`: inside some sphere, or a majority of `rays` (1, 3, 5 or 7) crossing
+        parities along the fixed INSIDE_DIRECTIONS is odd.  The triangles must form a watertight surface.  votes=True (or an (N,) uint8
+        array to fill) -> (inside, votes), votes the odd parities of all `rays` rays: strictly between 0 and `rays` where the rays
+        disagree.  Without votes a point stops at its majority (stats()["rays"] tells how many rays that took)."""
+        return self._inside_query("rt_inside", points, rays, out, 0, "bool", votes, counters)
+
+    def signed_distance(self, points, rays=3, out=None, votes=False, counters=False):
+        """rt_signed_distance: closest_point's (N, 8) float32 records of an (N, 4) batch of points (make_points), the distance negative
+        where inside() holds -> records (split_nearest), same kind and device as `points`; on a miss within a finite radius the
+        distance is -radius inside, +radius outside (a truncated field).  rays, votes: as inside() -> (records, votes)."""
+        return self._inside_query("rt_signed_distance", points, rays, out, 8, "float32", votes, counters)
 
     def sweep_sphere(self, sweeps, out=None, counters=False):
         """rt_sweep_sphere: the first contact of each moving sphere of an (N, 8) batch (make_sweeps: origin, radius, direction, tmax)

@@ -27,6 +27,7 @@
 #include "device_layout.h"
 #include "direct_light.h"
 #include "half.h"
+#include "inside.h"
 #include "irradiance_query.h"
 #include "kernels.h"
 #include "path_query.h"
@@ -141,7 +142,7 @@ struct DeviceState {
     } pipe;
     bool used_two_lanes = false; // the last pipeline frame ran on two lanes (its allocation is reused by a frame of the same shape)
     uint32_t wf_spp = 0;         // spp the current wavefront allocation was sized for
-    struct Query { // ray, surface, direct-light and path queries: staging of host batches (rays or points in, records / bytes out, rt_intersect_all's and rt_closest_point_all's counts), grown on demand
+    struct Query { // ray, surface, direct-light and path queries: staging of host batches (rays or points in, records / bytes out, rt_intersect_all's and rt_closest_point_all's counts, rt_inside's and rt_signed_distance's votes), grown on demand
         DevMem in, out, counts;
         DevBuf<uint32_t> ao; // rt_ambient_occlusion: the per-point counts its kernel adds to, for host and device batches alike
         DevBuf<uint4> paths; // rt_radiance with several samples, rt_radiance_sh, rt_irradiance: one record per path of a chunk (at most RT_QUERY_CHUNK), which its reduction / projection adds up

@@ -1,9 +1,10 @@
 // rt_query.cpp — calls that trace or filter outside a frame: ray queries (rt_hip.h "Ray queries": rt_intersect, rt_occluded,
 // rt_intersect_all, rt_camera_rays), surface queries ("Surface queries": rt_surface, rt_ambient_occlusion; kernels in
 // surface_query.hip), the direct-light query ("Direct-light queries": rt_direct_light; kernel in direct_light.hip), the path query ("Path queries":
-// rt_radiance; kernels in path_query.hip), the probe query ("Probe queries": rt_radiance_sh; kernels in probe_query.hip), the irradiance query ("Irradiance queries": rt_irradiance; kernels in irradiance_query.hip), the closest-point queries ("Closest-point queries": rt_closest_point, rt_closest_point_all; kernels in closest_point.hip, closest_point_all.hip), the sphere sweep ("Sphere sweeps": rt_sweep_sphere; kernel in sweep.hip) and the image passes ("Feature buffers (AOVs) and denoising": rt_aovs, rt_sample_rays, rt_denoise; kernels in
+// rt_radiance; kernels in path_query.hip), the probe query ("Probe queries": rt_radiance_sh; kernels in probe_query.hip), the irradiance query ("Irradiance queries": rt_irradiance; kernels in irradiance_query.hip), the closest-point queries ("Closest-point queries": rt_closest_point, rt_closest_point_all; kernels in closest_point.hip, closest_point_all.hip), the inside test and the signed distance ("Inside tests and signed distance": rt_inside, rt_signed_distance; kernel in inside.hip), the sphere sweep ("Sphere sweeps": rt_sweep_sphere; kernel in sweep.hip) and the image passes ("Feature buffers (AOVs) and denoising": rt_aovs, rt_sample_rays, rt_denoise; kernels in
 // denoise.hip).  None of them touches the frame targets, the tile shares rt_read_* gather, or the running image of an accumulation.
 #include "rt_internal.h"
+#include "inside_rules.h"
 #include "query_plan.h"
 
 namespace rti {
@@ -46,7 +47,7 @@ void drain_streams(rt_ctx* ctx) { // after a failure: nothing of the call is lef
 }
 
 // ---- batch calls: an array of records in, one or two arrays of records out ------------------------------------------------------
-// run_batch is the procedure all twelve share; an entry function states its own checks, describes its arrays in a Batch, supplies the
+// run_batch is the procedure all fourteen share; an entry function states its own checks, describes its arrays in a Batch, supplies the
 // launches of one chunk and turns the Totals into rt_stats.
 
 enum Stage { ST_OUT, ST_COUNTS, ST_AO, ST_PATHS }; // a buffer of DeviceState::rq
@@ -464,6 +465,30 @@ int denoise(rt_ctx* ctx, const rt_denoise_params* dp, const float* rgb, const rt
     return RT_OK;
 }
 
+// rt_inside and rt_signed_distance: one answer per point (a byte, or an rt_nearest) and a second output, the votes.  A chunk is
+// RT_QUERY_CHUNK / rays points, so a launch traces at most RT_QUERY_CHUNK parity rays.  The rays traced are counted on the device
+// (rt_stats.rays), so every call zeroes and reads the device's counters.
+int inside_query(rt_ctx* ctx, const char* fn, const rt_point_query* points, size_t n, const rt_inside_params* p, BatchOut out, uint8_t* votes, bool distance) {
+    const double w0 = now_ms();
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (n == 0) return RT_OK;
+    if (!points || !p || !out.p) return ctx->fail(RT_ERR_BAD_ARG, "%s: %s is NULL with n = %zu", fn, !points ? "points" : !p ? "params" : out.name, n);
+    if (!rt::inside_rays_valid(p->rays)) return ctx->fail(RT_ERR_BAD_ARG, "%s: rays %u (1, 3, 5 or %u)", fn, p->rays, RT_INSIDE_MAX_RAYS);
+    if (p->flags & ~RT_QUERY_COUNTERS) return ctx->fail(RT_ERR_BAD_ARG, "%s: unknown flag bits 0x%x", fn, p->flags & ~RT_QUERY_COUNTERS);
+    if (!ctx->uploaded) return ctx->fail(RT_ERR_NOT_UPLOADED, "%s: no scene uploaded", fn);
+    const bool counters = (p->flags & RT_QUERY_COUNTERS) != 0;
+    const uint32_t rays = p->rays;
+    const size_t chunk = RT_QUERY_CHUNK / rays;
+    const Batch b{fn, n, {"points", points, sizeof(rt_point_query)}, {out, {"votes", votes, 1, 1, ST_COUNTS}}, chunk, chunk, RT_CNT_TRI_TESTS + 1u};
+    Totals t;
+    if (int rc = run_batch(ctx, b, t, [&](DeviceState& d, const DevScene& sc, const Chunk& ck) {
+            return rt::launch_inside(sc, ck.in, ck.out[0], static_cast<uint8_t*>(ck.out[1]), ck.m, rays, distance, counters, d.counters.get(), d.stream);
+        }))
+        return rc;
+    batch_stats(ctx, w0, t, counters, t.cn[RT_CNT_SEGMENTS]);
+    return RT_OK;
+}
+
 } // namespace
 
 } // namespace rti
@@ -548,6 +573,14 @@ int rt_closest_point_all(rt_ctx* ctx, const rt_point_query* points, size_t n, ui
         return rc;
     batch_stats(ctx, w0, t, counters, n);
     return RT_OK;
+}
+
+int rt_inside(rt_ctx* ctx, const rt_point_query* points, size_t n, const rt_inside_params* params, uint8_t* inside, uint8_t* votes) {
+    return inside_query(ctx, "rt_inside", points, n, params, {"inside", inside, 1, 1}, votes, false);
+}
+
+int rt_signed_distance(rt_ctx* ctx, const rt_point_query* points, size_t n, const rt_inside_params* params, rt_nearest* out, uint8_t* votes) {
+    return inside_query(ctx, "rt_signed_distance", points, n, params, {"out", out, sizeof(rt_nearest)}, votes, true);
 }
 
 // samples lanes per point and two optional outputs.  Every chunk (a host batch: max(1, RT_QUERY_CHUNK / samples) points; a device

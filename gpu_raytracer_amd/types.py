@@ -87,6 +87,7 @@ SH9 = np.dtype([("sh", f32, (9, 3)), ("segments", u32)])  # rt_sh9
 IRRADIANCE = np.dtype([("irradiance", f32, 3), ("segments", u32)])  # rt_irradiance_result
 POINT_QUERY = np.dtype([("position", f32, 3), ("radius", f32)])  # rt_point_query
 NEAREST = np.dtype([("position", f32, 3), ("distance", f32), ("u", f32), ("v", f32), ("prim_id", u32), ("material_id", u32)])  # rt_nearest
+INSIDE_PARAMS = np.dtype([("rays", u32), ("flags", u32), ("_pad", u32, 2)])  # rt_inside_params
 SWEEP = np.dtype([("origin", f32, 3), ("radius", f32), ("direction", f32, 3), ("tmax", f32)])  # rt_sweep
 SWEEP_HIT = np.dtype([("position", f32, 3), ("t", f32), ("u", f32), ("v", f32), ("prim_id", u32), ("material_id", u32)])  # rt_sweep_hit
 AOV_SAMPLES_PER_LAUNCH = 64  # RT_AOV_SAMPLES_PER_LAUNCH
@@ -108,7 +109,7 @@ EXPECTED_SIZES = {
     "TRIANGLE": 16, "AABB": 32, "BVH_NODE": 48, "WAVEFRONT_RAY": 76, "WAVEFRONT_COUNTERS": 60,
     "SCENE_METADATA_OFFSETS": 40, "PUSH_CONSTANTS": 128, "AOV": 32, "DENOISE_PARAMS": 32,
     "ADAPTIVE_PARAMS": 16, "ADAPTIVE_PIXEL": 32, "SURFACE_POINT": 32, "AO_PARAMS": 32, "LIGHTING": 16, "DIRECT_LIGHT_PARAMS": 16,
-    "PATH_PARAMS": 32, "PATH_RESULT": 16, "PROBE": 16, "SH9": 112, "IRRADIANCE": 16, "POINT_QUERY": 16, "NEAREST": 32,
+    "PATH_PARAMS": 32, "PATH_RESULT": 16, "PROBE": 16, "SH9": 112, "IRRADIANCE": 16, "POINT_QUERY": 16, "NEAREST": 32, "INSIDE_PARAMS": 16,
     "SWEEP": 32, "SWEEP_HIT": 32,
 }
 for _name, _size in EXPECTED_SIZES.items():

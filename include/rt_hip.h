@@ -224,7 +224,7 @@ int rt_get_stats(rt_ctx* ctx, rt_stats* out);
  * a new one at sample 0 by itself, as RT_FLAG_ACCUMULATE_RESTART does.  The other RT_FLAG_* bits change no bits and may differ.
  * The running image ends (the next accumulating call starts at 0) with rt_upload_scene*, rt_update_geometry, rt_dispatch_tile, any
  * rt_render without RT_FLAG_ACCUMULATE and an accumulating call that fails once it has passed its argument checks.  It survives rt_prepare,
- * rt_upload_textures, the ray queries, the surface queries, rt_direct_light, rt_radiance, rt_radiance_sh, rt_irradiance, rt_closest_point, rt_closest_point_all, rt_sweep_sphere, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
+ * rt_upload_textures, the ray queries, the surface queries, rt_direct_light, rt_radiance, rt_radiance_sh, rt_irradiance, rt_closest_point, rt_closest_point_all, rt_inside, rt_signed_distance, rt_sweep_sphere, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
  * Limit: RT_ACCUMULATE_MAX_SAMPLES samples (where the float sample count stops being exact); a call that would pass it is RT_ERR_BAD_ARG
  * and leaves the running image as it was.  rt_stats describes the call alone (its segments, pixels, kernel_ms).
  * A context over several devices, and a tile_rank / tile_world share, accumulates its own share of the pixels.
@@ -803,6 +803,74 @@ int rt_closest_point_all(rt_ctx* ctx, const rt_point_query* points, size_t n, ui
                          rt_nearest* out,   /* n * max_nearest records, query-major: point i's at out[i*max_nearest ..] */
                          uint32_t* counts,  /* n entries; may be NULL unless max_nearest == 0 */
                          uint32_t flags);   /* RT_QUERY_COUNTERS | RT_QUERY_COUNT_ALL */
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Inside tests and signed distance: on which side of the surface a point lies, and rt_closest_point's distance with that sign (no
+ * reference counterpart; Open3D's RaycastingScene::compute_occupancy / compute_signed_distance is the model): voxelisation, SDF and
+ * TSDF baking, seeding particles inside a solid, dropping light probes that landed inside walls, the sign of a de-penetration.  The
+ * sign is a majority vote of crossing parities along R fixed directions; the magnitude is rt_closest_point's.  Every bit is fixed by
+ * the calls above (csrc/inside_rules.h):
+ *
+ * Directions: D_0 .. D_6 = RT_INSIDE_DIRECTIONS below, used as given, not normalised: seven roughly unit-length vectors with no zero
+ *   component, the same for every point and every call, so that neighbouring points walk the tree coherently, and skewed so that
+ *   lattice points send no ray along the edges of axis-aligned or 45-degree tessellations.
+ * Vote k of point P: on the ray {origin = P, tmin = RT_MIN_RAY_DISTANCE, direction = D_k, tmax = +inf}, c_k = the number of
+ *   TRIANGLE candidates of rt_intersect_all's rule in that range: the frames' Moller-Trumbore on the record's v0, e1, e2 with
+ *   tmin < t < tmax, strictly, one record per triangle.  Spheres are not counted.  The vote is c_k & 1.  c_k is a count over all
+ *   triangles of the scene and does not depend on the tree: it is counts[] of rt_intersect_all(max_hits = 0, RT_QUERY_COUNT_ALL) for
+ *   that ray on the scene without its spheres.
+ * Tracing order: k = 0, 1, .., R - 1, R = params->rays, one of 1, 3, 5, 7.  odd = the odd votes so far, even = the even ones.
+ *   Without a `votes` array a point stops as soon as its majority is decided: odd * 2 > R or even * 2 > R; the votes not taken
+ *   cannot change it.  With a `votes` array all R rays are traced and votes[i] = odd.  tri_inside = odd * 2 > R.
+ * Spheres: sphere_inside = some sphere s has dot(oc, oc) < radius * radius, oc = P - centre, dot as in "Closest-point queries", in
+ *   f32; tested in index order, before any ray.  Without a `votes` array a point inside a sphere traces no ray.
+ * Result: inside = sphere_inside || tri_inside: the union of the solids.
+ * rt_inside reads the position only; the record's radius is ignored, NaN included.  A non-finite position component gives
+ *   inside = 0 and votes = 0 with nothing traced.
+ * rt_signed_distance: out[i] is rt_closest_point's record of point i bit for bit, and when the point is inside the sign bit of
+ *   `distance` is set.  That holds on a miss within a finite radius too: distance = -radius, the truncated field, so that a TSDF bake
+ *   keeps its cheap bounded walk.  A degenerate query by rt_closest_point's rules (a non-finite position component, a NaN radius,
+ *   radius <= 0) gives its unsigned miss record and votes = 0 without any walk.
+ * Limits: the answer means something only where the triangles form a watertight surface; neither orientation nor shared indices are
+ *   needed.  votes strictly between 0 and R is how a caller sees that the surface is not watertight around a point, or that a ray
+ *   grazed an edge.  Moller-Trumbore rejects |det| < 1e-5, so a triangle whose doubled area projected along D_k is below that is
+ *   transparent to vote k, as it is to the frames; and a point within 1e-5 of the surface along a ray can miss that crossing.
+ * The result follows from these rules alone: it does not depend on the tree in use (device build, host build,
+ *   RT_PREPARE_QUALITY_TREE, refitted), the device count, the kind of memory or the chunking.
+ * Buffers, chunking, the split over devices, synchronisation, errors and side effects as for rt_closest_point_all: each pointer is
+ * classified as for the other queries; all are host memory, or all device memory of one context device (points and the rt_nearest
+ * records 16-byte aligned; the byte arrays `inside` and `votes` 1-byte aligned), anything else is RT_ERR_BAD_ARG.  Batches go in
+ * chunks of at most RT_QUERY_CHUNK / rays points; a context over several devices splits a host batch into one contiguous range per
+ * device; synchronous, first waits for an rt_dispatch_tile in flight; the last frame, the rt_read_* results and a running
+ * accumulation are left alone.
+ * Errors: n == 0 is RT_OK; a NULL points, params or inside / out with n > 0, rays not in {1, 3, 5, 7} and flag bits other than
+ * RT_QUERY_COUNTERS are RT_ERR_BAD_ARG and change nothing; a call before any upload is RT_ERR_NOT_UPLOADED.  An empty scene gives
+ * inside = 0, votes = 0 and miss records; a scene of spheres alone works.
+ * Statistics: rays = the parity rays actually traced, counted on the device: n_valid * R with `votes`, fewer without; the other
+ * counts 0; kernel_ms the maximum over devices; node_visits / tri_tests only with RT_QUERY_COUNTERS, summed over the closest-point
+ * walk and the ray walks.
+ * --------------------------------------------------------------------------------------------------------------- */
+#define RT_INSIDE_MAX_RAYS 7u
+#define RT_INSIDE_DIRECTIONS \
+    { 0.5377f,  0.7431f,  0.3982f}, {-0.6241f,  0.3517f,  0.6977f}, { 0.2893f, -0.4719f,  0.8328f}, \
+    {-0.3361f, -0.8154f, -0.4703f}, { 0.8467f, -0.2249f, -0.4821f}, {-0.1873f,  0.5566f, -0.8094f}, \
+    { 0.4129f,  0.1683f, -0.8951f}
+
+typedef struct rt_inside_params {
+    uint32_t rays;  /* R: 1, 3, 5 or 7 */
+    uint32_t flags; /* RT_QUERY_COUNTERS */
+    uint32_t _pad[2];
+} rt_inside_params; /* 16 bytes */
+
+RT_STATIC_ASSERT(sizeof(rt_inside_params) == 16 && offsetof(rt_inside_params, flags) == 4, "rt_inside_params is 16 B, flags at 4");
+
+int rt_inside(rt_ctx* ctx, const rt_point_query* points, size_t n, const rt_inside_params* params,
+              uint8_t* inside, /* n entries: 1 inside, 0 outside */
+              uint8_t* votes); /* n entries: the odd votes of all R rays; may be NULL */
+
+int rt_signed_distance(rt_ctx* ctx, const rt_point_query* points, size_t n, const rt_inside_params* params,
+                       rt_nearest* out, /* n records: rt_closest_point's, the sign bit of distance set when inside */
+                       uint8_t* votes); /* n entries: the odd votes of all R rays; may be NULL */
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Sphere sweeps: the first contact of a moving sphere with the scene's surface (no reference counterpart; the "sphere cast" of the
