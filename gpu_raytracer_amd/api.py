@@ -662,6 +662,11 @@ class Context:
         names = ("transition_passes", "transition_lanes", "node_iters", "node_lanes", "leaf_iters", "leaf_lanes", "cycles_transition", "cycles_traversal")
         return dict(zip(names, [int(v) for v in out]))
 
+    def debug_stack_mark(self):
+        """Development aid: the most traversal-stack entries a lane of k_wf_trace held in the last pipeline frame rendered with counters=True
+        (WF_TOTAL_STACK_MAX, which rt_debug_counters reports in its first slot after such a frame)."""
+        return self.debug_counters()["transition_passes"]
+
     def debug_shadow_grid(self, light=None):
         """Development aid: the light grids (csrc/shadow_grid.h) of the first device.  light=None: totals and the last counted frame's use."""
         out = (C.c_ulonglong * 8)()

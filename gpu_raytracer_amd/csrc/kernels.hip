@@ -35,7 +35,7 @@ namespace {
 // ------------------------------------------------------------------------------------
 template <bool COUNT>
 __global__ __launch_bounds__(WAVE) void k_render_reference(DevScene sc, DevFrame fr, DevTargets tg) {
-    extern __shared__ uint2 s_stack[]; // DevScene::stack_entries * 64 64-bit entries
+    extern __shared__ uint2 s_stack[]; // (DevScene::stack_entries / 2 + 1) * 64 64-bit entries (lds_bytes below): one entry per visit
     PixelCoord px = block_pixel(fr);
     if (!px.valid) return;
     uint2* stack = s_stack + threadIdx.x;
@@ -121,7 +121,7 @@ __device__ __forceinline__ V3 ext_trace_path(const DevScene& sc, const DevFrame&
 // others trace their own samples n .. n+spp-1 and add them to S (and the odd-indexed ones to H); k_ad_image writes the targets.
 template <bool COUNT, bool AD>
 __global__ __launch_bounds__(WAVE) void k_render_extended(DevScene sc, DevFrame fr, DevTargets tg) {
-    extern __shared__ uint2 s_stack[]; // DevScene::stack_entries * 64 64-bit entries
+    extern __shared__ uint2 s_stack[]; // (DevScene::stack_entries / 2 + 1) * 64 64-bit entries (lds_bytes below): one entry per visit
     PixelCoord px = block_pixel(fr);
     if (AD) px.valid = px.valid && ad_lane_active(fr, blockIdx.x, threadIdx.x);
     uint2* stack = s_stack + threadIdx.x;
@@ -175,7 +175,7 @@ enum : uint32_t { ST_NEW_SAMPLE = 0, ST_CLOSEST_DONE = 1, ST_SHADOW_DONE = 2, ST
 
 template <bool COUNT, bool AD> // AD: the adaptive variant, as k_render_extended's
 __global__ __launch_bounds__(WAVE, RT_SM_MIN_WAVES) void k_render_extended_sm(DevScene sc, DevFrame fr, DevTargets tg) {
-    extern __shared__ uint2 s_stack[]; // DevScene::stack_entries * 64 64-bit entries
+    extern __shared__ uint2 s_stack[]; // (DevScene::stack_entries / 2 + 1) * 64 64-bit entries (lds_bytes below): one entry per visit
     PixelCoord px = block_pixel(fr);
     if (AD) px.valid = px.valid && ad_lane_active(fr, blockIdx.x, threadIdx.x);
     uint2* __restrict__ stack = s_stack + threadIdx.x;
