@@ -33,9 +33,11 @@ PREPARE_SHADOW_GRIDS = 1
 PREPARE_QUALITY_TREE = 2
 QUERY_COUNTERS = 1  # RT_QUERY_COUNTERS of rt_intersect / rt_occluded
 QUERY_CHUNK = 4194304  # RT_QUERY_CHUNK: host batches are staged in chunks of at most this many rays
-QUERY_COUNT_ALL = 2  # RT_QUERY_COUNT_ALL of rt_intersect_all / rt_closest_point_all: counts are all candidates in the range, not the records written
+QUERY_COUNT_ALL = 2  # RT_QUERY_COUNT_ALL of rt_intersect_all / rt_closest_point_all / rt_overlap_box: counts are all candidates in the range, not the records written
 MULTI_HIT_MAX = 16  # RT_MULTI_HIT_MAX: the most hits rt_intersect_all lists per ray
 NEAREST_MAX = 16  # RT_NEAREST_MAX: the most primitives rt_closest_point_all lists per point
+OVERLAP_MAX = 32  # RT_OVERLAP_MAX: the most primitives rt_overlap_box lists per box
+OVERLAP_ANY = 4  # RT_OVERLAP_ANY of rt_overlap_box: counts are 1 where anything touches the box, else 0, and the walk stops at the first
 INSIDE_MAX_RAYS = 7  # RT_INSIDE_MAX_RAYS: the most parity rays rt_inside / rt_signed_distance trace per point
 INSIDE_DIRECTIONS = np.array([  # RT_INSIDE_DIRECTIONS: direction k of vote k, used as given
     [0.5377, 0.7431, 0.3982], [-0.6241, 0.3517, 0.6977], [0.2893, -0.4719, 0.8328],
@@ -65,7 +67,7 @@ ABI_SYMBOLS = [
     "rt_get_stats", "rt_last_error", "rt_destroy", "rt_version",
     "rt_intersect", "rt_occluded", "rt_camera_rays", "rt_intersect_all",
     "rt_surface", "rt_ambient_occlusion", "rt_direct_light", "rt_radiance", "rt_radiance_sh", "rt_irradiance", "rt_closest_point", "rt_closest_point_all", "rt_sweep_sphere",
-    "rt_inside", "rt_signed_distance",
+    "rt_inside", "rt_signed_distance", "rt_overlap_box",
     "rt_update_geometry",
     "rt_accumulated_samples",
     "rt_aovs", "rt_sample_rays", "rt_denoise",
@@ -173,6 +175,17 @@ def _check_nearest_lists(a, n, max_nearest):
         raise ValueError("out: not C-contiguous")
     if a.shape[0] != n:
         raise ValueError(f"out: {a.shape[0]} rows for {n} points")
+
+
+def _check_prim_lists(a, n, max_prims):
+    """Raises unless `a` is a C-contiguous (n, max_prims) array of ids (rt_overlap_box's, query-major): uint32 for numpy, int32 for torch."""
+    _check_kind_dtype(a, "out", "int32" if _is_torch(a) else "uint32")
+    if len(a.shape) != 2 or a.shape[1] != max_prims:
+        raise ValueError(f"out: shape {tuple(a.shape)}, expected (N, {max_prims})")
+    if not _contiguous(a):
+        raise ValueError("out: not C-contiguous")
+    if a.shape[0] != n:
+        raise ValueError(f"out: {a.shape[0]} rows for {n} boxes")
 
 
 def _check_counts(a, n, what="rays"):
@@ -342,6 +355,23 @@ def make_sweeps(origins, directions, radius, tmax=float("inf")):
     records: ox oy oz radius dx dy dz tmax.  radius / tmax: scalars or (N,) arrays; contacts at 0 <= t < tmax are reported."""
     out = make_rays(origins, directions, tmin=0.0, tmax=tmax)
     out[:, 3] = radius
+    return out
+
+
+def make_boxes(center, half_extent):
+    """(N, 3) centres (numpy or torch, the result has the same kind and device) -> an (N, 8) float32 batch of rt_box records:
+    cx cy cz 0 hx hy hz 0.  half_extent: a scalar, a triple or an (N, 3) array, >= 0 per axis; 0 is allowed (a slab, a segment, a point)."""
+    if _is_torch(center):
+        import torch
+        c = center.reshape(-1, 3)
+        out = torch.zeros((c.shape[0], 8), dtype=torch.float32, device=c.device)
+        h = half_extent if _is_torch(half_extent) else torch.as_tensor(np.asarray(half_extent, np.float32), device=c.device)
+    else:
+        c = np.asarray(center, np.float32).reshape(-1, 3)
+        out = np.zeros((c.shape[0], 8), np.float32)
+        h = np.asarray(half_extent, np.float32)
+    out[:, 0:3] = c
+    out[:, 4:7] = h
     return out
 
 
@@ -879,6 +909,40 @@ class Context:
         where inside() holds -> records (split_nearest), same kind and device as `points`; on a miss within a finite radius the
         distance is -radius inside, +radius outside (a truncated field).  rays, votes: as inside() -> (records, votes)."""
         return self._inside_query("rt_signed_distance", points, rays, out, 8, "float32", votes, counters)
+
+    def overlap_box(self, boxes, max_prims, *, out=None, counts=None, count_all=False, any_hit=False, counters=False):
+        """rt_overlap_box: the primitives that touch each closed axis-aligned box of an (N, 8) batch (make_boxes: centre, half extent)
+        -> (prims, counts), same kind and device as `boxes`.  prims: (N, max_prims) ids as split_hits gives prim, uint32 (numpy) /
+        int32 (torch, the same bits), the max_prims (0 .. OVERLAP_MAX) touching primitives of lowest key - spheres by index, then
+        triangles by index - ascending, unused slots PRIM_MISS; None for max_prims=0.  counts: (N,) uint32 / int32, the ids listed per
+        box; with count_all every touching primitive; with any_hit 1 where anything touches the box, else 0 (the walk stops at the
+        first).  max_prims=0 needs count_all or any_hit; any_hit needs max_prims=0 and excludes count_all."""
+        n = _check_batch(boxes, "boxes", 8, "float32")
+        if isinstance(max_prims, bool) or not isinstance(max_prims, (int, np.integer)) or not 0 <= max_prims <= OVERLAP_MAX:
+            raise ValueError(f"max_prims: {max_prims!r}, expected an integer in 0 .. {OVERLAP_MAX}")
+        max_prims = int(max_prims)
+        if any_hit and (count_all or max_prims > 0):
+            raise ValueError("any_hit: lists nothing and counts to one, which needs max_prims=0 and excludes count_all")
+        if max_prims == 0 and not (count_all or any_hit):
+            raise ValueError("max_prims: 0 lists nothing, which needs count_all=True (a pure count) or any_hit=True")
+        if out is not None and _is_torch(out) != _is_torch(boxes):
+            raise TypeError("out: must be the same kind (numpy / torch) as boxes")
+        if max_prims == 0:
+            out = None
+        elif out is None:
+            if _is_torch(boxes):
+                import torch
+                out = torch.empty((n, max_prims), dtype=torch.int32, device=boxes.device)
+            else:
+                out = np.empty((n, max_prims), np.uint32)
+        else:
+            _check_prim_lists(out, n, max_prims)
+        counts = _counts_like(counts, boxes, "boxes", n)
+        _sync_torch(boxes, out, counts)
+        flags = (QUERY_COUNTERS if counters else 0) | (QUERY_COUNT_ALL if count_all else 0) | (OVERLAP_ANY if any_hit else 0)
+        self._check(self.lib.rt_overlap_box(self._h, _addr(boxes), C.c_size_t(n), C.c_uint32(max_prims),
+                                            _addr(out) if out is not None else C.c_void_p(0), _addr(counts), C.c_uint32(flags)))
+        return out, counts
 
     def sweep_sphere(self, sweeps, out=None, counters=False):
         """rt_sweep_sphere: the first contact of each moving sphere of an (N, 8) batch (make_sweeps: origin, radius, direction, tmax)

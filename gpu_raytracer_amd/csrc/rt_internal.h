@@ -30,6 +30,7 @@
 #include "inside.h"
 #include "irradiance_query.h"
 #include "kernels.h"
+#include "overlap.h"
 #include "path_query.h"
 #include "probe_query.h"
 #include "ray_query.h"

@@ -224,7 +224,7 @@ int rt_get_stats(rt_ctx* ctx, rt_stats* out);
  * a new one at sample 0 by itself, as RT_FLAG_ACCUMULATE_RESTART does.  The other RT_FLAG_* bits change no bits and may differ.
  * The running image ends (the next accumulating call starts at 0) with rt_upload_scene*, rt_update_geometry, rt_dispatch_tile, any
  * rt_render without RT_FLAG_ACCUMULATE and an accumulating call that fails once it has passed its argument checks.  It survives rt_prepare,
- * rt_upload_textures, the ray queries, the surface queries, rt_direct_light, rt_radiance, rt_radiance_sh, rt_irradiance, rt_closest_point, rt_closest_point_all, rt_inside, rt_signed_distance, rt_sweep_sphere, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
+ * rt_upload_textures, the ray queries, the surface queries, rt_direct_light, rt_radiance, rt_radiance_sh, rt_irradiance, rt_closest_point, rt_closest_point_all, rt_inside, rt_signed_distance, rt_overlap_box, rt_sweep_sphere, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
  * Limit: RT_ACCUMULATE_MAX_SAMPLES samples (where the float sample count stops being exact); a call that would pass it is RT_ERR_BAD_ARG
  * and leaves the running image as it was.  rt_stats describes the call alone (its segments, pixels, kernel_ms).
  * A context over several devices, and a tile_rank / tile_world share, accumulates its own share of the pixels.
@@ -370,7 +370,7 @@ int rt_occluded(rt_ctx* ctx, const rt_ray* rays, size_t n, uint8_t* occluded, ui
  * Statistics, synchronisation and side effects as for rt_intersect: synchronous, first waits for an rt_dispatch_tile in flight;
  * rays = n, the other counts 0, kernel_ms the maximum over devices, node_visits / tri_tests only with RT_QUERY_COUNTERS; the last
  * frame, the rt_read_* results and a running accumulation are left alone. */
-#define RT_QUERY_COUNT_ALL 2u   /* rt_intersect_all and rt_closest_point_all only */
+#define RT_QUERY_COUNT_ALL 2u   /* rt_intersect_all, rt_closest_point_all and rt_overlap_box only */
 #define RT_MULTI_HIT_MAX 16u
 
 int rt_intersect_all(rt_ctx* ctx, const rt_ray* rays, size_t n, uint32_t max_hits,
@@ -951,6 +951,77 @@ RT_STATIC_ASSERT(sizeof(rt_sweep_hit) == 32 && offsetof(rt_sweep_hit, position) 
 
 /* First contact of each of the n moving spheres. */
 int rt_sweep_sphere(rt_ctx* ctx, const rt_sweep* sweeps, size_t n, rt_sweep_hit* out, uint32_t flags);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Overlap queries: the primitives that touch caller-supplied axis-aligned boxes (no reference counterpart; the OverlapBox /
+ * contactTest of the collision libraries and the triangle-box test behind surface voxelisers are the model): the shell of a
+ * voxelisation (rt_inside gives the solid), marquee and brush selection, trigger volumes and broad phase, "is this probe cell
+ * empty".  rt_closest_point_all with the box's circumscribed sphere lists at most RT_NEAREST_MAX ids, pays a closest-point
+ * evaluation per candidate and over-reports by the volume ratio of sphere to box, without bound for a slab.
+ * The answer is one f32 statement (csrc/overlap_rules.h; every operation one f32 rounding, nothing fused), with dot and cross as
+ * in "Sphere sweeps", c = center, h = half_extent, and every test in its positive form, so that a NaN makes it false.  A primitive
+ * TOUCHES the box iff all its tests hold.
+ * Triangle, from its record's v0, e1, e2; a0 = v0 - c, a1 = (v0 + e1) - c, a2 = (v0 + e2) - c (Akenine-Moeller 2001, thirteen axes):
+ *   0. all nine components of a0, a1, a2 are finite: a triangle with a non-finite vertex is never listed
+ *   1. per axis x, y, z:  min_k a_k[x] <= h[x] && max_k a_k[x] >= -h[x]
+ *   2. n = cross(e1, e2); d = dot(n, a0); r = dot(|n|, h):  d <= r && d >= -r
+ *   3. for f in (e1, e2 - e1, e2) and each unit axis, cross(unit, f) without its multiplications by 0 and 1:
+ *        x:  p_k = f.y * a_k.z - f.z * a_k.y;  r = |f.z| * h.y + |f.y| * h.z
+ *        y:  p_k = f.z * a_k.x - f.x * a_k.z;  r = |f.z| * h.x + |f.x| * h.z
+ *        z:  p_k = f.x * a_k.y - f.y * a_k.x;  r = |f.y| * h.x + |f.x| * h.y
+ *      min_k p_k <= r && max_k p_k >= -r, and (p_0 + p_1) + p_2 is not a NaN (min and max themselves ignore a NaN operand)
+ *   The box is closed: a triangle that only touches a face, an edge or a corner is listed, one that lies an ulp outside is not.  A
+ *   degenerate triangle comes out as the segment or point test.
+ * Sphere i (centre o, radius R), a surface as for rt_closest_point: g = |o - c| per axis; near = max(g - h, 0); far = g + h;
+ *   rr = R * R; touches iff dot(near, near) <= rr && dot(far, far) >= rr.  A box wholly inside the ball is not touched.
+ * A degenerate query - a non-finite component of center or half_extent, or a negative half extent - touches nothing, without a
+ *   walk.  The kernel checks this itself.  half_extent = 0 on an axis is allowed: a slab, a segment, a point.
+ * Order: key = prim_id ^ 0x80000000 as for rt_closest_point: spheres first by sphere index, then triangles by original triangle
+ *   index.
+ * List mode (flags without RT_QUERY_COUNT_ALL and RT_OVERLAP_ANY): box i's min(total, max_prims) touching primitives of lowest key,
+ *   ascending in key, as ids in rt_hit.prim_id's encoding at prims[i * max_prims ..] (query-major); unused slots are 0xFFFFFFFF.
+ *   counts[i] = the number written; `counts` may be NULL.  1 <= max_prims <= RT_OVERLAP_MAX.
+ * RT_QUERY_COUNT_ALL: the same ids; counts[i] = the number of all touching primitives, which can exceed max_prims.  max_prims == 0
+ *   is allowed with it, needs a non-NULL counts and ignores `prims`: a pure count.
+ * RT_OVERLAP_ANY: requires max_prims == 0 and a non-NULL counts, and excludes RT_QUERY_COUNT_ALL; counts[i] = 1 if anything touches
+ *   box i, else 0.  The walk stops at the first touching primitive; which one that is depends on the tree, so it is not reported.
+ *   This is the fast occupancy path.
+ * The result follows from these rules alone, so it does not depend on the tree in use (device build, host build,
+ *   RT_PREPARE_QUALITY_TREE, refitted), the device count, the kind of memory or the chunking, and after rt_update_geometry it is that
+ *   of a fresh upload of the moved scene.  The tree only culls: a child box is skipped when it lies further from the query box on
+ *   some axis than a margin past the statement's own rounding.  The list gives no spatial bound - a key says
+ *   nothing about where its primitive lies - so list mode and RT_QUERY_COUNT_ALL both visit every node the box reaches, and a box
+ *   that spans the scene tests every primitive of it, as RT_QUERY_COUNT_ALL with radius = +inf does for rt_closest_point_all; a full
+ *   list only spares the test of a record whose key is above its last entry's.
+ * Buffers, chunking, the split over devices, synchronisation, side effects and statistics as for rt_closest_point_all: the three
+ *   pointers are all host memory or all device memory of one context device (boxes 16-byte aligned, prims and counts 4-byte
+ *   aligned), anything else is RT_ERR_BAD_ARG; batches go in chunks of at most RT_QUERY_CHUNK / max(max_prims, 1) boxes; a context
+ *   over several devices splits a host batch into one contiguous range per device; synchronous, first waits for an rt_dispatch_tile
+ *   in flight; rays = n, the other counts 0, kernel_ms the maximum over devices, node_visits / tri_tests (the records read) only
+ *   with RT_QUERY_COUNTERS; the last frame, the rt_read_* results and a running accumulation are left alone.
+ * Errors: n == 0 is RT_OK; a NULL boxes, or a NULL prims with max_prims > 0, max_prims > RT_OVERLAP_MAX, max_prims == 0 without
+ *   RT_QUERY_COUNT_ALL or RT_OVERLAP_ANY and counts, RT_OVERLAP_ANY with max_prims > 0 or with RT_QUERY_COUNT_ALL, and unknown flag
+ *   bits are RT_ERR_BAD_ARG and change nothing; a call before any upload is RT_ERR_NOT_UPLOADED.  An empty scene gives counts of 0
+ *   and ids of 0xFFFFFFFF.
+ * --------------------------------------------------------------------------------------------------------------- */
+typedef struct rt_box {      /* an axis-aligned box, closed */
+    float center[3];
+    uint32_t _pad0;          /* pads are ignored */
+    float half_extent[3];    /* >= 0 per axis; 0 is allowed (a slab, a segment, a point) */
+    uint32_t _pad1;
+} rt_box; /* 32 bytes */
+
+RT_STATIC_ASSERT(sizeof(rt_box) == 32 && offsetof(rt_box, center) == 0 && offsetof(rt_box, _pad0) == 12 && offsetof(rt_box, half_extent) == 16 &&
+                     offsetof(rt_box, _pad1) == 28,
+                 "rt_box is 32 B: center, _pad0 at 12, half_extent at 16, _pad1 at 28");
+
+#define RT_OVERLAP_MAX 32u
+#define RT_OVERLAP_ANY 4u   /* rt_overlap_box only: counts[i] = 1 if anything touches box i, else 0; stops at the first */
+
+int rt_overlap_box(rt_ctx* ctx, const rt_box* boxes, size_t n, uint32_t max_prims,
+                   uint32_t* prims,   /* n * max_prims ids, query-major, rt_hit.prim_id's encoding; unused slots 0xFFFFFFFF */
+                   uint32_t* counts,  /* n entries; may be NULL unless max_prims == 0 */
+                   uint32_t flags);   /* RT_QUERY_COUNTERS | RT_QUERY_COUNT_ALL | RT_OVERLAP_ANY */
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Geometry updates: new positions for the uploaded scene, in place (no reference counterpart; Embree's refit build,
