@@ -1,7 +1,7 @@
 // closest_point_all_rules.h — the nearest-K query (rt_closest_point_all, include/rt_hip.h "Closest-point queries"), stated once.
 //
 // What closest_point_rules.h states for the single nearest primitive stays as it is and is used as it is: the candidate of a triangle
-// and of a sphere, the order among candidates, the lower bound of a node's child boxes, the visiting order and the stack discipline.
+// and of a sphere, the order among candidates, the lower bound of a node's child boxes and the visiting order.
 // This file adds the two things a collecting query needs: a sorted list of the K lowest candidates with the bound that follows from
 // it, and the walk of cp_walk culled by that bound.  Two pieces of code call it: the kernel (closest_point_all.hip) and the host walk
 // of tests/check_closest_point_all.cpp, which holds every record and count to a brute-force sort before any kernel runs.  The same
@@ -74,50 +74,31 @@ RT_RULE uint32_t cp_list_count(const CpList& l) {
     return COUNT_ALL ? l.total : l.n;
 }
 
-// ---- 8. The walk: cp_walk's loop (rule 5) - the same groups, cp_node_bounds / cp_pass / cp_first_slot, one stack entry per visit at
-// most, the same clamp of a leaf's length - with every record offered to the list and both cp_pass calls held against cp_list_cull
-// instead of the best distance.  The stack bound of rule 5 does not depend on what culls, so it holds here unchanged.
+// ---- 8. The walk: group_walk (group_walk.h) with cp_walk's bound and order, every record offered to the list and both passes held
+// against cp_list_cull instead of the best distance.
+template <bool COUNT_ALL>
+struct CpAllVisit {
+    const float* p;
+    float p_max, L[8];
+    CpList& list;
+
+    RT_RULE uint32_t enter(const uint32_t w[20]) {
+        uint32_t code;
+        cp_node_bounds(w, p, p_max, L, code);
+        return code;
+    }
+    RT_RULE uint32_t pass(uint32_t occupied) const { return cp_pass(L, cp_list_cull<COUNT_ALL>(list), occupied); }
+    template <class Access>
+    RT_RULE bool leaf(Access& acc, uint32_t slot, const float q[9], const uint32_t ids[3]) {
+        float v, wgt;
+        cp_list_offer<COUNT_ALL>(acc, list, cp_order(cp_triangle(q, q + 3, q + 6, p, v, wgt), ids[1] ^ RT_PRIM_SPHERE_FLAG), slot);
+        return false;
+    }
+};
 template <bool COUNT_ALL, class Access>
 RT_RULE void cp_walk_all(Access& acc, uint32_t n_nodes, const float p[3], CpList& list) {
-    if (n_nodes == 0u) return;
-    const float p_max = cp_p_max(p);
-    uint32_t g_base = 0u, g_bits = 1u | (1u << 8); // the root as the only child of a group
-    int sp = 0;
-    for (;;) {
-        if ((g_bits & 0xFFu) == 0u) {
-            if (sp == 0) break;
-            sp--;
-            acc.pop(sp, g_base, g_bits);
-        }
-        const uint32_t i = cp_first_slot(g_bits, (g_bits >> 16) & 7u);
-        g_bits ^= 1u << i;
-        const uint32_t idx = g_base + cp_popc((g_bits >> 8) & ((1u << i) - 1u)); // inner slots below i
-        if (g_bits & 0xFFu) {
-            acc.push(sp, g_base, g_bits);
-            sp++;
-        }
-        uint32_t w[20], code;
-        float L[8];
-        acc.node(idx, w);
-        cp_node_bounds(w, p, p_max, L, code);
-        const uint32_t imask = w[3] >> 24, lmask = w[6] & 0xFFu;
-        uint32_t t = cp_pass(L, cp_list_cull<COUNT_ALL>(list), lmask);
-        while (t) {
-            const uint32_t sl = cp_first_slot(t, code);
-            t ^= 1u << sl;
-            const uint32_t first = w[5] + RT_DEV_LEAF_STRIDE * cp_popc(lmask & ((1u << sl) - 1u));
-            uint32_t len = 1u;
-            for (uint32_t x = 0; x < len; x++) {
-                float q[9], v, wgt;
-                uint32_t ids[3];
-                acc.record(first + x, q, ids);
-                if (x == 0u) len = ids[2] < RT_DEV_LEAF_STRIDE ? ids[2] : RT_DEV_LEAF_STRIDE; // 1..4; never past the leaf's own records
-                cp_list_offer<COUNT_ALL>(acc, list, cp_order(cp_triangle(q, q + 3, q + 6, p, v, wgt), ids[1] ^ RT_PRIM_SPHERE_FLAG), first + x);
-            }
-        }
-        g_base = w[4];
-        g_bits = cp_pass(L, cp_list_cull<COUNT_ALL>(list), imask) | (imask << 8) | (code << 16); // by the bound the leaves left
-    }
+    CpAllVisit<COUNT_ALL> v{p, cp_p_max(p), {}, list};
+    group_walk(acc, n_nodes, v);
 }
 
 } // namespace rt

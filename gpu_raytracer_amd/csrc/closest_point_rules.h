@@ -2,8 +2,8 @@
 //
 // Two pieces of code answer it: the kernel (closest_point.hip) and the host walk of tests/check_closest_point.cpp, which holds the
 // whole walk to a brute force before any kernel runs.  Both call what is here: the candidate of a triangle and of a sphere, the order
-// among candidates, the lower bound of a node's eight child boxes and the group walk with its stack discipline.  Plain inline
-// functions under the RT_RULE convention of bvh_rules.h: host and device under hipcc, host only under any other compiler.  Every
+// among candidates, the lower bound of a node's eight child boxes and the visitor that group_walk (group_walk.h) runs.  Plain inline
+// functions under the RT_RULE convention of group_walk.h: host and device under hipcc, host only under any other compiler.  Every
 // operation is one f32 rounding (the build uses -ffp-contract=off; the one fused operation is written fmaf), so numpy reproduces
 // the bits (tests/closest_point_cases.py).
 #ifndef RT_CLOSEST_POINT_RULES_H
@@ -12,13 +12,7 @@
 #include <cmath>
 #include <cstdint>
 
-#include "bvh_rules.h"
-
-#ifdef __HIPCC__
-#define RT_CP_UNROLL _Pragma("unroll")
-#else
-#define RT_CP_UNROLL
-#endif
+#include "group_walk.h"
 
 namespace rt {
 
@@ -161,81 +155,35 @@ RT_RULE uint32_t cp_pass(const float L[8], float best_dist2, uint32_t occupied) 
 }
 RT_RULE float cp_p_max(const float p[3]) { return rule_max(rule_max(fabsf(p[0]), fabsf(p[1])), fabsf(p[2])); }
 
-// The set slot of the 8-bit mask m (!= 0) with the smallest (slot XOR code): first_slot of device_common.h.
-RT_RULE uint32_t cp_first_slot(uint32_t m, uint32_t code) {
-    uint32_t q = m & 0xFFu;
-    if (code & 1u) q = ((q & 0x55u) << 1) | ((q >> 1) & 0x55u);
-    if (code & 2u) q = ((q & 0x33u) << 2) | ((q >> 2) & 0x33u);
-    if (code & 4u) q = ((q & 0x0Fu) << 4) | (q >> 4);
-    return (uint32_t)__builtin_ctz(q) ^ code;
-}
-RT_RULE uint32_t cp_popc(uint32_t x) {
-#ifdef __HIP_DEVICE_COMPILE__
-    return (uint32_t)__popc(x);
-#else
-    return (uint32_t)__builtin_popcount(x);
-#endif
-}
-
-// ---- 5. The walk.  The caller supplies how a node and a record are read, the stack and the counters:
-//   void node(uint32_t idx, uint32_t w[20])                   the words of node idx, and one node visit
-//   void record(uint32_t slot, float q[9], uint32_t ids[3])   v0 e1 e2 | material_id, prim_id, leaf_count of record `slot`, and one test
-//   void push(int sp, uint32_t base, uint32_t bits) / void pop(int sp, uint32_t& base, uint32_t& bits)     entry sp of the lane's stack
-// A GROUP is what is left of a node's inner children: g_base = the node's child_base, g_bits = the slots still to visit (bits 0..7),
-// the node's imask (bits 8..15) and the node's code (bits 16..18), so that a group taken off the stack keeps its order: its slots are
-// visited in increasing (slot XOR code), nearest corner first.  A visit takes one slot off the current group, parks the rest if any
-// is left - AT MOST ONE ENTRY PER VISIT - then tests the node's leaves that pass the bound, in the same order; then its inner
-// children that pass the bound of the best distance the leaves left become the current group.  A parked child that
-// has since fallen outside the best distance costs one node visit and is culled there.
-// Stack: entries are only added on the way down, one per level at most, and the level that holds the deepest inner nodes parks
-// nothing below it, so a tree of `depth` inner levels holds at most depth - 1 entries at a time: inside the depth + 2 =
-// DevScene::stack_entries / 2 + 1 entries the query kernels give a lane (k_rq_trace's LDS sizing).
+// ---- 5. The walk: group_walk (group_walk.h, which states the groups, the stack discipline and its bound) visited by the best
+// candidate so far.  `code`: the corner of the node nearest p first.
 struct CpBest {
     uint64_t order;  // cp_order of the best candidate so far, cp_start(radius) while there is none
     uint32_t slot;   // its record in DevScene::tris, or its sphere index; 0xFFFFFFFF: none
 };
+struct CpVisit {
+    const float* p;
+    float p_max, L[8];
+    CpBest& best;
+
+    RT_RULE uint32_t enter(const uint32_t w[20]) {
+        uint32_t code;
+        cp_node_bounds(w, p, p_max, L, code);
+        return code;
+    }
+    RT_RULE uint32_t pass(uint32_t occupied) const { return cp_pass(L, cp_best_dist2(best.order), occupied); }
+    template <class Access>
+    RT_RULE bool leaf(Access&, uint32_t slot, const float q[9], const uint32_t ids[3]) {
+        float v, wgt;
+        const uint64_t c = cp_order(cp_triangle(q, q + 3, q + 6, p, v, wgt), ids[1] ^ RT_PRIM_SPHERE_FLAG);
+        if (c < best.order) best.order = c, best.slot = slot;
+        return false;
+    }
+};
 template <class Access>
 RT_RULE void cp_walk(Access& acc, uint32_t n_nodes, const float p[3], CpBest& best) {
-    if (n_nodes == 0u) return;
-    const float p_max = cp_p_max(p);
-    uint32_t g_base = 0u, g_bits = 1u | (1u << 8); // the root as the only child of a group
-    int sp = 0;
-    for (;;) {
-        if ((g_bits & 0xFFu) == 0u) {
-            if (sp == 0) break;
-            sp--;
-            acc.pop(sp, g_base, g_bits);
-        }
-        const uint32_t i = cp_first_slot(g_bits, (g_bits >> 16) & 7u);
-        g_bits ^= 1u << i;
-        const uint32_t idx = g_base + cp_popc((g_bits >> 8) & ((1u << i) - 1u)); // inner slots below i
-        if (g_bits & 0xFFu) {
-            acc.push(sp, g_base, g_bits);
-            sp++;
-        }
-        uint32_t w[20], code;
-        float L[8];
-        acc.node(idx, w);
-        cp_node_bounds(w, p, p_max, L, code);
-        const uint32_t imask = w[3] >> 24, lmask = w[6] & 0xFFu;
-        uint32_t t = cp_pass(L, cp_best_dist2(best.order), lmask);
-        while (t) {
-            const uint32_t sl = cp_first_slot(t, code);
-            t ^= 1u << sl;
-            const uint32_t first = w[5] + RT_DEV_LEAF_STRIDE * cp_popc(lmask & ((1u << sl) - 1u));
-            uint32_t len = 1u;
-            for (uint32_t x = 0; x < len; x++) {
-                float q[9], v, wgt;
-                uint32_t ids[3];
-                acc.record(first + x, q, ids);
-                if (x == 0u) len = ids[2] < RT_DEV_LEAF_STRIDE ? ids[2] : RT_DEV_LEAF_STRIDE; // 1..4; never past the leaf's own records
-                const uint64_t c = cp_order(cp_triangle(q, q + 3, q + 6, p, v, wgt), ids[1] ^ RT_PRIM_SPHERE_FLAG);
-                if (c < best.order) best.order = c, best.slot = first + x;
-            }
-        }
-        g_base = w[4];
-        g_bits = cp_pass(L, cp_best_dist2(best.order), imask) | (imask << 8) | (code << 16); // by the best the leaves left
-    }
+    CpVisit v{p, cp_p_max(p), {}, best};
+    group_walk(acc, n_nodes, v);
 }
 
 // ---- 6. The answer, as the eight words of an rt_nearest: position | distance = sqrtf(dist2) | u, v (the weights of v1 and v2; 0 for

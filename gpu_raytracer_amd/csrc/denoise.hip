@@ -23,7 +23,7 @@ namespace {
 // ---------------------------------------------------------------------------------------------------------------------------------
 // acc per pixel: [albedo sum xyz, depth sum] [normal sum xyz, hits] while the call runs; the rt_aov record once it has ended.
 __global__ __launch_bounds__(WAVE) void k_aov_samples(DevScene sc, DevFrame fr, uint32_t s0, uint32_t ns, float4* __restrict__ acc) {
-    extern __shared__ uint2 s_stack[]; // (DevScene::stack_entries / 2 + 1) * 64 64-bit entries
+    extern __shared__ uint2 s_stack[]; // lane_stack_entries * 64 64-bit entries
     const PixelCoord px = block_pixel(fr);
     if (!px.valid) return;
     uint2* stack = s_stack + threadIdx.x;
@@ -167,7 +167,7 @@ namespace rt {
 hipError_t launch_aov_samples(const DevScene& sc, const DevFrame& fr, uint32_t s0, uint32_t ns, void* acc, hipStream_t stream) {
     if (fr.n_owned_tiles == 0 || ns == 0) return hipSuccess;
     const dim3 grid(fr.n_owned_tiles * blocks_per_tile(fr.tile_size)), block(WAVE);
-    const size_t lds = (size_t)(sc.stack_entries / 2u + 1u) * WAVE * sizeof(uint2); // one entry per level, as lds_bytes in kernels.hip
+    const size_t lds = lane_stack_bytes(sc);
     hipLaunchKernelGGL(k_aov_samples, grid, block, lds, stream, sc, fr, s0, ns, reinterpret_cast<float4*>(acc));
     return hipGetLastError();
 }

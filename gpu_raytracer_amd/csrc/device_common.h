@@ -59,6 +59,19 @@ struct Hit {
 struct Counts {
     uint32_t nodes, tris;
 };
+// a lane's walk counts into the query counters
+__device__ __forceinline__ void flush_counts(unsigned long long* counters, const Counts& cnt) {
+    atomicAdd(&counters[RT_CNT_NODE_VISITS], (unsigned long long)cnt.nodes);
+    atomicAdd(&counters[RT_CNT_TRI_TESTS], (unsigned long long)cnt.tris);
+}
+
+// The per-lane stack of the one-wave-per-block kernels, in dynamic LDS, lane-interleaved.  The one-ray-per-lane walks and the volume
+// queries' group_walk park only the group of siblings still to visit (a node's leaves are tested right after its visit), one entry
+// per level: half of DevScene::stack_entries, which is sized for the queue pipeline's walk (it also parks postponed leaf groups).  At
+// 512 bytes per entry and wave this decides how many waves fit a CU: depth 11 -> 6 KB, 26 waves per CU.  What a kernel keeps behind
+// the stack (a hit list, the lights) starts lane_stack_entries * WAVE entries in.
+__host__ __device__ __forceinline__ uint32_t lane_stack_entries(const DevScene& sc) { return sc.stack_entries / 2u + 1u; }
+__host__ __device__ __forceinline__ size_t lane_stack_bytes(const DevScene& sc) { return (size_t)lane_stack_entries(sc) * WAVE * sizeof(uint2); }
 
 // ------------------------------------------------------------------------------------
 // Ray generation.  Ray::from_screen_coordinates (shader/src/ray.rs:22-53) for mode 0,

@@ -33,12 +33,12 @@ __device__ __forceinline__ bool segment_valid(V3 o, V3 d, float dist) {
 template <bool COUNT>
 __global__ __launch_bounds__(WAVE, COUNT ? RT_DL_MIN_WAVES - 2 : RT_DL_MIN_WAVES) void k_dl_direct(DevScene sc, rt::DirectLightArgs a, const float4* __restrict__ points, uint4* __restrict__ out,
                                                      uint32_t n, unsigned long long* __restrict__ counters) {
-    // (DevScene::stack_entries / 2 + 1) * 64 64-bit stack entries, then n_lights DevLight, then (a.grids) n_lights DevShadowGrid
+    // lane_stack_entries * 64 64-bit stack entries, then n_lights DevLight, then (a.grids) n_lights DevShadowGrid
     extern __shared__ uint2 s_stack[];
     __shared__ uint32_t s_upto[WAVE], s_occ[WAVE];
     const uint32_t lane = threadIdx.x;
     uint2* stack = s_stack + lane;
-    DevLight* s_lights = reinterpret_cast<DevLight*>(s_stack + (size_t)(sc.stack_entries / 2u + 1u) * WAVE);
+    DevLight* s_lights = reinterpret_cast<DevLight*>(s_stack + (size_t)lane_stack_entries(sc) * WAVE);
     DevShadowGrid* s_grids = reinterpret_cast<DevShadowGrid*>(s_lights + sc.n_lights);
     stage_lights(s_lights, sc);
     if (a.grids) {
@@ -158,7 +158,7 @@ hipError_t launch_direct_light(const DevScene& sc, const DirectLightArgs& a, con
                                unsigned long long* counters, hipStream_t stream) {
     if (n == 0) return hipSuccess;
     const dim3 grid((n + WAVE - 1) / WAVE), block(WAVE);
-    const size_t lds = (size_t)(sc.stack_entries / 2u + 1u) * WAVE * sizeof(uint2) // one entry per level, as launch_ray_query
+    const size_t lds = lane_stack_bytes(sc)
                        + (size_t)sc.n_lights * (sizeof(DevLight) + (a.grids ? sizeof(DevShadowGrid) : 0));
     const float4* p = reinterpret_cast<const float4*>(points);
     uint4* o = reinterpret_cast<uint4*>(out);

@@ -4,16 +4,14 @@
 //
 // Nothing that decides a bit is stated here: the directions, sphere containment, the stop rule, the majority and the signing are in
 // inside_rules.h; a vote is the count traverse_all (multi_hit_walk.h) gives a list of capacity 0 with COUNT_ALL, the walk of
-// rt_intersect_all's pure count; the magnitude is cp_walk (closest_point_rules.h) through the LaneAccess of k_cp_nearest.  One lane
+// rt_intersect_all's pure count; the magnitude is k_cp_nearest's lane (cp_nearest_lane, query_lane.h).  One lane
 // per point, one wave per block, the launch shape of k_cp_nearest; the per-lane stack in LDS serves the closest-point walk first and
 // then each ray walk in turn - every walk starts and ends with an empty stack, and a lane runs them one after another.
 #include "inside.h"
 
-#include "closest_point_lane.h"
-#include "closest_point_rules.h"
-#include "device_common.h"
 #include "inside_rules.h"
 #include "multi_hit_walk.h"
+#include "query_lane.h"
 
 using namespace rtdev;
 
@@ -24,7 +22,7 @@ namespace {
 template <bool COUNT, bool DISTANCE>
 __global__ __launch_bounds__(WAVE) void k_inside(DevScene sc, const float4* __restrict__ points, void* __restrict__ out, uint8_t* __restrict__ votes,
                                                   uint32_t n, uint32_t rays, unsigned long long* __restrict__ counters) {
-    extern __shared__ uint2 s_stack[]; // (DevScene::stack_entries / 2 + 1) * 64 64-bit entries
+    extern __shared__ uint2 s_stack[]; // lane_stack_entries * 64 64-bit entries
     const uint32_t i = blockIdx.x * WAVE + threadIdx.x;
     if (i >= n) return;
     const float4 pq = points[i];
@@ -38,34 +36,8 @@ __global__ __launch_bounds__(WAVE) void k_inside(DevScene sc, const float4* __re
             sphere_inside = sphere_inside || rt::inside_sphere(sc.spheres[s].center, sc.spheres[s].radius, p);
     uint32_t r[8];
     if (DISTANCE) { // k_cp_nearest's answer
-        LaneAccess<COUNT> acc;
-        acc.nodes = reinterpret_cast<const uint4*>(sc.nodes);
-        acc.tris = sc.tris;
-        acc.stack = stack;
-        acc.cnt = {0u, 0u};
-        rt::cp_answer_miss(pq.w, r);
-        if (valid) {
-            rt::CpBest best;
-            best.order = rt::cp_start(pq.w);
-            best.slot = 0xFFFFFFFFu;
-            float pos[3];
-            for (uint32_t s = 0; s < sc.n_spheres; s++) { // the spheres by brute force, in index order
-                const uint64_t c = rt::cp_order(rt::cp_sphere(sc.spheres[s].center, sc.spheres[s].radius, p, pos), s);
-                if (c < best.order) best.order = c, best.slot = s;
-            }
-            rt::cp_walk(acc, sc.n_nodes, p, best);
-            if (best.slot != 0xFFFFFFFFu) {
-                if ((uint32_t)best.order & RT_PRIM_SPHERE_FLAG) { // a triangle's key
-                    float q[9];
-                    uint32_t ids[3];
-                    LaneAccess<false>{nullptr, sc.tris, nullptr, {0u, 0u}}.record(best.slot, q, ids);
-                    rt::cp_answer_triangle(q, ids[0], best.order, p, r);
-                } else {
-                    const DevSphere& s = sc.spheres[best.slot];
-                    rt::cp_answer_sphere(s.center, s.radius, s.material_id, best.order, p, r);
-                }
-            }
-        }
+        LaneAccess<COUNT> acc(sc, s_stack);
+        cp_nearest_lane(sc, acc, p, pq.w, r); // `valid` is its own test of the query
         cnt = acc.cnt;
     }
     // the votes, in order; a lane whose votes are not asked for stops at its majority, and traces nothing inside a sphere
@@ -94,10 +66,7 @@ __global__ __launch_bounds__(WAVE) void k_inside(DevScene sc, const float4* __re
     }
     if (votes) votes[i] = (uint8_t)odd;
     atomicAdd(&counters[RT_CNT_SEGMENTS], (unsigned long long)traced);
-    if (COUNT) {
-        atomicAdd(&counters[RT_CNT_NODE_VISITS], (unsigned long long)cnt.nodes);
-        atomicAdd(&counters[RT_CNT_TRI_TESTS], (unsigned long long)cnt.tris);
-    }
+    if (COUNT) flush_counts(counters, cnt);
 }
 
 } // namespace
@@ -109,7 +78,7 @@ hipError_t launch_inside(const DevScene& sc, const void* points, void* out, uint
     if (n == 0) return hipSuccess;
     if (!inside_rays_valid(rays) || !counters) return hipErrorInvalidValue;
     const dim3 grid((n + WAVE - 1) / WAVE), block(WAVE);
-    const size_t lds = (size_t)(sc.stack_entries / 2u + 1u) * WAVE * sizeof(uint2); // as launch_closest_point: one stack for both walks
+    const size_t lds = lane_stack_bytes(sc); // one stack for both walks
     const float4* p = reinterpret_cast<const float4*>(points);
     if (distance) {
         if (count) hipLaunchKernelGGL((k_inside<true, true>), grid, block, lds, stream, sc, p, out, votes, n, rays, counters);

@@ -35,7 +35,7 @@ namespace {
 // ------------------------------------------------------------------------------------
 template <bool COUNT>
 __global__ __launch_bounds__(WAVE) void k_render_reference(DevScene sc, DevFrame fr, DevTargets tg) {
-    extern __shared__ uint2 s_stack[]; // (DevScene::stack_entries / 2 + 1) * 64 64-bit entries (lds_bytes below): one entry per visit
+    extern __shared__ uint2 s_stack[]; // lane_stack_entries * 64 64-bit entries: one entry per visit
     PixelCoord px = block_pixel(fr);
     if (!px.valid) return;
     uint2* stack = s_stack + threadIdx.x;
@@ -121,7 +121,7 @@ __device__ __forceinline__ V3 ext_trace_path(const DevScene& sc, const DevFrame&
 // others trace their own samples n .. n+spp-1 and add them to S (and the odd-indexed ones to H); k_ad_image writes the targets.
 template <bool COUNT, bool AD>
 __global__ __launch_bounds__(WAVE) void k_render_extended(DevScene sc, DevFrame fr, DevTargets tg) {
-    extern __shared__ uint2 s_stack[]; // (DevScene::stack_entries / 2 + 1) * 64 64-bit entries (lds_bytes below): one entry per visit
+    extern __shared__ uint2 s_stack[]; // lane_stack_entries * 64 64-bit entries: one entry per visit
     PixelCoord px = block_pixel(fr);
     if (AD) px.valid = px.valid && ad_lane_active(fr, blockIdx.x, threadIdx.x);
     uint2* stack = s_stack + threadIdx.x;
@@ -175,7 +175,7 @@ enum : uint32_t { ST_NEW_SAMPLE = 0, ST_CLOSEST_DONE = 1, ST_SHADOW_DONE = 2, ST
 
 template <bool COUNT, bool AD> // AD: the adaptive variant, as k_render_extended's
 __global__ __launch_bounds__(WAVE, RT_SM_MIN_WAVES) void k_render_extended_sm(DevScene sc, DevFrame fr, DevTargets tg) {
-    extern __shared__ uint2 s_stack[]; // (DevScene::stack_entries / 2 + 1) * 64 64-bit entries (lds_bytes below): one entry per visit
+    extern __shared__ uint2 s_stack[]; // lane_stack_entries * 64 64-bit entries: one entry per visit
     PixelCoord px = block_pixel(fr);
     if (AD) px.valid = px.valid && ad_lane_active(fr, blockIdx.x, threadIdx.x);
     uint2* __restrict__ stack = s_stack + threadIdx.x;
@@ -428,11 +428,6 @@ __global__ __launch_bounds__(WAVE, RT_SM_MIN_WAVES) void k_render_extended_sm(De
 
 namespace rt {
 
-// The one-ray-per-lane walks park only the group of siblings still to visit (a node's leaves are tested right after its visit),
-// one entry per level: half of DevScene::stack_entries, which is sized for the queue pipeline's walk (it also parks postponed leaf
-// groups).  At 512 bytes per entry and wave this decides how many waves fit a CU: depth 11 -> 6 KB, 26 waves per CU.
-static size_t lds_bytes(const DevScene& sc) { return (size_t)(sc.stack_entries / 2u + 1u) * WAVE * sizeof(uint2); }
-
 __global__ __launch_bounds__(256) void k_combine_rgba8(const uint32_t* __restrict__ red, const uint32_t* __restrict__ green, const uint32_t* __restrict__ blue,
                                                         uint32_t* __restrict__ out, size_t n) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
@@ -471,9 +466,9 @@ hipError_t launch_render_reference(const DevScene& sc, const DevFrame& fr, const
     if (n_tiles == 0) return hipSuccess;
     dim3 grid(n_tiles * blocks_per_tile(fr.tile_size)), block(WAVE);
     if (counters)
-        hipLaunchKernelGGL(k_render_reference<true>, grid, block, lds_bytes(sc), stream, sc, fr, tg);
+        hipLaunchKernelGGL(k_render_reference<true>, grid, block, lane_stack_bytes(sc), stream, sc, fr, tg);
     else
-        hipLaunchKernelGGL(k_render_reference<false>, grid, block, lds_bytes(sc), stream, sc, fr, tg);
+        hipLaunchKernelGGL(k_render_reference<false>, grid, block, lane_stack_bytes(sc), stream, sc, fr, tg);
     return hipGetLastError();
 }
 
@@ -483,22 +478,22 @@ hipError_t launch_render_extended(const DevScene& sc, const DevFrame& fr, const 
     dim3 grid(n_tiles * blocks_per_tile(fr.tile_size)), block(WAVE);
     if (kernel != FrameKernel::MEGAKERNEL_SM) { // the nested loops (also the one-pass kernel)
         if (fr.adaptive && counters)
-            hipLaunchKernelGGL((k_render_extended<true, true>), grid, block, lds_bytes(sc), stream, sc, fr, tg);
+            hipLaunchKernelGGL((k_render_extended<true, true>), grid, block, lane_stack_bytes(sc), stream, sc, fr, tg);
         else if (fr.adaptive)
-            hipLaunchKernelGGL((k_render_extended<false, true>), grid, block, lds_bytes(sc), stream, sc, fr, tg);
+            hipLaunchKernelGGL((k_render_extended<false, true>), grid, block, lane_stack_bytes(sc), stream, sc, fr, tg);
         else if (counters)
-            hipLaunchKernelGGL((k_render_extended<true, false>), grid, block, lds_bytes(sc), stream, sc, fr, tg);
+            hipLaunchKernelGGL((k_render_extended<true, false>), grid, block, lane_stack_bytes(sc), stream, sc, fr, tg);
         else
-            hipLaunchKernelGGL((k_render_extended<false, false>), grid, block, lds_bytes(sc), stream, sc, fr, tg);
+            hipLaunchKernelGGL((k_render_extended<false, false>), grid, block, lane_stack_bytes(sc), stream, sc, fr, tg);
     } else {
         if (fr.adaptive && counters)
-            hipLaunchKernelGGL((k_render_extended_sm<true, true>), grid, block, lds_bytes(sc), stream, sc, fr, tg);
+            hipLaunchKernelGGL((k_render_extended_sm<true, true>), grid, block, lane_stack_bytes(sc), stream, sc, fr, tg);
         else if (fr.adaptive)
-            hipLaunchKernelGGL((k_render_extended_sm<false, true>), grid, block, lds_bytes(sc), stream, sc, fr, tg);
+            hipLaunchKernelGGL((k_render_extended_sm<false, true>), grid, block, lane_stack_bytes(sc), stream, sc, fr, tg);
         else if (counters)
-            hipLaunchKernelGGL((k_render_extended_sm<true, false>), grid, block, lds_bytes(sc), stream, sc, fr, tg);
+            hipLaunchKernelGGL((k_render_extended_sm<true, false>), grid, block, lane_stack_bytes(sc), stream, sc, fr, tg);
         else
-            hipLaunchKernelGGL((k_render_extended_sm<false, false>), grid, block, lds_bytes(sc), stream, sc, fr, tg);
+            hipLaunchKernelGGL((k_render_extended_sm<false, false>), grid, block, lane_stack_bytes(sc), stream, sc, fr, tg);
     }
     return hipGetLastError();
 }

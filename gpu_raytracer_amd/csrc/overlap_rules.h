@@ -2,8 +2,8 @@
 //
 // Two pieces of code answer it: the kernel (overlap.hip) and the host walk of tests/check_overlap.cpp, which holds the whole walk to a
 // brute force over all primitives before any kernel runs.  Both call what is here: when a triangle and when a sphere TOUCHES a closed
-// axis-aligned box, the list of the K lowest keys, which child boxes of a node the query box reaches, and the group walk with
-// cp_walk's stack discipline.  The RT_RULE convention of closest_point_rules.h: host and device under hipcc, host only elsewhere;
+// axis-aligned box, the list of the K lowest keys, which child boxes of a node the query box reaches, and the visitor that
+// group_walk (group_walk.h) runs.  The RT_RULE convention of group_walk.h: host and device under hipcc, host only elsewhere;
 // every operation is one f32 rounding and nothing is fused (the build uses -ffp-contract=off), so numpy reproduces the bits
 // (tests/overlap_cases.py).  dot is cp_dot.
 //
@@ -179,55 +179,33 @@ RT_RULE uint32_t ov_node_reach(const uint32_t w[20], const OvBox& b, uint32_t& c
     return reach;
 }
 
-// ---- 6. The walk: cp_walk's groups and stack discipline (closest_point_rules.h rule 5) - a visit takes one slot off the current
-// group, parks the rest if any is left, AT MOST ONE ENTRY PER VISIT, tests the node's leaves, then its inner children become the
-// current group - so a tree of `depth` inner levels holds at most depth - 1 entries: inside the DevScene::stack_entries / 2 + 1 the
-// query kernels give a lane.  What a node's box reaches does not change during a walk, so one mask serves its leaves and its inner
-// children.  The caller supplies cp_walk's node / record / push / pop and the list of rule 4.  In ANY mode the walk ends at the first
+// ---- 6. The walk: group_walk (group_walk.h).  What a node's box reaches does not change during a walk, so one mask serves its
+// leaves and its inner children.  The caller supplies the Access with the list of rule 4.  In ANY mode the walk ends at the first
 // touching primitive (the caller does not start it when a sphere already touches).
+template <int MODE>
+struct OvVisit {
+    const OvBox& b;
+    OvList& list;
+    uint32_t reach;
+
+    RT_RULE uint32_t enter(const uint32_t w[20]) {
+        uint32_t code;
+        reach = ov_node_reach(w, b, code);
+        return code;
+    }
+    RT_RULE uint32_t pass(uint32_t occupied) const { return reach & occupied; }
+    template <class Access>
+    RT_RULE bool leaf(Access& acc, uint32_t, const float q[9], const uint32_t ids[3]) {
+        const uint32_t key = ids[1] ^ RT_PRIM_SPHERE_FLAG;
+        if (!(ov_list_wants<MODE>(list, key) && ov_triangle(q, q + 3, q + 6, b.c, b.h))) return false;
+        ov_list_offer(acc, list, key);
+        return MODE == OV_ANY;
+    }
+};
 template <int MODE, class Access>
 RT_RULE void ov_walk(Access& acc, uint32_t n_nodes, const OvBox& b, OvList& list) {
-    if (n_nodes == 0u) return;
-    uint32_t g_base = 0u, g_bits = 1u | (1u << 8); // the root as the only child of a group
-    int sp = 0;
-    for (;;) {
-        if ((g_bits & 0xFFu) == 0u) {
-            if (sp == 0) break;
-            sp--;
-            acc.pop(sp, g_base, g_bits);
-        }
-        const uint32_t i = cp_first_slot(g_bits, (g_bits >> 16) & 7u);
-        g_bits ^= 1u << i;
-        const uint32_t idx = g_base + cp_popc((g_bits >> 8) & ((1u << i) - 1u)); // inner slots below i
-        if (g_bits & 0xFFu) {
-            acc.push(sp, g_base, g_bits);
-            sp++;
-        }
-        uint32_t w[20], code;
-        acc.node(idx, w);
-        const uint32_t reach = ov_node_reach(w, b, code);
-        const uint32_t imask = w[3] >> 24, lmask = w[6] & 0xFFu;
-        uint32_t t = reach & lmask;
-        while (t) {
-            const uint32_t sl = cp_first_slot(t, code);
-            t ^= 1u << sl;
-            const uint32_t first = w[5] + RT_DEV_LEAF_STRIDE * cp_popc(lmask & ((1u << sl) - 1u));
-            uint32_t len = 1u;
-            for (uint32_t x = 0; x < len; x++) {
-                float q[9];
-                uint32_t ids[3];
-                acc.record(first + x, q, ids);
-                if (x == 0u) len = ids[2] < RT_DEV_LEAF_STRIDE ? ids[2] : RT_DEV_LEAF_STRIDE; // 1..4; never past the leaf's own records
-                const uint32_t key = ids[1] ^ RT_PRIM_SPHERE_FLAG;
-                if (ov_list_wants<MODE>(list, key) && ov_triangle(q, q + 3, q + 6, b.c, b.h)) {
-                    ov_list_offer(acc, list, key);
-                    if (MODE == OV_ANY) return;
-                }
-            }
-        }
-        g_base = w[4];
-        g_bits = (reach & imask) | (imask << 8) | (code << 16);
-    }
+    OvVisit<MODE> v{b, list, 0u};
+    group_walk(acc, n_nodes, v);
 }
 
 } // namespace rt

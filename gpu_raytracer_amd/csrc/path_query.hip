@@ -28,7 +28,7 @@ template <bool COUNT>
 __global__ __launch_bounds__(WAVE, RT_PQ_MIN_WAVES) void k_pq_trace(DevScene sc, rt::PathArgs a, const float4* __restrict__ rays, uint64_t first,
                                                                                                uint32_t lanes, uint4* __restrict__ dst,
                                                                                                unsigned long long* __restrict__ counters) {
-    extern __shared__ uint2 s_stack[]; // (DevScene::stack_entries / 2 + 1) * 64 64-bit entries
+    extern __shared__ uint2 s_stack[]; // lane_stack_entries * 64 64-bit entries
     const uint32_t lane = threadIdx.x;
     uint2* stack = s_stack + lane;
     const uint32_t S = a.samples;
@@ -138,7 +138,7 @@ namespace rt {
 hipError_t launch_path_query(const DevScene& sc, const PathArgs& a, const void* rays, uint64_t first, uint32_t n, void* scratch, void* out, bool count,
                              unsigned long long* counters, hipStream_t stream) {
     if (n == 0) return hipSuccess;
-    const size_t lds = (size_t)(sc.stack_entries / 2u + 1u) * WAVE * sizeof(uint2); // one entry per level, as launch_surface_query
+    const size_t lds = lane_stack_bytes(sc);
     const uint32_t lanes = n * a.samples;                                          // <= RT_QUERY_CHUNK (the caller's chunking)
     const float4* r = reinterpret_cast<const float4*>(rays);
     uint4* o = reinterpret_cast<uint4*>(out);

@@ -20,7 +20,7 @@ namespace {
 template <bool COUNT, bool ANY_HIT>
 __global__ __launch_bounds__(WAVE) void k_rq_trace(DevScene sc, const float4* __restrict__ rays, void* __restrict__ out, uint32_t n,
                                                     unsigned long long* __restrict__ counters) {
-    extern __shared__ uint2 s_stack[]; // (DevScene::stack_entries / 2 + 1) * 64 64-bit entries
+    extern __shared__ uint2 s_stack[]; // lane_stack_entries * 64 64-bit entries
     const uint32_t i = blockIdx.x * WAVE + threadIdx.x;
     if (i >= n) return;
     uint2* stack = s_stack + threadIdx.x;
@@ -54,10 +54,7 @@ __global__ __launch_bounds__(WAVE) void k_rq_trace(DevScene sc, const float4* __
         }
         reinterpret_cast<uint4*>(out)[i] = make_uint4(__float_as_uint(hit.t), __float_as_uint(uv[0]), __float_as_uint(uv[1]), hit.prim);
     }
-    if (COUNT) {
-        atomicAdd(&counters[RT_CNT_NODE_VISITS], (unsigned long long)cnt.nodes);
-        atomicAdd(&counters[RT_CNT_TRI_TESTS], (unsigned long long)cnt.tris);
-    }
+    if (COUNT) flush_counts(counters, cnt);
 }
 
 // One rt_ray per lane -> max_hits rt_hit records at out[i * max_hits ..] (the listed candidates, then misses) and, counts != null,
@@ -79,7 +76,7 @@ __global__ __launch_bounds__(WAVE) void k_rq_trace_all(DevScene sc, const float4
     valid = valid && tmin < tmax;
     Counts cnt = {0u, 0u};
     HitList list;
-    list.init(reinterpret_cast<uint32_t*>(s_stack + (size_t)(sc.stack_entries / 2u + 1u) * WAVE) + threadIdx.x, max_hits, tmax);
+    list.init(reinterpret_cast<uint32_t*>(s_stack + (size_t)lane_stack_entries(sc) * WAVE) + threadIdx.x, max_hits, tmax);
     if (valid) {
         for (uint32_t s = 0; s < sc.n_spheres; s++) {
             float t;
@@ -104,10 +101,7 @@ __global__ __launch_bounds__(WAVE) void k_rq_trace_all(DevScene sc, const float4
         rec[k] = r;
     }
     if (counts) counts[i] = COUNT_ALL ? list.total : list.n;
-    if (COUNT) {
-        atomicAdd(&counters[RT_CNT_NODE_VISITS], (unsigned long long)cnt.nodes);
-        atomicAdd(&counters[RT_CNT_TRI_TESTS], (unsigned long long)cnt.tris);
-    }
+    if (COUNT) flush_counts(counters, cnt);
 }
 
 // rt_camera_rays: camera_ray of the frames at the pixel centres, one lane per pixel.
@@ -131,7 +125,7 @@ hipError_t launch_ray_query(const DevScene& sc, const void* rays, void* out, uin
                             hipStream_t stream) {
     if (n == 0) return hipSuccess;
     const dim3 grid((n + WAVE - 1) / WAVE), block(WAVE);
-    const size_t lds = (size_t)(sc.stack_entries / 2u + 1u) * WAVE * sizeof(uint2); // one entry per level, as lds_bytes in kernels.hip
+    const size_t lds = lane_stack_bytes(sc);
     const float4* r = reinterpret_cast<const float4*>(rays);
     if (any_hit) {
         if (counters) hipLaunchKernelGGL((k_rq_trace<true, true>), grid, block, lds, stream, sc, r, out, n, counters);
@@ -147,7 +141,7 @@ hipError_t launch_ray_query_all(const DevScene& sc, const void* rays, void* hits
                                 unsigned long long* counters, hipStream_t stream) {
     if (n == 0) return hipSuccess;
     const dim3 grid((n + WAVE - 1) / WAVE), block(WAVE);
-    const size_t lds = (size_t)(sc.stack_entries / 2u + 1u) * WAVE * sizeof(uint2) + (size_t)max_hits * 3u * WAVE * sizeof(uint32_t); // stack + list
+    const size_t lds = lane_stack_bytes(sc) + (size_t)max_hits * 3u * WAVE * sizeof(uint32_t); // stack + list
     const float4* r = reinterpret_cast<const float4*>(rays);
     uint4* h = reinterpret_cast<uint4*>(hits);
     if (count_all) {

@@ -19,7 +19,7 @@ namespace {
 template <bool COUNT>
 __global__ __launch_bounds__(WAVE) void k_sq_surface(DevScene sc, const float4* __restrict__ rays, uint4* __restrict__ out, uint32_t n,
                                                       unsigned long long* __restrict__ counters) {
-    extern __shared__ uint2 s_stack[]; // (DevScene::stack_entries / 2 + 1) * 64 64-bit entries
+    extern __shared__ uint2 s_stack[]; // lane_stack_entries * 64 64-bit entries
     const uint32_t i = blockIdx.x * WAVE + threadIdx.x;
     if (i >= n) return;
     uint2* stack = s_stack + threadIdx.x;
@@ -51,10 +51,7 @@ __global__ __launch_bounds__(WAVE) void k_sq_surface(DevScene sc, const float4* 
     }
     out[2 * (size_t)i] = r0;
     out[2 * (size_t)i + 1] = r1;
-    if (COUNT) {
-        atomicAdd(&counters[RT_CNT_NODE_VISITS], (unsigned long long)cnt.nodes);
-        atomicAdd(&counters[RT_CNT_TRI_TESTS], (unsigned long long)cnt.tris);
-    }
+    if (COUNT) flush_counts(counters, cnt);
 }
 
 // One lane per (point, sample): lane g of the batch (g0 = the launch's first) is sample g % S of point g / S, so a point's samples sit
@@ -102,10 +99,7 @@ __global__ __launch_bounds__(WAVE) void k_sq_ao(DevScene sc, const float4* __res
         const uint32_t c = (uint32_t)__popcll(votes & run);
         if (c) atomicAdd(&unoccluded[p], c);
     }
-    if (COUNT) {
-        atomicAdd(&counters[RT_CNT_NODE_VISITS], (unsigned long long)cnt.nodes);
-        atomicAdd(&counters[RT_CNT_TRI_TESTS], (unsigned long long)cnt.tris);
-    }
+    if (COUNT) flush_counts(counters, cnt);
 }
 
 __global__ __launch_bounds__(256) void k_sq_ao_finish(const uint32_t* __restrict__ unoccluded, uint32_t n, float samples, float* __restrict__ visibility,
@@ -124,7 +118,7 @@ namespace rt {
 hipError_t launch_surface_query(const DevScene& sc, const void* rays, void* out, uint32_t n, unsigned long long* counters, hipStream_t stream) {
     if (n == 0) return hipSuccess;
     const dim3 grid((n + WAVE - 1) / WAVE), block(WAVE);
-    const size_t lds = (size_t)(sc.stack_entries / 2u + 1u) * WAVE * sizeof(uint2); // one entry per level, as launch_ray_query
+    const size_t lds = lane_stack_bytes(sc);
     const float4* r = reinterpret_cast<const float4*>(rays);
     uint4* o = reinterpret_cast<uint4*>(out);
     if (counters) hipLaunchKernelGGL((k_sq_surface<true>), grid, block, lds, stream, sc, r, o, n, counters);
@@ -135,7 +129,7 @@ hipError_t launch_surface_query(const DevScene& sc, const void* rays, void* out,
 hipError_t launch_ao(const DevScene& sc, const void* points, uint64_t first, uint32_t n, const AoParams& ap, uint32_t* unoccluded,
                      unsigned long long* counters, hipStream_t stream) {
     const uint64_t lanes = (uint64_t)n * ap.samples;
-    const size_t lds = (size_t)(sc.stack_entries / 2u + 1u) * WAVE * sizeof(uint2);
+    const size_t lds = lane_stack_bytes(sc);
     const float4* p = reinterpret_cast<const float4*>(points);
     for (uint64_t g0 = 0; g0 < lanes; g0 += RT_AO_LAUNCH_LANES) {
         const uint64_t m = std::min<uint64_t>(RT_AO_LAUNCH_LANES, lanes - g0);

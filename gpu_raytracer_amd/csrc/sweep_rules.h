@@ -2,8 +2,8 @@
 //
 // Two pieces of code answer it: the kernel (sweep.hip) and the host walk of tests/check_sweep.cpp, which holds the whole walk to a
 // brute force before any kernel runs.  Both call what is here: the time of first contact with a triangle and with a sphere, the order
-// among candidates, the lower bound of a node's eight child boxes widened by the radius, and the group walk with cp_walk's stack
-// discipline.  It builds on closest_point_rules.h: the overlap at the start and the reported point are the closest-point statement
+// among candidates, the lower bound of a node's eight child boxes widened by the radius, and the visitor that group_walk
+// (group_walk.h) runs.  It builds on closest_point_rules.h: the overlap at the start and the reported point are the closest-point statement
 // (cp_triangle, cp_sphere), the order is cp_order.  Every operation is one f32 rounding (the build uses -ffp-contract=off; the only
 // fused operations are written fmaf, and they are in the box bound, not in the answer), so numpy reproduces the bits
 // (tests/sweep_cases.py).
@@ -182,57 +182,30 @@ RT_RULE uint32_t sw_pass(const float L[8], float best_t, uint32_t occupied) {
 }
 RT_RULE uint32_t sw_octant(const float d[3]) { return (cp_bits(d[0]) >> 31) | ((cp_bits(d[1]) >> 31) << 1) | ((cp_bits(d[2]) >> 31) << 2); }
 
-// ---- 5. The walk: cp_walk's (closest_point_rules.h, rule 5) with the ray's octant for the point's corner code.  The same Access
-// (node, record, push, pop), the same groups - g_base = the node's child_base, g_bits = the slots still to visit (bits 0..7) and the
-// node's imask (bits 8..15); the octant is the query's and needs no place in the entry - and the same discipline: a visit takes one
-// slot off the current group, in increasing (slot XOR octant), nearest first along the ray, parks the rest if any is left - AT MOST
-// ONE ENTRY PER VISIT - tests the node's leaves that pass the bound, in the same order, and then makes the inner children that pass
-// the bound of the best time the leaves left the current group.  So the stack bound carries over: at most depth - 1 entries inside
-// the depth + 2 = DevScene::stack_entries / 2 + 1 a lane is given.
+// ---- 5. The walk: group_walk (group_walk.h) visited by the best time so far, with the ray's octant for every node's code: nearest
+// first along the ray.
+struct SwVisit {
+    const SwQuery& q;
+    float c_max, inv[3], L[8];
+    uint32_t code, alive;
+    CpBest& best;
+
+    RT_RULE uint32_t enter(const uint32_t w[20]) {
+        sw_node_bounds(w, q, inv, code, c_max, L, alive);
+        return code;
+    }
+    RT_RULE uint32_t pass(uint32_t occupied) const { return sw_pass(L, sw_best_t(best.order), occupied & alive); }
+    template <class Access>
+    RT_RULE bool leaf(Access&, uint32_t slot, const float rec[9], const uint32_t ids[3]) {
+        const uint64_t c = cp_order(sw_triangle(rec, rec + 3, rec + 6, q), ids[1] ^ RT_PRIM_SPHERE_FLAG);
+        if (c < best.order) best.order = c, best.slot = slot;
+        return false;
+    }
+};
 template <class Access>
 RT_RULE void sw_walk(Access& acc, uint32_t n_nodes, const SwQuery& q, CpBest& best) {
-    if (n_nodes == 0u) return;
-    const float c_max = cp_p_max(q.c);
-    const float inv[3] = {1.0f / q.d[0], 1.0f / q.d[1], 1.0f / q.d[2]};
-    const uint32_t code = sw_octant(q.d);
-    uint32_t g_base = 0u, g_bits = 1u | (1u << 8); // the root as the only child of a group
-    int sp = 0;
-    for (;;) {
-        if ((g_bits & 0xFFu) == 0u) {
-            if (sp == 0) break;
-            sp--;
-            acc.pop(sp, g_base, g_bits);
-        }
-        const uint32_t i = cp_first_slot(g_bits, code);
-        g_bits ^= 1u << i;
-        const uint32_t idx = g_base + cp_popc((g_bits >> 8) & ((1u << i) - 1u)); // inner slots below i
-        if (g_bits & 0xFFu) {
-            acc.push(sp, g_base, g_bits);
-            sp++;
-        }
-        uint32_t w[20], alive;
-        float L[8];
-        acc.node(idx, w);
-        sw_node_bounds(w, q, inv, code, c_max, L, alive);
-        const uint32_t imask = w[3] >> 24, lmask = w[6] & 0xFFu;
-        uint32_t t = sw_pass(L, sw_best_t(best.order), lmask & alive);
-        while (t) {
-            const uint32_t sl = cp_first_slot(t, code);
-            t ^= 1u << sl;
-            const uint32_t first = w[5] + RT_DEV_LEAF_STRIDE * cp_popc(lmask & ((1u << sl) - 1u));
-            uint32_t len = 1u;
-            for (uint32_t x = 0; x < len; x++) {
-                float rec[9];
-                uint32_t ids[3];
-                acc.record(first + x, rec, ids);
-                if (x == 0u) len = ids[2] < RT_DEV_LEAF_STRIDE ? ids[2] : RT_DEV_LEAF_STRIDE; // 1..4; never past the leaf's own records
-                const uint64_t c = cp_order(sw_triangle(rec, rec + 3, rec + 6, q), ids[1] ^ RT_PRIM_SPHERE_FLAG);
-                if (c < best.order) best.order = c, best.slot = first + x;
-            }
-        }
-        g_base = w[4];
-        g_bits = sw_pass(L, sw_best_t(best.order), imask & alive) | (imask << 8); // by the best the leaves left
-    }
+    SwVisit v{q, cp_p_max(q.c), {1.0f / q.d[0], 1.0f / q.d[1], 1.0f / q.d[2]}, {}, sw_octant(q.d), 0u, best};
+    group_walk(acc, n_nodes, v);
 }
 
 // ---- 6. The answer, as the eight words of an rt_sweep_hit: position | t | u, v | prim_id as rt_hit | the record's material id,

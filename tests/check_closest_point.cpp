@@ -16,54 +16,13 @@
 
 #include "bvh_builder.h"
 #include "closest_point_rules.h"
+#include "host_access.h"
 
 using namespace rt;
 
 namespace {
 
 int g_fail = 0;
-
-struct HostAccess {
-    const BvhBuild* b;
-    std::vector<uint64_t> stack; // the entries a lane of the kernel owns: DevScene::stack_entries / 2 + 1
-    int max_sp = 0;
-    unsigned long long nodes = 0, tris = 0;
-
-    void node(uint32_t idx, uint32_t w[20]) {
-        if (idx >= b->nodes.size()) {
-            std::printf("FAIL: node %u out of %zu\n", idx, b->nodes.size());
-            std::exit(1);
-        }
-        static_assert(sizeof(DevNode8) == 80, "DevNode8 is 20 words");
-        std::memcpy(w, &b->nodes[idx], sizeof(DevNode8));
-        nodes++;
-    }
-    void record(uint32_t slot, float q[9], uint32_t ids[3]) {
-        if (slot >= b->tris.size()) {
-            std::printf("FAIL: record %u out of %zu\n", slot, b->tris.size());
-            std::exit(1);
-        }
-        const DevTri& t = b->tris[slot];
-        for (int a = 0; a < 3; a++) q[a] = t.v0[a], q[3 + a] = t.e1[a], q[6 + a] = t.e2[a];
-        ids[0] = t.material_id, ids[1] = t.prim_id, ids[2] = t.leaf_count;
-        tris++;
-    }
-    void push(int sp, uint32_t base, uint32_t bits) {
-        if (sp < 0 || (size_t)sp >= stack.size()) {
-            std::printf("FAIL: stack entry %d of %zu\n", sp, stack.size());
-            std::exit(1);
-        }
-        stack[(size_t)sp] = ((uint64_t)base << 32) | bits;
-        if (sp + 1 > max_sp) max_sp = sp + 1;
-    }
-    void pop(int sp, uint32_t& base, uint32_t& bits) {
-        if (sp < 0 || (size_t)sp >= stack.size()) {
-            std::printf("FAIL: stack entry %d of %zu\n", sp, stack.size());
-            std::exit(1);
-        }
-        base = (uint32_t)(stack[(size_t)sp] >> 32), bits = (uint32_t)stack[(size_t)sp];
-    }
-};
 
 struct Sphere {
     float centre[3], radius;
@@ -155,8 +114,7 @@ int main(int argc, char** argv) {
     qs.push_back({{0.0f, 0.0f, 0.0f}, 3.0e38f}); // radius * radius overflows to +inf: every finite distance is accepted
 
     HostAccess acc;
-    acc.b = &b;
-    acc.stack.resize((2u * b.depth + 2u) / 2u + 1u); // DevScene::stack_entries / 2 + 1, the kernel's LDS per lane
+    acc.init(b);
     size_t found = 0;
     for (size_t k = 0; k < qs.size(); k++) {
         const Query& q = qs[k];

@@ -22,6 +22,7 @@
 
 #include "bvh_builder.h"
 #include "closest_point_all_rules.h"
+#include "host_access.h"
 
 using namespace rt;
 
@@ -29,63 +30,6 @@ namespace {
 
 int g_fail = 0;
 const float COUNT_ALL_RADIUS = 2.0f;
-
-struct HostAccess {
-    const BvhBuild* b;
-    std::vector<uint64_t> stack; // the entries a lane of the kernel owns: DevScene::stack_entries / 2 + 1
-    std::vector<uint32_t> list;  // the words a lane of the kernel owns: 3 * max_nearest
-    int max_sp = 0;
-    unsigned long long nodes = 0, tris = 0;
-
-    void node(uint32_t idx, uint32_t w[20]) {
-        if (idx >= b->nodes.size()) {
-            std::printf("FAIL: node %u out of %zu\n", idx, b->nodes.size());
-            std::exit(1);
-        }
-        static_assert(sizeof(DevNode8) == 80, "DevNode8 is 20 words");
-        std::memcpy(w, &b->nodes[idx], sizeof(DevNode8));
-        nodes++;
-    }
-    void record(uint32_t slot, float q[9], uint32_t ids[3]) {
-        if (slot >= b->tris.size()) {
-            std::printf("FAIL: record %u out of %zu\n", slot, b->tris.size());
-            std::exit(1);
-        }
-        const DevTri& t = b->tris[slot];
-        for (int a = 0; a < 3; a++) q[a] = t.v0[a], q[3 + a] = t.e1[a], q[6 + a] = t.e2[a];
-        ids[0] = t.material_id, ids[1] = t.prim_id, ids[2] = t.leaf_count;
-        tris++;
-    }
-    void check_sp(int sp) const {
-        if (sp < 0 || (size_t)sp >= stack.size()) {
-            std::printf("FAIL: stack entry %d of %zu\n", sp, stack.size());
-            std::exit(1);
-        }
-    }
-    void push(int sp, uint32_t base, uint32_t bits) {
-        check_sp(sp);
-        stack[(size_t)sp] = ((uint64_t)base << 32) | bits;
-        if (sp + 1 > max_sp) max_sp = sp + 1;
-    }
-    void pop(int sp, uint32_t& base, uint32_t& bits) {
-        check_sp(sp);
-        base = (uint32_t)(stack[(size_t)sp] >> 32), bits = (uint32_t)stack[(size_t)sp];
-    }
-    void check_k(uint32_t k) const {
-        if ((size_t)3 * k + 2 >= list.size()) {
-            std::printf("FAIL: list entry %u of %zu\n", k, list.size() / 3);
-            std::exit(1);
-        }
-    }
-    void list_get(uint32_t k, uint32_t& d2, uint32_t& key, uint32_t& slot) const {
-        check_k(k);
-        d2 = list[3 * k], key = list[3 * k + 1], slot = list[3 * k + 2];
-    }
-    void list_set(uint32_t k, uint32_t d2, uint32_t key, uint32_t slot) {
-        check_k(k);
-        list[3 * k] = d2, list[3 * k + 1] = key, list[3 * k + 2] = slot;
-    }
-};
 
 struct Sphere {
     float centre[3], radius;
@@ -111,7 +55,7 @@ void answer(const BvhBuild& b, const std::vector<Sphere>& spheres, uint64_t orde
 
 // what k_cp_nearest_all does for one lane: K records and the count
 template <bool COUNT_ALL>
-uint32_t kernel_lane(HostAccess& acc, const std::vector<Sphere>& spheres, const Query& q, uint32_t K, uint32_t* out) {
+uint32_t kernel_lane(HostListAccess& acc, const std::vector<Sphere>& spheres, const Query& q, uint32_t K, uint32_t* out) {
     acc.list.assign((size_t)3 * K, 0xDEADBEEFu);
     CpList list;
     cp_list_init(list, K, q.radius);
@@ -208,10 +152,11 @@ int main(int argc, char** argv) {
     qs.push_back({{0.0f, 0.0f, 0.0f}, -1.0f});
 
     const uint32_t Ks[3] = {1u, 4u, 16u};
-    HostAccess acc[3][2], single;
+    HostListAccess acc[3][2];
+    HostAccess single;
     for (auto& row : acc)
-        for (HostAccess& a : row) a.b = &b, a.stack.resize((2u * b.depth + 2u) / 2u + 1u); // DevScene::stack_entries / 2 + 1, the kernel's LDS per lane
-    single.b = &b, single.stack.resize((2u * b.depth + 2u) / 2u + 1u);
+        for (HostListAccess& a : row) a.init(b);
+    single.init(b);
     size_t listed[3] = {0, 0, 0}, overfull[3] = {0, 0, 0};
     int fails[3][2] = {{0, 0}, {0, 0}, {0, 0}};
     std::vector<std::pair<uint64_t, uint32_t>> cand; // (order, slot), every record and sphere
@@ -247,7 +192,7 @@ int main(int argc, char** argv) {
                 const uint32_t K = Ks[ki];
                 Query qq = q;
                 if (all && std::isinf(q.radius)) qq.radius = COUNT_ALL_RADIUS;
-                HostAccess& a = acc[ki][all];
+                HostListAccess& a = acc[ki][all];
                 uint32_t got[16 * 8], want[16 * 8];
                 const unsigned long long n1 = a.nodes, t1 = a.tris;
                 const uint32_t got_count = all ? kernel_lane<true>(a, spheres, qq, K, got) : kernel_lane<false>(a, spheres, qq, K, got);

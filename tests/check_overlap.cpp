@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "bvh_builder.h"
+#include "host_access.h"
 #include "overlap_rules.h"
 
 using namespace rt;
@@ -25,63 +26,6 @@ namespace {
 
 int g_fail = 0;
 const uint32_t K_MAX = 32u; // RT_OVERLAP_MAX
-
-struct HostAccess {
-    const BvhBuild* b;
-    std::vector<uint64_t> stack; // the entries a lane of the kernel owns: DevScene::stack_entries / 2 + 1
-    std::vector<uint32_t> list;  // the words a lane of the kernel owns: max_prims
-    int max_sp = 0;
-    unsigned long long nodes = 0, tris = 0;
-
-    void node(uint32_t idx, uint32_t w[20]) {
-        if (idx >= b->nodes.size()) {
-            std::printf("FAIL: node %u out of %zu\n", idx, b->nodes.size());
-            std::exit(1);
-        }
-        static_assert(sizeof(DevNode8) == 80, "DevNode8 is 20 words");
-        std::memcpy(w, &b->nodes[idx], sizeof(DevNode8));
-        nodes++;
-    }
-    void record(uint32_t slot, float q[9], uint32_t ids[3]) {
-        if (slot >= b->tris.size()) {
-            std::printf("FAIL: record %u out of %zu\n", slot, b->tris.size());
-            std::exit(1);
-        }
-        const DevTri& t = b->tris[slot];
-        for (int a = 0; a < 3; a++) q[a] = t.v0[a], q[3 + a] = t.e1[a], q[6 + a] = t.e2[a];
-        ids[0] = t.material_id, ids[1] = t.prim_id, ids[2] = t.leaf_count;
-        tris++;
-    }
-    void check_sp(int sp) const {
-        if (sp < 0 || (size_t)sp >= stack.size()) {
-            std::printf("FAIL: stack entry %d of %zu\n", sp, stack.size());
-            std::exit(1);
-        }
-    }
-    void push(int sp, uint32_t base, uint32_t bits) {
-        check_sp(sp);
-        stack[(size_t)sp] = ((uint64_t)base << 32) | bits;
-        if (sp + 1 > max_sp) max_sp = sp + 1;
-    }
-    void pop(int sp, uint32_t& base, uint32_t& bits) {
-        check_sp(sp);
-        base = (uint32_t)(stack[(size_t)sp] >> 32), bits = (uint32_t)stack[(size_t)sp];
-    }
-    void check_k(uint32_t k) const {
-        if ((size_t)k >= list.size()) {
-            std::printf("FAIL: list entry %u of %zu\n", k, list.size());
-            std::exit(1);
-        }
-    }
-    uint32_t list_get(uint32_t k) const {
-        check_k(k);
-        return list[k];
-    }
-    void list_set(uint32_t k, uint32_t key) {
-        check_k(k);
-        list[k] = key;
-    }
-};
 
 struct Sphere {
     float centre[3], radius;
@@ -94,7 +38,7 @@ struct Query {
 
 // what k_overlap_box does for one lane: K ids and the count
 template <int MODE>
-uint32_t kernel_lane(HostAccess& acc, const std::vector<Sphere>& spheres, const Query& q, uint32_t K, uint32_t* out) {
+uint32_t kernel_lane(HostKeyAccess& acc, const std::vector<Sphere>& spheres, const Query& q, uint32_t K, uint32_t* out) {
     acc.list.assign((size_t)K, 0xDEADBEEFu);
     OvList list;
     ov_list_init(list, MODE == OV_ANY ? 0u : K);
@@ -192,11 +136,10 @@ int main(int argc, char** argv) {
     const size_t n_degenerate = 5;
 
     const uint32_t Ks[3] = {1u, 4u, K_MAX};
-    const size_t lane_stack = (2u * b.depth + 2u) / 2u + 1u; // DevScene::stack_entries / 2 + 1, the kernel's LDS per lane
-    HostAccess acc[3][2], any;
+    HostKeyAccess acc[3][2], any;
     for (auto& row : acc)
-        for (HostAccess& a : row) a.b = &b, a.stack.resize(lane_stack);
-    any.b = &b, any.stack.resize(lane_stack);
+        for (HostKeyAccess& a : row) a.init(b);
+    any.init(b);
     size_t listed[3] = {0, 0, 0}, overfull[3] = {0, 0, 0}, n_small = 0, touched = 0;
     unsigned long long small_nodes = 0, small_tris = 0;
     int fails[3][2] = {{0, 0}, {0, 0}, {0, 0}}, any_fails = 0, nonfinite_listed = 0;
@@ -231,7 +174,7 @@ int main(int argc, char** argv) {
         for (int ki = 0; ki < 3; ki++)
             for (int all = 0; all < 2; all++) {
                 const uint32_t K = Ks[ki];
-                HostAccess& a = acc[ki][all];
+                HostKeyAccess& a = acc[ki][all];
                 uint32_t got[K_MAX], want[K_MAX];
                 const unsigned long long n1 = a.nodes, t1 = a.tris;
                 const uint32_t got_count = all ? kernel_lane<OV_COUNT_ALL>(a, spheres, q, K, got) : kernel_lane<OV_LIST>(a, spheres, q, K, got);

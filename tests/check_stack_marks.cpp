@@ -1,9 +1,9 @@
 // A MODEL of the traversal stacks' step rules, not the kernels: it replays, on the host builders' trees (gpu_raytracer_amd/csrc/
 // bvh_builder.cpp, methods 0 and 1), the two stack disciplines of the device walks and prints how many entries a lane ever holds.
 // Host code; built by tests/test_stack_cases.py with AddressSanitizer + UBSan, as tests/test_device_bvh.py builds check_bvh.cpp.
-//   (a) one entry per visit: `traverse` of device_common.h (and cp_walk, traverse_all, the sweep and parity walks): a visit takes a
-//       slot off the current group, parks the rest if any is left, tests the node's leaves at once.  Bound: depth - 1
-//       (closest_point_rules.h, rule 5).
+//   (a) one entry per visit: `traverse` of device_common.h (and traverse_all, the parity walks, and group_walk under the closest-point,
+//       nearest-K, sweep and overlap queries): a visit takes a slot off the current group, parks the rest if any is left, tests the
+//       node's leaves at once.  Bound: depth - 1 (group_walk.h).
 //   (b) k_wf_trace of wavefront.hip: 64 lanes in lock step; what is left of a node is a group G of inner children and a group T of
 //       leaves; a visit parks the siblings still to visit and, when the lane already holds a postponed T, the new T; the wave takes
 //       node steps while fewer than RT_WF8_LEAF_THRESHOLD (24) lanes hold a T, else one leaf slot per lane per leaf step.  Bound:

@@ -95,7 +95,7 @@ def test_model_marks_on_the_deck(checker, tmp_path, deck, method):
     assert lds < marks["mixed"]["mark_b"], "the deck's mixed waves must overflow the LDS part of the stack"
     for name, m in marks.items():
         assert max(m["mark_b"], m["mark_b_any"]) <= 2 * tree["real_depth"] + 2, name
-        assert m["mark_a"] <= tree["real_depth"] - 1, name  # closest_point_rules.h, rule 5
+        assert m["mark_a"] <= tree["real_depth"] - 1, name  # group_walk.h
     print("closest hits found through an overflow entry:", {name: m["via_overflow"] for name, m in marks.items()})
     n = len(rays["through"])
     assert marks["through"]["hits"] == n and marks["corner"]["hits"] == n  # card 0; the wall
