@@ -37,6 +37,8 @@ QUERY_COUNT_ALL = 2  # RT_QUERY_COUNT_ALL of rt_intersect_all / rt_closest_point
 MULTI_HIT_MAX = 16  # RT_MULTI_HIT_MAX: the most hits rt_intersect_all lists per ray
 NEAREST_MAX = 16  # RT_NEAREST_MAX: the most primitives rt_closest_point_all lists per point
 OVERLAP_MAX = 32  # RT_OVERLAP_MAX: the most primitives rt_overlap_box lists per box
+SWEEP_AXIS_SPHERE = 13  # RT_SWEEP_AXIS_SPHERE of rt_box_sweep_hit.axis: the contact is with a sphere primitive
+SWEEP_AXIS_NONE = 0xFFFFFFFF  # RT_SWEEP_AXIS_NONE: a miss, or in contact at the start
 OVERLAP_ANY = 4  # RT_OVERLAP_ANY of rt_overlap_box: counts are 1 where anything touches the box, else 0, and the walk stops at the first
 INSIDE_MAX_RAYS = 7  # RT_INSIDE_MAX_RAYS: the most parity rays rt_inside / rt_signed_distance trace per point
 INSIDE_DIRECTIONS = np.array([  # RT_INSIDE_DIRECTIONS: direction k of vote k, used as given
@@ -66,7 +68,7 @@ ABI_SYMBOLS = [
     "rt_read_rgb32f", "rt_read_rgba8_channels", "rt_read_rgba8_combined", "rt_read_hits",
     "rt_get_stats", "rt_last_error", "rt_destroy", "rt_version",
     "rt_intersect", "rt_occluded", "rt_camera_rays", "rt_intersect_all",
-    "rt_surface", "rt_ambient_occlusion", "rt_direct_light", "rt_radiance", "rt_radiance_sh", "rt_irradiance", "rt_closest_point", "rt_closest_point_all", "rt_sweep_sphere",
+    "rt_surface", "rt_ambient_occlusion", "rt_direct_light", "rt_radiance", "rt_radiance_sh", "rt_irradiance", "rt_closest_point", "rt_closest_point_all", "rt_sweep_sphere", "rt_sweep_box",
     "rt_inside", "rt_signed_distance", "rt_overlap_box",
     "rt_update_geometry",
     "rt_accumulated_samples",
@@ -379,6 +381,36 @@ def split_sweep_hits(records):
     """(N, 8) sweep records (rt_sweep_hit) -> (position (N, 3), t (N,), u (N,), v (N,), prim_id (N,), material_id (N,)): rt_nearest's
     layout with t where the distance is, so the ids come as split_nearest gives them."""
     return split_nearest(records)
+
+
+def make_box_sweeps(centers, half_extents, directions, tmax=float("inf")):
+    """(N, 3) centres and directions (numpy or torch, the result has the same kind and device) -> an (N, 12) float32 batch of
+    rt_box_sweep records: cx cy cz 0 hx hy hz 0 dx dy dz tmax.  half_extents: a scalar, a triple or an (N, 3) array, >= 0 per axis; 0
+    is allowed (a moving slab, segment, point).  tmax: a scalar or an (N,) array; contacts at 0 <= t < tmax are reported."""
+    boxes = make_boxes(centers, half_extents)
+    if _is_torch(boxes):
+        import torch
+        out = torch.zeros((boxes.shape[0], 12), dtype=torch.float32, device=boxes.device)
+        d = directions if _is_torch(directions) else torch.as_tensor(np.asarray(directions, np.float32), device=boxes.device)
+        tmax = tmax if _is_torch(tmax) else torch.as_tensor(np.asarray(tmax, np.float32), device=boxes.device)
+    else:
+        out = np.zeros((boxes.shape[0], 12), np.float32)
+        d = np.asarray(directions, np.float32)
+    out[:, 0:8] = boxes
+    out[:, 8:11] = d.reshape(-1, 3)
+    out[:, 11] = tmax
+    return out
+
+
+def split_box_sweep_hits(records):
+    """(N, 8) box-sweep records (rt_box_sweep_hit) -> (normal (N, 3), t (N,), axis (N,), prim_id (N,), material_id (N,)).  axis and the
+    ids are the records' uint32 words: uint32 for numpy, int64 for torch (a miss is 4294967295 = PRIM_MISS with axis SWEEP_AXIS_NONE)."""
+    if _is_torch(records):
+        import torch
+        words = [records[:, c].contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF for c in (4, 6, 7)]
+    else:
+        words = [np.ascontiguousarray(records[:, c]).view(np.uint32) for c in (4, 6, 7)]
+    return records[:, 0:3], records[:, 3], words[0], words[1], words[2]
 
 
 def split_lighting(lighting):
@@ -950,6 +982,13 @@ class Context:
         same kind and device as `sweeps`.  Only contacts at 0 <= t < tmax are reported; a miss is position 0, tmax as t and
         prim_id = PRIM_MISS.  The contact normal is origin + direction * t - position."""
         return self._query("rt_sweep_sphere", sweeps, out, 8, "float32", counters, in_name="sweeps")
+
+    def sweep_box(self, sweeps, out=None, counters=False):
+        """rt_sweep_box: the first contact of each moving axis-aligned box of an (N, 12) batch (make_box_sweeps: centre, half extent,
+        direction, tmax) with the scene's surface -> (N, 8) float32 rt_box_sweep_hit records (split_box_sweep_hits: normal, t, axis,
+        prim_id, material_id), same kind and device as `sweeps`.  Only contacts at 0 <= t < tmax are reported; a miss is normal 0,
+        tmax as t, axis SWEEP_AXIS_NONE and prim_id = PRIM_MISS; a start in contact is t = 0 with normal 0 and SWEEP_AXIS_NONE."""
+        return self._query("rt_sweep_box", sweeps, out, 8, "float32", counters, in_cols=12, in_name="sweeps")
 
     def camera_rays(self, width, height, camera, mode=MODE_LEGACY, out=None):
         """rt_camera_rays: the width x height pixel-centre rays of mode 0/1 as a (width * height, 8) batch, row-major, y down.

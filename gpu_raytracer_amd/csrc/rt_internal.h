@@ -38,6 +38,7 @@
 #include "shadow_grid.h"
 #include "surface_query.h"
 #include "sweep.h"
+#include "sweep_box.h"
 #include "wavefront.h"
 
 #define HIPCHK(ctx, call)                                                                                       \

@@ -224,7 +224,7 @@ int rt_get_stats(rt_ctx* ctx, rt_stats* out);
  * a new one at sample 0 by itself, as RT_FLAG_ACCUMULATE_RESTART does.  The other RT_FLAG_* bits change no bits and may differ.
  * The running image ends (the next accumulating call starts at 0) with rt_upload_scene*, rt_update_geometry, rt_dispatch_tile, any
  * rt_render without RT_FLAG_ACCUMULATE and an accumulating call that fails once it has passed its argument checks.  It survives rt_prepare,
- * rt_upload_textures, the ray queries, the surface queries, rt_direct_light, rt_radiance, rt_radiance_sh, rt_irradiance, rt_closest_point, rt_closest_point_all, rt_inside, rt_signed_distance, rt_overlap_box, rt_sweep_sphere, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
+ * rt_upload_textures, the ray queries, the surface queries, rt_direct_light, rt_radiance, rt_radiance_sh, rt_irradiance, rt_closest_point, rt_closest_point_all, rt_inside, rt_signed_distance, rt_overlap_box, rt_sweep_sphere, rt_sweep_box, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
  * Limit: RT_ACCUMULATE_MAX_SAMPLES samples (where the float sample count stops being exact); a call that would pass it is RT_ERR_BAD_ARG
  * and leaves the running image as it was.  rt_stats describes the call alone (its segments, pixels, kernel_ms).
  * A context over several devices, and a tile_rank / tile_world share, accumulates its own share of the pixels.
@@ -951,6 +951,90 @@ RT_STATIC_ASSERT(sizeof(rt_sweep_hit) == 32 && offsetof(rt_sweep_hit, position) 
 
 /* First contact of each of the n moving spheres. */
 int rt_sweep_sphere(rt_ctx* ctx, const rt_sweep* sweeps, size_t n, rt_sweep_hit* out, uint32_t flags);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Box sweeps: the first contact of a moving axis-aligned box with the scene's surface (no reference counterpart; the "box cast" of
+ * the collision libraries is the model): character and camera controllers with box or voxel hulls, continuous collision of a fast
+ * body, clearance of a crate-shaped probe along a path, conservative advancement of a trigger volume.  rt_sweep_sphere with the
+ * circumscribed sphere reports contacts the box never makes and with the inscribed one misses contacts; stepping rt_overlap_box along
+ * the path tunnels through thin geometry and gives no time.  The box keeps its orientation and its centre moves as
+ * centre(t) = center + direction * t; the answer is the smallest t in [0, tmax) at which the closed box touches the surface, with the
+ * contact's normal and the separating axis that closed last.  The surface is two-sided and a sphere primitive is its surface, as for
+ * rt_overlap_box.  The answer is one f32 statement (csrc/sweep_box_rules.h, whose header comment is the specification; every
+ * operation one f32 rounding, nothing fused), with dot, cross, min and max as in "Overlap queries", c = center, h = half_extent,
+ * d = direction, and every test in its positive form, so that a NaN makes it false.
+ * Triangle, from its record's v0, e1, e2; a0 = v0 - c, a1 = (v0 + e1) - c, a2 = (v0 + e2) - c: the thirteen axes of "Overlap queries",
+ *   numbered 0, 1, 2 the box axes x, y, z; 3 the normal n = cross(e1, e2); 4 + 3j + i cross(unit_i, f_j), f = (e1, e2 - e1, e2).  Per
+ *   axis p_k and r are the overlap statement's (for the normal p_0 = p_1 = p_2 = dot(n, a0)) and w is the projection of d in the form
+ *   of p_k (d[a]; dot(n, d); f.y*d.z - f.z*d.y, f.z*d.x - f.x*d.z, f.x*d.y - f.y*d.x).  lo = min_k p_k - r, hi = max_k p_k + r;
+ *     w > 0: enter = lo / w, exit = hi / w;   w < 0: enter = hi / w, exit = lo / w;   the axis holds iff enter <= exit
+ *     w == 0: the axis holds iff min_k p_k <= r && max_k p_k >= -r and constrains nothing;   w a NaN: it does not hold
+ *     an axis 4..12 holds only if (p_0 + p_1) + p_2 is no NaN
+ *   The running entry starts at (t_in = 0, RT_SWEEP_AXIS_NONE); an axis replaces it iff its enter is strictly larger; t_out is the
+ *   minimum of the exits, from +inf.  Contact iff all nine components of the a_k are finite, every axis holds and t_in <= t_out; then
+ *   t = t_in + 0.0f and axis is the one that set t_in.  t = 0 with RT_SWEEP_AXIS_NONE results exactly when the triangle touches the
+ *   box at the start by the statement of rt_overlap_box.
+ *   normal_a = (w > 0 ? -L_a : L_a) / sqrtf(dot(L, L)) + 0.0f for that axis' vector L (unit_a; n; (0, -f.z, f.y), (f.z, 0, -f.x),
+ *   (-f.y, f.x, 0)) and its w; 0 for RT_SWEEP_AXIS_NONE.
+ * Sphere i (centre o, radius R, rr = R*R): g = o - c; seen from the box its centre is P(t), P_a(t) = g_a - d_a*t; near and far as in
+ *   "Overlap queries".
+ *   touching at the start by the statement of rt_overlap_box                                            -> t = 0
+ *   otherwise dot(near, near) > rr (from outside), the minimum over the accepting pieces of the box widened by the ball:
+ *     faces, per axis a with d_a != 0: plane = h_a + R; t = (g_a - (d_a > 0 ? plane : -plane)) / d_a
+ *       accepts iff t >= 0 && |P_b(t)| <= h_b && |P_c(t)| <= h_c on the other two axes
+ *     edges along a, (b, c) = (a + 1, a + 2) mod 3, four signs: m_b = g_b -+ h_b, m_c = g_c -+ h_c; dd2 = d_b*d_b + d_c*d_c
+ *       bq = m_b*d_b + m_c*d_c; x = m_b*d_c - m_c*d_b; disc = dd2*rr - x*x; t = (bq - sqrtf(disc)) / dd2
+ *       accepts iff disc >= 0 && t >= 0 && |P_a(t)| <= h_a
+ *     corners, eight signs: m = g -+ h; b = dot(m, d); x = cross(m, d); disc = dot(d, d)*rr - dot(x, x)
+ *       t = (b - sqrtf(disc)) / dot(d, d);  accepts iff disc >= 0 && t >= 0
+ *   otherwise dot(far, far) < rr (from inside): the minimum over the eight corners of t = (b + sqrtf(disc)) / dot(d, d), accepted
+ *     iff disc >= 0 && t >= 0
+ *   t is that minimum + 0.0f.  A contact at t > 0 has axis RT_SWEEP_AXIS_SPHERE and, with P = P(t), the normal v / sqrtf(dot(v, v))
+ *   for v = clamp(P, -h, h) - P from outside and v = P - corner, corner_a = (P_a >= 0 ? -h_a : h_a), from inside; 0 where that length
+ *   is not > 0.  A contact at t = 0 has RT_SWEEP_AXIS_NONE and normal 0.
+ * Order: as for rt_sweep_sphere: (the bits of t, key) as one 64-bit unsigned number from (the bits of tmax, 0).  Only t < tmax is ever
+ *   accepted, strictly; at equal t spheres come before triangles, each kind by ascending index; among several primitives in contact
+ *   at the start the lowest key wins.
+ * A miss: normal 0, t = tmax as given, axis RT_SWEEP_AXIS_NONE, prim_id 0xFFFFFFFF, material_id 0.  A query with a non-finite
+ *   component of center, half_extent or direction, a negative half extent, a zero direction, or a tmax that is NaN or <= 0 is such a
+ *   miss without a walk.  The kernel checks this itself.
+ * The result follows from these rules alone: it does not depend on the tree in use, the device count, the kind of memory or the
+ *   chunking, and after rt_update_geometry it is that of a fresh upload of the moved scene.  The tree only culls, by the centre's
+ *   entry time into each box widened by the half extents and a margin past the statement's own rounding.
+ * Buffers, chunking, the split over devices, synchronisation, side effects, flags, statistics and errors as for rt_sweep_sphere; the
+ * records are 48 bytes in and 32 bytes out, device memory 16-byte aligned.
+ * --------------------------------------------------------------------------------------------------------------- */
+typedef struct rt_box_sweep {  /* its first 32 bytes are an rt_box, its last 16 the second half of an rt_sweep */
+    float center[3];       /* the box's centre at t = 0 */
+    uint32_t _pad0;        /* pads are ignored */
+    float half_extent[3];  /* >= 0 per axis, finite; 0 allowed (a moving slab, segment, point) */
+    uint32_t _pad1;
+    float direction[3];    /* need not be normalised; centre(t) = center + direction * t */
+    float tmax;            /* contacts at 0 <= t < tmax are reported; > 0, +inf allowed */
+} rt_box_sweep; /* 48 bytes */
+
+typedef struct rt_box_sweep_hit {
+    float normal[3];       /* unit, against the motion; 0 on a miss and for a start in contact */
+    float t;               /* time of first contact; tmax as given on a miss */
+    uint32_t axis;         /* which separating axis closed last: 0 .. 12, RT_SWEEP_AXIS_SPHERE or RT_SWEEP_AXIS_NONE */
+    uint32_t _reserved;    /* written as 0 */
+    uint32_t prim_id;      /* as rt_hit.prim_id; 0xFFFFFFFF = miss */
+    uint32_t material_id;  /* the record's material id, unchecked; 0 on a miss */
+} rt_box_sweep_hit; /* 32 bytes */
+
+#define RT_SWEEP_AXIS_SPHERE 13u
+#define RT_SWEEP_AXIS_NONE 0xFFFFFFFFu
+
+RT_STATIC_ASSERT(sizeof(rt_box_sweep) == 48 && offsetof(rt_box_sweep, center) == 0 && offsetof(rt_box_sweep, half_extent) == 16 &&
+                     offsetof(rt_box_sweep, direction) == 32 && offsetof(rt_box_sweep, tmax) == 44,
+                 "rt_box_sweep is 48 B: center, half_extent at 16, direction at 32, tmax at 44");
+RT_STATIC_ASSERT(sizeof(rt_box_sweep_hit) == 32 && offsetof(rt_box_sweep_hit, normal) == 0 && offsetof(rt_box_sweep_hit, t) == 12 &&
+                     offsetof(rt_box_sweep_hit, axis) == 16 && offsetof(rt_box_sweep_hit, prim_id) == 24 &&
+                     offsetof(rt_box_sweep_hit, material_id) == 28,
+                 "rt_box_sweep_hit is 32 B: normal, t at 12, axis at 16, prim_id at 24, material_id at 28");
+
+/* First contact of each of the n moving boxes. */
+int rt_sweep_box(rt_ctx* ctx, const rt_box_sweep* sweeps, size_t n, rt_box_sweep_hit* out, uint32_t flags); /* RT_QUERY_COUNTERS */
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Overlap queries: the primitives that touch caller-supplied axis-aligned boxes (no reference counterpart; the OverlapBox /
