@@ -68,7 +68,7 @@ ABI_SYMBOLS = [
     "rt_read_rgb32f", "rt_read_rgba8_channels", "rt_read_rgba8_combined", "rt_read_hits",
     "rt_get_stats", "rt_last_error", "rt_destroy", "rt_version",
     "rt_intersect", "rt_occluded", "rt_camera_rays", "rt_intersect_all",
-    "rt_surface", "rt_ambient_occlusion", "rt_direct_light", "rt_radiance", "rt_radiance_sh", "rt_irradiance", "rt_closest_point", "rt_closest_point_all", "rt_sweep_sphere", "rt_sweep_box",
+    "rt_surface", "rt_ambient_occlusion", "rt_direct_light", "rt_radiance", "rt_radiance_sh", "rt_irradiance", "rt_closest_point", "rt_closest_point_all", "rt_sweep_sphere", "rt_sweep_box", "rt_sweep_capsule",
     "rt_inside", "rt_signed_distance", "rt_overlap_box",
     "rt_update_geometry",
     "rt_accumulated_samples",
@@ -411,6 +411,38 @@ def split_box_sweep_hits(records):
     else:
         words = [np.ascontiguousarray(records[:, c]).view(np.uint32) for c in (4, 6, 7)]
     return records[:, 0:3], records[:, 3], words[0], words[1], words[2]
+
+
+def make_capsule_sweeps(origins, axes, directions, radius, tmax=float("inf")):
+    """(N, 3) origins (end A of each axis) and directions (numpy or torch, the result has the same kind and device) -> an (N, 12)
+    float32 batch of rt_capsule_sweep records: ox oy oz radius ax ay az 0 dx dy dz tmax.  axes: B - A, a triple or an (N, 3) array;
+    zero is allowed (a moving sphere).  radius / tmax: scalars or (N,) arrays; contacts at 0 <= t < tmax are reported."""
+    if _is_torch(origins):
+        import torch
+        o = origins.reshape(-1, 3)
+        out = torch.zeros((o.shape[0], 12), dtype=torch.float32, device=o.device)
+        conv = lambda x: x if _is_torch(x) else torch.as_tensor(np.asarray(x, np.float32), device=o.device)
+    else:
+        o = np.asarray(origins, np.float32).reshape(-1, 3)
+        out = np.zeros((o.shape[0], 12), np.float32)
+        conv = lambda x: np.asarray(x, np.float32)
+    out[:, 0:3] = o
+    out[:, 3] = conv(radius)
+    out[:, 4:7] = conv(axes).reshape(-1, 3)
+    out[:, 8:11] = conv(directions).reshape(-1, 3)
+    out[:, 11] = conv(tmax)
+    return out
+
+
+def split_capsule_sweep_hits(records):
+    """(N, 8) capsule-sweep records (rt_capsule_sweep_hit) -> (position (N, 3), t (N,), s (N,), prim_id (N,), material_id (N,)).  The
+    ids are the records' uint32 words: uint32 for numpy, int64 for torch (a miss is 4294967295 = PRIM_MISS)."""
+    if _is_torch(records):
+        import torch
+        words = [records[:, c].contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF for c in (6, 7)]
+    else:
+        words = [np.ascontiguousarray(records[:, c]).view(np.uint32) for c in (6, 7)]
+    return records[:, 0:3], records[:, 3], records[:, 4], words[0], words[1]
 
 
 def split_lighting(lighting):
@@ -989,6 +1021,13 @@ class Context:
         prim_id, material_id), same kind and device as `sweeps`.  Only contacts at 0 <= t < tmax are reported; a miss is normal 0,
         tmax as t, axis SWEEP_AXIS_NONE and prim_id = PRIM_MISS; a start in contact is t = 0 with normal 0 and SWEEP_AXIS_NONE."""
         return self._query("rt_sweep_box", sweeps, out, 8, "float32", counters, in_cols=12, in_name="sweeps")
+
+    def sweep_capsule(self, sweeps, out=None, counters=False):
+        """rt_sweep_capsule: the first contact of each moving capsule of an (N, 12) batch (make_capsule_sweeps: origin, radius, axis,
+        direction, tmax) with the scene's surface -> (N, 8) float32 rt_capsule_sweep_hit records (split_capsule_sweep_hits: position,
+        t, s, prim_id, material_id), same kind and device as `sweeps`.  Only contacts at 0 <= t < tmax are reported; a miss is position
+        0, tmax as t, s = 0 and prim_id = PRIM_MISS; with a zero axis the records are sweep_sphere's with s where u is."""
+        return self._query("rt_sweep_capsule", sweeps, out, 8, "float32", counters, in_cols=12, in_name="sweeps")
 
     def camera_rays(self, width, height, camera, mode=MODE_LEGACY, out=None):
         """rt_camera_rays: the width x height pixel-centre rays of mode 0/1 as a (width * height, 8) batch, row-major, y down.

@@ -39,6 +39,7 @@
 #include "surface_query.h"
 #include "sweep.h"
 #include "sweep_box.h"
+#include "sweep_capsule.h"
 #include "wavefront.h"
 
 #define HIPCHK(ctx, call)                                                                                       \

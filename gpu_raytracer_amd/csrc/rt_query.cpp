@@ -1,7 +1,7 @@
 // rt_query.cpp — calls that trace or filter outside a frame: ray queries (rt_hip.h "Ray queries": rt_intersect, rt_occluded,
 // rt_intersect_all, rt_camera_rays), surface queries ("Surface queries": rt_surface, rt_ambient_occlusion; kernels in
 // surface_query.hip), the direct-light query ("Direct-light queries": rt_direct_light; kernel in direct_light.hip), the path query ("Path queries":
-// rt_radiance; kernels in path_query.hip), the probe query ("Probe queries": rt_radiance_sh; kernels in probe_query.hip), the irradiance query ("Irradiance queries": rt_irradiance; kernels in irradiance_query.hip), the closest-point queries ("Closest-point queries": rt_closest_point, rt_closest_point_all; kernels in closest_point.hip, closest_point_all.hip), the inside test and the signed distance ("Inside tests and signed distance": rt_inside, rt_signed_distance; kernel in inside.hip), the sphere sweep ("Sphere sweeps": rt_sweep_sphere; kernel in sweep.hip), the box sweep ("Box sweeps": rt_sweep_box; kernel in sweep_box.hip), the overlap query ("Overlap queries": rt_overlap_box; kernel in overlap.hip) and the image passes ("Feature buffers (AOVs) and denoising": rt_aovs, rt_sample_rays, rt_denoise; kernels in
+// rt_radiance; kernels in path_query.hip), the probe query ("Probe queries": rt_radiance_sh; kernels in probe_query.hip), the irradiance query ("Irradiance queries": rt_irradiance; kernels in irradiance_query.hip), the closest-point queries ("Closest-point queries": rt_closest_point, rt_closest_point_all; kernels in closest_point.hip, closest_point_all.hip), the inside test and the signed distance ("Inside tests and signed distance": rt_inside, rt_signed_distance; kernel in inside.hip), the sphere sweep ("Sphere sweeps": rt_sweep_sphere; kernel in sweep.hip), the box sweep ("Box sweeps": rt_sweep_box; kernel in sweep_box.hip), the capsule sweep ("Capsule sweeps": rt_sweep_capsule; kernel in sweep_capsule.hip), the overlap query ("Overlap queries": rt_overlap_box; kernel in overlap.hip) and the image passes ("Feature buffers (AOVs) and denoising": rt_aovs, rt_sample_rays, rt_denoise; kernels in
 // denoise.hip).  None of them touches the frame targets, the tile shares rt_read_* gather, or the running image of an accumulation.
 #include "rt_internal.h"
 #include "inside_rules.h"
@@ -48,7 +48,7 @@ void drain_streams(rt_ctx* ctx) { // after a failure: nothing of the call is lef
 }
 
 // ---- batch calls: an array of records in, one or two arrays of records out ------------------------------------------------------
-// run_batch is the procedure all sixteen share; an entry function states its own checks, describes its arrays in a Batch, supplies the
+// run_batch is the procedure all seventeen share; an entry function states its own checks, describes its arrays in a Batch, supplies the
 // launches of one chunk and turns the Totals into rt_stats.
 
 enum Stage { ST_OUT, ST_COUNTS, ST_AO, ST_PATHS }; // a buffer of DeviceState::rq
@@ -205,7 +205,7 @@ void batch_stats(rt_ctx* ctx, double w0, const Totals& t, bool counters, uint64_
     st.wall_ms = now_ms() - w0;
 }
 
-// rt_intersect, rt_occluded, rt_surface, rt_closest_point, rt_sweep_sphere, rt_sweep_box: one record in, one record out, one lane of `launch` per record.
+// rt_intersect, rt_occluded, rt_surface, rt_closest_point, rt_sweep_sphere, rt_sweep_box, rt_sweep_capsule: one record in, one record out, one lane of `launch` per record.
 using RecordLaunch = hipError_t (*)(const DevScene&, const void*, void*, uint32_t, unsigned long long*, hipStream_t);
 int record_query(rt_ctx* ctx, const char* fn, BatchIn in, size_t n, BatchOut out, uint32_t flags, RecordLaunch launch) {
     const double w0 = now_ms();
@@ -520,6 +520,10 @@ int rt_sweep_sphere(rt_ctx* ctx, const rt_sweep* sweeps, size_t n, rt_sweep_hit*
 
 int rt_sweep_box(rt_ctx* ctx, const rt_box_sweep* sweeps, size_t n, rt_box_sweep_hit* out, uint32_t flags) {
     return record_query(ctx, "rt_sweep_box", {"sweeps", sweeps, sizeof(rt_box_sweep)}, n, {"out", out, sizeof(rt_box_sweep_hit)}, flags, rt::launch_sweep_box);
+}
+
+int rt_sweep_capsule(rt_ctx* ctx, const rt_capsule_sweep* sweeps, size_t n, rt_capsule_sweep_hit* out, uint32_t flags) {
+    return record_query(ctx, "rt_sweep_capsule", {"sweeps", sweeps, sizeof(rt_capsule_sweep)}, n, {"out", out, sizeof(rt_capsule_sweep_hit)}, flags, rt::launch_sweep_capsule);
 }
 
 // max_hits records per ray and a second output, the counts.  A chunk is RT_QUERY_CHUNK / max(max_hits, 1) rays: its hit records never

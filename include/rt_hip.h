@@ -224,7 +224,7 @@ int rt_get_stats(rt_ctx* ctx, rt_stats* out);
  * a new one at sample 0 by itself, as RT_FLAG_ACCUMULATE_RESTART does.  The other RT_FLAG_* bits change no bits and may differ.
  * The running image ends (the next accumulating call starts at 0) with rt_upload_scene*, rt_update_geometry, rt_dispatch_tile, any
  * rt_render without RT_FLAG_ACCUMULATE and an accumulating call that fails once it has passed its argument checks.  It survives rt_prepare,
- * rt_upload_textures, the ray queries, the surface queries, rt_direct_light, rt_radiance, rt_radiance_sh, rt_irradiance, rt_closest_point, rt_closest_point_all, rt_inside, rt_signed_distance, rt_overlap_box, rt_sweep_sphere, rt_sweep_box, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
+ * rt_upload_textures, the ray queries, the surface queries, rt_direct_light, rt_radiance, rt_radiance_sh, rt_irradiance, rt_closest_point, rt_closest_point_all, rt_inside, rt_signed_distance, rt_overlap_box, rt_sweep_sphere, rt_sweep_box, rt_sweep_capsule, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
  * Limit: RT_ACCUMULATE_MAX_SAMPLES samples (where the float sample count stops being exact); a call that would pass it is RT_ERR_BAD_ARG
  * and leaves the running image as it was.  rt_stats describes the call alone (its segments, pixels, kernel_ms).
  * A context over several devices, and a tile_rank / tile_world share, accumulates its own share of the pixels.
@@ -1035,6 +1035,73 @@ RT_STATIC_ASSERT(sizeof(rt_box_sweep_hit) == 32 && offsetof(rt_box_sweep_hit, no
 
 /* First contact of each of the n moving boxes. */
 int rt_sweep_box(rt_ctx* ctx, const rt_box_sweep* sweeps, size_t n, rt_box_sweep_hit* out, uint32_t flags); /* RT_QUERY_COUNTERS */
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Capsule sweeps: the first contact of a moving capsule with the scene's surface (no reference counterpart; the "capsule cast" of
+ * the collision libraries is the model): the body that character and camera controllers move.  A chain of rt_sweep_sphere calls
+ * along the axis misses what passes between the spheres, rt_sweep_box with the capsule's bounding box reports contacts at corners
+ * the rounded body never makes, and one fat sphere is wrong by the length of the body.  The capsule is every point within radius of
+ * the segment A(t) .. B(t), A(t) = origin + direction * t, B(t) = A(t) + axis; it keeps its orientation.  The answer is the smallest
+ * t in [0, tmax) at which it touches the surface, the point of the primitive in contact and the place s on the axis (0 at A, 1 at
+ * B) nearest to it.  The surface is two-sided and a sphere primitive is its surface, as for rt_sweep_sphere.  The answer is one f32
+ * statement (csrc/sweep_capsule_rules.h, whose header comment is the specification; every operation one f32 rounding, nothing
+ * fused), built from the pieces of "Sphere sweeps" (the pushed-out face, sw_vertex, sw_edge) with r = radius, d = direction:
+ * Closest pair cap_triangle(v0, e1, e2, P, axis) -> dist2, s, v, w of the axis segment from P and a triangle: the first candidate
+ *   with the strictly smallest dist2 of: end P by the closest-point statement (s = 0); end P + axis (s = 1); the axis against the
+ *   edges (v0, e1), (v0, e2), (v0 + e1, e2 - e1) as two clamped segments, each only if dot(axis, axis) > 0 and dot(e, e) > 0; the
+ *   axis piercing the triangle (dist2 = 0), only if dot(axis, axis) > 0, the ends' heights over the plane have strictly opposite
+ *   signs and the crossing point's weights satisfy v >= 0, w >= 0, v + w <= 1.
+ * Triangle: cap_triangle at the start <= r * r -> t = 0.  Otherwise, with ap_k = A - v_k and mB_k = ap_k + axis, the minimum over the
+ *   accepting pieces of: the seven pieces of "Sphere sweeps" from ap_k (end A); the same seven from mB_k (end B); the cylinder wall
+ *   against the vertices, sw_edge(mB_k, axis), k = 0, 1, 2; the cylinder wall against the edges, the face piece on (mB_0, e1, axis),
+ *   (mB_0, e2, axis), (mB_1, e2 - e1, axis) accepted as a parallelogram (both weights in [0, 1]); t is that minimum + 0.0f.
+ * Sphere i (centre C, radius R): dmin the distance of C from the axis segment, dmax the larger of the ends' distances.
+ *   dmin - R <= r && R - dmax <= r -> t = 0.  From outside (dmin > R): the minimum of the two ends' entering roots and the cylinder's
+ *   (sw_edge's form) against R + r.  Otherwise: the smaller of the two ends' leaving roots against R - r.
+ * The hit: for a triangle s, v, w = cap_triangle at P = origin + direction * t (per component) and position = v0 + (e1 v + e2 w); for
+ *   a sphere s is the clamped foot of C on the axis at that pose from outside, the end farther from C (A on a tie) from inside, and
+ *   position the nearest point of the sphere to that axis point.  A contact at t = 0 carries the closest pair of the start pose.
+ * With axis == 0 exactly the call returns rt_sweep_sphere's t, position, prim_id and material_id bit for bit, with s = 0.
+ * Order: as for rt_sweep_sphere: (the bits of t, key) as one 64-bit unsigned number from (the bits of tmax, 0).  Only t < tmax is ever
+ *   accepted, strictly; at equal t spheres come before triangles, each kind by ascending index.
+ * A miss: position 0, t = tmax as given, s = 0, prim_id 0xFFFFFFFF, material_id 0.  A query with a non-finite component of origin,
+ *   axis or direction, a zero direction, a radius that is NaN, <= 0 or infinite, or a tmax that is NaN or <= 0 is such a miss
+ *   without a walk.  The kernel checks this itself.
+ * The result follows from these rules alone: it does not depend on the tree in use, the device count, the kind of memory or the
+ *   chunking, and after rt_update_geometry it is that of a fresh upload of the moved scene.  The tree only culls, by the entry time
+ *   of the centre of the capsule's bounding box into each child box widened by that box's half extents and a margin past the
+ *   statement's own rounding; the bound is loose for a long diagonal capsule.
+ * Buffers, chunking, the split over devices, synchronisation, side effects, flags, statistics and errors as for rt_sweep_sphere; the
+ * records are 48 bytes in and 32 bytes out, device memory 16-byte aligned.
+ * --------------------------------------------------------------------------------------------------------------- */
+typedef struct rt_capsule_sweep {  /* an rt_sweep with 16 bytes inserted at offset 16 */
+    float origin[3];       /* end A of the axis at t = 0 */
+    float radius;          /* > 0, finite */
+    float axis[3];         /* B - A; zero allowed (a moving sphere) */
+    uint32_t _pad;         /* ignored */
+    float direction[3];    /* need not be normalised; A(t) = origin + direction * t */
+    float tmax;            /* contacts at 0 <= t < tmax are reported; > 0, +inf allowed */
+} rt_capsule_sweep; /* 48 bytes */
+
+typedef struct rt_capsule_sweep_hit {
+    float position[3];     /* the point of the primitive in contact; 0 on a miss */
+    float t;               /* time of first contact; tmax as given on a miss */
+    float s;               /* where on the axis the contact is nearest: 0 at A .. 1 at B; 0 on a miss */
+    uint32_t _reserved;    /* written as 0 */
+    uint32_t prim_id;      /* as rt_hit.prim_id; 0xFFFFFFFF = miss */
+    uint32_t material_id;  /* the record's material id, unchecked; 0 on a miss */
+} rt_capsule_sweep_hit; /* 32 bytes */
+
+RT_STATIC_ASSERT(sizeof(rt_capsule_sweep) == 48 && offsetof(rt_capsule_sweep, origin) == 0 && offsetof(rt_capsule_sweep, radius) == 12 &&
+                     offsetof(rt_capsule_sweep, axis) == 16 && offsetof(rt_capsule_sweep, direction) == 32 && offsetof(rt_capsule_sweep, tmax) == 44,
+                 "rt_capsule_sweep is 48 B: origin, radius at 12, axis at 16, direction at 32, tmax at 44");
+RT_STATIC_ASSERT(sizeof(rt_capsule_sweep_hit) == 32 && offsetof(rt_capsule_sweep_hit, position) == 0 && offsetof(rt_capsule_sweep_hit, t) == 12 &&
+                     offsetof(rt_capsule_sweep_hit, s) == 16 && offsetof(rt_capsule_sweep_hit, prim_id) == 24 &&
+                     offsetof(rt_capsule_sweep_hit, material_id) == 28,
+                 "rt_capsule_sweep_hit is 32 B: position, t at 12, s at 16, prim_id at 24, material_id at 28");
+
+/* First contact of each of the n moving capsules. */
+int rt_sweep_capsule(rt_ctx* ctx, const rt_capsule_sweep* sweeps, size_t n, rt_capsule_sweep_hit* out, uint32_t flags); /* RT_QUERY_COUNTERS */
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Overlap queries: the primitives that touch caller-supplied axis-aligned boxes (no reference counterpart; the OverlapBox /
