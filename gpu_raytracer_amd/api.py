@@ -33,13 +33,15 @@ PREPARE_SHADOW_GRIDS = 1
 PREPARE_QUALITY_TREE = 2
 QUERY_COUNTERS = 1  # RT_QUERY_COUNTERS of rt_intersect / rt_occluded
 QUERY_CHUNK = 4194304  # RT_QUERY_CHUNK: host batches are staged in chunks of at most this many rays
-QUERY_COUNT_ALL = 2  # RT_QUERY_COUNT_ALL of rt_intersect_all / rt_closest_point_all / rt_overlap_box: counts are all candidates in the range, not the records written
+QUERY_COUNT_ALL = 2  # RT_QUERY_COUNT_ALL of rt_intersect_all / rt_closest_point_all / rt_overlap_box / rt_contact_capsule: counts are all candidates in the range, not the records written
 MULTI_HIT_MAX = 16  # RT_MULTI_HIT_MAX: the most hits rt_intersect_all lists per ray
 NEAREST_MAX = 16  # RT_NEAREST_MAX: the most primitives rt_closest_point_all lists per point
 OVERLAP_MAX = 32  # RT_OVERLAP_MAX: the most primitives rt_overlap_box lists per box
 SWEEP_AXIS_SPHERE = 13  # RT_SWEEP_AXIS_SPHERE of rt_box_sweep_hit.axis: the contact is with a sphere primitive
 SWEEP_AXIS_NONE = 0xFFFFFFFF  # RT_SWEEP_AXIS_NONE: a miss, or in contact at the start
 OVERLAP_ANY = 4  # RT_OVERLAP_ANY of rt_overlap_box: counts are 1 where anything touches the box, else 0, and the walk stops at the first
+CONTACT_MAX = 16  # RT_CONTACT_MAX: the most primitives rt_contact_capsule lists per capsule
+CONTACT_ANY = 4  # RT_CONTACT_ANY of rt_contact_capsule: counts are 1 where anything is in range of the capsule, else 0, and the walk stops at the first
 INSIDE_MAX_RAYS = 7  # RT_INSIDE_MAX_RAYS: the most parity rays rt_inside / rt_signed_distance trace per point
 INSIDE_DIRECTIONS = np.array([  # RT_INSIDE_DIRECTIONS: direction k of vote k, used as given
     [0.5377, 0.7431, 0.3982], [-0.6241, 0.3517, 0.6977], [0.2893, -0.4719, 0.8328],
@@ -69,7 +71,7 @@ ABI_SYMBOLS = [
     "rt_get_stats", "rt_last_error", "rt_destroy", "rt_version",
     "rt_intersect", "rt_occluded", "rt_camera_rays", "rt_intersect_all",
     "rt_surface", "rt_ambient_occlusion", "rt_direct_light", "rt_radiance", "rt_radiance_sh", "rt_irradiance", "rt_closest_point", "rt_closest_point_all", "rt_sweep_sphere", "rt_sweep_box", "rt_sweep_capsule",
-    "rt_inside", "rt_signed_distance", "rt_overlap_box",
+    "rt_inside", "rt_signed_distance", "rt_overlap_box", "rt_contact_capsule",
     "rt_update_geometry",
     "rt_accumulated_samples",
     "rt_aovs", "rt_sample_rays", "rt_denoise",
@@ -177,6 +179,17 @@ def _check_nearest_lists(a, n, max_nearest):
         raise ValueError("out: not C-contiguous")
     if a.shape[0] != n:
         raise ValueError(f"out: {a.shape[0]} rows for {n} points")
+
+
+def _check_contact_lists(a, n, max_contacts):
+    """Raises unless `a` is a C-contiguous float32 (n, max_contacts, 8) array: rt_contact_capsule's records, query-major."""
+    _check_kind_dtype(a, "out", "float32")
+    if len(a.shape) != 3 or tuple(a.shape[1:]) != (max_contacts, 8):
+        raise ValueError(f"out: shape {tuple(a.shape)}, expected (N, {max_contacts}, 8)")
+    if not _contiguous(a):
+        raise ValueError("out: not C-contiguous")
+    if a.shape[0] != n:
+        raise ValueError(f"out: {a.shape[0]} rows for {n} capsules")
 
 
 def _check_prim_lists(a, n, max_prims):
@@ -443,6 +456,32 @@ def split_capsule_sweep_hits(records):
     else:
         words = [np.ascontiguousarray(records[:, c]).view(np.uint32) for c in (6, 7)]
     return records[:, 0:3], records[:, 3], records[:, 4], words[0], words[1]
+
+
+def make_capsules(origin, radius, axis):
+    """(N, 3) origins (end A of each axis; numpy or torch, the result has the same kind and device) -> an (N, 8) float32 batch of
+    rt_capsule records: ox oy oz radius ax ay az 0, the first eight columns of make_capsule_sweeps.  radius: a scalar or an (N,) array,
+    > 0, inf allowed.  axis: B - A, a triple or an (N, 3) array; zero is allowed (a resting sphere)."""
+    if _is_torch(origin):
+        import torch
+        o = origin.reshape(-1, 3)
+        out = torch.zeros((o.shape[0], 8), dtype=torch.float32, device=o.device)
+        conv = lambda x: x if _is_torch(x) else torch.as_tensor(np.asarray(x, np.float32), device=o.device)
+    else:
+        o = np.asarray(origin, np.float32).reshape(-1, 3)
+        out = np.zeros((o.shape[0], 8), np.float32)
+        conv = lambda x: np.asarray(x, np.float32)
+    out[:, 0:3] = o
+    out[:, 3] = conv(radius)
+    out[:, 4:7] = conv(axis).reshape(-1, 3)
+    return out
+
+
+def split_contacts(records):
+    """(N, 8) contact records (rt_contact; contact_capsule's out.reshape(-1, 8)) -> (position (N, 3), distance (N,), s (N,), prim_id
+    (N,), material_id (N,)): rt_capsule_sweep_hit's layout with the distance where t is, so the ids come as split_capsule_sweep_hits
+    gives them (an unused slot is 4294967295 = PRIM_MISS).  normal = (origin + axis * s - position) / distance, depth = radius - distance."""
+    return split_capsule_sweep_hits(records)
 
 
 def split_lighting(lighting):
@@ -1006,6 +1045,38 @@ class Context:
         flags = (QUERY_COUNTERS if counters else 0) | (QUERY_COUNT_ALL if count_all else 0) | (OVERLAP_ANY if any_hit else 0)
         self._check(self.lib.rt_overlap_box(self._h, _addr(boxes), C.c_size_t(n), C.c_uint32(max_prims),
                                             _addr(out) if out is not None else C.c_void_p(0), _addr(counts), C.c_uint32(flags)))
+        return out, counts
+
+    def contact_capsule(self, capsules, max_contacts, *, out=None, counts=None, count_all=False, any_hit=False, counters=False):
+        """rt_contact_capsule: the primitives each resting capsule of an (N, 8) batch (make_capsules: origin, radius, axis) touches ->
+        (out, counts), same kind and device as `capsules`.  out: (N, max_contacts, 8) float32 rt_contact records (split_contacts takes
+        out.reshape(-1, 8): position, distance, s, prim_id, material_id), the max_contacts (0 .. CONTACT_MAX) nearest primitives whose
+        distance from the axis segment is strictly below the radius, nearest first, unused slots miss records; None for
+        max_contacts=0.  counts: (N,) uint32 (numpy) / int32 (torch), the records listed per capsule; with count_all every primitive
+        in range; with any_hit 1 where anything is in range, else 0 (the walk stops at the first: the occupancy test).
+        max_contacts=0 needs count_all or any_hit; any_hit needs max_contacts=0 and excludes count_all.  With a zero axis the
+        records are closest_point_all's with s = 0 where u is."""
+        n = _check_batch(capsules, "capsules", 8, "float32")
+        if isinstance(max_contacts, bool) or not isinstance(max_contacts, (int, np.integer)) or not 0 <= max_contacts <= CONTACT_MAX:
+            raise ValueError(f"max_contacts: {max_contacts!r}, expected an integer in 0 .. {CONTACT_MAX}")
+        max_contacts = int(max_contacts)
+        if any_hit and (count_all or max_contacts > 0):
+            raise ValueError("any_hit: lists nothing and counts to one, which needs max_contacts=0 and excludes count_all")
+        if max_contacts == 0 and not (count_all or any_hit):
+            raise ValueError("max_contacts: 0 lists nothing, which needs count_all=True (a pure count) or any_hit=True")
+        if out is not None and _is_torch(out) != _is_torch(capsules):
+            raise TypeError("out: must be the same kind (numpy / torch) as capsules")
+        if max_contacts == 0:
+            out = None
+        elif out is None:
+            out = _empty_like_batch(capsules, (n, max_contacts, 8), "float32")
+        else:
+            _check_contact_lists(out, n, max_contacts)
+        counts = _counts_like(counts, capsules, "capsules", n)
+        _sync_torch(capsules, out, counts)
+        flags = (QUERY_COUNTERS if counters else 0) | (QUERY_COUNT_ALL if count_all else 0) | (CONTACT_ANY if any_hit else 0)
+        self._check(self.lib.rt_contact_capsule(self._h, _addr(capsules), C.c_size_t(n), C.c_uint32(max_contacts),
+                                                _addr(out) if out is not None else C.c_void_p(0), _addr(counts), C.c_uint32(flags)))
         return out, counts
 
     def sweep_sphere(self, sweeps, out=None, counters=False):

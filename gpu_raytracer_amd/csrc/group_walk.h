@@ -1,7 +1,7 @@
-// group_walk.h — the walk of the wide BVH that the volume queries share (closest point, nearest-K, sphere sweep, box overlap), stated
+// group_walk.h — the walk of the wide BVH that the volume queries share (closest point, nearest-K, the sweeps, box overlap, contact), stated
 // once: the groups, the stack discipline with its bound, and the loop.  What differs between the queries - the bound of a node's child
 // boxes, which slots pass it, what is done with a record - is a Visit, stated in the query's own rules header next to the statements
-// it calls (CpVisit, CpAllVisit, SwVisit, OvVisit).
+// it calls (CpVisit, CpAllVisit, SwVisit, OvVisit, CcVisit).
 //
 // The convention of every rules header: plain inline functions under RT_RULE (bvh_rules.h) - host and device under hipcc, host only
 // under any other compiler - so the kernel and the host check (tests/check_*.cpp) run the same statements; loops over slots and axes

@@ -1,6 +1,6 @@
 // query_lane.h — how one lane of a volume-query kernel reads a node and a record and keeps its stack and its list: the Access that
-// group_walk (group_walk.h) asks of its caller, stated once for k_cp_nearest, k_cp_nearest_all, k_sweep_sphere, k_overlap_box and
-// k_inside; and the closest-point answer of one lane, which k_cp_nearest and k_inside share.
+// group_walk (group_walk.h) asks of its caller, stated once for k_cp_nearest, k_cp_nearest_all, k_sweep_sphere, k_overlap_box,
+// k_contact_capsule and k_inside; and the closest-point answer of one lane, which k_cp_nearest and k_inside share.
 #ifndef RT_QUERY_LANE_H
 #define RT_QUERY_LANE_H
 
@@ -46,7 +46,8 @@ struct LaneAccess {
 };
 
 // The lists live behind the launch's stack (lane_stack_entries), lane-interleaved like it.
-// Nearest-K (closest_point_all_rules.h, rule 7): word f of entry k of this lane at list[(3 * k + f) * WAVE], k < max_nearest.
+// Nearest-K (closest_point_all_rules.h, rule 7; the contact query's list is the same): word f of entry k of this lane at
+// list[(3 * k + f) * WAVE], k < max_nearest.
 template <bool COUNT>
 struct LaneListAccess : LaneAccess<COUNT> {
     uint32_t* list;

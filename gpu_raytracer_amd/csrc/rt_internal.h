@@ -22,6 +22,7 @@
 #include "bvh_builder.h"
 #include "closest_point.h"
 #include "closest_point_all.h"
+#include "contact_capsule.h"
 #include "denoise.h"
 #include "device_build.h"
 #include "device_layout.h"

@@ -224,7 +224,7 @@ int rt_get_stats(rt_ctx* ctx, rt_stats* out);
  * a new one at sample 0 by itself, as RT_FLAG_ACCUMULATE_RESTART does.  The other RT_FLAG_* bits change no bits and may differ.
  * The running image ends (the next accumulating call starts at 0) with rt_upload_scene*, rt_update_geometry, rt_dispatch_tile, any
  * rt_render without RT_FLAG_ACCUMULATE and an accumulating call that fails once it has passed its argument checks.  It survives rt_prepare,
- * rt_upload_textures, the ray queries, the surface queries, rt_direct_light, rt_radiance, rt_radiance_sh, rt_irradiance, rt_closest_point, rt_closest_point_all, rt_inside, rt_signed_distance, rt_overlap_box, rt_sweep_sphere, rt_sweep_box, rt_sweep_capsule, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
+ * rt_upload_textures, the ray queries, the surface queries, rt_direct_light, rt_radiance, rt_radiance_sh, rt_irradiance, rt_closest_point, rt_closest_point_all, rt_inside, rt_signed_distance, rt_overlap_box, rt_sweep_sphere, rt_sweep_box, rt_sweep_capsule, rt_contact_capsule, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
  * Limit: RT_ACCUMULATE_MAX_SAMPLES samples (where the float sample count stops being exact); a call that would pass it is RT_ERR_BAD_ARG
  * and leaves the running image as it was.  rt_stats describes the call alone (its segments, pixels, kernel_ms).
  * A context over several devices, and a tile_rank / tile_world share, accumulates its own share of the pixels.
@@ -370,7 +370,7 @@ int rt_occluded(rt_ctx* ctx, const rt_ray* rays, size_t n, uint8_t* occluded, ui
  * Statistics, synchronisation and side effects as for rt_intersect: synchronous, first waits for an rt_dispatch_tile in flight;
  * rays = n, the other counts 0, kernel_ms the maximum over devices, node_visits / tri_tests only with RT_QUERY_COUNTERS; the last
  * frame, the rt_read_* results and a running accumulation are left alone. */
-#define RT_QUERY_COUNT_ALL 2u   /* rt_intersect_all, rt_closest_point_all and rt_overlap_box only */
+#define RT_QUERY_COUNT_ALL 2u   /* rt_intersect_all, rt_closest_point_all, rt_overlap_box and rt_contact_capsule only */
 #define RT_MULTI_HIT_MAX 16u
 
 int rt_intersect_all(rt_ctx* ctx, const rt_ray* rays, size_t n, uint32_t max_hits,
@@ -1173,6 +1173,88 @@ int rt_overlap_box(rt_ctx* ctx, const rt_box* boxes, size_t n, uint32_t max_prim
                    uint32_t* prims,   /* n * max_prims ids, query-major, rt_hit.prim_id's encoding; unused slots 0xFFFFFFFF */
                    uint32_t* counts,  /* n entries; may be NULL unless max_prims == 0 */
                    uint32_t flags);   /* RT_QUERY_COUNTERS | RT_QUERY_COUNT_ALL | RT_OVERLAP_ANY */
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Contact queries: the primitives a RESTING capsule touches (no reference counterpart; computePenetration / the contact manifold
+ * and CheckCapsule / CheckSphere of the collision libraries are the model): what a character or camera controller pushes out of on
+ * every step, and "is this pose free".  rt_sweep_capsule answers t = 0 for a capsule that starts in contact and names one primitive,
+ * the lowest key and not the deepest; rt_overlap_box with the bounding box over-reports at the corners; a chain of
+ * rt_closest_point_all calls along the axis misses what lies between the points and lists a primitive once per point.
+ * The capsule is every point within radius of the segment A .. B, A = origin, B = origin + axis.  For each capsule the call lists
+ * the max_contacts nearest primitives whose distance from the axis segment is below the radius, nearest first, each with the point
+ * of the primitive, the distance and the place s on the axis (0 at A, 1 at B), so that
+ *   normal = ((origin + axis * s) - position) / distance,   depth = radius - distance
+ * give the push-out.  The surface is two-sided and a sphere primitive is its surface.  The answer is one f32 statement
+ * (csrc/contact_capsule_rules.h, whose header comment is the specification; every operation one f32 rounding, nothing fused):
+ * Triangle, from its record's v0, e1, e2: dist2, s, v, w = cap_triangle(v0, e1, e2, origin, axis) of "Capsule sweeps";
+ *   position = v0 + (e1 v + e2 w).  An axis that pierces the triangle has dist2 = 0.
+ * Sphere i (centre C, radius R): dmin the distance of C from the axis segment with its clamped foot f, lenA and lenB the ends'
+ *   distances and dmax the larger, as in "Capsule sweeps".  The first that holds:
+ *     outside,        dmin > R:                d = dmin - R, s = f
+ *     wholly inside,  dmax < R:                d = R - dmax, s = the end farther from C, A on a tie
+ *     crossing,       dmin <= R && R <= dmax:  d = 0, s = the smallest root in [0, 1] of |A - C + axis s| = R: with mA = A - C,
+ *                     b = dot(mA, axis), c = dot(mA, mA) - R * R, disc = b * b - aa * c, q = disc > 0 ? sqrtf(disc) : 0,
+ *                     s = aa > 0 ? clamp((lenA > R ? -b - q : q - b) / aa) : 0
+ *   and dist2 = d * d; none holds for a NaN centre or radius, and dist2 is a NaN.  position is the nearest point of the sphere to
+ *   origin + axis * s by the closest-point statement.
+ * Order and range: rt_closest_point_all's: (the bits of dist2, key) as one 64-bit unsigned number, in range iff below (the bits of
+ *   radius * radius, 0).  Only dist2 < radius * radius is accepted, strictly; a NaN or infinite dist2 never; at equal dist2 spheres
+ *   come before triangles, each kind by ascending index.  rt_sweep_capsule's start-in-contact test is <=: a listed contact implies
+ *   t = 0 there for the same pose, and the converse fails only at dist2 == radius * radius.
+ * A degenerate query - a non-finite component of origin or axis, or a radius that is NaN or <= 0 - lists nothing, without a walk.
+ *   The kernel checks this itself.  radius = +inf is allowed, as for rt_closest_point; axis = 0 is allowed: with it the call returns
+ *   rt_closest_point_all's records (position, distance, prim_id, material_id) and counts bit for bit, with s = 0.
+ * List mode (flags without RT_QUERY_COUNT_ALL and RT_CONTACT_ANY): capsule i's min(total, max_contacts) nearest contacts at
+ *   out[i * max_contacts ..] (query-major), nearest first; unused slots are misses: position 0, distance = radius as given, s = 0,
+ *   prim_id 0xFFFFFFFF, material_id 0.  counts[i] = the number written; `counts` may be NULL.  1 <= max_contacts <= RT_CONTACT_MAX.
+ * RT_QUERY_COUNT_ALL: the same records; counts[i] = the number of all primitives in range, which can exceed max_contacts.
+ *   max_contacts == 0 is allowed with it, needs a non-NULL counts and ignores `out`: a pure count.
+ * RT_CONTACT_ANY: requires max_contacts == 0 and a non-NULL counts, and excludes RT_QUERY_COUNT_ALL; counts[i] = 1 if anything is in
+ *   range of capsule i, else 0.  The walk stops at the first primitive in range; which one that is depends on the tree, so it is not
+ *   reported.  This is the occupancy test.
+ * The result follows from these rules alone: it does not depend on the tree in use, the device count, the kind of memory or the
+ *   chunking, and after rt_update_geometry it is that of a fresh upload of the moved scene.  The tree only culls, by the distance
+ *   between each child box and the axis segment's bounding box less a margin past the statement's own rounding (DESIGN.md section
+ *   4); the bound is loose for a long diagonal capsule.
+ * Buffers, chunking (RT_QUERY_CHUNK / max(max_contacts, 1) capsules), the split over devices, synchronisation, side effects and
+ *   statistics as for rt_closest_point_all; the records are 32 bytes in and 32 bytes out, device memory 16-byte aligned (counts
+ *   4-byte).
+ * Errors: n == 0 is RT_OK; a NULL capsules, or a NULL out with max_contacts > 0, max_contacts > RT_CONTACT_MAX, max_contacts == 0
+ *   without RT_QUERY_COUNT_ALL or RT_CONTACT_ANY and counts, RT_CONTACT_ANY with max_contacts > 0 or with RT_QUERY_COUNT_ALL, and
+ *   unknown flag bits are RT_ERR_BAD_ARG and change nothing; a call before any upload is RT_ERR_NOT_UPLOADED.  An empty scene gives
+ *   counts of 0 and misses.
+ * --------------------------------------------------------------------------------------------------------------- */
+typedef struct rt_capsule {  /* the first 32 bytes of an rt_capsule_sweep */
+    float origin[3];       /* end A of the axis */
+    float radius;          /* > 0; +inf allowed */
+    float axis[3];         /* B - A; zero allowed (a resting sphere: rt_closest_point_all) */
+    uint32_t _pad;         /* ignored */
+} rt_capsule; /* 32 bytes */
+
+typedef struct rt_contact {  /* rt_capsule_sweep_hit's layout with the distance where t is */
+    float position[3];     /* the point of the primitive nearest the axis; 0 in an unused slot */
+    float distance;        /* its distance from the axis segment, < radius; the radius as given in an unused slot */
+    float s;               /* where on the axis: 0 at A .. 1 at B; 0 in an unused slot */
+    uint32_t _reserved;    /* written as 0 */
+    uint32_t prim_id;      /* as rt_hit.prim_id; 0xFFFFFFFF = unused slot */
+    uint32_t material_id;  /* the record's material id, unchecked; 0 in an unused slot */
+} rt_contact; /* 32 bytes */
+
+RT_STATIC_ASSERT(sizeof(rt_capsule) == 32 && offsetof(rt_capsule, origin) == 0 && offsetof(rt_capsule, radius) == 12 &&
+                     offsetof(rt_capsule, axis) == 16 && offsetof(rt_capsule, _pad) == 28,
+                 "rt_capsule is 32 B: origin, radius at 12, axis at 16, _pad at 28");
+RT_STATIC_ASSERT(sizeof(rt_contact) == 32 && offsetof(rt_contact, position) == 0 && offsetof(rt_contact, distance) == 12 &&
+                     offsetof(rt_contact, s) == 16 && offsetof(rt_contact, _reserved) == 20 && offsetof(rt_contact, prim_id) == 24 &&
+                     offsetof(rt_contact, material_id) == 28,
+                 "rt_contact is 32 B: position, distance at 12, s at 16, _reserved at 20, prim_id at 24, material_id at 28");
+
+#define RT_CONTACT_MAX 16u
+#define RT_CONTACT_ANY 4u   /* rt_contact_capsule only: counts[i] = 1 if anything is in range of capsule i, else 0; stops at the first */
+
+int rt_contact_capsule(rt_ctx* ctx, const rt_capsule* capsules, size_t n, uint32_t max_contacts,
+                       rt_contact* out,   /* n * max_contacts records, query-major; unused slots are misses */
+                       uint32_t* counts,  /* n entries; may be NULL unless max_contacts == 0 */
+                       uint32_t flags);   /* RT_QUERY_COUNTERS | RT_QUERY_COUNT_ALL | RT_CONTACT_ANY */
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Geometry updates: new positions for the uploaded scene, in place (no reference counterpart; Embree's refit build,
