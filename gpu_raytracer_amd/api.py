@@ -71,7 +71,7 @@ ABI_SYMBOLS = [
     "rt_get_stats", "rt_last_error", "rt_destroy", "rt_version",
     "rt_intersect", "rt_occluded", "rt_camera_rays", "rt_intersect_all",
     "rt_surface", "rt_ambient_occlusion", "rt_direct_light", "rt_radiance", "rt_radiance_sh", "rt_irradiance", "rt_closest_point", "rt_closest_point_all", "rt_sweep_sphere", "rt_sweep_box", "rt_sweep_capsule",
-    "rt_inside", "rt_signed_distance", "rt_overlap_box", "rt_contact_capsule",
+    "rt_inside", "rt_signed_distance", "rt_overlap_box", "rt_contact_capsule", "rt_overlap_obb", "rt_sweep_obb",
     "rt_update_geometry",
     "rt_accumulated_samples",
     "rt_aovs", "rt_sample_rays", "rt_denoise",
@@ -415,8 +415,41 @@ def make_box_sweeps(centers, half_extents, directions, tmax=float("inf")):
     return out
 
 
+def make_obbs(center, half_extent, rotation):
+    """(N, 3) centres (numpy or torch, the result has the same kind and device) -> an (N, 12) float32 batch of rt_obb records:
+    cx cy cz 0 hx hy hz 0 qx qy qz qw.  half_extent as for make_boxes, along the box's own axes.  rotation: a quaternion x, y, z, w
+    or an (N, 4) array of them, turning the box's axes into world axes; it need not be normalised."""
+    boxes = make_boxes(center, half_extent)
+    if _is_torch(boxes):
+        import torch
+        out = torch.zeros((boxes.shape[0], 12), dtype=torch.float32, device=boxes.device)
+        q = rotation if _is_torch(rotation) else torch.as_tensor(np.asarray(rotation, np.float32), device=boxes.device)
+    else:
+        out = np.zeros((boxes.shape[0], 12), np.float32)
+        q = np.asarray(rotation, np.float32)
+    out[:, 0:8] = boxes
+    out[:, 8:12] = q
+    return out
+
+
+def make_obb_sweeps(center, half_extent, rotation, direction, tmax=float("inf")):
+    """(N, 3) centres and world directions (numpy or torch, the result has the same kind and device) -> an (N, 16) float32 batch of
+    rt_obb_sweep records: cx cy cz 0 hx hy hz 0 qx qy qz qw dx dy dz tmax.  half_extent and rotation as for make_obbs; tmax: a scalar
+    or an (N,) array; contacts at 0 <= t < tmax are reported."""
+    sweeps = make_box_sweeps(center, half_extent, direction, tmax)
+    boxes = make_obbs(center, half_extent, rotation)
+    if _is_torch(boxes):
+        import torch
+        out = torch.zeros((boxes.shape[0], 16), dtype=torch.float32, device=boxes.device)
+    else:
+        out = np.zeros((boxes.shape[0], 16), np.float32)
+    out[:, 0:12] = boxes
+    out[:, 12:16] = sweeps[:, 8:12]
+    return out
+
+
 def split_box_sweep_hits(records):
-    """(N, 8) box-sweep records (rt_box_sweep_hit) -> (normal (N, 3), t (N,), axis (N,), prim_id (N,), material_id (N,)).  axis and the
+    """(N, 8) box-sweep records (rt_box_sweep_hit, of sweep_box or sweep_obb) -> (normal (N, 3), t (N,), axis (N,), prim_id (N,), material_id (N,)).  axis and the
     ids are the records' uint32 words: uint32 for numpy, int64 for torch (a miss is 4294967295 = PRIM_MISS with axis SWEEP_AXIS_NONE)."""
     if _is_torch(records):
         import torch
@@ -1020,7 +1053,16 @@ class Context:
         triangles by index - ascending, unused slots PRIM_MISS; None for max_prims=0.  counts: (N,) uint32 / int32, the ids listed per
         box; with count_all every touching primitive; with any_hit 1 where anything touches the box, else 0 (the walk stops at the
         first).  max_prims=0 needs count_all or any_hit; any_hit needs max_prims=0 and excludes count_all."""
-        n = _check_batch(boxes, "boxes", 8, "float32")
+        return self._overlap("rt_overlap_box", boxes, 8, max_prims, out, counts, count_all, any_hit, counters)
+
+    def overlap_obb(self, boxes, max_prims, *, out=None, counts=None, count_all=False, any_hit=False, counters=False):
+        """rt_overlap_obb: overlap_box for the closed oriented boxes of an (N, 12) batch (make_obbs: centre, half extent, rotation
+        quaternion x y z w, which need not be normalised) -> (prims, counts) exactly as overlap_box gives them.  With the rotation
+        (0, 0, 0, 1) the answer is overlap_box's."""
+        return self._overlap("rt_overlap_obb", boxes, 12, max_prims, out, counts, count_all, any_hit, counters)
+
+    def _overlap(self, fn, boxes, cols, max_prims, out, counts, count_all, any_hit, counters):
+        n = _check_batch(boxes, "boxes", cols, "float32")
         if isinstance(max_prims, bool) or not isinstance(max_prims, (int, np.integer)) or not 0 <= max_prims <= OVERLAP_MAX:
             raise ValueError(f"max_prims: {max_prims!r}, expected an integer in 0 .. {OVERLAP_MAX}")
         max_prims = int(max_prims)
@@ -1043,8 +1085,8 @@ class Context:
         counts = _counts_like(counts, boxes, "boxes", n)
         _sync_torch(boxes, out, counts)
         flags = (QUERY_COUNTERS if counters else 0) | (QUERY_COUNT_ALL if count_all else 0) | (OVERLAP_ANY if any_hit else 0)
-        self._check(self.lib.rt_overlap_box(self._h, _addr(boxes), C.c_size_t(n), C.c_uint32(max_prims),
-                                            _addr(out) if out is not None else C.c_void_p(0), _addr(counts), C.c_uint32(flags)))
+        self._check(getattr(self.lib, fn)(self._h, _addr(boxes), C.c_size_t(n), C.c_uint32(max_prims),
+                                          _addr(out) if out is not None else C.c_void_p(0), _addr(counts), C.c_uint32(flags)))
         return out, counts
 
     def contact_capsule(self, capsules, max_contacts, *, out=None, counts=None, count_all=False, any_hit=False, counters=False):
@@ -1092,6 +1134,13 @@ class Context:
         prim_id, material_id), same kind and device as `sweeps`.  Only contacts at 0 <= t < tmax are reported; a miss is normal 0,
         tmax as t, axis SWEEP_AXIS_NONE and prim_id = PRIM_MISS; a start in contact is t = 0 with normal 0 and SWEEP_AXIS_NONE."""
         return self._query("rt_sweep_box", sweeps, out, 8, "float32", counters, in_cols=12, in_name="sweeps")
+
+    def sweep_obb(self, sweeps, out=None, counters=False):
+        """rt_sweep_obb: sweep_box for the moving oriented boxes of an (N, 16) batch (make_obb_sweeps: centre, half extent, rotation,
+        direction, tmax) -> (N, 8) float32 rt_box_sweep_hit records (split_box_sweep_hits), same kind and device as `sweeps`.  The
+        normal is in world space, `axis` is read in the box's frame; misses and starts in contact as sweep_box reports them.  With the
+        rotation (0, 0, 0, 1) the answer is sweep_box's."""
+        return self._query("rt_sweep_obb", sweeps, out, 8, "float32", counters, in_cols=16, in_name="sweeps")
 
     def sweep_capsule(self, sweeps, out=None, counters=False):
         """rt_sweep_capsule: the first contact of each moving capsule of an (N, 12) batch (make_capsule_sweeps: origin, radius, axis,

@@ -72,12 +72,16 @@ RT_RULE bool ov_cross_axes(const float f[3], const float a0[3], const float a1[3
            ov_span(f[2] * a0[0] - f[0] * a0[2], f[2] * a1[0] - f[0] * a1[2], f[2] * a2[0] - f[0] * a2[2], g[2] * h[0] + g[0] * h[2]) &&
            ov_span(f[0] * a0[1] - f[1] * a0[0], f[0] * a1[1] - f[1] * a1[0], f[0] * a2[1] - f[1] * a2[0], g[1] * h[0] + g[0] * h[1]);
 }
-RT_RULE bool ov_triangle(const float v0[3], const float e1[3], const float e2[3], const float c[3], const float h[3]) {
+// The statement is written once, over a source of the relative vertices: `rel(a, p0, p1, p2)` gives component a of a0, a1, a2.
+// ov_triangle's source is its own subtraction, made axis by axis inside the loop as it always was; ov_triangle_rel's is a caller
+// that has the three relative vertices already, in another frame (obb_rules.h: a0, a1, a2, e1, e2 in the box's own axes).
+template <class Rel>
+RT_RULE bool ov_triangle_from(const Rel& rel, const float e1[3], const float e2[3], const float h[3]) {
     float a0[3], a1[3], a2[3];
     bool ok = true;
     RT_CP_UNROLL
     for (int a = 0; a < 3; a++) {
-        a0[a] = v0[a] - c[a], a1[a] = (v0[a] + e1[a]) - c[a], a2[a] = (v0[a] + e2[a]) - c[a];
+        rel(a, a0[a], a1[a], a2[a]);
         ok = ok && ov_finite(a0[a]) && ov_finite(a1[a]) && ov_finite(a2[a]);
         ok = ok && ov_min(ov_min(a0[a], a1[a]), a2[a]) <= h[a] && ov_max(ov_max(a0[a], a1[a]), a2[a]) >= -h[a];
     }
@@ -88,6 +92,21 @@ RT_RULE bool ov_triangle(const float v0[3], const float e1[3], const float e2[3]
     if (!(d <= r && d >= -r)) return false;
     const float f1[3] = {e2[0] - e1[0], e2[1] - e1[1], e2[2] - e1[2]};
     return ov_cross_axes(e1, a0, a1, a2, h) && ov_cross_axes(f1, a0, a1, a2, h) && ov_cross_axes(e2, a0, a1, a2, h);
+}
+// (sweep_box_rules.h uses the same two sources for sb_triangle_from, with q.c as c: change them with both statements in mind)
+struct OvFromRecord { // a_k = v0 - c, (v0 + e1) - c, (v0 + e2) - c
+    const float *v0, *e1, *e2, *c;
+    RT_RULE void operator()(int a, float& p0, float& p1, float& p2) const { p0 = v0[a] - c[a], p1 = (v0[a] + e1[a]) - c[a], p2 = (v0[a] + e2[a]) - c[a]; }
+};
+struct OvFromRelative {
+    const float *a0, *a1, *a2;
+    RT_RULE void operator()(int a, float& p0, float& p1, float& p2) const { p0 = a0[a], p1 = a1[a], p2 = a2[a]; }
+};
+RT_RULE bool ov_triangle(const float v0[3], const float e1[3], const float e2[3], const float c[3], const float h[3]) {
+    return ov_triangle_from(OvFromRecord{v0, e1, e2, c}, e1, e2, h);
+}
+RT_RULE bool ov_triangle_rel(const float a0[3], const float a1[3], const float a2[3], const float e1[3], const float e2[3], const float h[3]) {
+    return ov_triangle_from(OvFromRelative{a0, a1, a2}, e1, e2, h);
 }
 
 // ---- 3. A sphere is its surface, as in rt_closest_point:

@@ -32,6 +32,7 @@
 #include "irradiance_query.h"
 #include "kernels.h"
 #include "overlap.h"
+#include "overlap_obb.h"
 #include "path_query.h"
 #include "probe_query.h"
 #include "ray_query.h"
@@ -41,6 +42,7 @@
 #include "sweep.h"
 #include "sweep_box.h"
 #include "sweep_capsule.h"
+#include "sweep_obb.h"
 #include "wavefront.h"
 
 #define HIPCHK(ctx, call)                                                                                       \

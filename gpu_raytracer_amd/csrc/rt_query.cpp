@@ -206,7 +206,7 @@ void batch_stats(rt_ctx* ctx, double w0, const Totals& t, bool counters, uint64_
     st.wall_ms = now_ms() - w0;
 }
 
-// rt_intersect, rt_occluded, rt_surface, rt_closest_point, rt_sweep_sphere, rt_sweep_box, rt_sweep_capsule: one record in, one record out, one lane of `launch` per record.
+// rt_intersect, rt_occluded, rt_surface, rt_closest_point, rt_sweep_sphere, rt_sweep_box, rt_sweep_obb, rt_sweep_capsule: one record in, one record out, one lane of `launch` per record.
 using RecordLaunch = hipError_t (*)(const DevScene&, const void*, void*, uint32_t, unsigned long long*, hipStream_t);
 int record_query(rt_ctx* ctx, const char* fn, BatchIn in, size_t n, BatchOut out, uint32_t flags, RecordLaunch launch) {
     const double w0 = now_ms();
@@ -491,6 +491,41 @@ int inside_query(rt_ctx* ctx, const char* fn, const rt_point_query* points, size
     return RT_OK;
 }
 
+// max_prims ids per box and a second output, the counts: rt_closest_point_all's shape with 4-byte records.  A chunk is RT_QUERY_CHUNK /
+// max(max_prims, 1) boxes.
+static_assert(RT_OVERLAP_MAX == rt::OV_PRIMS_MAX, "the kernel's list holds RT_OVERLAP_MAX entries");
+// rt_overlap_box and rt_overlap_obb: the same argument checks and batch, with the record's size and the launcher of each.
+using OverlapLaunch = hipError_t (*)(const DevScene&, const void*, uint32_t*, uint32_t*, uint32_t, uint32_t, int, unsigned long long*, hipStream_t);
+int overlap_query(rt_ctx* ctx, const char* fn, const void* boxes, size_t box_size, size_t n, uint32_t max_prims, uint32_t* prims, uint32_t* counts,
+                  uint32_t flags, OverlapLaunch launch) {
+    const double w0 = now_ms();
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (n == 0) return RT_OK;
+    if (!boxes || (!prims && max_prims > 0)) return ctx->fail(RT_ERR_BAD_ARG, "%s: %s is NULL with n = %zu", fn, !boxes ? "boxes" : "prims", n);
+    if (max_prims > RT_OVERLAP_MAX) return ctx->fail(RT_ERR_BAD_ARG, "%s: max_prims %u (0 .. %u)", fn, max_prims, RT_OVERLAP_MAX);
+    const uint32_t known = RT_QUERY_COUNTERS | RT_QUERY_COUNT_ALL | RT_OVERLAP_ANY;
+    if (flags & ~known) return ctx->fail(RT_ERR_BAD_ARG, "%s: unknown flag bits 0x%x", fn, flags & ~known);
+    const bool counters = (flags & RT_QUERY_COUNTERS) != 0, all = (flags & RT_QUERY_COUNT_ALL) != 0, any = (flags & RT_OVERLAP_ANY) != 0;
+    if (any && (all || max_prims > 0)) return ctx->fail(RT_ERR_BAD_ARG, "%s: RT_OVERLAP_ANY needs max_prims 0 and excludes RT_QUERY_COUNT_ALL", fn);
+    if (max_prims == 0 && ((!all && !any) || !counts))
+        return ctx->fail(RT_ERR_BAD_ARG, "%s: max_prims 0 needs RT_QUERY_COUNT_ALL or RT_OVERLAP_ANY, and counts", fn);
+    if (!ctx->uploaded) return ctx->fail(RT_ERR_NOT_UPLOADED, "%s: no scene uploaded", fn);
+    if (max_prims == 0) prims = nullptr; // ignored: a pure count
+    const int mode = any ? rt::OV_ANY : all ? rt::OV_COUNT_ALL : rt::OV_LIST;
+    const size_t chunk = RT_QUERY_CHUNK / std::max(max_prims, 1u);
+    const Batch b{fn, n, {"boxes", boxes, box_size},
+                  {{"prims", prims, max_prims * sizeof(uint32_t), 4}, {"counts", counts, sizeof(uint32_t), 4, ST_COUNTS}},
+                  chunk, chunk, counters ? RT_CNT_TRI_TESTS + 1u : 0u};
+    Totals t;
+    if (int rc = run_batch(ctx, b, t, [&](DeviceState& d, const DevScene& sc, const Chunk& ck) {
+            return launch(sc, ck.in, static_cast<uint32_t*>(ck.out[0]), static_cast<uint32_t*>(ck.out[1]), ck.m, max_prims, mode,
+                          counters ? d.counters.get() : nullptr, d.stream);
+        }))
+        return rc;
+    batch_stats(ctx, w0, t, counters, n);
+    return RT_OK;
+}
+
 } // namespace
 
 } // namespace rti
@@ -521,6 +556,10 @@ int rt_sweep_sphere(rt_ctx* ctx, const rt_sweep* sweeps, size_t n, rt_sweep_hit*
 
 int rt_sweep_box(rt_ctx* ctx, const rt_box_sweep* sweeps, size_t n, rt_box_sweep_hit* out, uint32_t flags) {
     return record_query(ctx, "rt_sweep_box", {"sweeps", sweeps, sizeof(rt_box_sweep)}, n, {"out", out, sizeof(rt_box_sweep_hit)}, flags, rt::launch_sweep_box);
+}
+
+int rt_sweep_obb(rt_ctx* ctx, const rt_obb_sweep* sweeps, size_t n, rt_box_sweep_hit* out, uint32_t flags) {
+    return record_query(ctx, "rt_sweep_obb", {"sweeps", sweeps, sizeof(rt_obb_sweep)}, n, {"out", out, sizeof(rt_box_sweep_hit)}, flags, rt::launch_sweep_obb);
 }
 
 int rt_sweep_capsule(rt_ctx* ctx, const rt_capsule_sweep* sweeps, size_t n, rt_capsule_sweep_hit* out, uint32_t flags) {
@@ -585,37 +624,11 @@ int rt_closest_point_all(rt_ctx* ctx, const rt_point_query* points, size_t n, ui
     return RT_OK;
 }
 
-// max_prims ids per box and a second output, the counts: rt_closest_point_all's shape with 4-byte records.  A chunk is RT_QUERY_CHUNK /
-// max(max_prims, 1) boxes.
-static_assert(RT_OVERLAP_MAX == rt::OV_PRIMS_MAX, "the kernel's list holds RT_OVERLAP_MAX entries");
 int rt_overlap_box(rt_ctx* ctx, const rt_box* boxes, size_t n, uint32_t max_prims, uint32_t* prims, uint32_t* counts, uint32_t flags) {
-    const char* fn = "rt_overlap_box";
-    const double w0 = now_ms();
-    if (!ctx) return RT_ERR_BAD_ARG;
-    if (n == 0) return RT_OK;
-    if (!boxes || (!prims && max_prims > 0)) return ctx->fail(RT_ERR_BAD_ARG, "%s: %s is NULL with n = %zu", fn, !boxes ? "boxes" : "prims", n);
-    if (max_prims > RT_OVERLAP_MAX) return ctx->fail(RT_ERR_BAD_ARG, "%s: max_prims %u (0 .. %u)", fn, max_prims, RT_OVERLAP_MAX);
-    const uint32_t known = RT_QUERY_COUNTERS | RT_QUERY_COUNT_ALL | RT_OVERLAP_ANY;
-    if (flags & ~known) return ctx->fail(RT_ERR_BAD_ARG, "%s: unknown flag bits 0x%x", fn, flags & ~known);
-    const bool counters = (flags & RT_QUERY_COUNTERS) != 0, all = (flags & RT_QUERY_COUNT_ALL) != 0, any = (flags & RT_OVERLAP_ANY) != 0;
-    if (any && (all || max_prims > 0)) return ctx->fail(RT_ERR_BAD_ARG, "%s: RT_OVERLAP_ANY needs max_prims 0 and excludes RT_QUERY_COUNT_ALL", fn);
-    if (max_prims == 0 && ((!all && !any) || !counts))
-        return ctx->fail(RT_ERR_BAD_ARG, "%s: max_prims 0 needs RT_QUERY_COUNT_ALL or RT_OVERLAP_ANY, and counts", fn);
-    if (!ctx->uploaded) return ctx->fail(RT_ERR_NOT_UPLOADED, "%s: no scene uploaded", fn);
-    if (max_prims == 0) prims = nullptr; // ignored: a pure count
-    const int mode = any ? rt::OV_ANY : all ? rt::OV_COUNT_ALL : rt::OV_LIST;
-    const size_t chunk = RT_QUERY_CHUNK / std::max(max_prims, 1u);
-    const Batch b{fn, n, {"boxes", boxes, sizeof(rt_box)},
-                  {{"prims", prims, max_prims * sizeof(uint32_t), 4}, {"counts", counts, sizeof(uint32_t), 4, ST_COUNTS}},
-                  chunk, chunk, counters ? RT_CNT_TRI_TESTS + 1u : 0u};
-    Totals t;
-    if (int rc = run_batch(ctx, b, t, [&](DeviceState& d, const DevScene& sc, const Chunk& ck) {
-            return rt::launch_overlap_box(sc, ck.in, static_cast<uint32_t*>(ck.out[0]), static_cast<uint32_t*>(ck.out[1]), ck.m, max_prims, mode,
-                                          counters ? d.counters.get() : nullptr, d.stream);
-        }))
-        return rc;
-    batch_stats(ctx, w0, t, counters, n);
-    return RT_OK;
+    return overlap_query(ctx, "rt_overlap_box", boxes, sizeof(rt_box), n, max_prims, prims, counts, flags, rt::launch_overlap_box);
+}
+int rt_overlap_obb(rt_ctx* ctx, const rt_obb* boxes, size_t n, uint32_t max_prims, uint32_t* prims, uint32_t* counts, uint32_t flags) {
+    return overlap_query(ctx, "rt_overlap_obb", boxes, sizeof(rt_obb), n, max_prims, prims, counts, flags, rt::launch_overlap_obb);
 }
 
 // max_contacts records per capsule and a second output, the counts: rt_closest_point_all's shape with rt_overlap_box's modes.  A

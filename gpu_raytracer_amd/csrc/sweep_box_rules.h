@@ -108,12 +108,16 @@ RT_RULE void sb_cross_axes(SbSpan& s, uint32_t first, const float f[3], const fl
 }
 RT_RULE bool sb_over(const SbSpan& s, float limit) { return !s.ok || s.t_in > s.t_out || s.t_in > limit; }
 // the time of first contact, +inf when there is none or when it is later than `limit`; axis and w_in of the axis that set it
-RT_RULE float sb_triangle(const float v0[3], const float e1[3], const float e2[3], const SbQuery& q, float limit, uint32_t& axis, float& w_in) {
+// The statement is written once, over a source of the relative vertices (overlap_rules.h, OvFromRecord / OvFromRelative): sb_triangle's
+// is its own subtraction from q.c, made axis by axis inside the loop as it always was; sb_triangle_rel's is a caller that has a0, a1,
+// a2, e1, e2 and q.h, q.d in another frame already (obb_rules.h; q.c is not read).
+template <class Rel>
+RT_RULE float sb_triangle_from(const Rel& rel, const float e1[3], const float e2[3], const SbQuery& q, float limit, uint32_t& axis, float& w_in) {
     float a0[3], a1[3], a2[3];
     SbSpan s{0.0f, INFINITY, 0.0f, SB_AXIS_NONE, true};
     RT_CP_UNROLL
     for (int a = 0; a < 3; a++) {
-        a0[a] = v0[a] - q.c[a], a1[a] = (v0[a] + e1[a]) - q.c[a], a2[a] = (v0[a] + e2[a]) - q.c[a];
+        rel(a, a0[a], a1[a], a2[a]);
         s.ok = s.ok && ov_finite(a0[a]) && ov_finite(a1[a]) && ov_finite(a2[a]);
         sb_axis(s, (uint32_t)a, ov_min(ov_min(a0[a], a1[a]), a2[a]), ov_max(ov_max(a0[a], a1[a]), a2[a]), q.h[a], q.d[a]);
     }
@@ -133,6 +137,13 @@ RT_RULE float sb_triangle(const float v0[3], const float e1[3], const float e2[3
     if (sb_over(s, limit)) return INFINITY;
     axis = s.axis, w_in = s.w_in;
     return s.t_in + 0.0f;
+}
+RT_RULE float sb_triangle(const float v0[3], const float e1[3], const float e2[3], const SbQuery& q, float limit, uint32_t& axis, float& w_in) {
+    return sb_triangle_from(OvFromRecord{v0, e1, e2, q.c}, e1, e2, q, limit, axis, w_in);
+}
+RT_RULE float sb_triangle_rel(const float a0[3], const float a1[3], const float a2[3], const float e1[3], const float e2[3], const SbQuery& q, float limit,
+                              uint32_t& axis, float& w_in) {
+    return sb_triangle_from(OvFromRelative{a0, a1, a2}, e1, e2, q, limit, axis, w_in);
 }
 RT_RULE void sb_axis_normal(const float e1[3], const float e2[3], uint32_t axis, float w_in, float normal[3]) {
     float L[3] = {axis == 0u ? 1.0f : 0.0f, axis == 1u ? 1.0f : 0.0f, axis == 2u ? 1.0f : 0.0f}; // no array is indexed by `axis`: registers

@@ -224,7 +224,7 @@ int rt_get_stats(rt_ctx* ctx, rt_stats* out);
  * a new one at sample 0 by itself, as RT_FLAG_ACCUMULATE_RESTART does.  The other RT_FLAG_* bits change no bits and may differ.
  * The running image ends (the next accumulating call starts at 0) with rt_upload_scene*, rt_update_geometry, rt_dispatch_tile, any
  * rt_render without RT_FLAG_ACCUMULATE and an accumulating call that fails once it has passed its argument checks.  It survives rt_prepare,
- * rt_upload_textures, the ray queries, the surface queries, rt_direct_light, rt_radiance, rt_radiance_sh, rt_irradiance, rt_closest_point, rt_closest_point_all, rt_inside, rt_signed_distance, rt_overlap_box, rt_sweep_sphere, rt_sweep_box, rt_sweep_capsule, rt_contact_capsule, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
+ * rt_upload_textures, the ray queries, the surface queries, rt_direct_light, rt_radiance, rt_radiance_sh, rt_irradiance, rt_closest_point, rt_closest_point_all, rt_inside, rt_signed_distance, rt_overlap_box, rt_sweep_sphere, rt_sweep_box, rt_sweep_capsule, rt_contact_capsule, rt_overlap_obb, rt_sweep_obb, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
  * Limit: RT_ACCUMULATE_MAX_SAMPLES samples (where the float sample count stops being exact); a call that would pass it is RT_ERR_BAD_ARG
  * and leaves the running image as it was.  rt_stats describes the call alone (its segments, pixels, kernel_ms).
  * A context over several devices, and a tile_rank / tile_world share, accumulates its own share of the pixels.
@@ -1255,6 +1255,75 @@ int rt_contact_capsule(rt_ctx* ctx, const rt_capsule* capsules, size_t n, uint32
                        rt_contact* out,   /* n * max_contacts records, query-major; unused slots are misses */
                        uint32_t* counts,  /* n entries; may be NULL unless max_contacts == 0 */
                        uint32_t flags);   /* RT_QUERY_COUNTERS | RT_QUERY_COUNT_ALL | RT_CONTACT_ANY */
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Oriented boxes: rt_overlap_box and rt_sweep_box for a box with an orientation (no reference counterpart; OverlapBox, BoxCast,
+ * contactTest and the box sweep of the collision libraries, which all take an orientation, are the model): a crate on a slope, a
+ * vehicle hull, a door leaf, a turned trigger volume.  The world-aligned bounding box of a turned box has up to 3 sqrt 3 times its
+ * volume and reports contacts the body never makes, the inscribed box tunnels, and turning the scene instead costs an
+ * rt_update_geometry per orientation.  The answer is one f32 statement (csrc/obb_rules.h, whose header comment is the specification;
+ * every operation one f32 rounding, nothing fused):
+ * Frame: rotation = (x, y, z, w) is the quaternion that turns the box's own axes into world axes; it need not be normalised.
+ *   n = ((x*x + y*y) + z*z) + w*w, s = 2.0f / n, xs = x*s, ys = y*s, zs = z*s, wx = w*xs, wy = w*ys, wz = w*zs, xx = x*xs, xy = x*ys,
+ *   xz = x*zs, yy = y*ys, yz = y*zs, zz = z*zs, R = [[1-(yy+zz), xy-wz, xz+wy], [xy+wz, 1-(xx+zz), yz-wx], [xz-wy, yz+wx, 1-(xx+yy)]],
+ *   whose columns are the box's axes in the world.  Into the frame: u'_j = (R_0j*u_0 + R_1j*u_1) + R_2j*u_2; back to the world:
+ *   u_a = (R_a0*u'_0 + R_a1*u'_1) + R_a2*u'_2.
+ * Triangle, from its record's v0, e1, e2: a_k as in "Overlap queries" (v0 - c, (v0 + e1) - c, (v0 + e2) - c), each taken into the
+ *   frame, with e1' = frame(e1), e2' = frame(e2) and, for the sweep, d' = frame(direction); then the thirteen axes of "Overlap
+ *   queries" / "Box sweeps" on (a'_0, a'_1, a'_2, e1', e2', h[, d']), f1 = e2' - e1', dd = dot(d', d'); "all nine components finite"
+ *   is asked of the a'_k.
+ * Sphere (centre o): o' = frame(o - c) per component, then the sphere rules of "Overlap queries" / "Box sweeps" with the sphere's
+ *   centre o', the box's centre 0, h and d'.
+ * rt_sweep_obb's record: t, axis, prim_id and material_id as in "Box sweeps", with `axis` read in the box's frame (0 - 2 the box's
+ *   own axes, 3 the triangle's normal, 4 - 12 the cross axes, RT_SWEEP_AXIS_SPHERE, RT_SWEEP_AXIS_NONE); normal = world(normal') +
+ *   0.0f per component, in world space.  Order and acceptance as there: (the bits of t, key) from (the bits of tmax, 0), strictly.
+ * A degenerate query - one that is degenerate by the rules of rt_overlap_box / rt_sweep_box on center, half_extent (direction, tmax),
+ *   a non-finite component of rotation, or an n that is not finite and > 0 (the zero quaternion; one whose n overflows or underflows
+ *   to 0) - touches nothing, or is the miss record carrying tmax as given, without a walk.  The kernel checks this itself.
+ * With rotation = (0, 0, 0, w), w finite and not 0 (a -0 among x, y, z included), R is the identity and both calls return
+ *   rt_overlap_box's and rt_sweep_box's bytes; the one exception is the sign of a zero component of a sphere contact's normal, which is always + here
+ *   (csrc/obb_rules.h, consequence (a)).  rt_sweep_obb answers t = 0 with RT_SWEEP_AXIS_NONE for a triangle exactly when
+ *   rt_overlap_obb lists that triangle for the start pose.
+ * The result follows from these rules alone: it does not depend on the tree in use, the device count, the kind of memory or the
+ *   chunking, and after rt_update_geometry it is that of a fresh upload of the moved scene.  The tree only culls, in world space, by
+ *   the bounding box of the turned box, H_a = (|R_a0|*h_0 + |R_a1|*h_1) + |R_a2|*h_2 and a margin; the bound
+ *   is loose for a long box turned 45 degrees.
+ * rt_overlap_obb: modes, list order and unused slots, counts, chunking (RT_QUERY_CHUNK / max(max_prims, 1) boxes), the split over
+ *   devices, buffer classification, synchronisation, side effects, statistics and error codes as for rt_overlap_box; the records
+ *   are 48 bytes in, device memory 16-byte aligned (prims and counts 4-byte).
+ * rt_sweep_obb: buffers, chunking, the split over devices, synchronisation, side effects, statistics and error codes as for
+ *   rt_sweep_box; the records are 64 bytes in and 32 bytes out, device memory 16-byte aligned.
+ * --------------------------------------------------------------------------------------------------------------- */
+typedef struct rt_obb {  /* its first 32 bytes are an rt_box */
+    float center[3];
+    uint32_t _pad0;          /* pads are ignored */
+    float half_extent[3];    /* >= 0 per axis, along the box's own axes; 0 is allowed */
+    uint32_t _pad1;
+    float rotation[4];       /* quaternion x, y, z, w: the box's axes -> world axes; any length that is finite and not 0 */
+} rt_obb; /* 48 bytes */
+
+typedef struct rt_obb_sweep {  /* its first 48 bytes are an rt_obb, its last 16 the second half of an rt_sweep */
+    float center[3];         /* of the box at t = 0 */
+    uint32_t _pad0;
+    float half_extent[3];
+    uint32_t _pad1;
+    float rotation[4];
+    float direction[3];      /* world space; not zero; need not be normalised: t is in units of it.  The box does not turn on the way */
+    float tmax;              /* > 0; +inf allowed */
+} rt_obb_sweep; /* 64 bytes */
+
+RT_STATIC_ASSERT(sizeof(rt_obb) == 48 && offsetof(rt_obb, center) == 0 && offsetof(rt_obb, _pad0) == 12 && offsetof(rt_obb, half_extent) == 16 &&
+                     offsetof(rt_obb, _pad1) == 28 && offsetof(rt_obb, rotation) == 32,
+                 "rt_obb is 48 B: center, _pad0 at 12, half_extent at 16, _pad1 at 28, rotation at 32");
+RT_STATIC_ASSERT(sizeof(rt_obb_sweep) == 64 && offsetof(rt_obb_sweep, center) == 0 && offsetof(rt_obb_sweep, half_extent) == 16 &&
+                     offsetof(rt_obb_sweep, rotation) == 32 && offsetof(rt_obb_sweep, direction) == 48 && offsetof(rt_obb_sweep, tmax) == 60,
+                 "rt_obb_sweep is 64 B: center, half_extent at 16, rotation at 32, direction at 48, tmax at 60");
+
+int rt_overlap_obb(rt_ctx* ctx, const rt_obb* boxes, size_t n, uint32_t max_prims,
+                   uint32_t* prims,   /* n * max_prims ids, query-major, rt_hit.prim_id's encoding; unused slots 0xFFFFFFFF */
+                   uint32_t* counts,  /* n entries; may be NULL unless max_prims == 0 */
+                   uint32_t flags);   /* RT_QUERY_COUNTERS | RT_QUERY_COUNT_ALL | RT_OVERLAP_ANY; max_prims <= RT_OVERLAP_MAX */
+int rt_sweep_obb(rt_ctx* ctx, const rt_obb_sweep* sweeps, size_t n, rt_box_sweep_hit* out, uint32_t flags); /* RT_QUERY_COUNTERS */
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Geometry updates: new positions for the uploaded scene, in place (no reference counterpart; Embree's refit build,
