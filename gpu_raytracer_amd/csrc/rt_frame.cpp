@@ -457,7 +457,7 @@ int wf_step_bounce(rt_ctx* ctx, DeviceState& d, WfRun& r, const WfLane& l, bool 
         gev = d.stage_events.data() + d.stage_events_used;
         d.stage_events_used += 2;
     }
-    HIPCHK(ctx, rt::wf_bounce(r.dsc, r.f, l.w, r.it, batch_samples(r), counters, l.st, gev));
+    HIPCHK(ctx, rt::wf_bounce(r.dsc, r.f, l.w, r.it, batch_samples(r), r.first, counters, l.st, gev));
     if (r.it >= r.f.max_bounce) r.phase = WfRun::RESOLVE;
     else if ((r.it & 7u) == 7u) {
         HIPCHK(ctx, hipMemcpyAsync(&r.alive, l.w.counters + rt::WF_EXT_COUNT, 4, hipMemcpyDeviceToHost, l.st));

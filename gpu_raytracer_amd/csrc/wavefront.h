@@ -63,6 +63,8 @@ struct WfBuffers {
     // it is the path's position in the extension queue: k_wf_finish writes a continuing path's record at the queue slot it reserves
     // (compaction), so every stage reads the live paths densely.  Positions include window padding: the arrays indexed by id hold
     // state_cap (wf_state_slots) records, those indexed by origin P.
+    // The depth-0 state of a frame that is not adaptive is a function of the frame and the slot (wavefront.hip, wf_camera_state): of the
+    // four records below k_wf_generate then stores only ray_o / ray_d, and only for the blocks whose camera segments walk the tree.
     float4* ray_o;       // [id] xyz origin (the current bounce's state; wf_bounce selects one of the two sets by bounce parity)
     float4* ray_d;       // [id] xyz direction (also the incoming direction of the current vertex), w = bits: origin slot of the path
     float4* thr;         // [id] xyz throughput, w = bits: hero channel | depth << 8
@@ -126,8 +128,8 @@ hipError_t wf_beams(const DevScene& sc, const DevFrame& fr, const WfBuffers& wb,
 hipError_t wf_generate(const DevScene& sc, const DevFrame& fr, const WfBuffers& wb, const DevTargets& tg, uint32_t first_sample, uint32_t n_samples, hipStream_t s);
 // Whether wf_bounce launches k_wf_shadow_grid, and so records the grid_events around it: the frame traces shadow segments and has light grids.
 inline bool wf_runs_shadow_grid(const DevFrame& fr, const WfBuffers& wb) { return !(fr.flags & RT_FLAG_NO_SHADOWS) && wb.grids; }
-hipError_t wf_bounce(const DevScene& sc, const DevFrame& fr, const WfBuffers& wb, uint32_t iteration, uint32_t n_samples, bool counters, hipStream_t s,
-                     hipEvent_t* grid_events = nullptr); // n_samples: samples per pixel in this batch (iteration 0); grid_events: two events recorded around the k_wf_shadow_grid launch
+hipError_t wf_bounce(const DevScene& sc, const DevFrame& fr, const WfBuffers& wb, uint32_t iteration, uint32_t n_samples, uint32_t first_sample, bool counters,
+                     hipStream_t s, hipEvent_t* grid_events = nullptr); // n_samples, first_sample: samples per pixel in this batch and its first sample, as wf_generate got them (iteration 0); grid_events: two events recorded around the k_wf_shadow_grid launch
 // first_sample: the batch's first sample of the launch (the adaptive variant keeps H, the sum over the odd-indexed samples, from it)
 hipError_t wf_resolve(const DevFrame& fr, const WfBuffers& wb, const DevTargets& tg, uint32_t n_samples, uint32_t first_sample, bool first_batch, bool last_batch,
                       hipStream_t s);

@@ -133,6 +133,38 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
 // generation: one lane per path slot (sample k of pixel (block b, lane l)).  AD: the adaptive variant (rt_render_adaptive): block b is
 // owned block fr.ad_blocks[b], a lane k_ad_select left out behaves like a lane outside the image, and a pixel's samples start at its own n.
 // ---------------------------------------------------------------------------------------------------------
+// The depth-0 state of path slot p, stated once.  p = sb * 64 + lane, and sample-block sb is sample k of pixel block b (wf_slot_block /
+// wf_slot_split, by RT_WF_BLOCK_MAJOR); the lane's pixel is block_pixel_at(fr, b, lane), which k_wf_generate leaves in pxy[p] as x | y << 16.
+// A camera path of a frame that is not adaptive is then a pure function of the frame and p: origin, direction and rng state are what
+// ext_sample_ray returns for (pixel, fr.sample_base + first_sample + k), the throughput is 1, the radiance 0, the hero channel 3 (none),
+// the depth 0 and the origin slot p itself.  So k_wf_generate stores none of it except the rays the persistent tree walk reads (blocks
+// without a beam list), and k_wf_trace_camera and the depth-0 launch of k_wf_finish derive it here (IMPLICIT); -ffp-contract=off makes
+// ext_sample_ray give the same bits wherever it is compiled, as the megakernels and the AOV kernels rely on already.
+// Adaptive frames (fr.adaptive, the AD variants) keep the stored state: a pixel's sample base there is its own count n, a per-pixel load
+// of the targets, so the host picks the IMPLICIT variants for non-adaptive frames only.
+__device__ __forceinline__ uint32_t wf_slot_block(uint32_t b, uint32_t k, uint32_t n_samples, uint32_t n_blocks) {
+    return RT_WF_BLOCK_MAJOR ? b * n_samples + k : k * n_blocks + b;
+}
+__device__ __forceinline__ void wf_slot_split(uint32_t sb, uint32_t n_samples, uint32_t n_blocks, uint32_t& b, uint32_t& k) {
+#if RT_WF_BLOCK_MAJOR
+    b = sb / n_samples, k = sb - b * n_samples; // sb = b * n_samples + k
+#else
+    k = sb / n_blocks, b = sb - k * n_blocks; // sb = k * n_blocks + b
+#endif
+}
+#define WF_DEPTH0_TW 3u /* thr.w at depth 0: channel 3 (none), depth 0 */
+// sample k of the batch at the pixel pxy names; returns the rng in the state the path continues from (rad.w)
+__device__ __forceinline__ SimpleRng wf_camera_state(const DevFrame& fr, uint32_t first_sample, uint32_t k, uint32_t pxy, V3& o, V3& d) {
+    return ext_sample_ray(fr.cam, fr.width, fr.frame_seed, fr.jitter, pxy & 0xFFFFu, pxy >> 16, fr.sample_base + first_sample + k, true, o, d);
+}
+// the same from the slot alone (pxy: the slot's word of WfBuffers::pxy, not 0xFFFFFFFF)
+__device__ __forceinline__ SimpleRng wf_camera_state_of(const DevFrame& fr, uint32_t n_samples, uint32_t n_blocks, uint32_t first_sample, uint32_t p, uint32_t pxy,
+                                                        V3& o, V3& d) {
+    uint32_t b, k;
+    wf_slot_split(p / WAVE, n_samples, n_blocks, b, k);
+    return wf_camera_state(fr, first_sample, k, pxy, o, d);
+}
+
 template <bool AD>
 __global__ __launch_bounds__(256) void k_wf_generate(DevFrame fr, rt::WfBuffers wb, DevTargets tg, uint32_t first_sample, uint32_t n_slots_blocks) {
     const uint32_t lane = threadIdx.x & 63u;
@@ -148,26 +180,32 @@ __global__ __launch_bounds__(256) void k_wf_generate(DevFrame fr, rt::WfBuffers 
     // the segments in flight at any moment (queue order survives compaction) come from a small part of the image
     const uint32_t n_samples = n_slots_blocks / max(1u, wb.n_blocks);
     for (uint32_t sb = wave; sb < n_slots_blocks; sb += n_waves) {
-#if RT_WF_BLOCK_MAJOR
-        const uint32_t b = sb / n_samples, k = sb - b * n_samples; // sb = b * n_samples + k
-#else
-        const uint32_t k = sb / wb.n_blocks, b = sb - k * wb.n_blocks; // sb = k * n_blocks + b
-#endif
+        uint32_t b, k;
+        wf_slot_split(sb, n_samples, wb.n_blocks, b, k);
         PixelCoord px = block_pixel_at(fr, AD ? fr.ad_blocks[b] : b, lane);
         uint32_t base = fr.sample_base;
         if (AD) {
             px.valid = px.valid && ad_lane_active(fr, fr.ad_blocks[b], lane);
             if (px.valid) base = ad_load(fr, tg, (size_t)px.y * fr.width + px.x).n;
         }
+        const uint32_t bc = wb.beam_count ? wb.beam_count[b] : RT_BEAM_OVERFLOW; // (no beam lists: every block's segments walk the tree)
         const uint32_t p = sb * WAVE + lane;
         if (px.valid) {
-            V3 o, d;
-            const SimpleRng rng = ext_sample_ray(fr.cam, fr.width, fr.frame_seed, fr.jitter, px.x, px.y, base + first_sample + k, true, o, d);
-            wb.ray_o[p] = make_float4(o.x, o.y, o.z, 0.0f);
-            wb.ray_d[p] = make_float4(d.x, d.y, d.z, __uint_as_float(p)); // w: the origin slot, where the path's sample_rad goes
-            wb.thr[p] = make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(3u)); // channel 3 (none), depth 0
-            wb.rad[p] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(rng.seed));
-            wb.pxy[p] = px.x | (px.y << 16);
+            const uint32_t pxy = px.x | (px.y << 16);
+            if (AD) { // the stored state: the pixel's own sample base
+                V3 o, d;
+                const SimpleRng rng = ext_sample_ray(fr.cam, fr.width, fr.frame_seed, fr.jitter, px.x, px.y, base + first_sample + k, true, o, d);
+                wb.ray_o[p] = make_float4(o.x, o.y, o.z, 0.0f);
+                wb.ray_d[p] = make_float4(d.x, d.y, d.z, __uint_as_float(p)); // w: the origin slot, where the path's sample_rad goes
+                wb.thr[p] = make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(WF_DEPTH0_TW));
+                wb.rad[p] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(rng.seed));
+            } else if (bc & RT_BEAM_OVERFLOW) { // (wave-uniform) the rays k_wf_trace<closest> reads; every other word of the state is derived (wf_camera_state)
+                V3 o, d;
+                wf_camera_state(fr, first_sample, k, pxy, o, d);
+                wb.ray_o[p] = make_float4(o.x, o.y, o.z, 0.0f);
+                wb.ray_d[p] = make_float4(d.x, d.y, d.z, __uint_as_float(p));
+            }
+            wb.pxy[p] = pxy;
         } else {
             wb.pxy[p] = 0xFFFFFFFFu;
             wb.sample_rad[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -185,7 +223,6 @@ __global__ __launch_bounds__(256) void k_wf_generate(DevFrame fr, rt::WfBuffers 
         // becomes the next extension queue only after this depth's traversal.  No atomics: the j-th block without a list owns the
         // entries [(j n_samples + k) 64, + 64), lanes without a pixel leave a sentinel
         if (wb.beam_count) {
-            const uint32_t bc = wb.beam_count[b];
             if (bc & RT_BEAM_OVERFLOW) wb.q_ext[1][((size_t)(bc & ~RT_BEAM_OVERFLOW) * n_samples + k) * WAVE + lane] = px.valid ? p : WF_SENTINEL;
         }
     }
@@ -699,9 +736,10 @@ __global__ __launch_bounds__(WAVE) void k_wf_beams(DevScene sc, DevFrame fr, rt:
 // Depth-0 closest hits from the block lists.  One wave per (pixel block, RT_BEAM_SAMPLES_PER_WAVE samples): the list's triangle records are
 // staged in LDS and those samples of the block's 64 pixels (path slots (b * n_samples + k) * 64 + lane, as k_wf_generate lays them out) are
 // tested against them, all lanes on the same triangle (broadcast LDS reads).  Blocks without a list are skipped: k_wf_generate put their
-// segments on a queue of their own for k_wf_trace.
-template <bool COUNT>
-__global__ __launch_bounds__(WAVE) void k_wf_trace_camera(DevScene sc, rt::WfBuffers wb, uint32_t n_samples) {
+// segments on a queue of their own for k_wf_trace.  IMPLICIT (frames that are not adaptive): a lane derives its segment from the frame and
+// its slot (wf_camera_state) - k_wf_generate has stored no ray for a block with a list; otherwise it loads the stored one.
+template <bool COUNT, bool IMPLICIT>
+__global__ __launch_bounds__(WAVE) void k_wf_trace_camera(DevScene sc, DevFrame fr, rt::WfBuffers wb, uint32_t n_samples, uint32_t first_sample) {
     extern __shared__ uint4 s_cam[]; // RT_BEAM_CAP * 3 quads + RT_BEAM_CAP floats (+ a per-lane walk stack behind them for the development probe)
     if (wb.totals[rt::WF_TOTAL_ERROR] != 0ull) return;
     const uint32_t lane = threadIdx.x;
@@ -728,17 +766,21 @@ __global__ __launch_bounds__(WAVE) void k_wf_trace_camera(DevScene sc, rt::WfBuf
             __syncthreads();
         }
         for (uint32_t k = k_first; k < k_end; k++) {
-            const uint32_t sb = RT_WF_BLOCK_MAJOR ? b * n_samples + k : k * wb.n_blocks + b;
-            const uint32_t p = sb * WAVE + lane;
-            const bool valid = wb.pxy[p] != 0xFFFFFFFFu;
+            const uint32_t p = wf_slot_block(b, k, n_samples, wb.n_blocks) * WAVE + lane;
+            const uint32_t pxy = wb.pxy[p];
+            const bool valid = pxy != 0xFFFFFFFFu;
             if (__ballot(valid) == 0ull) continue;
             V3 o = v3(0.0f, 0.0f, 0.0f), d = v3(0.0f, 0.0f, 1.0f);
             if (valid) {
-                float4 ro = wb.ray_o[p], rd = wb.ray_d[p];
-                RT_KEEP4_EARLY(ro);
-                RT_KEEP4_EARLY(rd);
-                o = f4v(ro);
-                d = f4v(rd);
+                if (IMPLICIT) {
+                    wf_camera_state(fr, first_sample, k, pxy, o, d);
+                } else {
+                    float4 ro = wb.ray_o[p], rd = wb.ray_d[p];
+                    RT_KEEP4_EARLY(ro);
+                    RT_KEEP4_EARLY(rd);
+                    o = f4v(ro);
+                    d = f4v(rd);
+                }
             }
             Hit hit;
             hit.t = valid ? RT_F32_MAX : -1.0f; // (lanes without a path never ask for another triangle)
@@ -1121,8 +1163,12 @@ __global__ void k_wf_advance(rt::WfBuffers wb) {
 // ---------------------------------------------------------------------------------------------------------
 // shading stage 2: ordered light sum, terminal shading or continuation
 // ---------------------------------------------------------------------------------------------------------
+// IMPLICIT: the depth-0 launch of a frame that is not adaptive.  The queue's ids are path slots, and throughput, radiance, channel, depth,
+// origin slot, incoming direction and rng state are not loaded but derived from the slot (wf_camera_state_of): three of the five records
+// of the round trip go.  The arithmetic on them is the same operations on those values, so the bits are those of the stored state.
+template <bool IMPLICIT>
 __global__ __launch_bounds__(256, RT_WF_SHADE_WAVES) void k_wf_finish(DevScene sc, DevFrame fr, rt::WfBuffers wb, const uint32_t* __restrict__ queue,
-                                                  uint32_t* __restrict__ next_queue) {
+                                                  uint32_t* __restrict__ next_queue, uint32_t n_samples, uint32_t first_sample) {
     __shared__ DevLight s_lights[RT_WF_MAX_LIGHTS];
     if (wb.totals[rt::WF_TOTAL_ERROR] != 0ull) return;
     stage_lights(s_lights, sc);
@@ -1146,14 +1192,25 @@ __global__ __launch_bounds__(256, RT_WF_SHADE_WAVES) void k_wf_finish(DevScene s
         if (id != WF_SENTINEL) { // the whole path record in one round trip
             vp = wb.vtx[2 * (size_t)id];
             vn = wb.vtx[2 * (size_t)id + 1];
-            th = wb.thr[id];
-            ra = wb.rad[id];
-            rdin = wb.ray_d[id];
-            RT_KEEP4(vp);
-            RT_KEEP4(vn);
-            RT_KEEP4(th);
-            RT_KEEP4(ra);
-            RT_KEEP4(rdin);
+            if (IMPLICIT) {
+                const uint32_t pxy = wb.pxy[id];
+                RT_KEEP4(vp);
+                RT_KEEP4(vn);
+                V3 o, d;
+                const SimpleRng rng0 = wf_camera_state_of(fr, n_samples, wb.n_blocks, first_sample, id, pxy, o, d);
+                th = make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(WF_DEPTH0_TW));
+                ra = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(rng0.seed));
+                rdin = make_float4(d.x, d.y, d.z, __uint_as_float(id));
+            } else {
+                th = wb.thr[id];
+                ra = wb.rad[id];
+                rdin = wb.ray_d[id];
+                RT_KEEP4(vp);
+                RT_KEEP4(vn);
+                RT_KEEP4(th);
+                RT_KEEP4(ra);
+                RT_KEEP4(rdin);
+            }
         }
         const uint32_t vis = __float_as_uint(vn.w); // one bit per light, cleared where the shadow stage found the light's segment occluded (bits of lights without a segment: unspecified)
         if (id != WF_SENTINEL && __float_as_uint(vp.w) == WF_NO_VERTEX) {
@@ -1354,8 +1411,10 @@ static void launch_trace(const DevScene& sc, const WfBuffers& wb, const uint32_t
     hipLaunchKernelGGL((k_wf_trace<COUNT, ANY>), dim3((uint32_t)cu_count() * trace_waves_per_cu(wb.capacity)), dim3(WAVE), lds, s, sc, wb, q, count_slot, cursor_slot, window_slot);
 }
 
-hipError_t wf_bounce(const DevScene& sc, const DevFrame& fr, const WfBuffers& wb_in, uint32_t iteration, uint32_t n_samples, bool counters, hipStream_t s, hipEvent_t* grid_events) {
+hipError_t wf_bounce(const DevScene& sc, const DevFrame& fr, const WfBuffers& wb_in, uint32_t iteration, uint32_t n_samples, uint32_t first_sample, bool counters,
+                     hipStream_t s, hipEvent_t* grid_events) {
     const dim3 sgrid(wf_shading_blocks()), sblock(256);
+    const bool implicit = !fr.adaptive; // depth 0 derives the camera state k_wf_generate<false> no longer stores (wf_camera_state)
     // the two path-state sets take turns by bounce parity: k_wf_finish reads the current one and writes the continuations into the other
     WfBuffers wb = wb_in;
     if (iteration & 1u) {
@@ -1372,10 +1431,13 @@ hipError_t wf_bounce(const DevScene& sc, const DevFrame& fr, const WfBuffers& wb
         const dim3 lgrid(std::min<uint32_t>(wb.n_blocks * ((n_samples + RT_BEAM_SAMPLES_PER_WAVE - 1u) / RT_BEAM_SAMPLES_PER_WAVE), (uint32_t)cu_count() * 96u));
         const size_t list_lds = (size_t)RT_BEAM_CAP * (3 * sizeof(uint4) + sizeof(float)), walk_lds = (size_t)std::max(1u, sc.stack_entries) * WAVE * sizeof(uint2);
         if (counters) {
-            hipLaunchKernelGGL((k_wf_trace_camera<true>), lgrid, dim3(WAVE), wb.probe == 2u ? (size_t)RT_BEAM_CAP * 64 + walk_lds : list_lds, s, sc, wb, n_samples);
+            const size_t lds = wb.probe == 2u ? (size_t)RT_BEAM_CAP * 64 + walk_lds : list_lds;
+            if (implicit) hipLaunchKernelGGL((k_wf_trace_camera<true, true>), lgrid, dim3(WAVE), lds, s, sc, fr, wb, n_samples, first_sample);
+            else hipLaunchKernelGGL((k_wf_trace_camera<true, false>), lgrid, dim3(WAVE), lds, s, sc, fr, wb, n_samples, first_sample);
             launch_trace<true, false>(sc, wb, wb.q_ext[1], WF_FB_COUNT, WF_FB_CURSOR, WF_SHADOW2_WINDOW, s);
         } else {
-            hipLaunchKernelGGL((k_wf_trace_camera<false>), lgrid, dim3(WAVE), list_lds, s, sc, wb, n_samples);
+            if (implicit) hipLaunchKernelGGL((k_wf_trace_camera<false, true>), lgrid, dim3(WAVE), list_lds, s, sc, fr, wb, n_samples, first_sample);
+            else hipLaunchKernelGGL((k_wf_trace_camera<false, false>), lgrid, dim3(WAVE), list_lds, s, sc, fr, wb, n_samples, first_sample);
             launch_trace<false, false>(sc, wb, wb.q_ext[1], WF_FB_COUNT, WF_FB_CURSOR, WF_SHADOW2_WINDOW, s);
         }
     } else if (counters) launch_trace<true, false>(sc, wb, cur_q, WF_EXT_COUNT, WF_EXT_CURSOR, WF_EXT_WINDOW, s);
@@ -1394,7 +1456,8 @@ hipError_t wf_bounce(const DevScene& sc, const DevFrame& fr, const WfBuffers& wb
         if (counters) launch_trace<true, true>(sc, wb, wb.q_shadow, WF_SHADOW_COUNT, WF_SHADOW_CURSOR, WF_SHADOW_WINDOW, s);
         else launch_trace<false, true>(sc, wb, wb.q_shadow, WF_SHADOW_COUNT, WF_SHADOW_CURSOR, WF_SHADOW_WINDOW, s);
     }
-    hipLaunchKernelGGL(k_wf_finish, sgrid, sblock, 0, s, sc, fr, wb, (const uint32_t*)cur_q, next_q);
+    if (iteration == 0 && implicit) hipLaunchKernelGGL(k_wf_finish<true>, sgrid, sblock, 0, s, sc, fr, wb, (const uint32_t*)cur_q, next_q, n_samples, first_sample);
+    else hipLaunchKernelGGL(k_wf_finish<false>, sgrid, sblock, 0, s, sc, fr, wb, (const uint32_t*)cur_q, next_q, n_samples, first_sample);
     hipLaunchKernelGGL(k_wf_advance, dim3(1), dim3(1), 0, s, wb);
     return hipGetLastError();
 }

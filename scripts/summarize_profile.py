@@ -21,11 +21,18 @@ newest = lambda pattern: sorted(glob.glob(pattern), key=os.path.getmtime)  # gpu
 stats = newest(os.path.join(src, "stats", "*", "*_kernel_stats.csv"))[-1]
 shutil.copy(stats, out + "_kernel_stats.csv")
 import re
-rows = [r for r in csv.DictReader(open(stats)) if match in r["Name"] and "<true" not in r["Name"]]
+# templated, but not on COUNT (k_wf_finish<IMPLICIT>: <true> is the depth-0 launch of a frame that is not adaptive): every variant is
+# measured, and runs in the counting frame too
+UNCOUNTED = ("k_wf_finish",)
+uncounted = lambda full: any(k + "<" in full for k in UNCOUNTED)
+counting = lambda full: "<true" in full and not uncounted(full)
+rows = [r for r in csv.DictReader(open(stats)) if match in r["Name"] and not counting(r["Name"])]
 
 
 def kname(full):
     n = re.search(r"(k_[a-z_0-9]+)", full).group(1)
+    if n == "k_wf_finish":
+        return n + ("<depth 0>" if "<true>" in full else "")
     if n != "k_wf_trace":
         return n
     return n + ("<shadow>" if "<false, true>" in full else "<closest>" if "<false, false>" in full else "")
@@ -37,9 +44,10 @@ read_factor = lambda kn: 1.0 if kn in GATHER_KERNELS else 2.0
 
 # bench.py renders warmup + steps frames plus ONE more with the counting kernel variants (<true, ...>, excluded
 # here); kernels that are not templated on COUNT also run in that extra frame
-nframes = lambda full: frames if "<" in full else frames + 1
+nframes = lambda full: frames if "<" in full and not uncounted(full) else frames + 1
 summary = {"frames": frames, "kernels": {kname(r["Name"]): {"calls": int(r["Calls"]), "total_ms_per_frame": float(r["TotalDurationNs"]) / 1e6 / nframes(r["Name"]),
                                                              "avg_us": float(r["AverageNs"]) / 1e3} for r in rows}}
+assert len(summary["kernels"]) == len(rows), "two rows of the trace share a name here"
 summary["kernel_ms_per_frame"] = sum(v["total_ms_per_frame"] for v in summary["kernels"].values())
 pmc = {}
 by_kernel = collections.defaultdict(dict)
@@ -49,7 +57,7 @@ for d in ("pmc_fetch", "pmc_write", "pmc_l2", "pmc_sq", "pmc_sq2", "pmc_sq3"):
         continue
     agg = collections.defaultdict(float)
     for r in csv.DictReader(open(fs[-1])):
-        if match in r["Kernel_Name"] and "<true" not in r["Kernel_Name"]:
+        if match in r["Kernel_Name"] and not counting(r["Kernel_Name"]):
             v = float(r["Counter_Value"]) / nframes(r["Kernel_Name"])
             agg[r["Counter_Name"]] += v
             kn = kname(r["Kernel_Name"])
