@@ -323,9 +323,7 @@ int prepare_quality_tree(rt_ctx* ctx) {
     TreeBuild tb;
     if (build_tree(ctx, ctx->build_tris, 0, rt::BvhBuildOptions{}, tb) != RT_OK || tb.bvh.nodes.empty())
         return ctx->fail(RT_ERR_INTERNAL, "rt_prepare: the host build gave %zu nodes at depth %u (the device-built tree stays)", tb.bvh.nodes.size(), tb.bvh.depth);
-    if (int rc = install_tree(ctx, tb)) return rc;
-    ctx->frame_valid = false;
-    return RT_OK;
+    return install_tree(ctx, tb); // the last frame stays readable, as after RT_UPDATE_REBUILD: the targets do not depend on the tree
 }
 
 // The refit's view of the current tree (made once per tree, from the first device's arrays; every device holds the same tree): the
