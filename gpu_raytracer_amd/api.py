@@ -33,13 +33,13 @@ PREPARE_SHADOW_GRIDS = 1
 PREPARE_QUALITY_TREE = 2
 QUERY_COUNTERS = 1  # RT_QUERY_COUNTERS of rt_intersect / rt_occluded
 QUERY_CHUNK = 4194304  # RT_QUERY_CHUNK: host batches are staged in chunks of at most this many rays
-QUERY_COUNT_ALL = 2  # RT_QUERY_COUNT_ALL of rt_intersect_all / rt_closest_point_all / rt_overlap_box / rt_contact_capsule: counts are all candidates in the range, not the records written
+QUERY_COUNT_ALL = 2  # RT_QUERY_COUNT_ALL of rt_intersect_all / rt_closest_point_all / rt_overlap_box / rt_overlap_obb / rt_overlap_triangle / rt_contact_capsule: counts are all candidates in the range, not the records written
 MULTI_HIT_MAX = 16  # RT_MULTI_HIT_MAX: the most hits rt_intersect_all lists per ray
 NEAREST_MAX = 16  # RT_NEAREST_MAX: the most primitives rt_closest_point_all lists per point
-OVERLAP_MAX = 32  # RT_OVERLAP_MAX: the most primitives rt_overlap_box lists per box
+OVERLAP_MAX = 32  # RT_OVERLAP_MAX: the most primitives rt_overlap_box / rt_overlap_obb / rt_overlap_triangle list per query
 SWEEP_AXIS_SPHERE = 13  # RT_SWEEP_AXIS_SPHERE of rt_box_sweep_hit.axis: the contact is with a sphere primitive
 SWEEP_AXIS_NONE = 0xFFFFFFFF  # RT_SWEEP_AXIS_NONE: a miss, or in contact at the start
-OVERLAP_ANY = 4  # RT_OVERLAP_ANY of rt_overlap_box: counts are 1 where anything touches the box, else 0, and the walk stops at the first
+OVERLAP_ANY = 4  # RT_OVERLAP_ANY of rt_overlap_box / rt_overlap_obb / rt_overlap_triangle: counts are 1 where anything touches the box, else 0, and the walk stops at the first
 CONTACT_MAX = 16  # RT_CONTACT_MAX: the most primitives rt_contact_capsule lists per capsule
 CONTACT_ANY = 4  # RT_CONTACT_ANY of rt_contact_capsule: counts are 1 where anything is in range of the capsule, else 0, and the walk stops at the first
 INSIDE_MAX_RAYS = 7  # RT_INSIDE_MAX_RAYS: the most parity rays rt_inside / rt_signed_distance trace per point
@@ -71,7 +71,7 @@ ABI_SYMBOLS = [
     "rt_get_stats", "rt_last_error", "rt_destroy", "rt_version",
     "rt_intersect", "rt_occluded", "rt_camera_rays", "rt_intersect_all",
     "rt_surface", "rt_ambient_occlusion", "rt_direct_light", "rt_radiance", "rt_radiance_sh", "rt_irradiance", "rt_closest_point", "rt_closest_point_all", "rt_sweep_sphere", "rt_sweep_box", "rt_sweep_capsule",
-    "rt_inside", "rt_signed_distance", "rt_overlap_box", "rt_contact_capsule", "rt_overlap_obb", "rt_sweep_obb",
+    "rt_inside", "rt_signed_distance", "rt_overlap_box", "rt_contact_capsule", "rt_overlap_obb", "rt_sweep_obb", "rt_overlap_triangle",
     "rt_update_geometry",
     "rt_accumulated_samples",
     "rt_aovs", "rt_sample_rays", "rt_denoise",
@@ -192,7 +192,7 @@ def _check_contact_lists(a, n, max_contacts):
         raise ValueError(f"out: {a.shape[0]} rows for {n} capsules")
 
 
-def _check_prim_lists(a, n, max_prims):
+def _check_prim_lists(a, n, max_prims, what="boxes"):
     """Raises unless `a` is a C-contiguous (n, max_prims) array of ids (rt_overlap_box's, query-major): uint32 for numpy, int32 for torch."""
     _check_kind_dtype(a, "out", "int32" if _is_torch(a) else "uint32")
     if len(a.shape) != 2 or a.shape[1] != max_prims:
@@ -200,7 +200,7 @@ def _check_prim_lists(a, n, max_prims):
     if not _contiguous(a):
         raise ValueError("out: not C-contiguous")
     if a.shape[0] != n:
-        raise ValueError(f"out: {a.shape[0]} rows for {n} boxes")
+        raise ValueError(f"out: {a.shape[0]} rows for {n} {what}")
 
 
 def _check_counts(a, n, what="rays"):
@@ -429,6 +429,24 @@ def make_obbs(center, half_extent, rotation):
         q = np.asarray(rotation, np.float32)
     out[:, 0:8] = boxes
     out[:, 8:12] = q
+    return out
+
+
+def make_triangles(v0, v1, v2):
+    """Three (N, 3) arrays of vertices (numpy or torch, the result has the kind and device of v0) -> an (N, 12) float32 batch of
+    rt_query_triangle records: v0 0 v1 0 v2 0 (x y z per vertex).  Two or three equal vertices are allowed (a segment, a point)."""
+    if _is_torch(v0):
+        import torch
+        a = v0.reshape(-1, 3)
+        out = torch.zeros((a.shape[0], 12), dtype=torch.float32, device=a.device)
+        b, c = (v if _is_torch(v) else torch.as_tensor(np.asarray(v, np.float32), device=a.device) for v in (v1, v2))
+    else:
+        a = np.asarray(v0, np.float32).reshape(-1, 3)
+        out = np.zeros((a.shape[0], 12), np.float32)
+        b, c = np.asarray(v1, np.float32), np.asarray(v2, np.float32)
+    out[:, 0:3] = a
+    out[:, 4:7] = b.reshape(-1, 3)
+    out[:, 8:11] = c.reshape(-1, 3)
     return out
 
 
@@ -1061,8 +1079,16 @@ class Context:
         (0, 0, 0, 1) the answer is overlap_box's."""
         return self._overlap("rt_overlap_obb", boxes, 12, max_prims, out, counts, count_all, any_hit, counters)
 
-    def _overlap(self, fn, boxes, cols, max_prims, out, counts, count_all, any_hit, counters):
-        n = _check_batch(boxes, "boxes", cols, "float32")
+    def overlap_triangle(self, triangles, max_prims, *, out=None, counts=None, count_all=False, any_hit=False, counters=False):
+        """rt_overlap_triangle: the primitives that touch each closed triangle of an (N, 12) batch (make_triangles: three vertices; a
+        segment or a point is allowed, a non-finite vertex touches nothing) -> (prims, counts) exactly as overlap_box gives them.  A
+        sphere is its surface: a triangle wholly inside the ball does not touch it.  A query that is one of the scene's own triangles
+        lists that triangle and its neighbours."""
+        return self._overlap("rt_overlap_triangle", triangles, 12, max_prims, out, counts, count_all, any_hit, counters, name="triangles")
+
+    def _overlap(self, fn, boxes, cols, max_prims, out, counts, count_all, any_hit, counters, name="boxes"):
+        """The call every overlap query makes: `boxes` is its (N, cols) batch, `name` what the messages call it."""
+        n = _check_batch(boxes, name, cols, "float32")
         if isinstance(max_prims, bool) or not isinstance(max_prims, (int, np.integer)) or not 0 <= max_prims <= OVERLAP_MAX:
             raise ValueError(f"max_prims: {max_prims!r}, expected an integer in 0 .. {OVERLAP_MAX}")
         max_prims = int(max_prims)
@@ -1071,7 +1097,7 @@ class Context:
         if max_prims == 0 and not (count_all or any_hit):
             raise ValueError("max_prims: 0 lists nothing, which needs count_all=True (a pure count) or any_hit=True")
         if out is not None and _is_torch(out) != _is_torch(boxes):
-            raise TypeError("out: must be the same kind (numpy / torch) as boxes")
+            raise TypeError(f"out: must be the same kind (numpy / torch) as {name}")
         if max_prims == 0:
             out = None
         elif out is None:
@@ -1081,8 +1107,8 @@ class Context:
             else:
                 out = np.empty((n, max_prims), np.uint32)
         else:
-            _check_prim_lists(out, n, max_prims)
-        counts = _counts_like(counts, boxes, "boxes", n)
+            _check_prim_lists(out, n, max_prims, name)
+        counts = _counts_like(counts, boxes, name, n)
         _sync_torch(boxes, out, counts)
         flags = (QUERY_COUNTERS if counters else 0) | (QUERY_COUNT_ALL if count_all else 0) | (OVERLAP_ANY if any_hit else 0)
         self._check(getattr(self.lib, fn)(self._h, _addr(boxes), C.c_size_t(n), C.c_uint32(max_prims),

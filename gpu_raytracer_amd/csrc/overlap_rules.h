@@ -43,6 +43,17 @@ RT_RULE void ov_box_init(OvBox& b, const float c[3], const float h[3]) {
     for (int a = 0; a < 3; a++) b.c[a] = c[a], b.h[a] = h[a], b.lo[a] = c[a] - h[a], b.hi[a] = c[a] + h[a];
     b.reach = cp_p_max(c) + ov_max(ov_max(h[0], h[1]), h[2]);
 }
+// The same from finite bounds lo <= hi that are exact (overlap_triangle_rules.h: the min and max of a triangle's vertices), for a
+// caller whose leaf test does not read c and h: the node test holds the child boxes against lo and hi as given, c = 0.5 lo + 0.5 hi
+// serves the visiting order only, h = hi - c is not read by the node test, and reach = max_a max(|lo_a|, |hi_a|) bounds every
+// coordinate of the query as max_a |c_a| + max_a h_a does above.
+RT_RULE void ov_box_init_bounds(OvBox& b, const float lo[3], const float hi[3]) {
+    b.reach = 0.0f;
+    for (int a = 0; a < 3; a++) {
+        b.lo[a] = lo[a], b.hi[a] = hi[a], b.c[a] = 0.5f * lo[a] + 0.5f * hi[a], b.h[a] = hi[a] - b.c[a];
+        b.reach = ov_max(b.reach, ov_max(fabsf(lo[a]), fabsf(hi[a])));
+    }
+}
 
 // ---- 2. A triangle, from its record's v0, e1, e2 (the stored f32 differences).  Relative to the centre its vertices are
 //   a0 = v0 - c,  a1 = (v0 + e1) - c,  a2 = (v0 + e2) - c

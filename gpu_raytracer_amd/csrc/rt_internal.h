@@ -1,4 +1,4 @@
-// rt_internal.h — what the host units of the C ABI (rt_context / rt_scene / rt_frame / rt_readback / rt_query .cpp) share: the owner of
+// rt_internal.h — what the host units of the C ABI (rt_context / rt_scene / rt_frame / rt_readback / rt_query / rt_mesh_query .cpp) share: the owner of
 // device memory, the per-device state grouped by lifetime, the context, and the helpers more than one unit calls.  Nothing here is
 // exported from the library.
 #ifndef RT_INTERNAL_H
@@ -33,6 +33,7 @@
 #include "kernels.h"
 #include "overlap.h"
 #include "overlap_obb.h"
+#include "overlap_triangle.h"
 #include "path_query.h"
 #include "probe_query.h"
 #include "ray_query.h"
@@ -253,6 +254,11 @@ void copy_share(uint8_t* dst, const uint8_t* src, size_t elem, uint32_t w, uint3
                 uint32_t n_owned); // rt_readback.cpp, with the next
 int consolidate_on_first_device(rt_ctx* ctx, uint32_t w, uint32_t h);
 int classify_ptr(rt_ctx* ctx, const char* fn, const char* what, const void* p, QueryPtr& q, uintptr_t align = 16); // rt_query.cpp
+// rt_query.cpp: the argument checks and the batch of rt_overlap_box, for every call of its shape (rt_overlap_obb; rt_overlap_triangle
+// in rt_mesh_query.cpp).  in_name: the input array in messages; in_size: bytes per input record; launch: the call's kernel launcher.
+using OverlapLaunch = hipError_t (*)(const DevScene&, const void*, uint32_t*, uint32_t*, uint32_t, uint32_t, int, unsigned long long*, hipStream_t);
+int overlap_query(rt_ctx* ctx, const char* fn, const char* in_name, const void* in, size_t in_size, size_t n, uint32_t max_prims, uint32_t* prims,
+                  uint32_t* counts, uint32_t flags, OverlapLaunch launch);
 
 } // namespace rti
 #endif

@@ -1,7 +1,7 @@
 // rt_query.cpp — calls that trace or filter outside a frame: ray queries (rt_hip.h "Ray queries": rt_intersect, rt_occluded,
 // rt_intersect_all, rt_camera_rays), surface queries ("Surface queries": rt_surface, rt_ambient_occlusion; kernels in
 // surface_query.hip), the direct-light query ("Direct-light queries": rt_direct_light; kernel in direct_light.hip), the path query ("Path queries":
-// rt_radiance; kernels in path_query.hip), the probe query ("Probe queries": rt_radiance_sh; kernels in probe_query.hip), the irradiance query ("Irradiance queries": rt_irradiance; kernels in irradiance_query.hip), the closest-point queries ("Closest-point queries": rt_closest_point, rt_closest_point_all; kernels in closest_point.hip, closest_point_all.hip), the inside test and the signed distance ("Inside tests and signed distance": rt_inside, rt_signed_distance; kernel in inside.hip), the sphere sweep ("Sphere sweeps": rt_sweep_sphere; kernel in sweep.hip), the box sweep ("Box sweeps": rt_sweep_box; kernel in sweep_box.hip), the capsule sweep ("Capsule sweeps": rt_sweep_capsule; kernel in sweep_capsule.hip), the overlap query ("Overlap queries": rt_overlap_box; kernel in overlap.hip), the contact query ("Contact queries": rt_contact_capsule; kernel in contact_capsule.hip) and the image passes ("Feature buffers (AOVs) and denoising": rt_aovs, rt_sample_rays, rt_denoise; kernels in
+// rt_radiance; kernels in path_query.hip), the probe query ("Probe queries": rt_radiance_sh; kernels in probe_query.hip), the irradiance query ("Irradiance queries": rt_irradiance; kernels in irradiance_query.hip), the closest-point queries ("Closest-point queries": rt_closest_point, rt_closest_point_all; kernels in closest_point.hip, closest_point_all.hip), the inside test and the signed distance ("Inside tests and signed distance": rt_inside, rt_signed_distance; kernel in inside.hip), the sphere sweep ("Sphere sweeps": rt_sweep_sphere; kernel in sweep.hip), the box sweep ("Box sweeps": rt_sweep_box; kernel in sweep_box.hip), the capsule sweep ("Capsule sweeps": rt_sweep_capsule; kernel in sweep_capsule.hip), the overlap query ("Overlap queries": rt_overlap_box; kernel in overlap.hip; its checks and batch, overlap_query, also serve rt_overlap_obb and rt_mesh_query.cpp), the contact query ("Contact queries": rt_contact_capsule; kernel in contact_capsule.hip) and the image passes ("Feature buffers (AOVs) and denoising": rt_aovs, rt_sample_rays, rt_denoise; kernels in
 // denoise.hip).  None of them touches the frame targets, the tile shares rt_read_* gather, or the running image of an accumulation.
 #include "rt_internal.h"
 #include "contact_capsule_rules.h"
@@ -491,17 +491,19 @@ int inside_query(rt_ctx* ctx, const char* fn, const rt_point_query* points, size
     return RT_OK;
 }
 
-// max_prims ids per box and a second output, the counts: rt_closest_point_all's shape with 4-byte records.  A chunk is RT_QUERY_CHUNK /
-// max(max_prims, 1) boxes.
 static_assert(RT_OVERLAP_MAX == rt::OV_PRIMS_MAX, "the kernel's list holds RT_OVERLAP_MAX entries");
-// rt_overlap_box and rt_overlap_obb: the same argument checks and batch, with the record's size and the launcher of each.
-using OverlapLaunch = hipError_t (*)(const DevScene&, const void*, uint32_t*, uint32_t*, uint32_t, uint32_t, int, unsigned long long*, hipStream_t);
-int overlap_query(rt_ctx* ctx, const char* fn, const void* boxes, size_t box_size, size_t n, uint32_t max_prims, uint32_t* prims, uint32_t* counts,
-                  uint32_t flags, OverlapLaunch launch) {
+
+} // namespace
+
+// max_prims ids per record and a second output, the counts: rt_closest_point_all's shape with 4-byte records.  A chunk is RT_QUERY_CHUNK /
+// max(max_prims, 1) records.  rt_overlap_box, rt_overlap_obb and rt_overlap_triangle (rt_mesh_query.cpp): the same argument checks and batch, with the input's name,
+// the record's size and the launcher of each.
+int overlap_query(rt_ctx* ctx, const char* fn, const char* in_name, const void* in, size_t in_size, size_t n, uint32_t max_prims, uint32_t* prims,
+                  uint32_t* counts, uint32_t flags, OverlapLaunch launch) {
     const double w0 = now_ms();
     if (!ctx) return RT_ERR_BAD_ARG;
     if (n == 0) return RT_OK;
-    if (!boxes || (!prims && max_prims > 0)) return ctx->fail(RT_ERR_BAD_ARG, "%s: %s is NULL with n = %zu", fn, !boxes ? "boxes" : "prims", n);
+    if (!in || (!prims && max_prims > 0)) return ctx->fail(RT_ERR_BAD_ARG, "%s: %s is NULL with n = %zu", fn, !in ? in_name : "prims", n);
     if (max_prims > RT_OVERLAP_MAX) return ctx->fail(RT_ERR_BAD_ARG, "%s: max_prims %u (0 .. %u)", fn, max_prims, RT_OVERLAP_MAX);
     const uint32_t known = RT_QUERY_COUNTERS | RT_QUERY_COUNT_ALL | RT_OVERLAP_ANY;
     if (flags & ~known) return ctx->fail(RT_ERR_BAD_ARG, "%s: unknown flag bits 0x%x", fn, flags & ~known);
@@ -513,7 +515,7 @@ int overlap_query(rt_ctx* ctx, const char* fn, const void* boxes, size_t box_siz
     if (max_prims == 0) prims = nullptr; // ignored: a pure count
     const int mode = any ? rt::OV_ANY : all ? rt::OV_COUNT_ALL : rt::OV_LIST;
     const size_t chunk = RT_QUERY_CHUNK / std::max(max_prims, 1u);
-    const Batch b{fn, n, {"boxes", boxes, box_size},
+    const Batch b{fn, n, {in_name, in, in_size},
                   {{"prims", prims, max_prims * sizeof(uint32_t), 4}, {"counts", counts, sizeof(uint32_t), 4, ST_COUNTS}},
                   chunk, chunk, counters ? RT_CNT_TRI_TESTS + 1u : 0u};
     Totals t;
@@ -525,8 +527,6 @@ int overlap_query(rt_ctx* ctx, const char* fn, const void* boxes, size_t box_siz
     batch_stats(ctx, w0, t, counters, n);
     return RT_OK;
 }
-
-} // namespace
 
 } // namespace rti
 
@@ -625,10 +625,10 @@ int rt_closest_point_all(rt_ctx* ctx, const rt_point_query* points, size_t n, ui
 }
 
 int rt_overlap_box(rt_ctx* ctx, const rt_box* boxes, size_t n, uint32_t max_prims, uint32_t* prims, uint32_t* counts, uint32_t flags) {
-    return overlap_query(ctx, "rt_overlap_box", boxes, sizeof(rt_box), n, max_prims, prims, counts, flags, rt::launch_overlap_box);
+    return overlap_query(ctx, "rt_overlap_box", "boxes", boxes, sizeof(rt_box), n, max_prims, prims, counts, flags, rt::launch_overlap_box);
 }
 int rt_overlap_obb(rt_ctx* ctx, const rt_obb* boxes, size_t n, uint32_t max_prims, uint32_t* prims, uint32_t* counts, uint32_t flags) {
-    return overlap_query(ctx, "rt_overlap_obb", boxes, sizeof(rt_obb), n, max_prims, prims, counts, flags, rt::launch_overlap_obb);
+    return overlap_query(ctx, "rt_overlap_obb", "boxes", boxes, sizeof(rt_obb), n, max_prims, prims, counts, flags, rt::launch_overlap_obb);
 }
 
 // max_contacts records per capsule and a second output, the counts: rt_closest_point_all's shape with rt_overlap_box's modes.  A

@@ -224,7 +224,7 @@ int rt_get_stats(rt_ctx* ctx, rt_stats* out);
  * a new one at sample 0 by itself, as RT_FLAG_ACCUMULATE_RESTART does.  The other RT_FLAG_* bits change no bits and may differ.
  * The running image ends (the next accumulating call starts at 0) with rt_upload_scene*, rt_update_geometry, rt_dispatch_tile, any
  * rt_render without RT_FLAG_ACCUMULATE and an accumulating call that fails once it has passed its argument checks.  It survives rt_prepare,
- * rt_upload_textures, the ray queries, the surface queries, rt_direct_light, rt_radiance, rt_radiance_sh, rt_irradiance, rt_closest_point, rt_closest_point_all, rt_inside, rt_signed_distance, rt_overlap_box, rt_sweep_sphere, rt_sweep_box, rt_sweep_capsule, rt_contact_capsule, rt_overlap_obb, rt_sweep_obb, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
+ * rt_upload_textures, the ray queries, the surface queries, rt_direct_light, rt_radiance, rt_radiance_sh, rt_irradiance, rt_closest_point, rt_closest_point_all, rt_inside, rt_signed_distance, rt_overlap_box, rt_sweep_sphere, rt_sweep_box, rt_sweep_capsule, rt_contact_capsule, rt_overlap_obb, rt_sweep_obb, rt_overlap_triangle, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
  * Limit: RT_ACCUMULATE_MAX_SAMPLES samples (where the float sample count stops being exact); a call that would pass it is RT_ERR_BAD_ARG
  * and leaves the running image as it was.  rt_stats describes the call alone (its segments, pixels, kernel_ms).
  * A context over several devices, and a tile_rank / tile_world share, accumulates its own share of the pixels.
@@ -370,7 +370,7 @@ int rt_occluded(rt_ctx* ctx, const rt_ray* rays, size_t n, uint8_t* occluded, ui
  * Statistics, synchronisation and side effects as for rt_intersect: synchronous, first waits for an rt_dispatch_tile in flight;
  * rays = n, the other counts 0, kernel_ms the maximum over devices, node_visits / tri_tests only with RT_QUERY_COUNTERS; the last
  * frame, the rt_read_* results and a running accumulation are left alone. */
-#define RT_QUERY_COUNT_ALL 2u   /* rt_intersect_all, rt_closest_point_all, rt_overlap_box and rt_contact_capsule only */
+#define RT_QUERY_COUNT_ALL 2u   /* rt_intersect_all, rt_closest_point_all, rt_overlap_box, rt_overlap_obb, rt_overlap_triangle and rt_contact_capsule only */
 #define RT_MULTI_HIT_MAX 16u
 
 int rt_intersect_all(rt_ctx* ctx, const rt_ray* rays, size_t n, uint32_t max_hits,
@@ -1167,7 +1167,7 @@ RT_STATIC_ASSERT(sizeof(rt_box) == 32 && offsetof(rt_box, center) == 0 && offset
                  "rt_box is 32 B: center, _pad0 at 12, half_extent at 16, _pad1 at 28");
 
 #define RT_OVERLAP_MAX 32u
-#define RT_OVERLAP_ANY 4u   /* rt_overlap_box only: counts[i] = 1 if anything touches box i, else 0; stops at the first */
+#define RT_OVERLAP_ANY 4u   /* rt_overlap_box, rt_overlap_obb and rt_overlap_triangle only: counts[i] = 1 if anything touches box i, else 0; stops at the first */
 
 int rt_overlap_box(rt_ctx* ctx, const rt_box* boxes, size_t n, uint32_t max_prims,
                    uint32_t* prims,   /* n * max_prims ids, query-major, rt_hit.prim_id's encoding; unused slots 0xFFFFFFFF */
@@ -1324,6 +1324,65 @@ int rt_overlap_obb(rt_ctx* ctx, const rt_obb* boxes, size_t n, uint32_t max_prim
                    uint32_t* counts,  /* n entries; may be NULL unless max_prims == 0 */
                    uint32_t flags);   /* RT_QUERY_COUNTERS | RT_QUERY_COUNT_ALL | RT_OVERLAP_ANY; max_prims <= RT_OVERLAP_MAX */
 int rt_sweep_obb(rt_ctx* ctx, const rt_obb_sweep* sweeps, size_t n, rt_box_sweep_hit* out, uint32_t flags); /* RT_QUERY_COUNTERS */
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Triangle queries: the primitives of the scene that the caller's own triangles touch (no reference counterpart; Embree's
+ * rtcCollide and the collision managers of FCL / trimesh are the model): a moving mesh against the static scene, clash detection
+ * between an inserted part and a building, the seed of a cut or a CSG, self-intersection checks with the scene's own triangles as
+ * queries.  rt_overlap_box over each triangle's bounding box is a different and much looser query: a thin diagonal triangle's box
+ * is almost all empty space.  The answer is one f32 statement (csrc/overlap_triangle_rules.h, whose header comment is the
+ * specification; every operation one f32 rounding, nothing fused, every test in its positive form so that a NaN makes it false).
+ * dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z; cross(a, b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x).
+ * Query: q0, q1, q2 = v0, v1, v2 of the record; u1 = q1 - q0, u2 = q2 - q0, u3 = u2 - u1; qlo, qhi the per-axis min and max of the
+ *   three vertices (exact).  A query with a non-finite component touches nothing and is not walked; the kernel checks this itself.
+ *   A finite degenerate query (a segment, a point) is allowed.
+ * Triangle of the scene, from its record's v0, e1, e2: s0 = v0, s1 = v0 + e1, s2 = v0 + e2; f1 = e1, f2 = e2, f3 = e2 - e1.  It
+ *   touches iff all of these hold:
+ *   0. all nine components of the s_k are finite;
+ *   1. per coordinate axis a: min_k s_k[a] <= qhi[a] && max_k s_k[a] >= qlo[a];
+ *   2. with a_k = s_k - q0, for each of the 23 axes L below: pS_k = dot(L, a_k), pQ = (0, dot(L, u1), dot(L, u2));
+ *      min_k pS_k <= max pQ && max_k pS_k >= min pQ, and ((pS_0 + pS_1) + pS_2) + (pQ_1 + pQ_2) is not a NaN (the min and max are
+ *      fminf / fmaxf, which ignore a NaN operand).
+ *   The axes: nS = cross(f1, f2) and nQ = cross(u1, u2); the nine cross(u_i, f_j); cross(nQ, u_i) and cross(nS, f_j), which decide
+ *   coplanar pairs; cross(nS, u_i) and cross(nQ, f_j), which decide a pair in which one triangle is a segment.  Any vector is a
+ *   legitimate candidate for a separating axis, so a noisy axis from nearly parallel edges never wrongly separates in exact
+ *   arithmetic; only the rounding of the projections matters.
+ *   Two limits.  Two degenerate triangles (segments, points) can be listed although they are disjoint: for two parallel segments or
+ *   two points every axis is the zero vector and test 1 alone decides; this errs on the side of listing.  And "closed" means closed
+ *   on the record: the scene's vertices are the s_k above, and a vertex the caller shares with the scene is bit-equal only where
+ *   v0 + e reproduces it.
+ * Sphere (o, R), a surface as everywhere: near2 = the squared distance of "Closest-point queries" from o to the triangle (q0, u1,
+ *   u2), far2 = max_k dot(q_k - o, q_k - o), rr = R * R.  It touches iff near2 <= rr && far2 >= rr: a triangle wholly inside the
+ *   ball is not touched.
+ * The closed test lists, for a query that is one of the scene's own triangles, that triangle and its neighbours.
+ * The result follows from these rules alone: it does not depend on the tree in use, the device count, the kind of memory or the
+ *   chunking, and after rt_update_geometry it is that of a fresh upload of the moved scene.  The tree only culls, by the query's
+ *   bounds qlo, qhi and the margin of "Overlap queries" (DESIGN.md section 4).
+ * rt_overlap_triangle: key order (prim_id ^ 0x80000000: spheres by index, then triangles by original index), the modes (the list,
+ *   RT_QUERY_COUNT_ALL - with it max_prims 0 is allowed - and RT_OVERLAP_ANY), 1 <= max_prims <= RT_OVERLAP_MAX, unused slots
+ *   0xFFFFFFFF, counts (may be NULL unless max_prims == 0), chunking (RT_QUERY_CHUNK / max(max_prims, 1) triangles), the split over
+ *   devices, buffer classification (host or device memory, all of one kind), synchronisation, side effects (the last frame and a
+ *   running accumulation are left alone), statistics (rays = n; visits and records only with RT_QUERY_COUNTERS) and error codes as
+ *   for rt_overlap_box; the records are 48 bytes in, device memory 16-byte aligned (prims and counts 4-byte).
+ * --------------------------------------------------------------------------------------------------------------- */
+typedef struct rt_query_triangle {
+    float v0[3];
+    uint32_t _pad0;          /* pads are ignored */
+    float v1[3];
+    uint32_t _pad1;
+    float v2[3];
+    uint32_t _pad2;
+} rt_query_triangle; /* 48 bytes */
+
+RT_STATIC_ASSERT(sizeof(rt_query_triangle) == 48 && offsetof(rt_query_triangle, v0) == 0 && offsetof(rt_query_triangle, _pad0) == 12 &&
+                     offsetof(rt_query_triangle, v1) == 16 && offsetof(rt_query_triangle, _pad1) == 28 && offsetof(rt_query_triangle, v2) == 32 &&
+                     offsetof(rt_query_triangle, _pad2) == 44,
+                 "rt_query_triangle is 48 B: v0, _pad0 at 12, v1 at 16, _pad1 at 28, v2 at 32, _pad2 at 44");
+
+int rt_overlap_triangle(rt_ctx* ctx, const rt_query_triangle* triangles, size_t n, uint32_t max_prims,
+                        uint32_t* prims,   /* n * max_prims ids, query-major, rt_hit.prim_id's encoding; unused slots 0xFFFFFFFF */
+                        uint32_t* counts,  /* n entries; may be NULL unless max_prims == 0 */
+                        uint32_t flags);   /* RT_QUERY_COUNTERS | RT_QUERY_COUNT_ALL | RT_OVERLAP_ANY; max_prims <= RT_OVERLAP_MAX */
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Geometry updates: new positions for the uploaded scene, in place (no reference counterpart; Embree's refit build,
