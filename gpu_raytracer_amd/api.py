@@ -39,6 +39,7 @@ NEAREST_MAX = 16  # RT_NEAREST_MAX: the most primitives rt_closest_point_all lis
 OVERLAP_MAX = 32  # RT_OVERLAP_MAX: the most primitives rt_overlap_box / rt_overlap_obb / rt_overlap_triangle list per query
 SWEEP_AXIS_SPHERE = 13  # RT_SWEEP_AXIS_SPHERE of rt_box_sweep_hit.axis: the contact is with a sphere primitive
 SWEEP_AXIS_NONE = 0xFFFFFFFF  # RT_SWEEP_AXIS_NONE: a miss, or in contact at the start
+SWEEP_TRIANGLE_AXIS_SPHERE = 26  # RT_SWEEP_TRIANGLE_AXIS_SPHERE of rt_triangle_sweep_hit.axis: the contact is with a sphere primitive
 OVERLAP_ANY = 4  # RT_OVERLAP_ANY of rt_overlap_box / rt_overlap_obb / rt_overlap_triangle: counts are 1 where anything touches the box, else 0, and the walk stops at the first
 CONTACT_MAX = 16  # RT_CONTACT_MAX: the most primitives rt_contact_capsule lists per capsule
 CONTACT_ANY = 4  # RT_CONTACT_ANY of rt_contact_capsule: counts are 1 where anything is in range of the capsule, else 0, and the walk stops at the first
@@ -71,7 +72,7 @@ ABI_SYMBOLS = [
     "rt_get_stats", "rt_last_error", "rt_destroy", "rt_version",
     "rt_intersect", "rt_occluded", "rt_camera_rays", "rt_intersect_all",
     "rt_surface", "rt_ambient_occlusion", "rt_direct_light", "rt_radiance", "rt_radiance_sh", "rt_irradiance", "rt_closest_point", "rt_closest_point_all", "rt_sweep_sphere", "rt_sweep_box", "rt_sweep_capsule",
-    "rt_inside", "rt_signed_distance", "rt_overlap_box", "rt_contact_capsule", "rt_overlap_obb", "rt_sweep_obb", "rt_overlap_triangle",
+    "rt_inside", "rt_signed_distance", "rt_overlap_box", "rt_contact_capsule", "rt_overlap_obb", "rt_sweep_obb", "rt_overlap_triangle", "rt_sweep_triangle",
     "rt_update_geometry",
     "rt_accumulated_samples",
     "rt_aovs", "rt_sample_rays", "rt_denoise",
@@ -448,6 +449,31 @@ def make_triangles(v0, v1, v2):
     out[:, 4:7] = b.reshape(-1, 3)
     out[:, 8:11] = c.reshape(-1, 3)
     return out
+
+
+def make_triangle_sweeps(v0, v1, v2, direction, tmax=float("inf")):
+    """Three (N, 3) arrays of vertices at t = 0 and (N, 3) directions (numpy or torch, the result has the kind and device of v0) -> an
+    (N, 16) float32 batch of rt_triangle_sweep records: v0 0 v1 0 v2 0 dx dy dz tmax.  Equal vertices are allowed (a moving segment,
+    a moving point).  tmax: a scalar or an (N,) array; contacts at 0 <= t < tmax are reported."""
+    tris = make_triangles(v0, v1, v2)
+    if _is_torch(tris):
+        import torch
+        out = torch.zeros((tris.shape[0], 16), dtype=torch.float32, device=tris.device)
+        d = direction if _is_torch(direction) else torch.as_tensor(np.asarray(direction, np.float32), device=tris.device)
+        tmax = tmax if _is_torch(tmax) else torch.as_tensor(np.asarray(tmax, np.float32), device=tris.device)
+    else:
+        out = np.zeros((tris.shape[0], 16), np.float32)
+        d = np.asarray(direction, np.float32)
+    out[:, 0:12] = tris
+    out[:, 12:15] = d.reshape(-1, 3)
+    out[:, 15] = tmax
+    return out
+
+
+def split_triangle_sweep_hits(records):
+    """(N, 8) triangle-sweep records (rt_triangle_sweep_hit) -> (normal (N, 3), t (N,), axis (N,), prim_id (N,), material_id (N,)): the
+    layout of split_box_sweep_hits, with axis 0 .. 25, SWEEP_TRIANGLE_AXIS_SPHERE or SWEEP_AXIS_NONE."""
+    return split_box_sweep_hits(records)
 
 
 def make_obb_sweeps(center, half_extent, rotation, direction, tmax=float("inf")):
@@ -1167,6 +1193,15 @@ class Context:
         normal is in world space, `axis` is read in the box's frame; misses and starts in contact as sweep_box reports them.  With the
         rotation (0, 0, 0, 1) the answer is sweep_box's."""
         return self._query("rt_sweep_obb", sweeps, out, 8, "float32", counters, in_cols=16, in_name="sweeps")
+
+    def sweep_triangle(self, sweeps, out=None, counters=False):
+        """rt_sweep_triangle: the first contact of each moving triangle of an (N, 16) batch (make_triangle_sweeps: three vertices,
+        direction, tmax) with the scene -> (N, 8) float32 records, normal nx ny nz | t | axis | 0 | prim_id | material_id
+        (split_triangle_sweep_hits).  axis numbers the separating axis that closed last (0 - 2 the coordinate axes, 3 the scene
+        triangle's normal, 4 the moving triangle's, 5 - 13 the edge pairs, 14 - 25 the in-plane axes of coplanar and segment pairs),
+        SWEEP_TRIANGLE_AXIS_SPHERE for a sphere; a miss has normal 0, tmax as t, SWEEP_AXIS_NONE and prim_id = PRIM_MISS; a start in
+        contact - exactly where overlap_triangle lists something - is t = 0 with normal 0 and SWEEP_AXIS_NONE."""
+        return self._query("rt_sweep_triangle", sweeps, out, 8, "float32", counters, in_cols=16, in_name="sweeps")
 
     def sweep_capsule(self, sweeps, out=None, counters=False):
         """rt_sweep_capsule: the first contact of each moving capsule of an (N, 12) batch (make_capsule_sweeps: origin, radius, axis,

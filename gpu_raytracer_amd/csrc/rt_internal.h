@@ -44,6 +44,7 @@
 #include "sweep_box.h"
 #include "sweep_capsule.h"
 #include "sweep_obb.h"
+#include "sweep_triangle.h"
 #include "wavefront.h"
 
 #define HIPCHK(ctx, call)                                                                                       \
@@ -254,6 +255,23 @@ void copy_share(uint8_t* dst, const uint8_t* src, size_t elem, uint32_t w, uint3
                 uint32_t n_owned); // rt_readback.cpp, with the next
 int consolidate_on_first_device(rt_ctx* ctx, uint32_t w, uint32_t h);
 int classify_ptr(rt_ctx* ctx, const char* fn, const char* what, const void* p, QueryPtr& q, uintptr_t align = 16); // rt_query.cpp
+// rt_query.cpp: the one-record-in, one-record-out batch with its argument types, for every call of that shape (rt_intersect ..
+// rt_sweep_capsule there; rt_sweep_triangle in rt_mesh_query.cpp).  launch: the call's kernel launcher.
+enum Stage { ST_OUT, ST_COUNTS, ST_AO, ST_PATHS }; // a buffer of DeviceState::rq
+struct BatchIn {
+    const char* name; // in messages
+    const void* p;
+    size_t size;      // bytes per record
+};
+struct BatchOut {
+    const char* name = nullptr;
+    void* p = nullptr;    // null: an output the call does not have, or the caller did not ask for
+    size_t size = 0;
+    uintptr_t align = 16; // asked of device memory
+    Stage stage = ST_OUT; // where a host batch's chunk of it is written before it is copied back
+};
+using RecordLaunch = hipError_t (*)(const DevScene&, const void*, void*, uint32_t, unsigned long long*, hipStream_t);
+int record_query(rt_ctx* ctx, const char* fn, BatchIn in, size_t n, BatchOut out, uint32_t flags, RecordLaunch launch);
 // rt_query.cpp: the argument checks and the batch of rt_overlap_box, for every call of its shape (rt_overlap_obb; rt_overlap_triangle
 // in rt_mesh_query.cpp).  in_name: the input array in messages; in_size: bytes per input record; launch: the call's kernel launcher.
 using OverlapLaunch = hipError_t (*)(const DevScene&, const void*, uint32_t*, uint32_t*, uint32_t, uint32_t, int, unsigned long long*, hipStream_t);

@@ -1,6 +1,7 @@
 // rt_mesh_query.cpp — queries whose input is the caller's own geometry: the triangle query (rt_hip.h "Triangle queries":
-// rt_overlap_triangle; kernel in overlap_triangle.hip).  The argument checks and the batch are rt_overlap_box's, written once in
-// rt_query.cpp (rti::overlap_query); this unit supplies the record and the launcher.
+// rt_overlap_triangle; kernel in overlap_triangle.hip) and the triangle sweep (rt_hip.h "Triangle sweeps": rt_sweep_triangle; kernel
+// in sweep_triangle.hip).  The argument checks and the batches are rt_overlap_box's and rt_sweep_box's, written once in rt_query.cpp
+// (rti::overlap_query, rti::record_query); this unit supplies the records and the launchers.
 #include "rt_internal.h"
 
 using namespace rti;
@@ -10,6 +11,11 @@ extern "C" {
 int rt_overlap_triangle(rt_ctx* ctx, const rt_query_triangle* triangles, size_t n, uint32_t max_prims, uint32_t* prims, uint32_t* counts, uint32_t flags) {
     return overlap_query(ctx, "rt_overlap_triangle", "triangles", triangles, sizeof(rt_query_triangle), n, max_prims, prims, counts, flags,
                          rt::launch_overlap_triangle);
+}
+
+int rt_sweep_triangle(rt_ctx* ctx, const rt_triangle_sweep* sweeps, size_t n, rt_triangle_sweep_hit* out, uint32_t flags) {
+    return record_query(ctx, "rt_sweep_triangle", {"sweeps", sweeps, sizeof(rt_triangle_sweep)}, n, {"out", out, sizeof(rt_triangle_sweep_hit)}, flags,
+                        rt::launch_sweep_triangle);
 }
 
 } // extern "C"

@@ -49,10 +49,9 @@ void drain_streams(rt_ctx* ctx) { // after a failure: nothing of the call is lef
 }
 
 // ---- batch calls: an array of records in, one or two arrays of records out ------------------------------------------------------
-// run_batch is the procedure all eighteen share; an entry function states its own checks, describes its arrays in a Batch, supplies the
+// run_batch is the procedure all of them share; an entry function states its own checks, describes its arrays in a Batch, supplies the
 // launches of one chunk and turns the Totals into rt_stats.
 
-enum Stage { ST_OUT, ST_COUNTS, ST_AO, ST_PATHS }; // a buffer of DeviceState::rq
 DevMem& stage_of(DeviceState& d, Stage s) {
     switch (s) {
     case ST_COUNTS: return d.rq.counts;
@@ -62,18 +61,7 @@ DevMem& stage_of(DeviceState& d, Stage s) {
     }
 }
 
-struct BatchIn {
-    const char* name; // in messages
-    const void* p;
-    size_t size;      // bytes per record
-};
-struct BatchOut {
-    const char* name = nullptr;
-    void* p = nullptr;    // null: an output the call does not have, or the caller did not ask for
-    size_t size = 0;
-    uintptr_t align = 16; // asked of device memory
-    Stage stage = ST_OUT; // where a host batch's chunk of it is written before it is copied back
-};
+// BatchIn, BatchOut and Stage: rt_internal.h
 struct Batch {
     const char* fn;
     size_t n;
@@ -206,25 +194,6 @@ void batch_stats(rt_ctx* ctx, double w0, const Totals& t, bool counters, uint64_
     st.wall_ms = now_ms() - w0;
 }
 
-// rt_intersect, rt_occluded, rt_surface, rt_closest_point, rt_sweep_sphere, rt_sweep_box, rt_sweep_obb, rt_sweep_capsule: one record in, one record out, one lane of `launch` per record.
-using RecordLaunch = hipError_t (*)(const DevScene&, const void*, void*, uint32_t, unsigned long long*, hipStream_t);
-int record_query(rt_ctx* ctx, const char* fn, BatchIn in, size_t n, BatchOut out, uint32_t flags, RecordLaunch launch) {
-    const double w0 = now_ms();
-    if (!ctx) return RT_ERR_BAD_ARG;
-    if (n == 0) return RT_OK;
-    if (!in.p || !out.p) return ctx->fail(RT_ERR_BAD_ARG, "%s: %s is NULL with n = %zu", fn, !in.p ? in.name : out.name, n);
-    if (flags & ~RT_QUERY_COUNTERS) return ctx->fail(RT_ERR_BAD_ARG, "%s: unknown flag bits 0x%x", fn, flags & ~RT_QUERY_COUNTERS);
-    if (!ctx->uploaded) return ctx->fail(RT_ERR_NOT_UPLOADED, "%s: no scene uploaded", fn);
-    const bool counters = (flags & RT_QUERY_COUNTERS) != 0;
-    const Batch b{fn, n, in, {out, {}}, RT_QUERY_CHUNK, RT_QUERY_CHUNK, counters ? RT_CNT_TRI_TESTS + 1u : 0u};
-    Totals t;
-    if (int rc = run_batch(ctx, b, t, [&](DeviceState& d, const DevScene& sc, const Chunk& ck) {
-            return launch(sc, ck.in, ck.out[0], ck.m, counters ? d.counters.get() : nullptr, d.stream);
-        }))
-        return rc;
-    batch_stats(ctx, w0, t, counters, n);
-    return RT_OK;
-}
 hipError_t launch_closest_hit(const DevScene& sc, const void* rays, void* out, uint32_t n, unsigned long long* cnt, hipStream_t s) {
     return rt::launch_ray_query(sc, rays, out, n, false, cnt, s);
 }
@@ -494,6 +463,26 @@ int inside_query(rt_ctx* ctx, const char* fn, const rt_point_query* points, size
 static_assert(RT_OVERLAP_MAX == rt::OV_PRIMS_MAX, "the kernel's list holds RT_OVERLAP_MAX entries");
 
 } // namespace
+
+// rt_intersect, rt_occluded, rt_surface, rt_closest_point, rt_sweep_sphere, rt_sweep_box, rt_sweep_obb, rt_sweep_capsule, and
+// rt_sweep_triangle (rt_mesh_query.cpp): one record in, one record out, one lane of `launch` per record.
+int record_query(rt_ctx* ctx, const char* fn, BatchIn in, size_t n, BatchOut out, uint32_t flags, RecordLaunch launch) {
+    const double w0 = now_ms();
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (n == 0) return RT_OK;
+    if (!in.p || !out.p) return ctx->fail(RT_ERR_BAD_ARG, "%s: %s is NULL with n = %zu", fn, !in.p ? in.name : out.name, n);
+    if (flags & ~RT_QUERY_COUNTERS) return ctx->fail(RT_ERR_BAD_ARG, "%s: unknown flag bits 0x%x", fn, flags & ~RT_QUERY_COUNTERS);
+    if (!ctx->uploaded) return ctx->fail(RT_ERR_NOT_UPLOADED, "%s: no scene uploaded", fn);
+    const bool counters = (flags & RT_QUERY_COUNTERS) != 0;
+    const Batch b{fn, n, in, {out, {}}, RT_QUERY_CHUNK, RT_QUERY_CHUNK, counters ? RT_CNT_TRI_TESTS + 1u : 0u};
+    Totals t;
+    if (int rc = run_batch(ctx, b, t, [&](DeviceState& d, const DevScene& sc, const Chunk& ck) {
+            return launch(sc, ck.in, ck.out[0], ck.m, counters ? d.counters.get() : nullptr, d.stream);
+        }))
+        return rc;
+    batch_stats(ctx, w0, t, counters, n);
+    return RT_OK;
+}
 
 // max_prims ids per record and a second output, the counts: rt_closest_point_all's shape with 4-byte records.  A chunk is RT_QUERY_CHUNK /
 // max(max_prims, 1) records.  rt_overlap_box, rt_overlap_obb and rt_overlap_triangle (rt_mesh_query.cpp): the same argument checks and batch, with the input's name,

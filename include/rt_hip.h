@@ -224,7 +224,7 @@ int rt_get_stats(rt_ctx* ctx, rt_stats* out);
  * a new one at sample 0 by itself, as RT_FLAG_ACCUMULATE_RESTART does.  The other RT_FLAG_* bits change no bits and may differ.
  * The running image ends (the next accumulating call starts at 0) with rt_upload_scene*, rt_update_geometry, rt_dispatch_tile, any
  * rt_render without RT_FLAG_ACCUMULATE and an accumulating call that fails once it has passed its argument checks.  It survives rt_prepare,
- * rt_upload_textures, the ray queries, the surface queries, rt_direct_light, rt_radiance, rt_radiance_sh, rt_irradiance, rt_closest_point, rt_closest_point_all, rt_inside, rt_signed_distance, rt_overlap_box, rt_sweep_sphere, rt_sweep_box, rt_sweep_capsule, rt_contact_capsule, rt_overlap_obb, rt_sweep_obb, rt_overlap_triangle, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
+ * rt_upload_textures, the ray queries, the surface queries, rt_direct_light, rt_radiance, rt_radiance_sh, rt_irradiance, rt_closest_point, rt_closest_point_all, rt_inside, rt_signed_distance, rt_overlap_box, rt_sweep_sphere, rt_sweep_box, rt_sweep_capsule, rt_contact_capsule, rt_overlap_obb, rt_sweep_obb, rt_overlap_triangle, rt_sweep_triangle, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
  * Limit: RT_ACCUMULATE_MAX_SAMPLES samples (where the float sample count stops being exact); a call that would pass it is RT_ERR_BAD_ARG
  * and leaves the running image as it was.  rt_stats describes the call alone (its segments, pixels, kernel_ms).
  * A context over several devices, and a tile_rank / tile_world share, accumulates its own share of the pixels.
@@ -1383,6 +1383,94 @@ int rt_overlap_triangle(rt_ctx* ctx, const rt_query_triangle* triangles, size_t 
                         uint32_t* prims,   /* n * max_prims ids, query-major, rt_hit.prim_id's encoding; unused slots 0xFFFFFFFF */
                         uint32_t* counts,  /* n entries; may be NULL unless max_prims == 0 */
                         uint32_t flags);   /* RT_QUERY_COUNTERS | RT_QUERY_COUNT_ALL | RT_OVERLAP_ANY; max_prims <= RT_OVERLAP_MAX */
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Triangle sweeps: the first contact of the caller's own triangles, each in translation, with the scene's surface (no reference
+ * counterpart; the translational triangle cast of mesh collision libraries is the model): continuous collision for a moving mesh,
+ * which "Triangle queries" can only test where it stands.  Stepping rt_overlap_triangle along the path tunnels through thin
+ * geometry and gives no contact time; rt_sweep_box over the triangle's bounds reports contacts of empty space; chained sphere
+ * sweeps miss what lies between the spheres.  The answer is one f32 statement (csrc/sweep_triangle_rules.h, whose header comment is
+ * the specification; every operation one f32 rounding, nothing fused, every test in its positive form so that a NaN makes it
+ * false); dot and cross as in "Triangle queries".
+ * Query: q0, q1, q2, u1, u2, u3, qlo, qhi as in "Triangle queries", d = direction and tmax.  The triangle at time t is q_k + d t; a
+ *   finite segment or point is allowed.  A miss without a walk, which the kernel checks itself: a non-finite component of a vertex
+ *   or of d, a zero d, a tmax that is NaN or <= 0.
+ * Triangle of the scene, from its record's v0, e1, e2: s_k, f_j and a_k = s_k - q0 as in "Triangle queries".  Two convex bodies in
+ *   translation touch at t iff no axis of a complete static axis set separates them at t, and the axes of rt_overlap_triangle do
+ *   not depend on position: each gives an interval of t and the contact is the intersection of the intervals.  The 26 axes, whose
+ *   numbers are rt_triangle_sweep_hit.axis:
+ *     0, 1, 2  the coordinate axes;  3  nS = cross(f1, f2);  4  nQ = cross(u1, u2);  5 + 3(i-1) + (j-1)  cross(u_i, f_j);
+ *     14 - 16  cross(nQ, u_i);  17 - 19  cross(nS, f_j);  20 - 22  cross(nS, u_i);  23 - 25  cross(nQ, f_j).
+ *   Coordinate axis a: lo = min_k s_k[a] - qhi[a], hi = max_k s_k[a] - qlo[a], w = d[a].  Axis L of the other 23: pS_k = dot(L, a_k),
+ *   pQ = (0, dot(L, u1), dot(L, u2)), lo = min pS - max pQ, hi = max pS - min pQ, w = dot(L, d); it holds only if
+ *   ((pS_0 + pS_1) + pS_2) + (pQ_1 + pQ_2) is not a NaN.  Then, as in "Box sweeps": w > 0: enter = lo / w, exit = hi / w; w < 0:
+ *   the two swapped; in both cases the axis holds iff enter <= exit, it replaces the running entry (0, RT_SWEEP_AXIS_NONE) iff its
+ *   enter is strictly larger, and t_out is the minimum of the exits.  w == 0: the axis holds iff lo <= 0 && hi >= 0 and constrains
+ *   nothing.  w a NaN: the axis does not hold.
+ *   Contact iff all nine components of the s_k are finite, every axis holds and t_in <= t_out; then t = t_in + 0.0f and axis is
+ *   the one that set t_in (at equal enter the lowest number).  t = 0 with RT_SWEEP_AXIS_NONE results exactly when
+ *   rt_overlap_triangle lists the triangle for q0, q1, q2: the sign of a rounded difference is exact (csrc/sweep_triangle_rules.h
+ *   has the argument and its two remarks on overflow).
+ *   normal = (w_in > 0 ? -L : L) / sqrtf(dot(L, L)) + 0.0f for the closing axis' vector L, against the motion; 0 for
+ *   RT_SWEEP_AXIS_NONE, and 0 where that length is not finite or not > 0.
+ *   Three limits.  Two degenerate triangles (segments, points) may be reported although they never meet; "closed" means closed on
+ *   the record (both as in "Triangle queries"); and two coplanar triangles moving inside their common plane are decided exactly
+ *   only where the plane's coordinates are exact (a coordinate plane): elsewhere the answer is that of a pair tilted by rounding.
+ *   A fourth concerns spheres alone, below: a segment given as v1 == v0.
+ * Sphere (o, R), a surface as everywhere; near2, far2, rr as in "Triangle queries", dd = dot(d, d).  Touching at the start (near2
+ *   <= rr && far2 >= rr): t = 0, RT_SWEEP_AXIS_NONE.  Otherwise from outside (near2 > rr): the time of "Sphere sweeps" for a ball
+ *   of radius R that starts at o and moves by -d against the triangle (q0, u1, u2).  Otherwise from inside (far2 < rr): the minimum
+ *   over the three vertices, with m = o - q_k, of t = (dot(m, d) + sqrtf(disc)) / dd, disc = dd * rr - dot(cross(m, d), cross(m,
+ *   d)), accepted iff disc >= 0 && t >= 0.  A contact at t > 0 has axis RT_SWEEP_TRIANGLE_AXIS_SPHERE and as normal the unit
+ *   vector, with P = o - d t: from outside, from P to the closest point of the triangle (q0, u1, u2) to P; from inside, from the
+ *   vertex farthest from P to P; 0 if its length is not > 0.  A contact at t = 0 has RT_SWEEP_AXIS_NONE and normal 0.
+ *   The fourth limit: near2 is the closest-point statement's for a degenerate query too, and for a segment given as v1 == v0 its
+ *   edge rule divides 0 by 0 wherever the closest point is not v0 itself: near2 is a NaN, every test on it fails, and that segment
+ *   meets no sphere, at the start or later (rt_overlap_triangle's behaviour, carried over).  A segment given as v2 == v1 or as
+ *   v2 == v0, and a point, have no such case and meet spheres as stated; give a moving segment in one of these forms.  The
+ *   scene's triangles are not affected.
+ * Order and acceptance as for rt_sweep_box: only t < tmax is accepted, strictly; at equal t spheres come before triangles, and
+ *   within each kind the lowest index wins.  A miss: normal 0, t = tmax as given, axis RT_SWEEP_AXIS_NONE, prim_id 0xFFFFFFFF,
+ *   material_id 0.
+ * The result follows from these rules alone: it does not depend on the tree in use, the device count, the kind of memory or the
+ *   chunking, and after rt_update_geometry it is that of a fresh upload of the moved scene.  The tree only culls, by the box of
+ *   the query's bounds swept along d with the margin of "Box sweeps" (DESIGN.md section 4).
+ * rt_sweep_triangle: buffers (host or device memory, both of one kind, device memory 16-byte aligned), chunking (RT_QUERY_CHUNK
+ *   records), the split over devices, synchronisation, side effects (the last frame and a running accumulation are left alone),
+ *   statistics (rays = n; visits and records only with RT_QUERY_COUNTERS) and error codes as for rt_sweep_box.
+ * --------------------------------------------------------------------------------------------------------------- */
+typedef struct rt_triangle_sweep {
+    float v0[3];           /* the first 48 bytes are an rt_query_triangle: the triangle at t = 0 */
+    uint32_t _pad0;        /* pads are ignored */
+    float v1[3];
+    uint32_t _pad1;
+    float v2[3];
+    uint32_t _pad2;
+    float direction[3];    /* the last 16 bytes are the second half of an rt_sweep; not normalised: t is in units of |direction| */
+    float tmax;            /* only contacts with t < tmax are reported */
+} rt_triangle_sweep; /* 64 bytes */
+
+typedef struct rt_triangle_sweep_hit {
+    float normal[3];       /* unit, against the motion; 0 for a miss and for a start in contact */
+    float t;               /* time of first contact; tmax as given for a miss */
+    uint32_t axis;         /* which separating axis closed last: 0 .. 25, RT_SWEEP_TRIANGLE_AXIS_SPHERE or RT_SWEEP_AXIS_NONE */
+    uint32_t _reserved;    /* 0 */
+    uint32_t prim_id;      /* rt_hit.prim_id's encoding; 0xFFFFFFFF for a miss */
+    uint32_t material_id;
+} rt_triangle_sweep_hit; /* 32 bytes: rt_box_sweep_hit's layout */
+
+#define RT_SWEEP_TRIANGLE_AXIS_SPHERE 26u
+
+RT_STATIC_ASSERT(sizeof(rt_triangle_sweep) == 64 && offsetof(rt_triangle_sweep, v0) == 0 && offsetof(rt_triangle_sweep, _pad0) == 12 &&
+                     offsetof(rt_triangle_sweep, v1) == 16 && offsetof(rt_triangle_sweep, _pad1) == 28 && offsetof(rt_triangle_sweep, v2) == 32 &&
+                     offsetof(rt_triangle_sweep, _pad2) == 44 && offsetof(rt_triangle_sweep, direction) == 48 && offsetof(rt_triangle_sweep, tmax) == 60,
+                 "rt_triangle_sweep is 64 B: an rt_query_triangle, direction at 48, tmax at 60");
+RT_STATIC_ASSERT(sizeof(rt_triangle_sweep_hit) == 32 && offsetof(rt_triangle_sweep_hit, normal) == 0 && offsetof(rt_triangle_sweep_hit, t) == 12 &&
+                     offsetof(rt_triangle_sweep_hit, axis) == 16 && offsetof(rt_triangle_sweep_hit, _reserved) == 20 &&
+                     offsetof(rt_triangle_sweep_hit, prim_id) == 24 && offsetof(rt_triangle_sweep_hit, material_id) == 28,
+                 "rt_triangle_sweep_hit is 32 B: normal, t at 12, axis at 16, _reserved at 20, prim_id at 24, material_id at 28");
+
+int rt_sweep_triangle(rt_ctx* ctx, const rt_triangle_sweep* sweeps, size_t n, rt_triangle_sweep_hit* out, uint32_t flags); /* RT_QUERY_COUNTERS */
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Geometry updates: new positions for the uploaded scene, in place (no reference counterpart; Embree's refit build,
