@@ -72,7 +72,7 @@ ABI_SYMBOLS = [
     "rt_get_stats", "rt_last_error", "rt_destroy", "rt_version",
     "rt_intersect", "rt_occluded", "rt_camera_rays", "rt_intersect_all",
     "rt_surface", "rt_ambient_occlusion", "rt_direct_light", "rt_radiance", "rt_radiance_sh", "rt_irradiance", "rt_closest_point", "rt_closest_point_all", "rt_sweep_sphere", "rt_sweep_box", "rt_sweep_capsule",
-    "rt_inside", "rt_signed_distance", "rt_overlap_box", "rt_contact_capsule", "rt_overlap_obb", "rt_sweep_obb", "rt_overlap_triangle", "rt_sweep_triangle",
+    "rt_inside", "rt_signed_distance", "rt_overlap_box", "rt_contact_capsule", "rt_overlap_obb", "rt_sweep_obb", "rt_overlap_triangle", "rt_sweep_triangle", "rt_contact_triangle",
     "rt_update_geometry",
     "rt_accumulated_samples",
     "rt_aovs", "rt_sample_rays", "rt_denoise",
@@ -182,15 +182,15 @@ def _check_nearest_lists(a, n, max_nearest):
         raise ValueError(f"out: {a.shape[0]} rows for {n} points")
 
 
-def _check_contact_lists(a, n, max_contacts):
-    """Raises unless `a` is a C-contiguous float32 (n, max_contacts, 8) array: rt_contact_capsule's records, query-major."""
+def _check_contact_lists(a, n, max_contacts, what="capsules"):
+    """Raises unless `a` is a C-contiguous float32 (n, max_contacts, 8) array: rt_contact_capsule's or rt_contact_triangle's records, query-major."""
     _check_kind_dtype(a, "out", "float32")
     if len(a.shape) != 3 or tuple(a.shape[1:]) != (max_contacts, 8):
         raise ValueError(f"out: shape {tuple(a.shape)}, expected (N, {max_contacts}, 8)")
     if not _contiguous(a):
         raise ValueError("out: not C-contiguous")
     if a.shape[0] != n:
-        raise ValueError(f"out: {a.shape[0]} rows for {n} capsules")
+        raise ValueError(f"out: {a.shape[0]} rows for {n} {what}")
 
 
 def _check_prim_lists(a, n, max_prims, what="boxes"):
@@ -559,6 +559,28 @@ def split_contacts(records):
     (N,), material_id (N,)): rt_capsule_sweep_hit's layout with the distance where t is, so the ids come as split_capsule_sweep_hits
     gives them (an unused slot is 4294967295 = PRIM_MISS).  normal = (origin + axis * s - position) / distance, depth = radius - distance."""
     return split_capsule_sweep_hits(records)
+
+
+def make_contact_triangles(v0, v1, v2, margin):
+    """Three (N, 3) arrays of vertices (numpy or torch, the result has the kind and device of v0) and margins (a scalar or an (N,)
+    array, > 0, inf allowed) -> an (N, 12) float32 batch of rt_triangle_contact_query records: v0 margin v1 0 v2 0.  Equal vertices
+    are allowed (a segment, a point)."""
+    out = make_triangles(v0, v1, v2)
+    if _is_torch(out):
+        import torch
+        margin = margin if _is_torch(margin) else torch.as_tensor(np.asarray(margin, np.float32), device=out.device)
+    else:
+        margin = np.asarray(margin, np.float32)
+    out[:, 3] = margin
+    return out
+
+
+def split_triangle_contacts(records):
+    """(N, 8) triangle-contact records (rt_triangle_contact; contact_triangle's out.reshape(-1, 8)) -> (position (N, 3), distance
+    (N,), qu (N,), qv (N,), prim_id (N,), material_id (N,)): rt_nearest's layout with the query's weights where the primitive's are, so
+    the ids come as split_nearest gives them (an unused slot is 4294967295 = PRIM_MISS).  normal = ((v0 + (v1 - v0) qu + (v2 - v0) qv) -
+    position) / distance, depth = margin - distance."""
+    return split_nearest(records)
 
 
 def split_lighting(lighting):
@@ -1150,7 +1172,21 @@ class Context:
         in range; with any_hit 1 where anything is in range, else 0 (the walk stops at the first: the occupancy test).
         max_contacts=0 needs count_all or any_hit; any_hit needs max_contacts=0 and excludes count_all.  With a zero axis the
         records are closest_point_all's with s = 0 where u is."""
-        n = _check_batch(capsules, "capsules", 8, "float32")
+        return self._contact_query("rt_contact_capsule", capsules, "capsules", 8, max_contacts, out, counts, count_all, any_hit, counters)
+
+    def contact_triangle(self, tris, max_contacts, out=None, counts=None, count_all=False, any_hit=False, counters=False):
+        """rt_contact_triangle: the primitives near each resting triangle of an (N, 12) batch (make_contact_triangles: three vertices
+        and a margin) -> (out, counts), same kind and device as `tris`.  out: (N, max_contacts, 8) float32 rt_triangle_contact records
+        (split_triangle_contacts takes out.reshape(-1, 8): position, distance, qu, qv, prim_id, material_id), the max_contacts (0 ..
+        CONTACT_MAX) nearest primitives whose distance from the triangle is strictly below its margin, nearest first, unused slots
+        miss records; None for max_contacts=0.  position is the primitive's point, (qu, qv) the weights of the triangle's own v1 and
+        v2 at its point of the closest pair; two triangles that intersect are at distance 0.  counts, count_all and any_hit as for
+        contact_capsule.  With three equal vertices the records are closest_point_all's with qu = qv = 0."""
+        return self._contact_query("rt_contact_triangle", tris, "tris", 12, max_contacts, out, counts, count_all, any_hit, counters)
+
+    def _contact_query(self, fn, batch, in_name, in_cols, max_contacts, out, counts, count_all, any_hit, counters):
+        """contact_capsule and contact_triangle: the checks, the outputs and the call."""
+        n = _check_batch(batch, in_name, in_cols, "float32")
         if isinstance(max_contacts, bool) or not isinstance(max_contacts, (int, np.integer)) or not 0 <= max_contacts <= CONTACT_MAX:
             raise ValueError(f"max_contacts: {max_contacts!r}, expected an integer in 0 .. {CONTACT_MAX}")
         max_contacts = int(max_contacts)
@@ -1158,19 +1194,19 @@ class Context:
             raise ValueError("any_hit: lists nothing and counts to one, which needs max_contacts=0 and excludes count_all")
         if max_contacts == 0 and not (count_all or any_hit):
             raise ValueError("max_contacts: 0 lists nothing, which needs count_all=True (a pure count) or any_hit=True")
-        if out is not None and _is_torch(out) != _is_torch(capsules):
-            raise TypeError("out: must be the same kind (numpy / torch) as capsules")
+        if out is not None and _is_torch(out) != _is_torch(batch):
+            raise TypeError(f"out: must be the same kind (numpy / torch) as {in_name}")
         if max_contacts == 0:
             out = None
         elif out is None:
-            out = _empty_like_batch(capsules, (n, max_contacts, 8), "float32")
+            out = _empty_like_batch(batch, (n, max_contacts, 8), "float32")
         else:
-            _check_contact_lists(out, n, max_contacts)
-        counts = _counts_like(counts, capsules, "capsules", n)
-        _sync_torch(capsules, out, counts)
+            _check_contact_lists(out, n, max_contacts, in_name)
+        counts = _counts_like(counts, batch, in_name, n)
+        _sync_torch(batch, out, counts)
         flags = (QUERY_COUNTERS if counters else 0) | (QUERY_COUNT_ALL if count_all else 0) | (CONTACT_ANY if any_hit else 0)
-        self._check(self.lib.rt_contact_capsule(self._h, _addr(capsules), C.c_size_t(n), C.c_uint32(max_contacts),
-                                                _addr(out) if out is not None else C.c_void_p(0), _addr(counts), C.c_uint32(flags)))
+        self._check(getattr(self.lib, fn)(self._h, _addr(batch), C.c_size_t(n), C.c_uint32(max_contacts),
+                                          _addr(out) if out is not None else C.c_void_p(0), _addr(counts), C.c_uint32(flags)))
         return out, counts
 
     def sweep_sphere(self, sweeps, out=None, counters=False):

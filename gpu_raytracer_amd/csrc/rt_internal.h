@@ -23,6 +23,7 @@
 #include "closest_point.h"
 #include "closest_point_all.h"
 #include "contact_capsule.h"
+#include "contact_triangle.h"
 #include "denoise.h"
 #include "device_build.h"
 #include "device_layout.h"
@@ -277,6 +278,11 @@ int record_query(rt_ctx* ctx, const char* fn, BatchIn in, size_t n, BatchOut out
 using OverlapLaunch = hipError_t (*)(const DevScene&, const void*, uint32_t*, uint32_t*, uint32_t, uint32_t, int, unsigned long long*, hipStream_t);
 int overlap_query(rt_ctx* ctx, const char* fn, const char* in_name, const void* in, size_t in_size, size_t n, uint32_t max_prims, uint32_t* prims,
                   uint32_t* counts, uint32_t flags, OverlapLaunch launch);
+// rt_query.cpp: the argument checks and the batch of rt_contact_capsule, for every call of its shape (rt_contact_triangle in
+// rt_mesh_query.cpp).  out: max_contacts 32-byte records per query.  in_name, in_size, launch: as for overlap_query.
+using ContactLaunch = hipError_t (*)(const DevScene&, const void*, void*, uint32_t*, uint32_t, uint32_t, int, unsigned long long*, hipStream_t);
+int contact_query(rt_ctx* ctx, const char* fn, const char* in_name, const void* in, size_t in_size, size_t n, uint32_t max_contacts, void* out,
+                  uint32_t* counts, uint32_t flags, ContactLaunch launch);
 
 } // namespace rti
 #endif

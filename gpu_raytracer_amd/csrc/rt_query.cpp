@@ -1,7 +1,7 @@
 // rt_query.cpp — calls that trace or filter outside a frame: ray queries (rt_hip.h "Ray queries": rt_intersect, rt_occluded,
 // rt_intersect_all, rt_camera_rays), surface queries ("Surface queries": rt_surface, rt_ambient_occlusion; kernels in
 // surface_query.hip), the direct-light query ("Direct-light queries": rt_direct_light; kernel in direct_light.hip), the path query ("Path queries":
-// rt_radiance; kernels in path_query.hip), the probe query ("Probe queries": rt_radiance_sh; kernels in probe_query.hip), the irradiance query ("Irradiance queries": rt_irradiance; kernels in irradiance_query.hip), the closest-point queries ("Closest-point queries": rt_closest_point, rt_closest_point_all; kernels in closest_point.hip, closest_point_all.hip), the inside test and the signed distance ("Inside tests and signed distance": rt_inside, rt_signed_distance; kernel in inside.hip), the sphere sweep ("Sphere sweeps": rt_sweep_sphere; kernel in sweep.hip), the box sweep ("Box sweeps": rt_sweep_box; kernel in sweep_box.hip), the capsule sweep ("Capsule sweeps": rt_sweep_capsule; kernel in sweep_capsule.hip), the overlap query ("Overlap queries": rt_overlap_box; kernel in overlap.hip; its checks and batch, overlap_query, also serve rt_overlap_obb and rt_mesh_query.cpp), the contact query ("Contact queries": rt_contact_capsule; kernel in contact_capsule.hip) and the image passes ("Feature buffers (AOVs) and denoising": rt_aovs, rt_sample_rays, rt_denoise; kernels in
+// rt_radiance; kernels in path_query.hip), the probe query ("Probe queries": rt_radiance_sh; kernels in probe_query.hip), the irradiance query ("Irradiance queries": rt_irradiance; kernels in irradiance_query.hip), the closest-point queries ("Closest-point queries": rt_closest_point, rt_closest_point_all; kernels in closest_point.hip, closest_point_all.hip), the inside test and the signed distance ("Inside tests and signed distance": rt_inside, rt_signed_distance; kernel in inside.hip), the sphere sweep ("Sphere sweeps": rt_sweep_sphere; kernel in sweep.hip), the box sweep ("Box sweeps": rt_sweep_box; kernel in sweep_box.hip), the capsule sweep ("Capsule sweeps": rt_sweep_capsule; kernel in sweep_capsule.hip), the overlap query ("Overlap queries": rt_overlap_box; kernel in overlap.hip; its checks and batch, overlap_query, also serve rt_overlap_obb and rt_mesh_query.cpp), the contact query ("Contact queries": rt_contact_capsule; kernel in contact_capsule.hip; its checks and batch, contact_query, also serve rt_mesh_query.cpp) and the image passes ("Feature buffers (AOVs) and denoising": rt_aovs, rt_sample_rays, rt_denoise; kernels in
 // denoise.hip).  None of them touches the frame targets, the tile shares rt_read_* gather, or the running image of an accumulation.
 #include "rt_internal.h"
 #include "contact_capsule_rules.h"
@@ -517,6 +517,40 @@ int overlap_query(rt_ctx* ctx, const char* fn, const char* in_name, const void* 
     return RT_OK;
 }
 
+// max_contacts 32-byte records per query and a second output, the counts: rt_closest_point_all's shape with rt_overlap_box's modes.  A
+// chunk is RT_QUERY_CHUNK / max(max_contacts, 1) queries.  rt_contact_capsule and rt_contact_triangle (rt_mesh_query.cpp): the same
+// argument checks and batch, with the input's name, the record's size and the launcher of each.
+static_assert(RT_CONTACT_MAX == rt::CC_CONTACT_MAX && RT_CONTACT_MAX == rt::CT_CONTACT_MAX, "the kernels' lists hold RT_CONTACT_MAX entries");
+static_assert(sizeof(rt_contact) == 32 && sizeof(rt_triangle_contact) == 32, "contact_query writes 32-byte records");
+int contact_query(rt_ctx* ctx, const char* fn, const char* in_name, const void* in, size_t in_size, size_t n, uint32_t max_contacts, void* out,
+                  uint32_t* counts, uint32_t flags, ContactLaunch launch) {
+    const double w0 = now_ms();
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (n == 0) return RT_OK;
+    if (!in || (!out && max_contacts > 0)) return ctx->fail(RT_ERR_BAD_ARG, "%s: %s is NULL with n = %zu", fn, !in ? in_name : "out", n);
+    if (max_contacts > RT_CONTACT_MAX) return ctx->fail(RT_ERR_BAD_ARG, "%s: max_contacts %u (0 .. %u)", fn, max_contacts, RT_CONTACT_MAX);
+    const uint32_t known = RT_QUERY_COUNTERS | RT_QUERY_COUNT_ALL | RT_CONTACT_ANY;
+    if (flags & ~known) return ctx->fail(RT_ERR_BAD_ARG, "%s: unknown flag bits 0x%x", fn, flags & ~known);
+    const bool counters = (flags & RT_QUERY_COUNTERS) != 0, all = (flags & RT_QUERY_COUNT_ALL) != 0, any = (flags & RT_CONTACT_ANY) != 0;
+    if (any && (all || max_contacts > 0)) return ctx->fail(RT_ERR_BAD_ARG, "%s: RT_CONTACT_ANY needs max_contacts 0 and excludes RT_QUERY_COUNT_ALL", fn);
+    if (max_contacts == 0 && ((!all && !any) || !counts))
+        return ctx->fail(RT_ERR_BAD_ARG, "%s: max_contacts 0 needs RT_QUERY_COUNT_ALL or RT_CONTACT_ANY, and counts", fn);
+    if (!ctx->uploaded) return ctx->fail(RT_ERR_NOT_UPLOADED, "%s: no scene uploaded", fn);
+    if (max_contacts == 0) out = nullptr; // ignored: a pure count
+    const int mode = any ? rt::CC_ANY : all ? rt::CC_COUNT_ALL : rt::CC_LIST;
+    const size_t chunk = RT_QUERY_CHUNK / std::max(max_contacts, 1u);
+    const Batch b{fn, n, {in_name, in, in_size},
+                  {{"out", out, max_contacts * sizeof(rt_contact)}, {"counts", counts, sizeof(uint32_t), 4, ST_COUNTS}},
+                  chunk, chunk, counters ? RT_CNT_TRI_TESTS + 1u : 0u};
+    Totals t;
+    if (int rc = run_batch(ctx, b, t, [&](DeviceState& d, const DevScene& sc, const Chunk& ck) {
+            return launch(sc, ck.in, ck.out[0], static_cast<uint32_t*>(ck.out[1]), ck.m, max_contacts, mode, counters ? d.counters.get() : nullptr, d.stream);
+        }))
+        return rc;
+    batch_stats(ctx, w0, t, counters, n);
+    return RT_OK;
+}
+
 } // namespace rti
 
 using namespace rti;
@@ -620,37 +654,8 @@ int rt_overlap_obb(rt_ctx* ctx, const rt_obb* boxes, size_t n, uint32_t max_prim
     return overlap_query(ctx, "rt_overlap_obb", "boxes", boxes, sizeof(rt_obb), n, max_prims, prims, counts, flags, rt::launch_overlap_obb);
 }
 
-// max_contacts records per capsule and a second output, the counts: rt_closest_point_all's shape with rt_overlap_box's modes.  A
-// chunk is RT_QUERY_CHUNK / max(max_contacts, 1) capsules.
-static_assert(RT_CONTACT_MAX == rt::CC_CONTACT_MAX, "the kernel's list holds RT_CONTACT_MAX entries");
 int rt_contact_capsule(rt_ctx* ctx, const rt_capsule* capsules, size_t n, uint32_t max_contacts, rt_contact* out, uint32_t* counts, uint32_t flags) {
-    const char* fn = "rt_contact_capsule";
-    const double w0 = now_ms();
-    if (!ctx) return RT_ERR_BAD_ARG;
-    if (n == 0) return RT_OK;
-    if (!capsules || (!out && max_contacts > 0)) return ctx->fail(RT_ERR_BAD_ARG, "%s: %s is NULL with n = %zu", fn, !capsules ? "capsules" : "out", n);
-    if (max_contacts > RT_CONTACT_MAX) return ctx->fail(RT_ERR_BAD_ARG, "%s: max_contacts %u (0 .. %u)", fn, max_contacts, RT_CONTACT_MAX);
-    const uint32_t known = RT_QUERY_COUNTERS | RT_QUERY_COUNT_ALL | RT_CONTACT_ANY;
-    if (flags & ~known) return ctx->fail(RT_ERR_BAD_ARG, "%s: unknown flag bits 0x%x", fn, flags & ~known);
-    const bool counters = (flags & RT_QUERY_COUNTERS) != 0, all = (flags & RT_QUERY_COUNT_ALL) != 0, any = (flags & RT_CONTACT_ANY) != 0;
-    if (any && (all || max_contacts > 0)) return ctx->fail(RT_ERR_BAD_ARG, "%s: RT_CONTACT_ANY needs max_contacts 0 and excludes RT_QUERY_COUNT_ALL", fn);
-    if (max_contacts == 0 && ((!all && !any) || !counts))
-        return ctx->fail(RT_ERR_BAD_ARG, "%s: max_contacts 0 needs RT_QUERY_COUNT_ALL or RT_CONTACT_ANY, and counts", fn);
-    if (!ctx->uploaded) return ctx->fail(RT_ERR_NOT_UPLOADED, "%s: no scene uploaded", fn);
-    if (max_contacts == 0) out = nullptr; // ignored: a pure count
-    const int mode = any ? rt::CC_ANY : all ? rt::CC_COUNT_ALL : rt::CC_LIST;
-    const size_t chunk = RT_QUERY_CHUNK / std::max(max_contacts, 1u);
-    const Batch b{fn, n, {"capsules", capsules, sizeof(rt_capsule)},
-                  {{"out", out, max_contacts * sizeof(rt_contact)}, {"counts", counts, sizeof(uint32_t), 4, ST_COUNTS}},
-                  chunk, chunk, counters ? RT_CNT_TRI_TESTS + 1u : 0u};
-    Totals t;
-    if (int rc = run_batch(ctx, b, t, [&](DeviceState& d, const DevScene& sc, const Chunk& ck) {
-            return rt::launch_contact_capsule(sc, ck.in, ck.out[0], static_cast<uint32_t*>(ck.out[1]), ck.m, max_contacts, mode,
-                                              counters ? d.counters.get() : nullptr, d.stream);
-        }))
-        return rc;
-    batch_stats(ctx, w0, t, counters, n);
-    return RT_OK;
+    return contact_query(ctx, "rt_contact_capsule", "capsules", capsules, sizeof(rt_capsule), n, max_contacts, out, counts, flags, rt::launch_contact_capsule);
 }
 
 int rt_inside(rt_ctx* ctx, const rt_point_query* points, size_t n, const rt_inside_params* params, uint8_t* inside, uint8_t* votes) {

@@ -224,7 +224,7 @@ int rt_get_stats(rt_ctx* ctx, rt_stats* out);
  * a new one at sample 0 by itself, as RT_FLAG_ACCUMULATE_RESTART does.  The other RT_FLAG_* bits change no bits and may differ.
  * The running image ends (the next accumulating call starts at 0) with rt_upload_scene*, rt_update_geometry, rt_dispatch_tile, any
  * rt_render without RT_FLAG_ACCUMULATE and an accumulating call that fails once it has passed its argument checks.  It survives rt_prepare,
- * rt_upload_textures, the ray queries, the surface queries, rt_direct_light, rt_radiance, rt_radiance_sh, rt_irradiance, rt_closest_point, rt_closest_point_all, rt_inside, rt_signed_distance, rt_overlap_box, rt_sweep_sphere, rt_sweep_box, rt_sweep_capsule, rt_contact_capsule, rt_overlap_obb, rt_sweep_obb, rt_overlap_triangle, rt_sweep_triangle, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
+ * rt_upload_textures, the ray queries, the surface queries, rt_direct_light, rt_radiance, rt_radiance_sh, rt_irradiance, rt_closest_point, rt_closest_point_all, rt_inside, rt_signed_distance, rt_overlap_box, rt_sweep_sphere, rt_sweep_box, rt_sweep_capsule, rt_contact_capsule, rt_overlap_obb, rt_sweep_obb, rt_overlap_triangle, rt_sweep_triangle, rt_contact_triangle, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
  * Limit: RT_ACCUMULATE_MAX_SAMPLES samples (where the float sample count stops being exact); a call that would pass it is RT_ERR_BAD_ARG
  * and leaves the running image as it was.  rt_stats describes the call alone (its segments, pixels, kernel_ms).
  * A context over several devices, and a tile_rank / tile_world share, accumulates its own share of the pixels.
@@ -370,7 +370,7 @@ int rt_occluded(rt_ctx* ctx, const rt_ray* rays, size_t n, uint8_t* occluded, ui
  * Statistics, synchronisation and side effects as for rt_intersect: synchronous, first waits for an rt_dispatch_tile in flight;
  * rays = n, the other counts 0, kernel_ms the maximum over devices, node_visits / tri_tests only with RT_QUERY_COUNTERS; the last
  * frame, the rt_read_* results and a running accumulation are left alone. */
-#define RT_QUERY_COUNT_ALL 2u   /* rt_intersect_all, rt_closest_point_all, rt_overlap_box, rt_overlap_obb, rt_overlap_triangle and rt_contact_capsule only */
+#define RT_QUERY_COUNT_ALL 2u   /* rt_intersect_all, rt_closest_point_all, rt_overlap_box, rt_overlap_obb, rt_overlap_triangle and rt_contact_capsule only; also rt_contact_triangle */
 #define RT_MULTI_HIT_MAX 16u
 
 int rt_intersect_all(rt_ctx* ctx, const rt_ray* rays, size_t n, uint32_t max_hits,
@@ -1249,7 +1249,7 @@ RT_STATIC_ASSERT(sizeof(rt_contact) == 32 && offsetof(rt_contact, position) == 0
                  "rt_contact is 32 B: position, distance at 12, s at 16, _reserved at 20, prim_id at 24, material_id at 28");
 
 #define RT_CONTACT_MAX 16u
-#define RT_CONTACT_ANY 4u   /* rt_contact_capsule only: counts[i] = 1 if anything is in range of capsule i, else 0; stops at the first */
+#define RT_CONTACT_ANY 4u   /* rt_contact_capsule only: counts[i] = 1 if anything is in range of capsule i, else 0; stops at the first; also rt_contact_triangle */
 
 int rt_contact_capsule(rt_ctx* ctx, const rt_capsule* capsules, size_t n, uint32_t max_contacts,
                        rt_contact* out,   /* n * max_contacts records, query-major; unused slots are misses */
@@ -1471,6 +1471,70 @@ RT_STATIC_ASSERT(sizeof(rt_triangle_sweep_hit) == 32 && offsetof(rt_triangle_swe
                  "rt_triangle_sweep_hit is 32 B: normal, t at 12, axis at 16, _reserved at 20, prim_id at 24, material_id at 28");
 
 int rt_sweep_triangle(rt_ctx* ctx, const rt_triangle_sweep* sweeps, size_t n, rt_triangle_sweep_hit* out, uint32_t flags); /* RT_QUERY_COUNTERS */
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Triangle contacts: the primitives near the caller's own RESTING triangles, with the closest pair of points (no reference
+ * counterpart; FCL's distance, the contact manifold with a collision margin of Bullet and PhysX for mesh shapes and the clearance
+ * query of robot and tool-path planners are the model).  rt_overlap_triangle says "touches", rt_sweep_triangle says when; this says
+ * how far, from which primitive and at which pair of points: what de-penetration, resting contact and the step of conservative
+ * advancement need.
+ *
+ * For each query triangle v0, v1, v2 - equal vertices are allowed: a segment, a point - the max_contacts nearest primitives of the
+ * scene whose distance from the triangle is STRICTLY below `margin`, nearest first.  The distance of the query from a triangle of
+ * the scene is the distance of the two triangles as closed sets, 0 when they intersect; a sphere is its surface, as everywhere: the
+ * distance is that of the triangle from the surface, from outside, from inside, or 0 when the triangle crosses it.  One f32
+ * statement (csrc/contact_triangle_rules.h), independent of the tree:
+ *   a triangle of the scene: the least of the three query vertices against it, its three vertices against the query (a query
+ *   with an area only), the nine edge pairs as clamped segments, and 0 where an edge of one passes through the other; the first
+ *   of these in that order with the strictly smallest squared distance gives the pair of points;
+ *   a sphere: the query's point nearest the centre when that lies outside, its farthest vertex when the whole triangle lies
+ *   inside, else the point between the two that lies on the surface.
+ * A record gives the point of the PRIMITIVE, the distance and the weights of the QUERY's own point, so that
+ *   normal = ((v0 + (v1 - v0) qu + (v2 - v0) qv) - position) / distance     and     depth = margin - distance
+ * are the push-out.  Two triangles that intersect have distance 0 and no normal: the penetration depth of an intersecting pair is
+ * out of scope here.  A degenerate query - a non-finite vertex component, or a margin that is NaN or <= 0 - lists nothing; a margin
+ * of +inf is allowed.  With v0 == v1 == v2 the records are rt_closest_point_all's at that point with the margin as the radius, bit
+ * for bit (position, distance, prim_id, material_id; qu = qv = 0).  A segment is answered the same whichever two of its
+ * vertices coincide (rt_sweep_triangle's fourth limit does not apply here).
+ *
+ * rt_contact_triangle: everything that is not the statement above is rt_contact_capsule's, with `margin` where `radius` is: the
+ *   modes (the list; RT_QUERY_COUNT_ALL, with which max_contacts == 0 is allowed; RT_CONTACT_ANY), the order (bits of dist2, key),
+ *   the strict range dist2 < margin * margin, unused slots and counts, 1 <= max_contacts <= RT_CONTACT_MAX, chunking at
+ *   RT_QUERY_CHUNK / max(max_contacts, 1) triangles, the split over devices, buffers (host or device memory, all of one kind, device
+ *   memory 16-byte aligned, counts 4-byte), synchronisation, side effects (the last frame and a running accumulation are left alone),
+ *   statistics (rays = n; visits and records only with RT_QUERY_COUNTERS) and the error codes, one for one.  The tree only culls, by
+ *   the distance between the box of the query's vertices and each child box: loose for a large triangle askew to the axes.
+ * --------------------------------------------------------------------------------------------------------------- */
+typedef struct rt_triangle_contact_query {   /* rt_query_triangle's layout with the margin where _pad0 is (offset 12, where rt_point_query and rt_capsule keep the radius) */
+    float v0[3];
+    float margin;          /* only surface strictly nearer than this is listed; > 0, +inf allowed */
+    float v1[3];
+    uint32_t _pad1;        /* pads are ignored */
+    float v2[3];
+    uint32_t _pad2;
+} rt_triangle_contact_query; /* 48 bytes */
+
+typedef struct rt_triangle_contact {         /* rt_nearest's layout; qu, qv are the QUERY's weights */
+    float position[3];     /* the point of the scene's primitive nearest the query triangle; 0 in an unused slot */
+    float distance;        /* between the two; < margin; the margin as given in an unused slot */
+    float qu, qv;          /* the weights of the query's v1 and v2 at its own point of the closest pair; 0 in an unused slot */
+    uint32_t prim_id;      /* as rt_hit.prim_id; 0xFFFFFFFF = unused slot */
+    uint32_t material_id;  /* the record's material id, unchecked; 0 in an unused slot */
+} rt_triangle_contact; /* 32 bytes */
+
+RT_STATIC_ASSERT(sizeof(rt_triangle_contact_query) == 48 && offsetof(rt_triangle_contact_query, v0) == 0 && offsetof(rt_triangle_contact_query, margin) == 12 &&
+                     offsetof(rt_triangle_contact_query, v1) == 16 && offsetof(rt_triangle_contact_query, _pad1) == 28 &&
+                     offsetof(rt_triangle_contact_query, v2) == 32 && offsetof(rt_triangle_contact_query, _pad2) == 44,
+                 "rt_triangle_contact_query is 48 B: v0, margin at 12, v1 at 16, _pad1 at 28, v2 at 32, _pad2 at 44");
+RT_STATIC_ASSERT(sizeof(rt_triangle_contact) == 32 && offsetof(rt_triangle_contact, position) == 0 && offsetof(rt_triangle_contact, distance) == 12 &&
+                     offsetof(rt_triangle_contact, qu) == 16 && offsetof(rt_triangle_contact, qv) == 20 && offsetof(rt_triangle_contact, prim_id) == 24 &&
+                     offsetof(rt_triangle_contact, material_id) == 28,
+                 "rt_triangle_contact is 32 B: position, distance at 12, qu at 16, qv at 20, prim_id at 24, material_id at 28");
+
+int rt_contact_triangle(rt_ctx* ctx, const rt_triangle_contact_query* triangles, size_t n, uint32_t max_contacts,
+                        rt_triangle_contact* out,   /* n * max_contacts records, query-major; unused slots are misses */
+                        uint32_t* counts,           /* n entries; may be NULL unless max_contacts == 0 */
+                        uint32_t flags);            /* RT_QUERY_COUNTERS | RT_QUERY_COUNT_ALL | RT_CONTACT_ANY; max_contacts <= RT_CONTACT_MAX */
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Geometry updates: new positions for the uploaded scene, in place (no reference counterpart; Embree's refit build,
