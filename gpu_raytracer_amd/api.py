@@ -41,6 +41,7 @@ SWEEP_AXIS_SPHERE = 13  # RT_SWEEP_AXIS_SPHERE of rt_box_sweep_hit.axis: the con
 SWEEP_AXIS_NONE = 0xFFFFFFFF  # RT_SWEEP_AXIS_NONE: a miss, or in contact at the start
 SWEEP_TRIANGLE_AXIS_SPHERE = 26  # RT_SWEEP_TRIANGLE_AXIS_SPHERE of rt_triangle_sweep_hit.axis: the contact is with a sphere primitive
 OVERLAP_ANY = 4  # RT_OVERLAP_ANY of rt_overlap_box / rt_overlap_obb / rt_overlap_triangle: counts are 1 where anything touches the box, else 0, and the walk stops at the first
+POSED_MESH_MAX = 65536  # RT_POSED_MESH_MAX: the most triangles of a query mesh of rt_overlap_mesh / rt_sweep_mesh
 CONTACT_MAX = 16  # RT_CONTACT_MAX: the most primitives rt_contact_capsule lists per capsule
 CONTACT_ANY = 4  # RT_CONTACT_ANY of rt_contact_capsule: counts are 1 where anything is in range of the capsule, else 0, and the walk stops at the first
 INSIDE_MAX_RAYS = 7  # RT_INSIDE_MAX_RAYS: the most parity rays rt_inside / rt_signed_distance trace per point
@@ -73,6 +74,7 @@ ABI_SYMBOLS = [
     "rt_intersect", "rt_occluded", "rt_camera_rays", "rt_intersect_all",
     "rt_surface", "rt_ambient_occlusion", "rt_direct_light", "rt_radiance", "rt_radiance_sh", "rt_irradiance", "rt_closest_point", "rt_closest_point_all", "rt_sweep_sphere", "rt_sweep_box", "rt_sweep_capsule",
     "rt_inside", "rt_signed_distance", "rt_overlap_box", "rt_contact_capsule", "rt_overlap_obb", "rt_sweep_obb", "rt_overlap_triangle", "rt_sweep_triangle", "rt_contact_triangle",
+    "rt_overlap_mesh", "rt_sweep_mesh",
     "rt_update_geometry",
     "rt_accumulated_samples",
     "rt_aovs", "rt_sample_rays", "rt_denoise",
@@ -489,6 +491,95 @@ def make_obb_sweeps(center, half_extent, rotation, direction, tmax=float("inf"))
         out = np.zeros((boxes.shape[0], 16), np.float32)
     out[:, 0:12] = boxes
     out[:, 12:16] = sweeps[:, 8:12]
+    return out
+
+
+def make_poses(position, rotation):
+    """(N, 3) positions (numpy or torch, the result has the same kind and device) -> an (N, 8) float32 batch of rt_pose records:
+    px py pz 0 qx qy qz qw.  rotation: a quaternion x, y, z, w or an (N, 4) array of them, turning the mesh's axes into world axes,
+    as for make_obbs; it need not be normalised.  The position is added after the rotation."""
+    if _is_torch(position):
+        import torch
+        p = position.reshape(-1, 3)
+        out = torch.zeros((p.shape[0], 8), dtype=torch.float32, device=p.device)
+        q = rotation if _is_torch(rotation) else torch.as_tensor(np.asarray(rotation, np.float32), device=p.device)
+    else:
+        p = np.asarray(position, np.float32).reshape(-1, 3)
+        out = np.zeros((p.shape[0], 8), np.float32)
+        q = np.asarray(rotation, np.float32)
+    out[:, 0:3] = p
+    out[:, 4:8] = q
+    return out
+
+
+def make_pose_sweeps(position, rotation, direction, tmax=float("inf")):
+    """(N, 3) positions and world directions (numpy or torch, the result has the same kind and device) -> an (N, 12) float32 batch of
+    rt_pose_sweep records: px py pz 0 qx qy qz qw dx dy dz tmax.  position and rotation as for make_poses; the direction is not
+    turned by the pose; tmax: a scalar or an (N,) array; contacts at 0 <= t < tmax are reported."""
+    poses = make_poses(position, rotation)
+    if _is_torch(poses):
+        import torch
+        out = torch.zeros((poses.shape[0], 12), dtype=torch.float32, device=poses.device)
+        d = direction if _is_torch(direction) else torch.as_tensor(np.asarray(direction, np.float32), device=poses.device)
+        tmax = tmax if _is_torch(tmax) else torch.as_tensor(np.asarray(tmax, np.float32), device=poses.device)
+    else:
+        out = np.zeros((poses.shape[0], 12), np.float32)
+        d = np.asarray(direction, np.float32)
+    out[:, 0:8] = poses
+    out[:, 8:11] = d.reshape(-1, 3)
+    out[:, 11] = tmax
+    return out
+
+
+def split_mesh_sweep_hits(records):
+    """(N, 8) posed-mesh sweep records (rt_mesh_sweep_hit) -> (normal (N, 3), t (N,), axis (N,), triangle (N,), prim_id (N,),
+    material_id (N,)): split_triangle_sweep_hits with the mesh triangle that touches first, PRIM_MISS for a miss.  The words are uint32
+    for numpy, int64 for torch."""
+    if _is_torch(records):
+        import torch
+        words = [records[:, c].contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF for c in (4, 5, 6, 7)]
+    else:
+        words = [np.ascontiguousarray(records[:, c]).view(np.uint32) for c in (4, 5, 6, 7)]
+    return records[:, 0:3], records[:, 3], words[0], words[1], words[2], words[3]
+
+
+def pose_frames(poses):
+    """The rotation matrices of an (N, 8) batch of poses (or the first 8 columns of an (N, 12) batch of pose sweeps) -> (R (N, 3, 3)
+    float32, valid (N,) bool): the frame of csrc/obb_rules.h rule 1 in numpy float32, operation for operation, and the validity of
+    csrc/mesh_pose_rules.h rule 1 (position and rotation finite, the squared norm finite and > 0)."""
+    poses = np.asarray(poses, np.float32)
+    x, y, z, w = (poses[:, 4 + k] for k in range(4))
+    with np.errstate(all="ignore"):
+        n = ((x * x + y * y) + z * z) + w * w
+        s = np.float32(2.0) / n
+        xs, ys, zs = x * s, y * s, z * s
+        wx, wy, wz = w * xs, w * ys, w * zs
+        xx, xy, xz, yy, yz, zz = x * xs, x * ys, x * zs, y * ys, y * zs, z * zs
+        one = np.float32(1.0)
+        R = np.stack([one - (yy + zz), xy - wz, xz + wy, xy + wz, one - (xx + zz), yz - wx, xz - wy, yz + wx, one - (xx + yy)], axis=1).reshape(-1, 3, 3)
+    valid = np.isfinite(poses[:, 0:3]).all(axis=1) & np.isfinite(poses[:, 4:8]).all(axis=1) & np.isfinite(n) & (n > 0)
+    return R.astype(np.float32), valid
+
+
+def pose_triangles(mesh, poses):
+    """The (M, 12) mesh (make_triangles) at each pose of an (N, 8) batch (make_poses; an (N, 12) batch of pose sweeps is read the same)
+    -> (N, M, 12) float32 rt_query_triangle records: the posing statement of rt_overlap_mesh / rt_sweep_mesh in numpy float32,
+    operation for operation - w_a = ((R_a0 v_0 + R_a1 v_1) + R_a2 v_2) + position_a with R = pose_frames(poses) - so row [i, j] is
+    bit for bit the triangle the device judges for pose i and mesh triangle j.  What the tests compare with, and what a caller
+    draws the body with.  The rows of an invalid pose are not to be used (the calls answer it without looking at them)."""
+    mesh, poses = np.asarray(mesh, np.float32), np.asarray(poses, np.float32)
+    if mesh.ndim != 2 or mesh.shape[1] != 12:
+        raise ValueError(f"mesh: shape {mesh.shape}, expected (M, 12)")
+    if poses.ndim != 2 or poses.shape[1] not in (8, 12):
+        raise ValueError(f"poses: shape {poses.shape}, expected (N, 8) or (N, 12)")
+    R, _ = pose_frames(poses)
+    out = np.zeros((poses.shape[0], mesh.shape[0], 12), np.float32)
+    with np.errstate(all="ignore"):
+        for k in range(3):
+            v = mesh[None, :, 4 * k:4 * k + 3]  # (1, M, 3)
+            for a in range(3):
+                r = (R[:, a, 0, None] * v[:, :, 0] + R[:, a, 1, None] * v[:, :, 1]) + R[:, a, 2, None] * v[:, :, 2]
+                out[:, :, 4 * k + a] = r + poses[:, a, None]
     return out
 
 
@@ -1238,6 +1329,47 @@ class Context:
         SWEEP_TRIANGLE_AXIS_SPHERE for a sphere; a miss has normal 0, tmax as t, SWEEP_AXIS_NONE and prim_id = PRIM_MISS; a start in
         contact - exactly where overlap_triangle lists something - is t = 0 with normal 0 and SWEEP_AXIS_NONE."""
         return self._query("rt_sweep_triangle", sweeps, out, 8, "float32", counters, in_cols=16, in_name="sweeps")
+
+    def _posed_mesh(self, mesh, batch, cols, name):
+        """What overlap_mesh and sweep_mesh check of their inputs: (m, n)."""
+        m = _check_batch(mesh, "mesh", 12, "float32")
+        n = _check_batch(batch, name, cols, "float32")
+        if not 1 <= m <= POSED_MESH_MAX:
+            raise ValueError(f"mesh: {m} triangles, expected 1 .. {POSED_MESH_MAX}")
+        return m, n
+
+    def overlap_mesh(self, mesh, poses, *, first=False, any_hit=False, counters=False):
+        """rt_overlap_mesh: the (M, 12) mesh (make_triangles, 1 .. POSED_MESH_MAX triangles), given once, at each pose of an (N, 8)
+        batch (make_poses) -> pairs, or (pairs, first) with first=True; (N,) uint32 (numpy) / int32 (torch, the same bits), same kind
+        and device as `poses`.  pairs: the number of (mesh triangle, primitive) pairs that touch - the sum of overlap_triangle's
+        count_all counts over pose_triangles(mesh, poses)[i], at most 0xFFFFFFFF; first: the lowest mesh triangle that touches
+        anything, PRIM_MISS if none.  any_hit: pairs is 1 where anything touches, else 0, and a pose stops at its first touch;
+        it excludes first.  An invalid pose (non-finite position or rotation, a zero quaternion) touches nothing.  mesh, poses and
+        the results are all host or all device memory of one device."""
+        m, n = self._posed_mesh(mesh, poses, 8, "poses")
+        if any_hit and first:
+            raise ValueError("first: any_hit may stop at any touching triangle, which excludes first")
+        pairs = _counts_like(None, poses, "poses", n)
+        low = _counts_like(None, poses, "poses", n) if first else None
+        _sync_torch(mesh, poses, pairs, low)
+        flags = (QUERY_COUNTERS if counters else 0) | (OVERLAP_ANY if any_hit else 0)
+        self._check(self.lib.rt_overlap_mesh(self._h, _addr(mesh), C.c_size_t(m), _addr(poses), C.c_size_t(n), _addr(pairs),
+                                             _addr(low) if low is not None else C.c_void_p(0), C.c_uint32(flags)))
+        return (pairs, low) if first else pairs
+
+    def sweep_mesh(self, mesh, sweeps, out=None, counters=False):
+        """rt_sweep_mesh: the first contact of the (M, 12) mesh (make_triangles, 1 .. POSED_MESH_MAX triangles), given once, posed
+        and moved by each record of an (N, 12) batch (make_pose_sweeps: position, rotation, world direction, tmax) -> (N, 8) float32
+        rt_mesh_sweep_hit records, normal nx ny nz | t | axis | triangle | prim_id | material_id (split_mesh_sweep_hits), same kind
+        and device as `sweeps`: sweep_triangle's record of the posed triangle pose_triangles(mesh, sweeps)[i, triangle] that touches
+        first - at equal t the lowest scene key, then the lowest mesh triangle.  A miss, and an invalid pose, has normal 0, tmax as
+        t, SWEEP_AXIS_NONE and triangle = prim_id = PRIM_MISS."""
+        m, n = self._posed_mesh(mesh, sweeps, 12, "sweeps")
+        out = _out_like(out, sweeps, "sweeps", n, 8, "float32")
+        _sync_torch(mesh, sweeps, out)
+        self._check(self.lib.rt_sweep_mesh(self._h, _addr(mesh), C.c_size_t(m), _addr(sweeps), C.c_size_t(n), _addr(out),
+                                           C.c_uint32(QUERY_COUNTERS if counters else 0)))
+        return out
 
     def sweep_capsule(self, sweeps, out=None, counters=False):
         """rt_sweep_capsule: the first contact of each moving capsule of an (N, 12) batch (make_capsule_sweeps: origin, radius, axis,

@@ -15,7 +15,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "librt_hip.so")
-SOURCES = ["kernels.hip", "wavefront.hip", "adaptive.hip", "device_build.hip", "shadow_grid.hip", "ray_query.hip", "surface_query.hip", "direct_light.hip", "path_query.hip", "probe_query.hip", "irradiance_query.hip", "closest_point.hip", "closest_point_all.hip", "inside.hip", "sweep.hip", "sweep_box.hip", "sweep_obb.hip", "sweep_capsule.hip", "overlap.hip", "overlap_obb.hip", "overlap_triangle.hip", "sweep_triangle.hip", "contact_capsule.hip", "contact_triangle.hip", "refit.hip", "denoise.hip", "rt_context.cpp", "rt_scene.cpp", "rt_frame.cpp", "rt_readback.cpp", "rt_query.cpp", "rt_mesh_query.cpp", "bvh_builder.cpp", "rt_host_api.cpp"]
+SOURCES = ["kernels.hip", "wavefront.hip", "adaptive.hip", "device_build.hip", "shadow_grid.hip", "ray_query.hip", "surface_query.hip", "direct_light.hip", "path_query.hip", "probe_query.hip", "irradiance_query.hip", "closest_point.hip", "closest_point_all.hip", "inside.hip", "sweep.hip", "sweep_box.hip", "sweep_obb.hip", "sweep_capsule.hip", "overlap.hip", "overlap_obb.hip", "overlap_triangle.hip", "sweep_triangle.hip", "contact_capsule.hip", "contact_triangle.hip", "posed_mesh.hip", "refit.hip", "denoise.hip", "rt_context.cpp", "rt_scene.cpp", "rt_frame.cpp", "rt_readback.cpp", "rt_query.cpp", "rt_mesh_query.cpp", "rt_posed_query.cpp", "bvh_builder.cpp", "rt_host_api.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize", "-mllvm", "-enable-post-misched=0",
          "-Wall", "-Wno-unused-function", "-pthread", "-I" + os.path.join(HERE, "..", "include")]
 

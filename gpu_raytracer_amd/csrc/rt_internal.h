@@ -1,4 +1,4 @@
-// rt_internal.h — what the host units of the C ABI (rt_context / rt_scene / rt_frame / rt_readback / rt_query / rt_mesh_query .cpp) share: the owner of
+// rt_internal.h — what the host units of the C ABI (rt_context / rt_scene / rt_frame / rt_readback / rt_query / rt_mesh_query / rt_posed_query .cpp) share: the owner of
 // device memory, the per-device state grouped by lifetime, the context, and the helpers more than one unit calls.  Nothing here is
 // exported from the library.
 #ifndef RT_INTERNAL_H
@@ -36,6 +36,7 @@
 #include "overlap_obb.h"
 #include "overlap_triangle.h"
 #include "path_query.h"
+#include "posed_mesh.h"
 #include "probe_query.h"
 #include "ray_query.h"
 #include "refit.h"
@@ -154,6 +155,7 @@ struct DeviceState {
     struct Query { // ray, surface, direct-light and path queries: staging of host batches (rays or points in, records / bytes out, rt_intersect_all's and rt_closest_point_all's counts, rt_inside's and rt_signed_distance's votes), grown on demand
         DevMem in, out, counts;
         DevBuf<uint32_t> ao; // rt_ambient_occlusion: the per-point counts its kernel adds to, for host and device batches alike
+        DevMem mesh;         // rt_overlap_mesh, rt_sweep_mesh: a host mesh's copy on this device, for the duration of the call
         DevBuf<uint4> paths; // rt_radiance with several samples, rt_radiance_sh, rt_irradiance: one record per path of a chunk (at most RT_QUERY_CHUNK), which its reduction / projection adds up
     } rq;
     // RT_FLAG_ACCUMULATE: the running sum of the context's accumulation over this device's pixels (DevTargets::run_sum), frame-pixel
@@ -283,6 +285,13 @@ int overlap_query(rt_ctx* ctx, const char* fn, const char* in_name, const void* 
 using ContactLaunch = hipError_t (*)(const DevScene&, const void*, void*, uint32_t*, uint32_t, uint32_t, int, unsigned long long*, hipStream_t);
 int contact_query(rt_ctx* ctx, const char* fn, const char* in_name, const void* in, size_t in_size, size_t n, uint32_t max_contacts, void* out,
                   uint32_t* counts, uint32_t flags, ContactLaunch launch);
+// rt_query.cpp: the argument checks and the batch of the posed-mesh calls (rt_overlap_mesh, rt_sweep_mesh in rt_posed_query.cpp): a mesh
+// of m rt_query_triangle given once, one record per pose in, one or two per pose out (out1.p null: none).  launch gets the mesh as
+// the device holds it; mode is handed through to it.
+using PoseLaunch = hipError_t (*)(const DevScene&, const void* mesh, uint32_t m, const void* poses, void* out0, void* out1, uint32_t n, uint32_t mode,
+                                  unsigned long long*, hipStream_t);
+int pose_query(rt_ctx* ctx, const char* fn, const void* mesh, size_t m, BatchIn in, size_t n, BatchOut out0, BatchOut out1, uint32_t flags, uint32_t mode,
+               PoseLaunch launch);
 
 } // namespace rti
 #endif

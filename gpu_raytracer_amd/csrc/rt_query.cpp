@@ -1,7 +1,7 @@
 // rt_query.cpp — calls that trace or filter outside a frame: ray queries (rt_hip.h "Ray queries": rt_intersect, rt_occluded,
 // rt_intersect_all, rt_camera_rays), surface queries ("Surface queries": rt_surface, rt_ambient_occlusion; kernels in
 // surface_query.hip), the direct-light query ("Direct-light queries": rt_direct_light; kernel in direct_light.hip), the path query ("Path queries":
-// rt_radiance; kernels in path_query.hip), the probe query ("Probe queries": rt_radiance_sh; kernels in probe_query.hip), the irradiance query ("Irradiance queries": rt_irradiance; kernels in irradiance_query.hip), the closest-point queries ("Closest-point queries": rt_closest_point, rt_closest_point_all; kernels in closest_point.hip, closest_point_all.hip), the inside test and the signed distance ("Inside tests and signed distance": rt_inside, rt_signed_distance; kernel in inside.hip), the sphere sweep ("Sphere sweeps": rt_sweep_sphere; kernel in sweep.hip), the box sweep ("Box sweeps": rt_sweep_box; kernel in sweep_box.hip), the capsule sweep ("Capsule sweeps": rt_sweep_capsule; kernel in sweep_capsule.hip), the overlap query ("Overlap queries": rt_overlap_box; kernel in overlap.hip; its checks and batch, overlap_query, also serve rt_overlap_obb and rt_mesh_query.cpp), the contact query ("Contact queries": rt_contact_capsule; kernel in contact_capsule.hip; its checks and batch, contact_query, also serve rt_mesh_query.cpp) and the image passes ("Feature buffers (AOVs) and denoising": rt_aovs, rt_sample_rays, rt_denoise; kernels in
+// rt_radiance; kernels in path_query.hip), the probe query ("Probe queries": rt_radiance_sh; kernels in probe_query.hip), the irradiance query ("Irradiance queries": rt_irradiance; kernels in irradiance_query.hip), the closest-point queries ("Closest-point queries": rt_closest_point, rt_closest_point_all; kernels in closest_point.hip, closest_point_all.hip), the inside test and the signed distance ("Inside tests and signed distance": rt_inside, rt_signed_distance; kernel in inside.hip), the sphere sweep ("Sphere sweeps": rt_sweep_sphere; kernel in sweep.hip), the box sweep ("Box sweeps": rt_sweep_box; kernel in sweep_box.hip), the capsule sweep ("Capsule sweeps": rt_sweep_capsule; kernel in sweep_capsule.hip), the overlap query ("Overlap queries": rt_overlap_box; kernel in overlap.hip; its checks and batch, overlap_query, also serve rt_overlap_obb and rt_mesh_query.cpp), the contact query ("Contact queries": rt_contact_capsule; kernel in contact_capsule.hip; its checks and batch, contact_query, also serve rt_mesh_query.cpp), the checks, the mesh placement and the batch of the posed-mesh queries ("Posed meshes": pose_query, which serves rt_posed_query.cpp; kernels in posed_mesh.hip) and the image passes ("Feature buffers (AOVs) and denoising": rt_aovs, rt_sample_rays, rt_denoise; kernels in
 // denoise.hip).  None of them touches the frame targets, the tile shares rt_read_* gather, or the running image of an accumulation.
 #include "rt_internal.h"
 #include "contact_capsule_rules.h"
@@ -545,6 +545,55 @@ int contact_query(rt_ctx* ctx, const char* fn, const char* in_name, const void* 
     Totals t;
     if (int rc = run_batch(ctx, b, t, [&](DeviceState& d, const DevScene& sc, const Chunk& ck) {
             return launch(sc, ck.in, ck.out[0], static_cast<uint32_t*>(ck.out[1]), ck.m, max_contacts, mode, counters ? d.counters.get() : nullptr, d.stream);
+        }))
+        return rc;
+    batch_stats(ctx, w0, t, counters, n);
+    return RT_OK;
+}
+
+// rt_overlap_mesh and rt_sweep_mesh (rt_posed_query.cpp): a mesh of m triangles given once and one record per pose in, one or two
+// records per pose out.  The mesh lives where the poses and the outputs live: device memory of the poses' device is handed to the
+// launcher as it is; a host mesh is copied into rq.mesh of every device that takes a share of the poses, once per call and ahead of
+// the launches on that device's stream.  A chunk is max(1, RT_QUERY_CHUNK / m) poses, so a launch poses at most RT_QUERY_CHUNK
+// triangles (or one pose's).  The entry states the checks that are its own (flags, `first` with RT_OVERLAP_ANY) before it calls.
+static_assert(sizeof(rt_query_triangle) == 48 && sizeof(rt_pose) == 32 && sizeof(rt_pose_sweep) == 48 && sizeof(rt_mesh_sweep_hit) == 32,
+              "the records posed_mesh.hip reads and writes");
+int pose_query(rt_ctx* ctx, const char* fn, const void* mesh, size_t m, BatchIn in, size_t n, BatchOut out0, BatchOut out1, uint32_t flags, uint32_t mode,
+               PoseLaunch launch) {
+    const double w0 = now_ms();
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (n == 0) return RT_OK;
+    if (!mesh || !in.p || !out0.p) return ctx->fail(RT_ERR_BAD_ARG, "%s: %s is NULL with n = %zu", fn, !mesh ? "mesh" : !in.p ? in.name : out0.name, n);
+    if (m < 1 || m > RT_POSED_MESH_MAX) return ctx->fail(RT_ERR_BAD_ARG, "%s: m %zu (1 .. %u)", fn, m, RT_POSED_MESH_MAX);
+    if (!ctx->uploaded) return ctx->fail(RT_ERR_NOT_UPLOADED, "%s: no scene uploaded", fn);
+    const bool counters = (flags & RT_QUERY_COUNTERS) != 0;
+    if (int rcp = sync_pending(ctx)) return rcp;
+    QueryPtr pm, pin;
+    if (int rc = classify_ptr(ctx, fn, "mesh", mesh, pm)) return rc;
+    if (int rc = classify_ptr(ctx, fn, in.name, in.p, pin)) return rc;
+    if (pm.device != pin.device || pm.dev != pin.dev)
+        return ctx->fail(RT_ERR_BAD_ARG, "%s: mesh and %s must both be host memory or both device memory of the same device", fn, in.name);
+    for (const BatchOut* o : {&out0, &out1}) { // run_batch asks again; asked here so that nothing is copied for a call it refuses
+        QueryPtr po;
+        if (!o->p) continue;
+        if (int rc = classify_ptr(ctx, fn, o->name, o->p, po, o->align)) return rc;
+        if (po.device != pin.device || po.dev != pin.dev)
+            return ctx->fail(RT_ERR_BAD_ARG, "%s: mesh, %s and the outputs must all be host memory or all device memory of the same device", fn, in.name);
+    }
+    const size_t nd = ctx->devs.size(), mesh_bytes = m * sizeof(rt_query_triangle);
+    if (!pm.device)
+        for (size_t j = 0; j < nd; j++) {
+            if (device_range(n, nd, j).count == 0) continue;
+            DeviceState& d = ctx->devs[j];
+            HIPCHK(ctx, hipSetDevice(d.device));
+            HIPCHK(ctx, d.rq.mesh.reserve(mesh_bytes));
+            HIPCHK(ctx, hipMemcpyAsync(d.rq.mesh.get(), mesh, mesh_bytes, hipMemcpyHostToDevice, d.stream));
+        }
+    const size_t chunk = std::max<size_t>(1, RT_QUERY_CHUNK / m);
+    const Batch b{fn, n, in, {out0, out1}, chunk, chunk, counters ? RT_CNT_TRI_TESTS + 1u : 0u};
+    Totals t;
+    if (int rc = run_batch(ctx, b, t, [&](DeviceState& d, const DevScene& sc, const Chunk& ck) {
+            return launch(sc, pm.device ? mesh : d.rq.mesh.get(), (uint32_t)m, ck.in, ck.out[0], ck.out[1], ck.m, mode, counters ? d.counters.get() : nullptr, d.stream);
         }))
         return rc;
     batch_stats(ctx, w0, t, counters, n);

@@ -100,6 +100,9 @@ TRIANGLE_SWEEP = np.dtype([("v0", f32, 3), ("_pad0", u32), ("v1", f32, 3), ("_pa
 TRIANGLE_SWEEP_HIT = np.dtype([("normal", f32, 3), ("t", f32), ("axis", u32), ("_reserved", u32), ("prim_id", u32), ("material_id", u32)])  # rt_triangle_sweep_hit
 TRIANGLE_CONTACT_QUERY = np.dtype([("v0", f32, 3), ("margin", f32), ("v1", f32, 3), ("_pad1", u32), ("v2", f32, 3), ("_pad2", u32)])  # rt_triangle_contact_query
 TRIANGLE_CONTACT = np.dtype([("position", f32, 3), ("distance", f32), ("qu", f32), ("qv", f32), ("prim_id", u32), ("material_id", u32)])  # rt_triangle_contact
+POSE = np.dtype([("position", f32, 3), ("_pad0", u32), ("rotation", f32, 4)])  # rt_pose
+POSE_SWEEP = np.dtype([("position", f32, 3), ("_pad0", u32), ("rotation", f32, 4), ("direction", f32, 3), ("tmax", f32)])  # rt_pose_sweep
+MESH_SWEEP_HIT = np.dtype([("normal", f32, 3), ("t", f32), ("axis", u32), ("triangle", u32), ("prim_id", u32), ("material_id", u32)])  # rt_mesh_sweep_hit
 CAPSULE_SWEEP = np.dtype([("origin", f32, 3), ("radius", f32), ("axis", f32, 3), ("_pad", u32), ("direction", f32, 3), ("tmax", f32)])  # rt_capsule_sweep
 CAPSULE_SWEEP_HIT = np.dtype([("position", f32, 3), ("t", f32), ("s", f32), ("_reserved", u32), ("prim_id", u32), ("material_id", u32)])  # rt_capsule_sweep_hit
 CAPSULE = np.dtype([("origin", f32, 3), ("radius", f32), ("axis", f32, 3), ("_pad", u32)])  # rt_capsule
@@ -126,7 +129,7 @@ EXPECTED_SIZES = {
     "PATH_PARAMS": 32, "PATH_RESULT": 16, "PROBE": 16, "SH9": 112, "IRRADIANCE": 16, "POINT_QUERY": 16, "NEAREST": 32, "INSIDE_PARAMS": 16,
     "SWEEP": 32, "SWEEP_HIT": 32, "BOX": 32, "BOX_SWEEP": 48, "BOX_SWEEP_HIT": 32, "CAPSULE_SWEEP": 48, "CAPSULE_SWEEP_HIT": 32,
     "CAPSULE": 32, "CONTACT": 32, "OBB": 48, "OBB_SWEEP": 64, "TRIANGLE_QUERY": 48, "TRIANGLE_SWEEP": 64, "TRIANGLE_SWEEP_HIT": 32,
-    "TRIANGLE_CONTACT_QUERY": 48, "TRIANGLE_CONTACT": 32,
+    "TRIANGLE_CONTACT_QUERY": 48, "TRIANGLE_CONTACT": 32, "POSE": 32, "POSE_SWEEP": 48, "MESH_SWEEP_HIT": 32,
 }
 for _name, _size in EXPECTED_SIZES.items():
     assert globals()[_name].itemsize == _size, (_name, globals()[_name].itemsize, _size)

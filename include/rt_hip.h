@@ -224,7 +224,7 @@ int rt_get_stats(rt_ctx* ctx, rt_stats* out);
  * a new one at sample 0 by itself, as RT_FLAG_ACCUMULATE_RESTART does.  The other RT_FLAG_* bits change no bits and may differ.
  * The running image ends (the next accumulating call starts at 0) with rt_upload_scene*, rt_update_geometry, rt_dispatch_tile, any
  * rt_render without RT_FLAG_ACCUMULATE and an accumulating call that fails once it has passed its argument checks.  It survives rt_prepare,
- * rt_upload_textures, the ray queries, the surface queries, rt_direct_light, rt_radiance, rt_radiance_sh, rt_irradiance, rt_closest_point, rt_closest_point_all, rt_inside, rt_signed_distance, rt_overlap_box, rt_sweep_sphere, rt_sweep_box, rt_sweep_capsule, rt_contact_capsule, rt_overlap_obb, rt_sweep_obb, rt_overlap_triangle, rt_sweep_triangle, rt_contact_triangle, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
+ * rt_upload_textures, the ray queries, the surface queries, rt_direct_light, rt_radiance, rt_radiance_sh, rt_irradiance, rt_closest_point, rt_closest_point_all, rt_inside, rt_signed_distance, rt_overlap_box, rt_sweep_sphere, rt_sweep_box, rt_sweep_capsule, rt_contact_capsule, rt_overlap_obb, rt_sweep_obb, rt_overlap_triangle, rt_sweep_triangle, rt_contact_triangle, rt_overlap_mesh, rt_sweep_mesh, rt_camera_rays, rt_aovs, rt_sample_rays, rt_denoise, rt_get_stats and rt_read_*.  A call rejected for its arguments changes nothing.
  * Limit: RT_ACCUMULATE_MAX_SAMPLES samples (where the float sample count stops being exact); a call that would pass it is RT_ERR_BAD_ARG
  * and leaves the running image as it was.  rt_stats describes the call alone (its segments, pixels, kernel_ms).
  * A context over several devices, and a tile_rank / tile_world share, accumulates its own share of the pixels.
@@ -1535,6 +1535,87 @@ int rt_contact_triangle(rt_ctx* ctx, const rt_triangle_contact_query* triangles,
                         rt_triangle_contact* out,   /* n * max_contacts records, query-major; unused slots are misses */
                         uint32_t* counts,           /* n entries; may be NULL unless max_contacts == 0 */
                         uint32_t flags);            /* RT_QUERY_COUNTERS | RT_QUERY_COUNT_ALL | RT_CONTACT_ANY; max_contacts <= RT_CONTACT_MAX */
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Posed meshes: the caller's own mesh of m triangles, given ONCE, at n candidate poses (no reference counterpart; the call of
+ * FCL, Bullet, PhysX and Embree's rtcCollide that takes a shape once and a transform per query is the model): a planner's robot link
+ * at many configurations, a hull dropped at many spots.  "Triangle queries" and "Triangle sweeps" answer per triangle: their caller
+ * transforms n * m triangles, ships 64 bytes for each, gets n * m records back and reduces them per pose.  Here the device poses the
+ * triangles, one lane runs per posed triangle with the statements of those two sections, and the reduction per pose happens on the
+ * device; in a sweep the lanes of a pose share the body's best time so far, so that each culls by the body's first contact.
+ *
+ * The answer for a pose is BY DEFINITION the reduction of rt_overlap_triangle / rt_sweep_triangle over the posed triangles, bit for
+ * bit, and the posing is one f32 statement (csrc/mesh_pose_rules.h, whose header comment is the specification; every operation
+ * one f32 rounding, nothing fused):
+ *   R = the frame of `rotation` as in "Oriented boxes" (the quaternion x, y, z, w need not be normalised);
+ *   vertex v of the mesh becomes  w_a = ((R_a0 * v_0 + R_a1 * v_1) + R_a2 * v_2) + position_a.
+ * A pose is valid iff its three position components are finite and the rotation is valid as in "Oriented boxes" (all four
+ * components finite, the squared norm finite and > 0).  An invalid pose is answered without a walk: rt_overlap_mesh gives pairs = 0
+ * and first = 0xFFFFFFFF, rt_sweep_mesh the miss record below.  A posed triangle is then judged by the triangle call's own rule:
+ * a non-finite mesh vertex makes that triangle touch nothing, a zero direction or a tmax that is NaN or <= 0 a miss.  With rotation
+ * (0, 0, 0, w), w != 0, and position 0 the posed vertices are the mesh's, up to the sign of a zero.
+ *
+ * With T_ij = mesh triangle j posed by pose i:
+ * rt_overlap_mesh: c_j = the count rt_overlap_triangle gives T_ij with RT_QUERY_COUNT_ALL and max_prims = 0.
+ *   pairs[i] = min(sum_j c_j, 0xFFFFFFFF), the sum taken in 64 bits; first[i] = the lowest j with c_j > 0, else 0xFFFFFFFF.
+ *   RT_OVERLAP_ANY: pairs[i] = 1 if some c_j > 0, else 0, and the pose may stop at the first touch; `first` must then be NULL
+ *   (RT_ERR_BAD_ARG otherwise).
+ * rt_sweep_mesh: h_j = rt_sweep_triangle's record for (T_ij, direction, tmax); the direction is in world space and is NOT turned by
+ *   the pose.  The answer is h_j of the hit with the least (bits of t, prim_id ^ 0x80000000, j), its _reserved word replaced by j:
+ *   at equal time spheres come before triangles, a lower scene index before a higher, a lower mesh triangle before a higher.  If
+ *   every h_j is a miss: normal 0, t = tmax as given, axis RT_SWEEP_AXIS_NONE, triangle = prim_id = 0xFFFFFFFF, material_id 0.
+ * Arguments: 1 <= m <= RT_POSED_MESH_MAX, else RT_ERR_BAD_ARG; n = 0 is RT_OK and touches nothing, as for rt_sweep_triangle.
+ * Buffers: mesh, the poses and the outputs are all host memory or all device memory of one device; device memory 16-byte aligned,
+ *   pairs and first 4-byte.  A host mesh is copied to every device that takes part, once per call.  Chunks are
+ *   max(1, RT_QUERY_CHUNK / m) poses; the split over devices is by poses.
+ * Statistics: rays = n; visits and records only with RT_QUERY_COUNTERS.  The bytes of the answer are deterministic; with the
+ *   shared bound the counters of rt_sweep_mesh are not (they depend on which lane found the body's contact first).
+ * Everything else - synchronisation, side effects (the last frame and a running accumulation are left alone), error codes - as for
+ *   rt_sweep_triangle.  The result does not depend on the tree in use, the device count, the kind of memory or the chunking.
+ * Limit: a pose never spans more than one wave of the device, so a call with few poses and a very large mesh occupies few waves;
+ *   such a caller is better off with rt_sweep_triangle over its own posed triangles and its own reduction.
+ * --------------------------------------------------------------------------------------------------------------- */
+typedef struct rt_pose {
+    float position[3];     /* added after the rotation */
+    uint32_t _pad0;        /* ignored */
+    float rotation[4];     /* x, y, z, w: rt_obb's quaternion, mesh axes -> world axes; need not be normalised */
+} rt_pose; /* 32 bytes */
+
+typedef struct rt_pose_sweep {
+    float position[3];     /* the first 32 bytes are an rt_pose */
+    uint32_t _pad0;
+    float rotation[4];
+    float direction[3];    /* the last 16 bytes are the second half of an rt_sweep; world space, NOT turned by the pose; not normalised */
+    float tmax;            /* only contacts with t < tmax are reported */
+} rt_pose_sweep; /* 48 bytes */
+
+typedef struct rt_mesh_sweep_hit {
+    float normal[3];       /* rt_triangle_sweep_hit's fields, of the posed triangle that touches first */
+    float t;
+    uint32_t axis;
+    uint32_t triangle;     /* its index in the mesh; 0xFFFFFFFF for a miss */
+    uint32_t prim_id;
+    uint32_t material_id;
+} rt_mesh_sweep_hit; /* 32 bytes: rt_triangle_sweep_hit with `triangle` where _reserved is */
+
+#define RT_POSED_MESH_MAX 65536u  /* triangles in a query mesh */
+
+RT_STATIC_ASSERT(sizeof(rt_pose) == 32 && offsetof(rt_pose, position) == 0 && offsetof(rt_pose, _pad0) == 12 && offsetof(rt_pose, rotation) == 16,
+                 "rt_pose is 32 B: position, _pad0 at 12, rotation at 16");
+RT_STATIC_ASSERT(sizeof(rt_pose_sweep) == 48 && offsetof(rt_pose_sweep, position) == 0 && offsetof(rt_pose_sweep, _pad0) == 12 &&
+                     offsetof(rt_pose_sweep, rotation) == 16 && offsetof(rt_pose_sweep, direction) == 32 && offsetof(rt_pose_sweep, tmax) == 44,
+                 "rt_pose_sweep is 48 B: an rt_pose, direction at 32, tmax at 44");
+RT_STATIC_ASSERT(sizeof(rt_mesh_sweep_hit) == 32 && offsetof(rt_mesh_sweep_hit, normal) == 0 && offsetof(rt_mesh_sweep_hit, t) == 12 &&
+                     offsetof(rt_mesh_sweep_hit, axis) == 16 && offsetof(rt_mesh_sweep_hit, triangle) == 20 &&
+                     offsetof(rt_mesh_sweep_hit, prim_id) == 24 && offsetof(rt_mesh_sweep_hit, material_id) == 28,
+                 "rt_mesh_sweep_hit is 32 B: normal, t at 12, axis at 16, triangle at 20, prim_id at 24, material_id at 28");
+
+int rt_overlap_mesh(rt_ctx* ctx, const rt_query_triangle* mesh, size_t m, const rt_pose* poses, size_t n,
+                    uint32_t* pairs,   /* n entries */
+                    uint32_t* first,   /* n entries or NULL */
+                    uint32_t flags);   /* RT_QUERY_COUNTERS | RT_OVERLAP_ANY */
+int rt_sweep_mesh(rt_ctx* ctx, const rt_query_triangle* mesh, size_t m, const rt_pose_sweep* sweeps, size_t n, rt_mesh_sweep_hit* out,
+                  uint32_t flags);     /* RT_QUERY_COUNTERS */
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Geometry updates: new positions for the uploaded scene, in place (no reference counterpart; Embree's refit build,
